@@ -10,11 +10,18 @@ support, 10 M synthetic 150 bp reads per GPU with 1 % substitutions.  Reads are 
 ranks (weak scaling: 10 M per GPU), the read-only index is built on rank 0 and replicated with one
 RCCL broadcast at load time; there are no per-step collectives.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]        (N>1: launched by torch.distributed.run)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                             (N>1: launched by torch.distributed.run)
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` and, at N=1,
-`cpu_baseline` (the oracle = restated reference CPU path, timed on the host cores on a bounded
-sample of the same reads; the same sample doubles as a bit-exact parity check of the GPU output).
+Prints ONE JSON line on rank 0 (contract in the task description) with `roofline`.  A plain run sets up, warms up, times
+the K steps, writes the outputs (--dump-outputs) and prints the line; nothing else.  --full adds, at N=1, the side
+measurements: `cpu_baseline` (the oracle = restated reference CPU path, timed on the host cores on a bounded sample of the
+same reads; the same sample doubles as a bit-exact parity check of the GPU output), `int32_results_on_device`,
+`two_batches_in_flight` and `end_to_end`; with --kernel rank, the rank kernel's `cpu_baseline`.
+
+--dump-outputs DIR: after the timed steps, what the timed path computed in its last step, as float64 .npy files in DIR
+(dump_outputs(): the head of the output, a fixed seeded sample of the rest, and a summary of the whole; well under 64 MB).
+The inputs are seeded: the same arguments give the same inputs, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -208,6 +215,42 @@ def request_model(read_requests: float, write_requests: float, kernel_ms: float)
                                "micro benchmark's own gather + store mixes reach 90-96 % of this additive floor"}
 
 
+DUMP_HEAD = 1 << 17             # --dump-outputs: the first results of the output (whole reads), per node
+DUMP_SAMPLE = 1 << 20           # ... and this many seeded positions spread over all of it (float64: 8 MB + 8 MB)
+DUMP_SEED = 20240611
+
+
+def dump_outputs(path: str, name: str, d_out, rank: int, world: int) -> None:
+    """--dump-outputs: the int64 results the caller of the timed path received in its last step, as float64 .npy files in
+    `path` (the values are column indices or -1, exact in float64):
+      <name>_head.npy        the first results of the output
+      <name>_sample_pos.npy  a fixed, seeded, sorted sample of positions in the whole output
+      <name>_sample.npy      the results at those positions
+      <name>_summary.npy     [number of results, number >= 0, sum of all results] over the whole output
+    At most ~17 MB per call (the head and the sample are split among the ranks); rank r of N > 1 writes rank<r>_<name>_*."""
+    os.makedirs(path, exist_ok=True)
+    if world > 1:
+        name = "rank%d_%s" % (rank, name)
+    n = d_out.numel()
+    head = d_out[:min(n, DUMP_HEAD // world)]
+    m = DUMP_SAMPLE // world
+    if n <= m:
+        pos = np.arange(n, dtype=np.int64)
+    else:
+        pos = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(n, size=m, replace=False)).astype(np.int64)
+    sample = d_out[torch.from_numpy(pos).to(d_out.device)]
+    found, total = 0, 0
+    CH = 1 << 28                                    # in pieces: no temporary the size of the output
+    for lo in range(0, n, CH):
+        found += int((d_out[lo:lo + CH] >= 0).sum().item())
+        total += int(d_out[lo:lo + CH].sum(dtype=torch.int64).item())
+    summary = [float(n), float(found), float(total)]
+    np.save(os.path.join(path, name + "_head.npy"), head.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, name + "_sample_pos.npy"), pos.astype(np.float64))
+    np.save(os.path.join(path, name + "_sample.npy"), sample.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, name + "_summary.npy"), np.array(summary, dtype=np.float64))
+
+
 RANK_B_SURVEY = 72              # SURVEY 8d: one rank = 8 B count + 64 B block bits
 RANK_B_LAYOUT = 8 + 1 + 16 + 8  # this layout: pos + symbol + one 16-byte quad {bits, count} + result
 
@@ -225,7 +268,7 @@ def rank_bench(args, rank: int, world: int, local_rank: int, dev) -> int:
     gen = torch.Generator(device=dev)
     gen.manual_seed(7 + rank)
 
-    def measure(index, n_cols, cols, label):
+    def measure(index, n_cols, cols, label, name):
         d_pos = torch.randint(0, n_cols + 1, (Q,), dtype=torch.int64, device=dev, generator=gen)
         d_sym = acgt[torch.randint(0, 4, (Q,), device=dev, generator=gen)]
         d_out = torch.empty(Q, dtype=torch.int64, device=dev)
@@ -252,11 +295,13 @@ def rank_bench(args, rank: int, world: int, local_rank: int, dev) -> int:
         if world > 1:
             elapsed = sdist.max_over_ranks(elapsed, dev)
         kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, name, d_out, rank, world)
         res = {"label": label, "columns": n_cols, "image_bytes": index.blob_bytes, "queries_per_gpu": Q,
                "ms_per_step": elapsed / args.steps * 1e3, "kernel_ms": kernel_ms,
                "ranks_per_s": Q * world * args.steps / elapsed, "kernel_only_ranks_per_s": Q / (kernel_ms * 1e-3)}
         cpu = None
-        if rank == 0 and not args.no_cpu_baseline:
+        if rank == 0 and args.full and not args.no_cpu_baseline:
             from oracle import OracleIndex
             orc = OracleIndex.from_bits(cols[0], cols[1], cols[2], cols[3], None, n_cols, 1, 0, 0)
             sample = min(Q, 4_000_000 * cores)
@@ -283,7 +328,7 @@ def rank_bench(args, rank: int, world: int, local_rank: int, dev) -> int:
     t0 = time.time()
     big = capi.Index.create(cols[0], cols[1], cols[2], cols[3], None, n_cols, 1, 0, 0, None, device=local_rank)
     log(f"rank image: {n_cols} columns, {big.blob_bytes / 1e6:.0f} MB ({time.time() - t0:.1f} s)")
-    hbm, cpu_hbm = measure(big, n_cols, cols, "four random bit vectors, HBM resident")
+    hbm, cpu_hbm = measure(big, n_cols, cols, "four random bit vectors, HBM resident", "rank_hbm")
     big.close()
     del cols
     # (2) cache resident: the config-2 index
@@ -291,7 +336,8 @@ def rank_bench(args, rank: int, world: int, local_rank: int, dev) -> int:
     bits = hostlib.build_bits([g.tobytes() for g in genomes], 30, False, True, n_threads=cores)
     small = capi.Index.create(bits.cols[0], bits.cols[1], bits.cols[2], bits.cols[3], bits.ssup, bits.n_nodes, 30,
                               bits.n_kmers, PRECALC, None, device=local_rank)
-    cache, cpu_cache = measure(small, bits.n_nodes, bits.cols, "config-2 index (coli3-like, k=30), cache resident")
+    cache, cpu_cache = measure(small, bits.n_nodes, bits.cols, "config-2 index (coli3-like, k=30), cache resident",
+                               "rank_cache")
     if rank == 0:
         ach = RANK_B_SURVEY * Q / (hbm["kernel_ms"] * 1e-3) / 1e9
         result = {
@@ -356,6 +402,11 @@ def run() -> int:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (CPU baseline with its parity check, int32 results, two batches in "
+                         "flight, end to end); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as float64 .npy files in DIR")
     ap.add_argument("--reads", type=int, default=int(os.environ.get("SBWT_BENCH_READS", 10_000_000)),
                     help="reads per GPU")
     ap.add_argument("--genome-len", type=int, default=int(os.environ.get("SBWT_BENCH_GENOME", 5_000_000)))
@@ -652,10 +703,12 @@ def run() -> int:
     status = index.workspace_status(d_ws.data_ptr(), stream)
     if status != 0:
         raise SystemExit(f"search kernel reported status {status}")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "kmer_results", d_out, rank, world)
     # The same K steps with int32 results on the device (sbwtgpu_*_dev_i32; n_nodes < 2^31): every kernel writes 4 bytes per
     # k-mer, half the write requests of a launch.  Reported beside the line: `value` is the reference's int64 interface.
     int32_leg = None
-    if one_call and world == 1 and not args.no_int32_leg and index.n_nodes < (1 << 31) and n_kmers * 8 <= (24 << 30):
+    if args.full and one_call and world == 1 and not args.no_int32_leg and index.n_nodes < (1 << 31) and n_kmers * 8 <= (24 << 30):
         d32 = torch.empty(n_kmers, dtype=torch.int32, device=dev)
 
         def step32():
@@ -687,7 +740,7 @@ def run() -> int:
     # ~0.5 ms in which its waves leave one by one (tools/timeline_fused.py); with a second launch queued behind, the chip
     # stays full.  Reported beside the line, never as `value`: `value` is one launch at a time, like its kernel_ms.
     two_in_flight = None
-    if one_call and world == 1 and not args.no_two_in_flight and n_kmers * 8 <= (24 << 30):
+    if args.full and one_call and world == 1 and not args.no_two_in_flight and n_kmers * 8 <= (24 << 30):
         side = torch.cuda.Stream(device=dev)
         outs, wss = [d_out, torch.empty_like(d_out)], [d_ws, torch.empty_like(d_ws)]
         sts = [torch.cuda.current_stream(), side]
@@ -870,8 +923,8 @@ def run() -> int:
             if world > 1:    # the ranks searched different reads
                 result["rank_reads_differ"] = bool(not torch.equal(gb[0], gb[1]))
 
-    # ---- CPU baseline (restated reference CPU path = the oracle), rank 0 at N=1 only ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    # ---- CPU baseline (restated reference CPU path = the oracle), rank 0 at N=1 only, --full ----
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         from oracle import OracleIndex  # test infrastructure: used here only as baseline + checker
         orc = OracleIndex.from_bits(bits.cols[0], bits.cols[1], bits.cols[2], bits.cols[3], bits.ssup, bits.n_nodes,
@@ -921,8 +974,8 @@ def run() -> int:
             print(json.dumps(result))
             raise SystemExit("PARITY FAILURE: GPU output differs from the oracle on the baseline sample")
 
-    # ---- end to end (SURVEY 8d "Timing"; sbwt_search.cpp:54-56,145,255-256): rank 0 at N=1 only ----
-    if rank == 0 and world == 1 and not args.no_end_to_end and args.config in (2, 5):
+    # ---- end to end (SURVEY 8d "Timing"; sbwt_search.cpp:54-56,145,255-256): rank 0 at N=1 only, --full ----
+    if args.full and rank == 0 and world == 1 and not args.no_end_to_end and args.config in (2, 5):
         try:
             result["end_to_end"] = end_to_end_leg(args, index, genomes, d_bases, m, streaming, dev)
         except Exception as ex:      # the headline must not die with its side measurement

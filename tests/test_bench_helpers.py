@@ -55,3 +55,37 @@ def test_request_model_prices_reads_and_writes_against_the_measured_ceilings():
     assert abs(rm["floor_ms"] - (154.194e6 / 55.7e9 + 169.645e6 * 64 / 6.46e12) * 1e3) < 1e-9
     assert 0.80 < rm["frac_of_deliverable"] < 0.95
     assert bench.request_model(1.0, 1.0, 0.0)["frac_of_deliverable"] is None
+
+
+def test_dump_outputs_writes_float64_head_sample_and_summary(tmp_path, monkeypatch):
+    # --dump-outputs: the last step's int64 results as float64 .npy files; the sample is seeded (two runs, same positions)
+    import torch
+    monkeypatch.setattr(bench, "torch", torch)
+    n = 3 * bench.DUMP_SAMPLE
+    out = torch.arange(n, dtype=torch.int64) % 1000 - 1                  # column indices and -1 (absent)
+    bench.dump_outputs(str(tmp_path / "a"), "kmer_results", out, 0, 1)
+    bench.dump_outputs(str(tmp_path / "b"), "kmer_results", out, 0, 1)
+    import numpy as np
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["kmer_results_head.npy", "kmer_results_sample.npy", "kmer_results_sample_pos.npy",
+                     "kmer_results_summary.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
+    head = np.load(tmp_path / "a" / "kmer_results_head.npy")
+    assert np.array_equal(head, out[:bench.DUMP_HEAD].numpy())
+    pos = np.load(tmp_path / "a" / "kmer_results_sample_pos.npy").astype(np.int64)
+    assert len(pos) == bench.DUMP_SAMPLE and np.all(np.diff(pos) > 0) and pos[-1] < n
+    assert np.array_equal(np.load(tmp_path / "a" / "kmer_results_sample.npy"), out.numpy()[pos])
+    found = int((out >= 0).sum())
+    assert list(np.load(tmp_path / "a" / "kmer_results_summary.npy")) == [n, found, int(out.sum())]
+    # a rank of N > 1 names its files and writes its share
+    bench.dump_outputs(str(tmp_path / "c"), "kmer_results", out, 1, 2)
+    assert len(np.load(tmp_path / "c" / "rank1_kmer_results_head.npy")) == bench.DUMP_HEAD // 2
+
+
+def test_plain_run_and_full_are_options():
+    import subprocess
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout

@@ -12,9 +12,9 @@ mkdir -p $O
 if [ "$PART" = 1 ] || [ "$PART" = all ]; then
 ( time timeout 1500 python -m pytest tests/ -q -m gpu ) > $O/gputest.log 2>&1; tail -4 $O/gputest.log
 ( for seed in 1 2 3 4; do SEED=$seed timeout 150 python tools/fuzz_gpu.py 100 2>&1 | tail -1 | sed "s/^/seed $seed: /"; done ) > $O/fuzz.log 2>&1; cat $O/fuzz.log
-timeout 900 python bench.py --steps 25 --warmup 3 > $O/c2_bench.json 2> $O/c2_bench.err
-timeout 400 python bench.py --config 5 --steps 10 --no-cli-full > $O/c5_bench.json 2> $O/c5_bench.err
-timeout 900 python bench.py --config 3 --steps 5 > $O/c3_bench.json 2> $O/c3_bench.err
+timeout 900 python bench.py --full --steps 25 --warmup 3 > $O/c2_bench.json 2> $O/c2_bench.err
+timeout 400 python bench.py --full --config 5 --steps 10 --no-cli-full > $O/c5_bench.json 2> $O/c5_bench.err
+timeout 900 python bench.py --full --config 3 --steps 5 > $O/c3_bench.json 2> $O/c3_bench.err
 PMC="FETCH_SIZE|WRITE_SIZE|TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum TCC_EA0_RDREQ_128B_sum|TCC_HIT_sum TCC_MISS_sum|SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES"
 prof() {   # prof <name> <config> <level> <variant> <reads> <bench args...>
   local name=$1 cfg=$2 lvl=$3 var=$4 reads=$5; shift 5
@@ -30,11 +30,11 @@ prof c2_level1 2 1 1 10000000 --steps 3 --image-level 1
 prof c2_level2 2 2 1 10000000 --steps 3 --image-level 2
 cp profiles/traffic.json $O/traffic.json
 # the committed lines: the same commands once more, now that traffic.json belongs to this code (roofline.traffic attached)
-timeout 900 python bench.py --steps 25 --warmup 3 --no-cpu-baseline --no-end-to-end > $O/c2_line.json 2>/dev/null
-timeout 400 python bench.py --config 5 --steps 10 --no-cpu-baseline --no-end-to-end > $O/c5_line.json 2>/dev/null
-timeout 900 python bench.py --config 3 --steps 5 --no-cpu-baseline --no-end-to-end > $O/c3_line.json 2>/dev/null
-timeout 600 python bench.py --steps 10 --image-level 1 --no-cpu-baseline --no-end-to-end > $O/c2_level1.json 2>/dev/null
-timeout 600 python bench.py --steps 10 --image-level 2 --no-cpu-baseline --no-end-to-end > $O/c2_level2.json 2>/dev/null
+timeout 900 python bench.py --full --steps 25 --warmup 3 --no-cpu-baseline --no-end-to-end > $O/c2_line.json 2>/dev/null
+timeout 400 python bench.py --full --config 5 --steps 10 --no-cpu-baseline --no-end-to-end > $O/c5_line.json 2>/dev/null
+timeout 900 python bench.py --full --config 3 --steps 5 --no-cpu-baseline --no-end-to-end > $O/c3_line.json 2>/dev/null
+timeout 600 python bench.py --full --steps 10 --image-level 1 --no-cpu-baseline --no-end-to-end > $O/c2_level1.json 2>/dev/null
+timeout 600 python bench.py --full --steps 10 --image-level 2 --no-cpu-baseline --no-end-to-end > $O/c2_level2.json 2>/dev/null
 fi   # part 1
 if [ "$PART" = 2 ] || [ "$PART" = all ]; then
 NREADS=10000000 timeout 900 python tools/robustness_bench.py > $O/robustness.jsonl 2> $O/robustness.err
@@ -71,10 +71,10 @@ fi
   NREADS=1000000 STEPS=50 python tools/overlap_steps.py 2>&1 | grep "^reads"
   K=63 STREAMING=0 NREADS=10000000 python tools/overlap_steps.py 2>&1 | grep "^reads" ) > $O/two_in_flight.txt 2>&1
 # the indexes beyond the Infinity Cache and beyond 2^31 columns (SURVEY 8d "G-hbm")
-timeout 900 python bench.py --config 6 --steps 5 --warmup 2 --no-end-to-end > $O/c6_hbm_bench.json 2> $O/c6_hbm_bench.err
-timeout 1200 python bench.py --config 6 --hbm-genome-len 2250000000 --steps 5 --warmup 2 --no-end-to-end > $O/c6_big_index_bench.json 2> $O/c6_big_index_bench.err
+timeout 900 python bench.py --full --config 6 --steps 5 --warmup 2 --no-end-to-end > $O/c6_hbm_bench.json 2> $O/c6_hbm_bench.err
+timeout 1200 python bench.py --full --config 6 --hbm-genome-len 2250000000 --steps 5 --warmup 2 --no-end-to-end > $O/c6_big_index_bench.json 2> $O/c6_big_index_bench.err
 # ... and 31 < k <= 63 there (round 6: the full image; k = 32 is what the GPU builder's 64-bit keys hold at that size)
-timeout 1200 python bench.py --config 6 --hbm-genome-len 2250000000 --hbm-k 32 --steps 5 --warmup 2 --no-end-to-end --no-cpu-baseline > $O/c6_big_index_k32.json 2> $O/c6_big_index_k32.err
+timeout 1200 python bench.py --full --config 6 --hbm-genome-len 2250000000 --hbm-k 32 --steps 5 --warmup 2 --no-end-to-end --no-cpu-baseline > $O/c6_big_index_k32.json 2> $O/c6_big_index_k32.err
 # long reads (round 6: the fused kernel's ticket table): whole genomes, 1 kbp and 10 kbp reads, >= 10^9 bases per batch, k = 30 and 63,
 # 1 % and 5 % substitutions, with the table and without (the general kernel)
 ( for K in 30 63; do for SUBS in 0.01 0.05; do K=$K SUBS=$SUBS timeout 600 python tools/long_read_bench.py 2>&1 | grep "^k="; done; done ) > $O/long_reads.txt 2>&1
