@@ -328,6 +328,38 @@ void sbwtgpu_free_host(void *p);
  * reference's scalar API arrives as batches of one); this frees the parked buffers and the calling thread's. */
 void sbwtgpu_release_cached_buffers(void);
 
+/* ---- k-bounded matching statistics (MS) ----
+ * Column j has the label L_j: its k characters, '$'-padded on the left for dummies (L_0 = $^k), in colex order.  The LCS
+ * array: lcs[0] = 0, lcs[j] = the length of the longest common suffix of L_{j-1} and L_j ('$' never counts), in [0, k-1].
+ * For a read s and each position i, MS gives len[i]: the largest d in [0, k] such that s[i-d+1 .. i] is upper-case ACGT and
+ * a suffix of some label -- for a string over ACGT of length <= k the same as a substring of an indexed k-mer -- and
+ * [first[i], second[i]]: the colex range of the columns whose labels end with that suffix ([0, n_nodes-1] when len[i] == 0).
+ * Any byte other than upper-case A/C/G/T ends a match (len 0 there).  len[i] == k exactly when the k-mer ending at i is in
+ * the index, and then first[i] == second[i] is its column.
+ *
+ * sbwtgpu_index_build_lcs builds the LCS array on the device (idempotent, thread-safe; 1 byte per column in an allocation
+ * of its own, not part of the image nor of its byte cap, plus 4 bytes per column of scratch while it runs; a replica made by
+ * adopt / bcast builds its own).  SBWTGPU_ERR_OOM leaves the index usable for everything else.  Every call below builds it
+ * first when needed.  Rank-only indexes: SBWTGPU_ERR_INVALID_ARG. */
+int  sbwtgpu_index_build_lcs(sbwtgpu_index *idx);
+/* out[0 .. n_nodes): the LCS array */
+int  sbwtgpu_index_get_lcs(const sbwtgpu_index *idx, uint8_t *out);
+/* read r = bases[read_off[r] .. read_off[r+1]); the result of base b goes to slot b (len[b], first[b], second[b]), so the
+ * arrays hold read_off[n_reads] entries.  first and second: both NULL (lengths only) or both non-NULL.  A read of 2^31 bases
+ * or more: SBWTGPU_ERR_READ_TOO_LONG. */
+int  sbwtgpu_matching_statistics_batch(const sbwtgpu_index *idx, const char *bases, const int64_t *read_off,
+                                       int64_t n_reads, uint8_t *len, int64_t *first, int64_t *second);
+/* The same on device buffers, asynchronous on `stream` (after the LCS array exists: the first call builds it and waits):
+ * slot b of d_len / d_first / d_second answers d_bases[b], for the reads d_read_off[0 .. n_reads] (device offsets into
+ * d_bases, total_bases = d_read_off[n_reads] - d_read_off[0]).  The workspace (sbwtgpu_ms_workspace_bytes, 16-byte aligned)
+ * receives the launch's counters, read back by sbwtgpu_ms_workspace_stats: { positions answered, bases walked (warm-up
+ * included), positions with len == k, contractions, contractions that recomputed their interval }. */
+int64_t sbwtgpu_ms_workspace_bytes(int64_t total_bases);
+int  sbwtgpu_matching_statistics_dev(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases,
+                                     const int64_t *d_read_off, int64_t n_reads, uint8_t *d_len, int64_t *d_first,
+                                     int64_t *d_second, void *d_workspace, int64_t workspace_bytes, void *stream);
+int  sbwtgpu_ms_workspace_stats(const void *d_workspace, void *stream, int64_t stats[5]);
+
 #ifdef __cplusplus
 }
 #endif

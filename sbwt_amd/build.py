@@ -44,8 +44,8 @@ def build_gpu(force=False) -> str:
     os.makedirs(LIB, exist_ok=True)
     out = os.path.join(LIB, "libsbwtgpu.so")
     srcs = [os.path.join(CSRC, f) for f in ("sbwt_search.hip", "sbwt_search_fused.hip", "sbwt_api_kernels.hip", "sbwt_derived.hip", "sbwt_build.hip", "sbwt_sort.hip",
-                                            "sbwt_format.hip", "sbwtgpu_capi.cpp")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("sbwt_device.h", "sbwt_kernels_common.h", "sbwt_scan.h", "sbwt_search_fused_loop.inc")] + \
+                                            "sbwt_format.hip", "sbwt_ms.hip", "sbwtgpu_capi.cpp")]
+    deps = srcs + [os.path.join(CSRC, f) for f in ("sbwt_device.h", "sbwt_kernels_common.h", "sbwt_scan.h", "sbwt_ms.h", "sbwt_search_fused_loop.inc")] + \
         [os.path.join(INC, "sbwtgpu.h")]
     if force or _newer(out, deps):
         _run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", out] + srcs + ["-ldl"])

@@ -42,6 +42,8 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_workspace_status", "sbwtgpu_workspace_stats", "sbwtgpu_kernel_times",
     "sbwtgpu_format_text_bound", "sbwtgpu_format_scratch_bytes", "sbwtgpu_format_results_dev",
     "sbwtgpu_search_text_batch", "sbwtgpu_search_text_stream", "sbwtgpu_free_host", "sbwtgpu_release_cached_buffers",
+    "sbwtgpu_index_build_lcs", "sbwtgpu_index_get_lcs", "sbwtgpu_matching_statistics_batch", "sbwtgpu_ms_workspace_bytes",
+    "sbwtgpu_matching_statistics_dev", "sbwtgpu_ms_workspace_stats",
 ]
 
 
@@ -147,6 +149,17 @@ def lib() -> C.CDLL:
     L.sbwtgpu_free_host.argtypes = [vp]
     L.sbwtgpu_free_host.restype = None
     L.sbwtgpu_release_cached_buffers.restype = None
+    try:                                        # (absent from older builds loaded through SBWTGPU_LIB for A/B runs)
+        L.sbwtgpu_index_build_lcs.argtypes = [vp]
+        L.sbwtgpu_index_get_lcs.argtypes = [vp, vp]
+        L.sbwtgpu_matching_statistics_batch.argtypes = [vp, vp, vp, i64, vp, vp, vp]
+        L.sbwtgpu_ms_workspace_bytes.argtypes = [i64]
+        L.sbwtgpu_ms_workspace_bytes.restype = i64
+        L.sbwtgpu_matching_statistics_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp]
+        L.sbwtgpu_ms_workspace_stats.argtypes = [vp, vp, C.POINTER(i64)]
+    except AttributeError:
+        if not os.environ.get("SBWTGPU_LIB"):
+            raise
     _lib = L
     return L
 
@@ -434,6 +447,51 @@ class Index:
         _check(lib().sbwtgpu_workspace_stats(d_ws, stream, st))
         return int(st[5])
 
+    # ---- k-bounded matching statistics (include/sbwtgpu.h) ----
+    def build_lcs(self) -> None:
+        """Builds the LCS array on the device (idempotent; every MS call does it when needed)."""
+        _check(lib().sbwtgpu_index_build_lcs(self._h))
+
+    def lcs(self) -> np.ndarray:
+        """The LCS array: lcs[j] = longest common suffix of the labels of columns j-1 and j ('$' never counts), lcs[0] = 0."""
+        out = np.empty(self.n_nodes, dtype=np.uint8)
+        _check(lib().sbwtgpu_index_get_lcs(self._h, out.ctypes.data))
+        return out
+
+    def matching_statistics(self, bases, read_off, intervals: bool = True):
+        """k-bounded matching statistics of every base: len (uint8), and with intervals=True also first, second (int64)
+        -- slot b answers bases[b] (arrays of read_off[-1] entries).  Returns len, or (len, first, second)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        n = int(read_off[-1]) if len(read_off) else 0
+        ln = np.zeros(n, dtype=np.uint8)
+        first = np.full(n, -12345, dtype=np.int64) if intervals else None
+        second = np.full(n, -12345, dtype=np.int64) if intervals else None
+        _check(lib().sbwtgpu_matching_statistics_batch(self._h, bases.ctypes.data, read_off.ctypes.data, max(len(read_off) - 1, 0),
+                                                       ln.ctypes.data, first.ctypes.data if intervals else None,
+                                                       second.ctypes.data if intervals else None))
+        return (ln, first, second) if intervals else ln
+
+    def matching_statistics_reads(self, reads: Sequence[bytes], intervals: bool = True):
+        """Per-read lists of the batch results of a list of byte strings."""
+        bases, off = concat_reads(reads)
+        res = self.matching_statistics(bases, off, intervals)
+        if not intervals:
+            return [res[off[i]:off[i + 1]] for i in range(len(reads))]
+        return [tuple(a[off[i]:off[i + 1]] for a in res) for i in range(len(reads))]
+
+    def matching_statistics_dev(self, d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_len: int,
+                                d_first: int, d_second: int, d_ws: int, ws_bytes: int, stream: int = 0):
+        """sbwtgpu_matching_statistics_dev (raw device pointers; d_first = d_second = 0: lengths only)."""
+        _check(lib().sbwtgpu_matching_statistics_dev(self._h, d_bases, total_bases, d_read_off, n_reads, d_len,
+                                                     d_first or None, d_second or None, d_ws, ws_bytes, stream))
+
+    def ms_workspace_stats(self, d_ws: int, stream: int = 0) -> dict:
+        """Counters of the last MS launch on a workspace."""
+        st = (C.c_int64 * 5)()
+        _check(lib().sbwtgpu_ms_workspace_stats(d_ws, stream, st))
+        return dict(zip(("positions", "walked", "full", "contractions", "recomputes"), (int(x) for x in st)))
+
     def workspace_status(self, d_ws: int, stream: int = 0) -> int:
         st = C.c_int(0)
         _check(lib().sbwtgpu_workspace_status(d_ws, stream, C.byref(st)))
@@ -450,3 +508,7 @@ def kernel_times() -> list:
 
 def search_workspace_bytes(total_bases: int) -> int:
     return int(lib().sbwtgpu_search_workspace_bytes(total_bases))
+
+
+def ms_workspace_bytes(total_bases: int) -> int:
+    return int(lib().sbwtgpu_ms_workspace_bytes(total_bases))

@@ -437,6 +437,30 @@ public:
                               int64_t *matched) const {
         detail::gpu_check(sbwtgpu_partial_search_batch(need_device(), bases, off, n, first, second, matched));
     }
+    // k-bounded matching statistics (include/sbwtgpu.h): for every base, the length of the longest suffix ending there that
+    // is a suffix of some column label (capped at k; 0 at any byte other than upper-case ACGT) and, optionally, the colex
+    // interval of those labels.  A batch of one, like streaming_search.
+    struct MatchingStatistics { std::vector<uint8_t> len; std::vector<int64_t> first, second; };
+    MatchingStatistics matching_statistics(const std::string &input, bool intervals = true) const {
+        MatchingStatistics ms;
+        const int64_t off[2] = {0, (int64_t)input.size()};
+        ms.len.resize(input.size());
+        if (intervals) { ms.first.resize(input.size()); ms.second.resize(input.size()); }
+        matching_statistics_batch(input.data(), off, 1, ms.len.data(), intervals ? ms.first.data() : nullptr,
+                                  intervals ? ms.second.data() : nullptr);
+        return ms;
+    }
+    // slot b of len / first / second answers bases[b]; first = second = nullptr: lengths only
+    void matching_statistics_batch(const char *bases, const int64_t *read_off, int64_t n_reads, uint8_t *len, int64_t *first,
+                                   int64_t *second) const {
+        detail::gpu_check(sbwtgpu_matching_statistics_batch(need_device(), bases, read_off, n_reads, len, first, second));
+    }
+    // lcs[j]: the longest common suffix of the labels of columns j-1 and j ('$' never counts); lcs[0] = 0
+    std::vector<uint8_t> get_lcs() const {
+        std::vector<uint8_t> out((size_t)n_nodes);
+        detail::gpu_check(sbwtgpu_index_get_lcs(need_device(), out.data()));
+        return out;
+    }
     // SBWT.hh:700-725 / :727-746: the k-mer of a column into buf (k chars, '$' for dummy positions, no NUL).  Both run
     // the same device kernel (select inside the block counts); `ss` is accepted for source compatibility.
     void get_kmer(int64_t colex_rank, char *buf) const {

@@ -3,6 +3,8 @@
 // batches; plus a minimal in-memory `build` so that indexes can be produced without KMC.
 //
 //   sbwt search -o <out> -i <index> -q <query> [-z]        (sbwt_search.cpp:151-157)
+//   sbwt matching-statistics -i <index> -q <query> -o <out> [-z] [--intervals]
+//               k-bounded matching statistics: one line per read, one token per base ("d", or "d,first,second")
 //   sbwt build  -i <in> -o <index> -k <k> [-p <precalc>] [--add-reverse-complements]
 //               [--no-streaming-support] [-t <threads>]      (subset of sbwt_build.cpp:40-55)
 // Extra, GPU-only flags of `search` (defaults keep the reference behaviour and output):
@@ -576,7 +578,106 @@ int build_main(int argc, char **argv) {
     return 0;
 }
 
-const vector<string> commands = {"build", "search"};
+// `sbwt matching-statistics`: the query handling of `search` (FASTA / FASTQ, gzipped, .txt lists of files), one line per
+// read with one token per base, each followed by a space (print_vector's layout): the match length d, or "d,first,second"
+// with --intervals.  Batches go to the GPU one at a time; the text is formatted on the host.
+void append_int(int64_t x, string &out) {
+    char buf[24];
+    int i = 0;
+    if (x == 0) buf[i++] = '0';
+    while (x > 0) { buf[i++] = (char)('0' + x % 10); x /= 10; }
+    while (i > 0) out.push_back(buf[--i]);
+}
+
+int matching_statistics_main(int argc, char **argv) {
+    int64_t micros_start = cur_time_micros();
+    set_log_level(LogLevel::MINOR);
+    Options opts({
+        {"out-file", 'o', true, "Output filename (a list of output files if the query file is a .txt list).", ""},
+        {"index-file", 'i', true, "Index input file.", ""},
+        {"query-file", 'q', true,
+         "The query in FASTA or FASTQ format, possibly gzipped. If the file extension is .txt, this is interpreted as a "
+         "list of query files, one per line, and --out-file as a list of output files.", ""},
+        {"gzip-output", 'z', false, "Writes output in gzipped form.", ""},
+        {"intervals", 0, false, "Print d,first,second (the colex interval of the matched suffix) instead of d.", ""},
+        {"gpu", 0, true, "HIP device to run on.", "0"},
+        {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "67108864"},
+        {"help", 'h', false, "Print usage", ""},
+    });
+    opts.parse(argc, argv);
+    if (argc == 1 || opts.count("help")) {
+        std::cerr << opts.help(argv[0], "k-bounded matching statistics of every base of all input reads.") << std::endl;
+        exit(1);
+    }
+    const string indexfile = opts.get("index-file");
+    check_readable(indexfile);
+    const string queryfile = opts.get("query-file"), outfile = opts.get("out-file");
+    const bool multi_file = queryfile.size() >= 4 && queryfile.substr(queryfile.size() - 4) == ".txt";
+    const vector<string> input_files = multi_file ? readlines(queryfile) : vector<string>{queryfile};
+    const vector<string> output_files = multi_file ? readlines(outfile) : vector<string>{outfile};
+    for (const string &file : input_files) check_readable(file);
+    for (const string &file : output_files) check_writable(file);
+    if (input_files.size() != output_files.size())
+        throw std::runtime_error("Number of input and output files does not match (" + std::to_string(input_files.size()) +
+                                 " vs " + std::to_string(output_files.size()) + ")");
+    const bool gzip_output = opts.count("gzip-output"), intervals = opts.count("intervals");
+    set_default_device(atoi(opts.get("gpu").c_str()));
+    int64_t batch_bases = atoll(opts.get("batch-bases").c_str());
+    if (batch_bases < 1) batch_bases = 1;
+
+    std::ifstream in(indexfile, std::ios::binary);
+    if (!in.good()) throw std::runtime_error("Error opening file: " + indexfile);
+    const string variant = load_string(in);
+    if (variant != "plain-matrix")
+        throw std::runtime_error("Error: only the plain-matrix variant is supported by the GPU search path (got " + variant + ")");
+    plain_matrix_sbwt_t index;
+    index.load(in);
+    int64_t positions = 0;
+    for (size_t f = 0; f < input_files.size(); f++) {
+        write_log("Running matching statistics from input file " + input_files[f] + " to output file " + output_files[f],
+                  LogLevel::MAJOR);
+        seq_io::Reader reader(input_files[f]);
+        seq_io::Buffered_ofstream writer(output_files[f], gzip_output);
+        bool more = true;
+        vector<char> bases;
+        vector<int64_t> read_off;
+        vector<uint8_t> len;
+        vector<int64_t> first, second;
+        string text;
+        while (more) {
+            bases.clear();
+            read_off.assign(1, 0);
+            more = reader.read_batch(bases, read_off, batch_bases);
+            const int64_t n_reads = (int64_t)read_off.size() - 1, total = read_off.back();
+            if (n_reads <= 0) continue;
+            len.resize((size_t)total);
+            if (intervals) { first.resize((size_t)total); second.resize((size_t)total); }
+            index.matching_statistics_batch(bases.data(), read_off.data(), n_reads, len.data(), intervals ? first.data() : nullptr,
+                                            intervals ? second.data() : nullptr);
+            text.clear();
+            for (int64_t r = 0; r < n_reads; r++) {
+                for (int64_t b = read_off[(size_t)r]; b < read_off[(size_t)r + 1]; b++) {
+                    append_int(len[(size_t)b], text);
+                    if (intervals) {
+                        text.push_back(',');
+                        append_int(first[(size_t)b], text);
+                        text.push_back(',');
+                        append_int(second[(size_t)b], text);
+                    }
+                    text.push_back(' ');
+                }
+                text.push_back('\n');
+            }
+            writer.write(text.data(), (int64_t)text.size());
+            positions += total;
+        }
+    }
+    write_log("us/base end-to-end: " + std::to_string((double)(cur_time_micros() - micros_start) / (double)std::max<int64_t>(1, positions)),
+              LogLevel::MAJOR);
+    return 0;
+}
+
+const vector<string> commands = {"build", "search", "matching-statistics"};
 
 void print_help(char **argv) {
     std::cerr << "Available commands: " << std::endl;
@@ -605,6 +706,7 @@ int main(int argc, char **argv) {   // sbwt.cpp:19-57
             fflush(nullptr);
             _exit(rc);
         }
+        else if (command == "matching-statistics") return matching_statistics_main(argc, argv);
         else throw std::runtime_error("Invalid command: " + command);
     } catch (const std::runtime_error &e) {
         std::cerr << "Runtime error: " << e.what() << '\n';

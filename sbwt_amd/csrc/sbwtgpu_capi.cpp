@@ -19,6 +19,7 @@
 
 #include "../../include/sbwtgpu.h"
 #include "sbwt_device.h"
+#include "sbwt_ms.h"
 
 namespace {
 
@@ -159,6 +160,10 @@ struct sbwtgpu_index {
     int device = 0;
     char *blob = nullptr;       // device
     bool owns_blob = true;
+    // the LCS array of matching statistics (sbwt_ms.hip): its own allocation, outside the blob and its byte cap, built on
+    // the first call that needs it (sbwtgpu_index_build_lcs); replicas (adopt / bcast) build their own
+    mutable std::mutex lcs_mu;
+    mutable unsigned char *lcs = nullptr;
     // probe length of the certificate walks: long enough that a random string of that length is almost
     // surely absent (log4(#k-mers) + 4), at least one char longer than the device prefix table
     int probe_len(bool allow_override = true) const {
@@ -758,6 +763,10 @@ void sbwtgpu_index_destroy(sbwtgpu_index *idx) {
     if (idx->blob && idx->owns_blob) {
         DeviceGuard guard(idx->device);
         (void)hipFree(idx->blob);
+    }
+    if (idx->lcs) {
+        DeviceGuard guard(idx->device);
+        (void)hipFree(idx->lcs);
     }
     delete idx;
 }
@@ -2451,6 +2460,153 @@ int sbwtgpu_search_text_batch(const sbwtgpu_index *idx, const char *bases, const
     char *shrunk = (char *)realloc(acc.buf, (size_t)(acc.len ? acc.len : 1));
     *text = shrunk ? shrunk : acc.buf;
     *text_bytes = acc.len;
+    return SBWTGPU_OK;
+}
+
+// ---- matching statistics (sbwt_ms.hip) ------------------------------------------------------------
+namespace {
+int lcs_build_locked(const sbwtgpu_index *idx) {
+    if (idx->lcs) return SBWTGPU_OK;
+    DeviceGuard guard(idx->device);
+    const int64_t n = idx->h.n_nodes;
+    DevBuf scratch;
+    unsigned char *d_lcs = nullptr;
+    // n + 1 entries (lcs[n] = 0), rounded up to whole 64-byte lines: the contraction reads aligned 8-byte words
+    const size_t lcs_bytes = (size_t)((n + 1 + 63) & ~(int64_t)63) + 64;
+    hipError_t e = hipMalloc((void **)&d_lcs, lcs_bytes);
+    if (e == hipSuccess) e = scratch.alloc((size_t)sbwt_lcs_scratch_bytes(n));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (d_lcs) (void)hipFree(d_lcs);
+        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "LCS array: hipMalloc failed: %s",
+                    hipGetErrorString(e));
+    }
+    Stream st;
+    e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMemsetAsync(d_lcs, 0, lcs_bytes, st.s);
+    if (e == hipSuccess) e = hipMemsetAsync(scratch.p, 0, (size_t)sbwt_lcs_scratch_bytes(n), st.s);
+    if (e == hipSuccess) {
+        sbwt_launch_build_lcs(idx->view(), scratch.p, d_lcs, st.s);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st.s);
+    if (e != hipSuccess) {
+        (void)hipFree(d_lcs);
+        return fail(SBWTGPU_ERR_HIP, "LCS build: %s", hipGetErrorString(e));
+    }
+    idx->lcs = d_lcs;
+    return SBWTGPU_OK;
+}
+int lcs_ensure(const sbwtgpu_index *idx) {
+    if (!idx) return fail(SBWTGPU_ERR_INVALID_ARG, "idx is NULL");
+    if (idx->h.rank_only) return fail(SBWTGPU_ERR_INVALID_ARG, "%s", RANK_ONLY_MSG);
+    std::lock_guard<std::mutex> lock(idx->lcs_mu);
+    return lcs_build_locked(idx);
+}
+int ms_check_ptrs(const int64_t *first, const int64_t *second) {
+    if ((first == nullptr) != (second == nullptr)) return fail(SBWTGPU_ERR_INVALID_ARG, "first and second must be both NULL or both non-NULL");
+    return SBWTGPU_OK;
+}
+}  // namespace
+
+int sbwtgpu_index_build_lcs(sbwtgpu_index *idx) { return lcs_ensure(idx); }
+
+int sbwtgpu_index_get_lcs(const sbwtgpu_index *idx, uint8_t *out) {
+    if (!out) return fail(SBWTGPU_ERR_INVALID_ARG, "out is NULL");
+    int rc = lcs_ensure(idx);
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(idx->device);
+    HIP_TRY(hipMemcpy(out, idx->lcs, (size_t)idx->h.n_nodes, hipMemcpyDeviceToHost));
+    return SBWTGPU_OK;
+}
+
+int64_t sbwtgpu_ms_workspace_bytes(int64_t total_bases) {
+    (void)total_bases;
+    return (int64_t)sizeof(SbwtMsWork);
+}
+
+int sbwtgpu_matching_statistics_dev(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases,
+                                    const int64_t *d_read_off, int64_t n_reads, uint8_t *d_len, int64_t *d_first,
+                                    int64_t *d_second, void *d_ws, int64_t ws_bytes, void *stream) {
+    int rc = lcs_ensure(idx);
+    if (rc != SBWTGPU_OK) return rc;
+    if ((rc = ms_check_ptrs(d_first, d_second)) != SBWTGPU_OK) return rc;
+    if (n_reads < 0 || total_bases < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative size");
+    if (total_bases >= ((int64_t)1 << 36))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "more than 2^36 bases in one call: split the batch");
+    if (!d_ws || ws_bytes < sbwtgpu_ms_workspace_bytes(total_bases))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "workspace missing or too small (%lld < %lld)", (long long)ws_bytes,
+                    (long long)sbwtgpu_ms_workspace_bytes(total_bases));
+    if (((uintptr_t)d_ws & 15) != 0) return fail(SBWTGPU_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+    if (n_reads > 0 && !d_read_off) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
+    if (total_bases > 0 && (!d_bases || !d_len)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
+    DeviceGuard guard(idx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(d_ws, 0, sizeof(SbwtMsWork), st));
+    sbwt_launch_ms(idx->view(), idx->lcs, d_bases, total_bases, reinterpret_cast<const long long *>(d_read_off), n_reads,
+                   d_len, reinterpret_cast<long long *>(d_first), reinterpret_cast<long long *>(d_second),
+                   static_cast<SbwtMsWork *>(d_ws), st);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_ms_workspace_stats(const void *d_ws, void *stream, int64_t stats[5]) {
+    if (!d_ws || !stats) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    SbwtMsWork w;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemcpyAsync(&w, d_ws, sizeof(w), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    stats[0] = (int64_t)w.n_out;
+    stats[1] = (int64_t)w.n_walk;
+    stats[2] = (int64_t)w.n_full;
+    stats[3] = (int64_t)w.n_contract;
+    stats[4] = (int64_t)w.n_recompute;
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_matching_statistics_batch(const sbwtgpu_index *idx, const char *bases, const int64_t *read_off,
+                                      int64_t n_reads, uint8_t *len, int64_t *first, int64_t *second) {
+    int rc = lcs_ensure(idx);
+    if (rc != SBWTGPU_OK) return rc;
+    if ((rc = ms_check_ptrs(first, second)) != SBWTGPU_OK) return rc;
+    if (n_reads < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative n_reads");
+    if (n_reads == 0) return SBWTGPU_OK;
+    if (!read_off) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    for (int64_t r = 0; r < n_reads; r++) {
+        const int64_t l = read_off[r + 1] - read_off[r];
+        if (l < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "read_off is not non-decreasing at read %lld", (long long)r);
+        if (l >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_READ_TOO_LONG, "read %lld has >= 2^31 bases", (long long)r);
+    }
+    const int64_t base0 = read_off[0], total = read_off[n_reads] - base0;
+    if (total == 0) return SBWTGPU_OK;
+    if (!bases || !len) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    DeviceGuard guard(idx->device);
+    Stream st;
+    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    // [bases][read_off][len][first][second][workspace], every part 256-byte aligned
+    const size_t o_off = up256((size_t)total + 8), o_len = o_off + up256((size_t)(n_reads + 1) * 8),
+                 o_f = o_len + up256((size_t)total), o_s = o_f + (first ? up256((size_t)total * 8) : 0),
+                 o_ws = o_s + (first ? up256((size_t)total * 8) : 0), bytes = o_ws + (size_t)sbwtgpu_ms_workspace_bytes(total);
+    DevBuf d;
+    HIP_TRY(d.alloc(bytes));
+    char *dv = static_cast<char *>(d.p);
+    std::vector<int64_t> o;
+    try { o.resize((size_t)n_reads + 1); } catch (...) { return fail(SBWTGPU_ERR_OOM, "out of host memory"); }
+    for (int64_t r = 0; r <= n_reads; r++) o[(size_t)r] = read_off[r] - base0;
+    HIP_TRY(hipMemcpyAsync(dv, bases + base0, (size_t)total, hipMemcpyHostToDevice, st.s));
+    HIP_TRY(hipMemcpyAsync(dv + o_off, o.data(), (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st.s));
+    rc = sbwtgpu_matching_statistics_dev(idx, dv, total, reinterpret_cast<const int64_t *>(dv + o_off), n_reads,
+                                         reinterpret_cast<uint8_t *>(dv + o_len), first ? reinterpret_cast<int64_t *>(dv + o_f) : nullptr,
+                                         first ? reinterpret_cast<int64_t *>(dv + o_s) : nullptr, dv + o_ws,
+                                         sbwtgpu_ms_workspace_bytes(total), st.s);
+    if (rc != SBWTGPU_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(len + base0, dv + o_len, (size_t)total, hipMemcpyDeviceToHost, st.s));
+    if (first) {
+        HIP_TRY(hipMemcpyAsync(first + base0, dv + o_f, (size_t)total * 8, hipMemcpyDeviceToHost, st.s));
+        HIP_TRY(hipMemcpyAsync(second + base0, dv + o_s, (size_t)total * 8, hipMemcpyDeviceToHost, st.s));
+    }
+    HIP_TRY(hipStreamSynchronize(st.s));
     return SBWTGPU_OK;
 }
 
