@@ -40,6 +40,8 @@ extern "C" {
 #define SBWTGPU_ERR_NOT_SINGLETON      -7   /* "Bug: k-mer search did not give a singleton interval" (SBWT.hh:410-413) */
 #define SBWTGPU_ERR_OOM                -8
 #define SBWTGPU_ERR_READ_TOO_LONG      -9   /* a single read of >= 2^31 bases */
+#define SBWTGPU_ERR_STALLED           -10   /* the sorted fused search kernel stopped making progress (a bug: the call
+                                               failed instead of hanging the device) */
 
 typedef struct sbwtgpu_index sbwtgpu_index;
 
@@ -276,7 +278,8 @@ int  sbwtgpu_search_encoded_dev(const sbwtgpu_index *idx, int64_t total_bases, c
                                 int64_t n_reads, int64_t *d_out, const int64_t *d_out_off,
                                 void *d_workspace, int64_t workspace_bytes, int streaming, void *stream);
 /* Synchronises `stream`, then reports the status word of the last search on this workspace
- * (0, or SBWTGPU_ERR_NOT_SINGLETON). */
+ * (0; SBWTGPU_ERR_NOT_SINGLETON: a k-mer search did not end on one column; SBWTGPU_ERR_STALLED: a workgroup of the
+ * sorted fused kernel made no progress for 2^20 waits and gave up). */
 int  sbwtgpu_workspace_status(const void *d_workspace, void *stream, int *status);
 /* Synchronises `stream`, then reports the work the last search on this workspace performed:
  * stats[0] streaming one-step extensions, [1] full searches, [2] interval updates executed past the

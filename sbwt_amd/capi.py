@@ -25,6 +25,7 @@ ERR_PRECALC_GT_K = -6
 ERR_NOT_SINGLETON = -7
 ERR_OOM = -8
 ERR_READ_TOO_LONG = -9
+ERR_STALLED = -10
 
 # every symbol include/sbwtgpu.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = [

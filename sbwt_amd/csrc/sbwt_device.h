@@ -145,7 +145,7 @@ static __host__ __device__ inline unsigned sbwt_pf_bits(unsigned long long h) { 
 // Workspace header (first 256 bytes of the search workspace).
 struct SbwtWorkHeader {
     unsigned long long ticket;      // next read to hand out
-    int status;                     // 0 or SBWTGPU_ERR_NOT_SINGLETON
+    int status;                     // 0, SBWTGPU_ERR_NOT_SINGLETON or SBWTGPU_ERR_STALLED
     int rg_sample;                  // reads the check kernel sampled for rg_long (0: ragged batches go the two-pass route)
     // work done by the last search launch (for the roofline's algorithmic-byte accounting)
     unsigned long long n_stream;    // streaming one-step extensions (SBWT.hh:562-575)

@@ -10,6 +10,7 @@ typedef unsigned long long u64;
 typedef long long i64;
 
 #define SBWT_ERR_NOT_SINGLETON (-7)
+#define SBWT_ERR_STALLED (-10)            // the sorted fused kernel's stall detector (SBWTGPU_ERR_STALLED)
 
 // ---------------------------------------------------------------------------------------------
 // small helpers

@@ -362,7 +362,12 @@
                 const unsigned pr = FZ_LDS32(&q_ctl[6]);
                 if (pr != sort_seen) { sort_seen = pr; sort_spins = 0; }
             }
-            if (++sort_spins > (1u << 20)) { if (lane == 0) ws->status = SBWT_ERR_NOT_SINGLETON; break; }
+            if (++sort_spins > (1u << 20)) {
+                // (the status value made where it is stored: a constant of its own would be hoisted out of the loop into one
+                // more vector register)
+                if (lane == 0) { int st_ = SBWT_ERR_STALLED; asm volatile("" : "+v"(st_)); ws->status = st_; }
+                break;
+            }
             FZ_SORT_STAT(12, 1);
             if (sort_spins < 64u) __builtin_amdgcn_s_sleep(8); else __builtin_amdgcn_s_sleep(64);     // (a long wait: longer naps)
             continue;

@@ -33,6 +33,14 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
+// a search's device status word (SbwtWorkHeader::status) as the call's result: a k-mer search that did not end on one column,
+// or the sorted fused kernel's stall detector (a workgroup that made no progress for 2^20 waits)
+static int fail_status(int status) {
+    if (status == SBWTGPU_ERR_STALLED)
+        return fail(SBWTGPU_ERR_STALLED, "Bug: the sorted fused search kernel stalled (no progress in a workgroup)");
+    return fail(SBWTGPU_ERR_NOT_SINGLETON, "Bug: k-mer search did not give a singleton interval");
+}
+
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
         hipError_t e_ = (expr);                                                                \
@@ -1553,7 +1561,7 @@ static int search_host_pipelined(const sbwtgpu_index *idx, const char *src_bases
             rc = fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "pipeline buffers: %s", hipGetErrorString(e));
     }
     if (rc != SBWTGPU_OK) { (void)hipGetLastError(); cleanup(); return rc; }
-    bool bug = false;
+    int bug = 0;                    // the first nonzero device status of a chunk
     struct Carve { char *bases; int64_t *roff, *ooff, *out; char *ws; };
     auto carve = [&](PipeSlot &P) {
         Carve c;
@@ -1593,7 +1601,7 @@ static int search_host_pipelined(const sbwtgpu_index *idx, const char *src_bases
         PipeSlot &P = S[c & 1];
         hipError_t e = hipStreamSynchronize(P.st);
         if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "stream synchronize: %s", hipGetErrorString(e));
-        if (P.h_status[0] != 0) bug = true;
+        if (P.h_status[0] != 0 && bug == 0) bug = P.h_status[0];
         const int64_t lo = cuts[(size_t)c], hi = cuts[(size_t)c + 1];
         if (!pin_out) parallel_memcpy(out32 ? (char *)(out32 + oo[lo]) : (char *)(out + oo[lo]), P.h_out, (size_t)((oo[hi] - oo[lo]) * vb));
         return SBWTGPU_OK;
@@ -1616,7 +1624,7 @@ static int search_host_pipelined(const sbwtgpu_index *idx, const char *src_bases
         pp.s[1] = S[1];
         g_pipe_parked.push_back(pp);
     }
-    if (bug) return fail(SBWTGPU_ERR_NOT_SINGLETON, "Bug: k-mer search did not give a singleton interval");
+    if (bug) return fail_status(bug);
     return SBWTGPU_OK;
 }
 
@@ -1692,8 +1700,8 @@ static int search_host_common(const sbwtgpu_index *idx, const char *bases, const
             HIP_TRY(hipMemcpyAsync(sl->host + o_out, sl->dev + o_out, back, hipMemcpyDeviceToHost, sl->stream));
             HIP_TRY(hipStreamSynchronize(sl->stream));
             memcpy(out + out0, sl->host + o_out, (size_t)n_out * 8);
-            if (reinterpret_cast<const SbwtWorkHeader *>(sl->host + o_ws)->status != 0)
-                return fail(SBWTGPU_ERR_NOT_SINGLETON, "Bug: k-mer search did not give a singleton interval");
+            const int status = reinterpret_cast<const SbwtWorkHeader *>(sl->host + o_ws)->status;
+            if (status != 0) return fail_status(status);
             return SBWTGPU_OK;
         }
     }
@@ -1715,8 +1723,7 @@ static int search_host_common(const sbwtgpu_index *idx, const char *bases, const
     SbwtWorkHeader hdr;
     HIP_TRY(hipMemcpyAsync(&hdr, d_ws.p, sizeof(hdr), hipMemcpyDeviceToHost, st.s));
     HIP_TRY(hipStreamSynchronize(st.s));
-    if (hdr.status != 0)
-        return fail(SBWTGPU_ERR_NOT_SINGLETON, "Bug: k-mer search did not give a singleton interval");
+    if (hdr.status != 0) return fail_status(hdr.status);
     return SBWTGPU_OK;
 }
 
@@ -2326,7 +2333,7 @@ int sbwtgpu_search_text_stream(const sbwtgpu_index *idx, const char *bases, cons
         S.d_scr = p;
     }
     int64_t total_queries = 0;
-    bool bug = false;
+    int bug = 0;                    // the first nonzero device status of a chunk
     // enqueue everything of chunk c on its slot's stream up to the copy of the text length
     auto submit = [&](int64_t c) -> int {
         Slot &S = slots[c % n_slots];
@@ -2394,7 +2401,7 @@ int sbwtgpu_search_text_stream(const sbwtgpu_index *idx, const char *bases, cons
         hipError_t e = hipStreamSynchronize(S.st);
         if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "stream synchronize: %s", hipGetErrorString(e));
         S.text_len = S.h_total[0];
-        if ((int)(S.h_total[1] & 0xffffffff) != 0) bug = true;
+        if ((int)(S.h_total[1] & 0xffffffff) != 0 && bug == 0) bug = (int)(S.h_total[1] & 0xffffffff);
         if (S.text_len < 0 || S.text_len > S.cap_text) return fail(SBWTGPU_ERR_HIP, "formatted text overflows its bound");
         e = hipMemcpyAsync(S.h_text, S.d_text, (size_t)S.text_len, hipMemcpyDeviceToHost, S.st);
         if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
@@ -2425,7 +2432,7 @@ int sbwtgpu_search_text_stream(const sbwtgpu_index *idx, const char *bases, cons
         return rc;
     }
     for (int s2 = 0; s2 < n_slots; s2++) park(idx->device, slots[s2]);
-    if (bug) return fail(SBWTGPU_ERR_NOT_SINGLETON, "Bug: k-mer search did not give a singleton interval");
+    if (bug) return fail_status(bug);
     if (n_queries) *n_queries = total_queries;
     return SBWTGPU_OK;
 }

@@ -924,7 +924,7 @@ def _search_dev(idx, bases, off, k, streaming):
     d_oo = torch.from_numpy(oo).to(dev)
     d_out = torch.full((int(oo[-1]),), -7, dtype=torch.int64, device=dev)
     wsb = capi.search_workspace_bytes(d_b.numel())
-    d_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    d_ws = torch.zeros(wsb, dtype=torch.uint8, device=dev)      # (a zeroed hint word: the kernel choice does not depend on recycled memory)
     idx.streaming_search_dev(d_b.data_ptr(), d_b.numel(), d_ro.data_ptr(), len(off) - 1, d_out.data_ptr(), d_oo.data_ptr(),
                              d_ws.data_ptr(), wsb, torch.cuda.current_stream().cuda_stream, streaming)
     torch.cuda.synchronize()

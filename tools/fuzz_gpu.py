@@ -24,7 +24,7 @@ def dev_i32(idx, bases, off, k, streaming):
         return np.zeros(0, dtype=np.int64)
     d_b, d_ro, d_oo = torch.from_numpy(np.ascontiguousarray(bases)).to(dev), torch.from_numpy(off).to(dev), torch.from_numpy(ooff).to(dev)
     wsb = capi.search_workspace_bytes(d_b.numel())
-    d_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    d_ws = torch.zeros(wsb, dtype=torch.uint8, device=dev)       # (a zeroed hint word: the kernel choice does not depend on recycled memory)
     d32 = torch.full((int(ooff[-1]),), -99, dtype=torch.int32, device=dev)
     idx.streaming_search_dev_i32(d_b.data_ptr(), d_b.numel(), d_ro.data_ptr(), len(off) - 1, d32.data_ptr(), d_oo.data_ptr(),
                                  d_ws.data_ptr(), wsb, torch.cuda.current_stream().cuda_stream, streaming)
