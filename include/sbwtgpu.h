@@ -107,7 +107,8 @@ int         sbwtgpu_device_count(int *count);
  *                     the device so that the per-k-mer search loop can use streaming steps internally
  *   "debug"           kernel experiment bits (0 = product behaviour); fused kernel: 32 = no anchors / seeds / resumed compares,
  *                     64 = the k > 31 walk (F_CMP) for every k
- *   "poison_results"  1: every search first fills its result range with 0xA5 (parity tests)
+ *   "poison_results"  1: every search first fills its result range with 0xA5, every matching-statistics call its len range
+ *                        with 0xFF and its interval range with 0xA5 (parity tests)
  *   "trans_ext", "trans_wide"   accepted and ignored (round-2 table formats)
  * Read when an index is CREATED (derived acceleration structures inside the device image; environment
  * variables of the same meaning: SBWTGPU_SPARSE_PRECALC, SBWTGPU_PROBE_FILTER, SBWTGPU_PATH_ORDER):

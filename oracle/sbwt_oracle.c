@@ -524,27 +524,28 @@ double orc_batch_search(const orc_index *idx, const char *bases, const int64_t *
     return mx;
 }
 
+/* get_kmer's step backward (SBWT.hh:707-721): the last character of column v's label ('$' at the root) and the column it
+ * is entered from */
+static char kmer_step_back(const orc_index *idx, int64_t *v) {
+    const int64_t n = idx->n_nodes;
+    if (*v == 0) return '$';
+    int64_t char_idx = 0;
+    while (char_idx + 1 < 4 && *v >= idx->C[char_idx + 1]) char_idx++;
+    const char c = IDX_TO_DNA[char_idx];
+    const int64_t char_rel_rank = *v - idx->C[char_idx];
+    int64_t p = 0, step = n;
+    while (step > 0) {
+        while (p + step <= n && orc_rank(idx, p + step, c) <= char_rel_rank) p += step;
+        step /= 2;
+    }
+    *v = p;
+    return c;
+}
+
 /* SBWT::get_kmer, SBWT.hh:700-725: the k-mer of column colex_rank, spelled backwards one incoming edge at a
  * time; the step backward is the reference's own galloping search on rank() (:713-720).  buf gets k chars, no NUL. */
 void orc_get_kmer(const orc_index *idx, int64_t colex_rank, char *buf) {
-    const int64_t k = idx->k, n = idx->n_nodes;
-    for (int64_t i = 0; i < k; i++) {
-        if (colex_rank == 0) {
-            buf[k - 1 - i] = '$';
-        } else {
-            int64_t char_idx = 0;
-            while (char_idx + 1 < 4 && colex_rank >= idx->C[char_idx + 1]) char_idx++;
-            char c = IDX_TO_DNA[char_idx];
-            buf[k - 1 - i] = c;
-            int64_t char_rel_rank = colex_rank - idx->C[char_idx];
-            int64_t p = 0, step = n;
-            while (step > 0) {
-                while (p + step <= n && orc_rank(idx, p + step, c) <= char_rel_rank) p += step;
-                step /= 2;
-            }
-            colex_rank = p;
-        }
-    }
+    for (int64_t i = 0; i < idx->k; i++) buf[idx->k - 1 - i] = kmer_step_back(idx, &colex_rank);
 }
 
 /* SubsetMatrixSelectSupport::select(pos, c), SubsetMatrixSelectSupport.hh:27-33 with sdsl select_1 semantics
@@ -692,4 +693,126 @@ double orc_search_file(const orc_index *idx, const char *query_path, const char 
     if (n_kmers_out) *n_kmers_out = n_kmers;
     if (query_secs) *query_secs = qsecs;
     return ok ? now_sec() - t0 : -1.0;
+}
+
+/* ------------------------------------------------------------------------- */
+/* Matching statistics and the LCS array, by their definitions                 */
+/* ------------------------------------------------------------------------- */
+/* Definition-level checkers for the device's matching statistics and LCS array.  The reference has
+ * no matching statistics: these are not restatements of its code.  They use update_interval from [0, n-1] and get_kmer's
+ * backward step only -- no LCS array, no contraction, nothing of the device algorithm. */
+
+/* interval of the d upper-case ACGT bases at s from [0, n-1]; the first precalc_k of them from the precalc table */
+static void ms_interval(const orc_index *idx, const char *s, int64_t d, int64_t *first, int64_t *second) {
+    const int64_t pk = idx->precalc_k;
+    if (pk > 0 && d >= pk) {
+        uint64_t data = 0;                        /* the layout of orc_do_precalc: prefix[i] = bits 2i .. 2i+1 */
+        for (int64_t i = pk - 1; i >= 0; i--) data = (data << 2) | (uint64_t)dna_to_idx(s[i]);
+        *first = idx->precalc[2 * data];
+        *second = idx->precalc[2 * data + 1];
+        update_interval(idx, s + pk, d - pk, first, second, NULL);
+    } else {
+        *first = 0;
+        *second = idx->n_nodes - 1;
+        update_interval(idx, s, d, first, second, NULL);
+    }
+}
+
+static void ms_read(const orc_index *idx, const char *s, int64_t len, uint8_t *out_len, int64_t *first, int64_t *second,
+                    int exhaustive) {
+    const int64_t k = idx->k, n = idx->n_nodes;
+    int64_t run = 0, prev = 0;
+    for (int64_t i = 0; i < len; i++) {
+        int64_t d = 0, f = 0, g = n - 1;
+        if (dna_to_idx(s[i]) < 0) {
+            run = 0;
+        } else {
+            run++;
+            d = run < k ? run : k;
+            /* labels are closed under substrings, so len[i] <= len[i-1] + 1 */
+            if (!exhaustive && prev + 1 < d) d = prev + 1;
+            for (; d > 0; d--) {
+                ms_interval(idx, s + i - d + 1, d, &f, &g);
+                if (f >= 0) break;
+            }
+            if (d == 0) { f = 0; g = n - 1; }
+        }
+        out_len[i] = (uint8_t)d;
+        if (first) { first[i] = f; second[i] = g; }
+        prev = d;
+    }
+}
+
+typedef struct {
+    const orc_index *idx; const char *bases; const int64_t *read_off; int64_t r0, r1;
+    uint8_t *len; int64_t *first, *second; int exhaustive; double secs;
+} ms_job;
+
+static void *ms_worker(void *arg) {
+    ms_job *jb = (ms_job *)arg;
+    double t0 = now_sec();
+    for (int64_t r = jb->r0; r < jb->r1; r++) {
+        const int64_t a = jb->read_off[r];
+        ms_read(jb->idx, jb->bases + a, jb->read_off[r + 1] - a, jb->len + a, jb->first ? jb->first + a : NULL,
+                jb->second ? jb->second + a : NULL, jb->exhaustive);
+    }
+    jb->secs = now_sec() - t0;
+    return NULL;
+}
+
+double orc_matching_statistics(const orc_index *idx, const char *bases, const int64_t *read_off, int64_t n_reads,
+                               uint8_t *len, int64_t *first, int64_t *second, int n_threads, int exhaustive) {
+    if (n_threads < 1) n_threads = 1;
+    if (n_threads > 256) n_threads = 256;
+    pthread_t th[256];
+    ms_job jobs[256];
+    /* threads over contiguous read ranges of about equal bases (a few long reads must not all land on one thread) */
+    const int64_t b0 = n_reads > 0 ? read_off[0] : 0, tot = n_reads > 0 ? read_off[n_reads] - b0 : 0;
+    int64_t r = 0;
+    for (int t = 0; t < n_threads; t++) {
+        const int64_t r0 = r, goal = b0 + tot * (t + 1) / n_threads;
+        while (r < n_reads && (t == n_threads - 1 || read_off[r + 1] <= goal)) r++;
+        jobs[t] = (ms_job){idx, bases, read_off, r0, r, len, first, second, exhaustive, 0.0};
+        pthread_create(&th[t], NULL, ms_worker, &jobs[t]);
+    }
+    double mx = 0;
+    for (int t = 0; t < n_threads; t++) {
+        pthread_join(th[t], NULL);
+        if (jobs[t].secs > mx) mx = jobs[t].secs;
+    }
+    return mx;
+}
+
+typedef struct { const orc_index *idx; const int64_t *cols; int64_t i0, i1; uint8_t *out; } lcs_job;
+
+static void *lcs_worker(void *arg) {
+    lcs_job *jb = (lcs_job *)arg;
+    const int64_t k = jb->idx->k;
+    for (int64_t i = jb->i0; i < jb->i1; i++) {
+        const int64_t j = jb->cols[i];
+        int64_t d = 0;
+        if (j > 0 && j < jb->idx->n_nodes) {
+            /* the labels of j-1 and j read from their right ends, as far as they agree ('$' never counts) */
+            int64_t a = j - 1, b = j;
+            while (d < k) {
+                const char ca = kmer_step_back(jb->idx, &a), cb = kmer_step_back(jb->idx, &b);
+                if (ca == '$' || ca != cb) break;
+                d++;
+            }
+        }
+        jb->out[i] = (uint8_t)d;
+    }
+    return NULL;
+}
+
+void orc_lcs(const orc_index *idx, const int64_t *cols, int64_t m, uint8_t *out, int n_threads) {
+    if (n_threads < 1) n_threads = 1;
+    if (n_threads > 256) n_threads = 256;
+    pthread_t th[256];
+    lcs_job jobs[256];
+    for (int t = 0; t < n_threads; t++) {
+        jobs[t] = (lcs_job){idx, cols, m * t / n_threads, m * (t + 1) / n_threads, out};
+        pthread_create(&th[t], NULL, lcs_worker, &jobs[t]);
+    }
+    for (int t = 0; t < n_threads; t++) pthread_join(th[t], NULL);
 }

@@ -121,6 +121,19 @@ int64_t orc_select(const orc_index *idx, int64_t j, char c);
 double orc_batch_rank(const orc_index *idx, const int64_t *pos, const char *sym, int64_t n, int64_t *out,
                       int n_threads);
 
+/* ---- definition-level checkers of the device's matching statistics and LCS array ----
+ * Not restatements of reference code: the reference has no matching statistics.  They rely on update_interval from
+ * [0, n-1] and get_kmer's backward step alone -- no LCS array, no contraction, nothing of the device algorithm. */
+/* Per base b of reads [0, n_reads) (bases[read_off[r] .. read_off[r+1])): len[b] = the largest d <= min(k, run of upper-case
+ * ACGT ending at b) such that the last d bases have a non-empty interval from [0, n-1]; that interval is (first[b], second[b]),
+ * (0, n-1) when len[b] == 0.  The search starts at min(k, run, len[b-1] + 1) (labels are closed under substrings), or at
+ * min(k, run) when `exhaustive`.  first/second may be NULL.  n_threads pthreads over contiguous read ranges; returns the
+ * slowest thread's time (seconds). */
+double orc_matching_statistics(const orc_index *idx, const char *bases, const int64_t *read_off, int64_t n_reads,
+                               uint8_t *len, int64_t *first, int64_t *second, int n_threads, int exhaustive);
+/* out[i] = the longest common suffix of get_kmer(cols[i] - 1) and get_kmer(cols[i]), '$' never counting; 0 for column 0. */
+void orc_lcs(const orc_index *idx, const int64_t *cols, int64_t m, uint8_t *out, int n_threads);
+
 /* Work accounting for the roofline's algorithmic bytes: replays the reference algorithm on
  * the batch and counts (a) streaming one-step extensions taken, (b) full search() calls,
  * (c) LF steps (interval updates actually executed inside update_sbwt_interval). */

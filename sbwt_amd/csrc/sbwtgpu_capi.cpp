@@ -113,8 +113,8 @@ static int g_fused_sort = [] { const char *e = getenv("SBWTGPU_FUSED_SORT"); ret
 static thread_local int t_out32 = 0;
 static int64_t g_ev_count = 0;
 // depth of the sparse (hashed) prefix table built at index creation (capped at k and at 31 = one 62-bit key)
-// debug aid for the parity tests: fill the result range with a poison pattern before every search, so that a
-// result the kernel never writes cannot inherit a correct value from an earlier launch
+// debug aid for the parity tests: fill the result range with a poison pattern before every search and every
+// matching-statistics call, so that a result the kernel never writes cannot inherit a correct value from an earlier launch
 static int g_poison = [] { const char *e = getenv("SBWTGPU_POISON_RESULTS"); return e ? atoi(e) : 0; }();
 static int g_probe_filter = [] { const char *e = getenv("SBWTGPU_PROBE_FILTER"); return e ? atoi(e) : 1; }();
 static int g_image_level = [] { const char *e = getenv("SBWTGPU_IMAGE_LEVEL"); return e ? atoi(e) : 0; }();
@@ -2550,6 +2550,17 @@ int sbwtgpu_matching_statistics_dev(const sbwtgpu_index *idx, const char *d_base
     DeviceGuard guard(idx->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_TRY(hipMemsetAsync(d_ws, 0, sizeof(SbwtMsWork), st));
+    if (g_poison && n_reads > 0 && total_bases > 0) {
+        // len 0xFF is above every k, so a slot the kernel skips cannot pass for an answer
+        int64_t b0 = 0;
+        HIP_TRY(hipMemcpyAsync(&b0, d_read_off, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemsetAsync(d_len + b0, 0xFF, (size_t)total_bases, st));
+        if (d_first) {
+            HIP_TRY(hipMemsetAsync(d_first + b0, 0xA5, (size_t)total_bases * 8, st));
+            HIP_TRY(hipMemsetAsync(d_second + b0, 0xA5, (size_t)total_bases * 8, st));
+        }
+    }
     sbwt_launch_ms(idx->view(), idx->lcs, d_bases, total_bases, reinterpret_cast<const long long *>(d_read_off), n_reads,
                    d_len, reinterpret_cast<long long *>(d_first), reinterpret_cast<long long *>(d_second),
                    static_cast<SbwtMsWork *>(d_ws), st);

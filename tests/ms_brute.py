@@ -58,6 +58,26 @@ class BruteMS:
         return L, F, S
 
 
+def probe_reads(seqs, k, rng):
+    """Exact substrings, substitutions, N / lower case / NUL / other bytes, short and empty reads, low complexity."""
+    reads = []
+    for s in seqs:
+        reads.append(s.encode())
+        a = rng.randrange(0, max(1, len(s) - 5))
+        reads.append(s[a:a + rng.randint(1, 3 * k + 5)].encode())
+        m = bytearray(s.encode())
+        for _ in range(max(1, len(m) // 10)):
+            m[rng.randrange(len(m))] = ord(rng.choice("ACGT"))
+        reads.append(bytes(m))
+    m = bytearray(seqs[0].encode())
+    for j, ch in enumerate(b"NacgtN\x00\xff$Z"):
+        if len(m):
+            m[(7 * j + 3) % len(m)] = ch
+    reads += [bytes(m), b"", b"A", b"AC"[: max(0, k - 1)], b"A" * (3 * k + 7), b"AC" * (2 * k + 3), b"ACGTTGCA" * 9,
+              b"N" * 5, b"\x00ACGT\x00", "".join(rng.choice("ACGT") for _ in range(4 * k + 20)).encode(), b""]
+    return reads
+
+
 def format_ms(lens, first=None, second=None) -> bytes:
     """The CLI's line for one read: one token per base, each followed by a space, then a newline."""
     if first is None:

@@ -2,6 +2,10 @@
 
 TEST INFRASTRUCTURE ONLY.  Imported by tests/, __graft_entry__.smoke() and the cpu_baseline leg
 of bench.py; never by anything under sbwt_amd/.
+
+matching_statistics() and lcs() are definition-level checkers of the device's matching statistics and LCS array, not
+restatements of reference code (the reference has no matching statistics): update_interval from [0, n-1] per candidate
+length, and the labels' characters read back one step at a time.
 """
 from __future__ import annotations
 
@@ -84,6 +88,10 @@ def lib() -> C.CDLL:
     L.orc_select.argtypes = [P, i64, C.c_char]
     L.orc_batch_rank.restype = C.c_double
     L.orc_batch_rank.argtypes = [P, vp, vp, i64, vp, C.c_int]
+    L.orc_matching_statistics.restype = C.c_double
+    L.orc_matching_statistics.argtypes = [P, vp, vp, i64, vp, vp, vp, C.c_int, C.c_int]
+    L.orc_lcs.restype = None
+    L.orc_lcs.argtypes = [P, vp, i64, vp, C.c_int]
     L.orc_count_work.restype = None
     L.orc_count_work.argtypes = [P, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     _lib = L
@@ -226,6 +234,30 @@ class OracleIndex:
         out = np.full(len(pos), -3, dtype=np.int64)
         secs = lib().orc_batch_rank(self._p, pos.ctypes.data, sym.ctypes.data, len(pos), out.ctypes.data, n_threads)
         return out, secs
+
+    def matching_statistics(self, bases: np.ndarray, read_off: np.ndarray, n_threads: int = 1, exhaustive: bool = False,
+                            intervals: bool = True):
+        """(len, first, second) -- or len alone -- of every base of the reads, slot b answering bases[b] (slots outside
+        [read_off[0], read_off[-1]) are 0 / -3), and the slowest thread's seconds: (..., seconds)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        n = int(read_off[-1]) if len(read_off) else 0
+        assert len(bases) >= n
+        ln = np.zeros(n, dtype=np.uint8)
+        first = np.full(n, -3, dtype=np.int64) if intervals else None
+        second = np.full(n, -3, dtype=np.int64) if intervals else None
+        secs = lib().orc_matching_statistics(self._p, bases.ctypes.data, read_off.ctypes.data, max(len(read_off) - 1, 0),
+                                             ln.ctypes.data, first.ctypes.data if intervals else None,
+                                             second.ctypes.data if intervals else None, n_threads, int(exhaustive))
+        return ((ln, first, second) if intervals else (ln,)) + (secs,)
+
+    def lcs(self, cols=None, n_threads: int = 1) -> np.ndarray:
+        """LCS of the labels of columns j-1 and j for every j of `cols` (all columns when None)."""
+        cols = np.arange(self.n_nodes, dtype=np.int64) if cols is None else np.ascontiguousarray(cols, dtype=np.int64)
+        assert ((cols >= 0) & (cols < self.n_nodes)).all()
+        out = np.zeros(len(cols), dtype=np.uint8)
+        lib().orc_lcs(self._p, cols.ctypes.data, len(cols), out.ctypes.data, n_threads)
+        return out
 
     def count_work(self, bases: np.ndarray, read_off: np.ndarray):
         bases = np.ascontiguousarray(bases, dtype=np.uint8)

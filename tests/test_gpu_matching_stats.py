@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from bruteforce import BruteSBWT, int_to_words
-from ms_brute import BruteMS, format_ms, lcs_array
+from ms_brute import BruteMS, format_ms, lcs_array, probe_reads
 from oracle import OracleIndex
 from sbwt_amd import capi, hostlib, synth
 
@@ -33,26 +33,6 @@ def make_index(seqs, k, rc=False, ssup=True):
     bits = hostlib.build_bits([s.encode() if isinstance(s, str) else s for s in seqs], k, rc, ssup)
     return bits, capi.Index.create(bits.cols[0], bits.cols[1], bits.cols[2], bits.cols[3], bits.ssup, bits.n_nodes, k,
                                    bits.n_kmers, 0)
-
-
-def probe_reads(seqs, k, rng):
-    """Exact substrings, substitutions, N / lower case / NUL / other bytes, short and empty reads, low complexity."""
-    reads = []
-    for s in seqs:
-        reads.append(s.encode())
-        a = rng.randrange(0, max(1, len(s) - 5))
-        reads.append(s[a:a + rng.randint(1, 3 * k + 5)].encode())
-        m = bytearray(s.encode())
-        for _ in range(max(1, len(m) // 10)):
-            m[rng.randrange(len(m))] = ord(rng.choice("ACGT"))
-        reads.append(bytes(m))
-    m = bytearray(seqs[0].encode())
-    for j, ch in enumerate(b"NacgtN\x00\xff$Z"):
-        if len(m):
-            m[(7 * j + 3) % len(m)] = ch
-    reads += [bytes(m), b"", b"A", b"AC"[: max(0, k - 1)], b"A" * (3 * k + 7), b"AC" * (2 * k + 3), b"ACGTTGCA" * 9,
-              b"N" * 5, b"\x00ACGT\x00", "".join(rng.choice("ACGT") for _ in range(4 * k + 20)).encode(), b""]
-    return reads
 
 
 def check_against_brute(idx, B, reads, label):

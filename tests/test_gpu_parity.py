@@ -339,7 +339,9 @@ def test_search_on_indexes_of_more_than_2_pow_30_and_2_pow_31_columns(gpu, L, k)
     (level 0).  streaming_search and search of reads from all over the sequence (substitutions, N, lower case) on every route
     against each other and, on a sample, against the oracle; int32 results refused beyond 2^31 columns.
     Round 6: k = 32 at 2.25 x 10^9 columns -- 31 < k <= 63 gets the full image there too (the second-level table without flags in
-    bit 31: position + 1, a lookup goes on past a full bucket), read by the fused kernel's WIDE + BIG instantiation."""
+    bit 31: position + 1, a lookup goes on past a full bucket), read by the fused kernel's WIDE + BIG instantiation.
+    Matching statistics of the same reads (k_lcs_pred and k_ms with MEGA ranks beyond 2^31 columns) against the oracle's
+    definition-level MS on 700 reads, and the LCS array at 20 k columns (windows around 2^30 and 2^31 among them)."""
     import torch
     if torch.cuda.mem_get_info()[1] < (250 << 30):
         pytest.skip("needs a GPU with 288 GB: the image of 2.25e9 columns is 130 GB, its builders' scratch as much again")
@@ -388,6 +390,18 @@ def test_search_on_indexes_of_more_than_2_pow_30_and_2_pow_31_columns(gpu, L, k)
     assert np.array_equal(mixed, ref_mixed)
     assert np.array_equal(_search_dev(idx, b2, o2, k, True), ref_mixed)
     assert text == b"".join(print_vector(ref_mixed[oo2[r]:oo2[r + 1]]) for r in range(len(o2) - 1))
+    # matching statistics of the same reads: the LCS array (MEGA ranks in k_lcs_pred beyond 2^31 columns) and k_ms;
+    # the LCS is kept only at sampled columns -- 20 k, with windows around 2^30, 2^31 (the mega boundary) and the ends
+    ms_len, ms_first, ms_second = idx.matching_statistics(bases, off)
+    assert np.array_equal(idx.matching_statistics(bases, off, intervals=False), ms_len)
+    free_b, total_b = torch.cuda.mem_get_info()
+    print("n = %d: device memory free after the LCS build %.1f of %.1f GiB" % (bits.n_nodes, free_b / 2**30, total_b / 2**30))
+    n = bits.n_nodes
+    rng = np.random.default_rng(9)
+    lcs_cols = np.concatenate([rng.integers(0, n, size=14_000)] +
+                              [np.arange(max(0, c - 1000), min(n, c + 1000)) for c in (0, 1 << 30, 1 << 31, n)])
+    lcs_cols = np.unique(lcs_cols)
+    lcs_got = idx.lcs()[lcs_cols]
     idx.close()
     del genome
     orc = OracleIndex.from_bits(bits.cols[0], bits.cols[1], bits.cols[2], bits.cols[3], bits.ssup, bits.n_nodes, k, bits.n_kmers, 8)
@@ -397,6 +411,18 @@ def test_search_on_indexes_of_more_than_2_pow_30_and_2_pow_31_columns(gpu, L, k)
     assert np.array_equal(got2[:len(want)], oracle_batch(orc, bases[:off[sample]], off[:sample + 1], False))
     assert 0.6 < (got >= 0).mean() < 0.85
     assert (got >= (1 << 31)).any() == big and (got >= (1 << 30)).any()
+    import bench
+    nt = max(1, min(16, bench.effective_cores()))
+    ms_want = orc.matching_statistics(bases, off[:sample + 1], n_threads=nt)
+    m = int(off[sample])
+    assert np.array_equal(ms_len[:m], ms_want[0]) and np.array_equal(ms_first[:m], ms_want[1])
+    assert np.array_equal(ms_second[:m], ms_want[2])
+    # len == k exactly where search() found the k-mer ending there (every read is 150 bases; not streaming_search, which
+    # takes lower case, SBWT.hh:544-581)
+    kmer_hit = (got2.reshape(len(off) - 1, 151 - k) >= 0)
+    assert np.array_equal((ms_len.reshape(len(off) - 1, 150) == k)[:, k - 1:], kmer_hit)
+    assert np.array_equal(lcs_got, orc.lcs(lcs_cols, n_threads=nt))
+    assert (ms_second >= (1 << 31)).any() == big and (ms_first >= (1 << 30)).any()
 
 
 def test_device_side_print_vector(gpu, genome_case):
