@@ -133,7 +133,10 @@ int         sbwtgpu_device_count(int *count);
  *                     with SBWTGPU_ERR_OOM if level 2 is still larger); it also steps down by itself when device
  *                     memory runs out.  SBWTGPU_MAX_IMAGE_BYTES.
  *   "force_mega"      1: rank-only images (arbitrary bit vectors) store their block counts relative to a 64-bit base as
- *                     images whose counts pass 2^32 do (tests of that layout at small sizes); default 0
+ *                     images whose counts pass 2^32 do (tests of that layout at small sizes); default 0.  It changes RANK-ONLY
+ *                     images only: the image of an SBWT (n_nodes - 1 set bits: everything but rank() is served) is the same
+ *                     with and without it, and its counts are relative only from 2^31 columns on.  That layout is tested on
+ *                     small SBWTs by a build with small mega blocks instead (-DSBWT_MEGA_SHIFT=12, sbwt_device.h).
  *   "sort_reads"      1: the path-order kernels take the reads in the order of their first k-mer's path position (a lookup
  *                     and a radix sort per batch inside the caller's workspace; pays only when nothing upstream orders the
  *                     reads and the index is large); default off (SBWTGPU_SORT_READS)

@@ -2,6 +2,8 @@
 snapshot; they are git-ignored).
 
   sbwt_amd/lib/libsbwtgpu.so   HIP kernels + C ABI (include/sbwtgpu.h), hipcc --offload-arch=gfx950
+  sbwt_amd/lib/libsbwtgpu_mega12.so  the same sources with -DSBWT_MEGA_SHIFT=12: a TEST build whose mega blocks hold 4096
+                               columns, so that a 250 k-column index spans 60 of them (tests/test_gpu_mega_small.py)
   sbwt_amd/lib/libsbwthost.so  GPU-free host helpers (include/sbwthost.h), g++
   sbwt_amd/bin/sbwt            the `sbwt search|build` CLI (C++ host mirror), g++ linked to libsbwtgpu.so
   oracle/liboracle.so          the CPU oracle (test infrastructure), gcc
@@ -40,16 +42,47 @@ def _glob(d, exts):
     return [os.path.join(d, f) for f in sorted(os.listdir(d)) if f.endswith(exts)]
 
 
+GPU_SRCS = [os.path.join(CSRC, f) for f in ("sbwt_search.hip", "sbwt_search_fused.hip", "sbwt_api_kernels.hip", "sbwt_derived.hip", "sbwt_build.hip", "sbwt_sort.hip",
+                                              "sbwt_format.hip", "sbwt_ms.hip", "sbwtgpu_capi.cpp")]
+GPU_DEPS = GPU_SRCS + [os.path.join(CSRC, f) for f in ("sbwt_device.h", "sbwt_kernels_common.h", "sbwt_scan.h", "sbwt_ms.h", "sbwt_search_fused_loop.inc")] + \
+    [os.path.join(INC, "sbwtgpu.h")]
+MEGA_TEST_SHIFT = 12
+MEGA_TEST_LIB = os.path.join(LIB, "libsbwtgpu_mega%d.so" % MEGA_TEST_SHIFT)
+
+
+def _hipcc_cmd(out, defines=()):
+    return [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared"] + list(defines) + ["-o", out] + GPU_SRCS + ["-ldl"]
+
+
 def build_gpu(force=False) -> str:
     os.makedirs(LIB, exist_ok=True)
     out = os.path.join(LIB, "libsbwtgpu.so")
-    srcs = [os.path.join(CSRC, f) for f in ("sbwt_search.hip", "sbwt_search_fused.hip", "sbwt_api_kernels.hip", "sbwt_derived.hip", "sbwt_build.hip", "sbwt_sort.hip",
-                                            "sbwt_format.hip", "sbwt_ms.hip", "sbwtgpu_capi.cpp")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("sbwt_device.h", "sbwt_kernels_common.h", "sbwt_scan.h", "sbwt_ms.h", "sbwt_search_fused_loop.inc")] + \
-        [os.path.join(INC, "sbwtgpu.h")]
-    if force or _newer(out, deps):
-        _run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", out] + srcs + ["-ldl"])
+    if force or _newer(out, GPU_DEPS):
+        _run(_hipcc_cmd(out))
     return out
+
+
+def start_gpu_mega_test(force=False):
+    """Starts the compiler for the test library when it is missing or older than a source (the rule of build_gpu) and returns
+    the process, or None: build_all lets it run beside the product library's compiler (two hipcc jobs in all)."""
+    os.makedirs(LIB, exist_ok=True)
+    if not (force or _newer(MEGA_TEST_LIB, GPU_DEPS)):
+        return None
+    cmd = _hipcc_cmd(MEGA_TEST_LIB, ["-DSBWT_MEGA_SHIFT=%d" % MEGA_TEST_SHIFT])
+    print("+", " ".join(cmd), flush=True)
+    return subprocess.Popen(cmd)
+
+
+def finish_gpu_mega_test(proc) -> str:
+    if proc is not None and proc.wait() != 0:
+        raise subprocess.CalledProcessError(proc.returncode, proc.args)
+    return MEGA_TEST_LIB
+
+
+def build_gpu_mega_test(force=False) -> str:
+    """libsbwtgpu_mega12.so: libsbwtgpu.so's sources with mega blocks of 2^12 columns instead of 2^31 (sbwt_device.h).  Test
+    infrastructure: loaded only through SBWTGPU_LIB, by the worker of tests/test_gpu_mega_small.py."""
+    return finish_gpu_mega_test(start_gpu_mega_test(force))
 
 
 def build_host(force=False) -> str:
@@ -82,7 +115,15 @@ def build_oracle(force=False) -> str:
 
 
 def build_all(force=False):
-    return [build_gpu(force), build_host(force), build_cli(force), build_oracle(force)]
+    mega = start_gpu_mega_test(force)
+    try:
+        built = [build_gpu(force), build_host(force), build_cli(force), build_oracle(force)]
+    except BaseException:
+        if mega is not None:
+            mega.kill()
+            mega.wait()
+        raise
+    return built + [finish_gpu_mega_test(mega)]
 
 
 if __name__ == "__main__":

@@ -41,8 +41,11 @@
 #pragma once
 #include <stdint.h>
 
+#ifndef SBWT_MEGA_SHIFT             // (-DSBWT_MEGA_SHIFT=12: the test build whose small indexes span many mega blocks, sbwt_amd/build.py)
 #define SBWT_MEGA_SHIFT 31          // columns per mega block = 2^31
-#define SBWT_GROUP_BASES 32         // bases per packed read group
+#endif
+static_assert(SBWT_MEGA_SHIFT >= 7 && SBWT_MEGA_SHIFT <= 31, "a mega block holds 2 .. 2^25 whole 64-column blocks, and its relative counts fit 32 bits");
+#define SBWT_GROUP_BASES 32        // bases per packed read group
 
 #ifndef SBWT_FUSED_SORT_DEFAULT
 #define SBWT_FUSED_SORT_DEFAULT 3632       // waves wait for 48 busy lanes | 14 << 8: the followers' finished reads go to the searchers while more than 40 reads wait in the followers' ring

@@ -1354,7 +1354,9 @@ void sbwt_launch_encode_chained(const char *d_bases, long long total_bases, uint
 // instantiation, as on a level-2 image): its derived structures hold full 32-bit unsigned columns and positions, which only
 // the fused kernel's BIG instantiation reads (sbwt_search_fused.hip).  Here that is the route of the few reads the fused
 // kernel hands on, of batches it declines, and of the cross-check variants.
-static inline bool view_is_big(const SbwtIndexView &ix) { return ix.big || ix.n_nodes >= ((1ll << 31) - 128); }
+// (more than one mega block: block counts may be relative, and of k_search_cert only the WIDE instantiation adds the base.  With
+// mega blocks of 2^31 columns the size test already says so; a test build with small mega blocks, sbwt_device.h, needs it said)
+static inline bool view_is_big(const SbwtIndexView &ix) { return ix.big || ix.n_mega > 1 || ix.n_nodes >= ((1ll << 31) - 128); }
 static inline SbwtIndexView general_view(const SbwtIndexView &ix) {
     SbwtIndexView v = ix;
     if (v.k > 32) v.has_safe = 0;

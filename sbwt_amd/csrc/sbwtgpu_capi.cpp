@@ -227,7 +227,13 @@ static inline int auto_variant(const SbwtBlobHeader &) { return 5; }
 
 extern "C" {
 
+#define SBWT_STR2(x) #x
+#define SBWT_STR(x) SBWT_STR2(x)
+#if SBWT_MEGA_SHIFT == 31
 const char *sbwtgpu_version(void) { return "sbwtgpu 0.1 (gfx950)"; }
+#else       // a test build with small mega blocks says so: its tests check that they loaded it
+const char *sbwtgpu_version(void) { return "sbwtgpu 0.1 (gfx950) mega_shift=" SBWT_STR(SBWT_MEGA_SHIFT); }
+#endif
 const char *sbwtgpu_last_error(void) { return g_err; }
 
 int sbwtgpu_set_tuning(const char *key, int64_t value) {
