@@ -367,6 +367,50 @@ int  sbwtgpu_matching_statistics_dev(const sbwtgpu_index *idx, const char *d_bas
                                      int64_t *d_second, void *d_workspace, int64_t workspace_bytes, void *stream);
 int  sbwtgpu_ms_workspace_stats(const void *d_workspace, void *stream, int64_t stats[5]);
 
+/* ---- unitigs: an index turned back into sequence ----
+ * The unitigs of the node-centric de Bruijn graph of the indexed k-mers, spelled on the device: every indexed k-mer exactly
+ * once, in about 1 + (k-1) / mean unitig length bytes per k-mer.  It is the inverse of sbwtgpu_build_plain_matrix:
+ * building from the unitigs with add_revcomp = 0 gives the rows, marks, n_nodes and n_kmers of the index back, bit for bit.
+ *
+ *   real column     its label has no '$': k backward steps from it do not pass column 0.  There are n_kmers of them.
+ *   out-neighbours  of a real column v: C[c] + rank_c(g) for each c in the set of g, the first column of v's suffix group.
+ *                   They are real.
+ *   in-neighbours   of w: the real members of the suffix group whose first column is pred(w); none if pred(w) is a dummy.
+ *                   (A group that holds a real column holds only real columns.)
+ *   internal edge   v -> w with outdeg(v) = 1 and indeg(w) = 1.
+ *   unitig          a maximal sequence of distinct real columns v1 .. vm joined by internal edges.
+ *   start           v is a start unless it has exactly one in-neighbour and that in-neighbour's out-degree is 1.
+ *   pure cycle      a component of internal edges with no start (a self-loop such as A^k is one of length 1).  It starts
+ *                   at its smallest column and is not closed again.
+ *   spelling        label(v1) followed by the last character of v2 .. vm: m + k - 1 bases, upper-case ACGT.
+ *   order           ascending column of v1.  The output is fully determined by the index: byte-identical between runs,
+ *                   image levels and devices.
+ *   strands         the graph is directed, not bidirected: on an index that holds reverse complements the unitigs come in
+ *                   reverse-complement pairs.  Merging them is out of scope.
+ *
+ * sbwtgpu_unitigs_create reads the blocks, the C array and the suffix-group marks only, so it serves every image level and
+ * layout; an index without marks gets them derived into scratch, the image is not changed.  Columns are 32-bit unsigned as
+ * in the image (indexes of 2^32 - 2^24 columns or more: SBWTGPU_ERR_INVALID_ARG), offsets into the bases 64-bit.  The work
+ * does not depend on the length of the longest unitig: list ranking by pointer jumping, at most ceil(log2 n_nodes) rounds.
+ * Scratch: 38 bytes per column, released before the call returns; the result: total_bases + 16 bytes per unitig.
+ * SBWTGPU_ERR_OOM leaves the index usable.  Rank-only indexes: SBWTGPU_ERR_INVALID_ARG.  An index with no real column
+ * gives 0 unitigs.  Thread-safe on an immutable handle like the query calls (a call owns its stream and its scratch). */
+typedef struct sbwtgpu_unitigs sbwtgpu_unitigs;
+int  sbwtgpu_unitigs_create(const sbwtgpu_index *idx, sbwtgpu_unitigs **out);      /* device-resident result */
+/* n_kmers = the sum of (length of unitig i) - k + 1 = the index's n_kmers */
+int  sbwtgpu_unitigs_info(const sbwtgpu_unitigs *u, int64_t *n_unitigs, int64_t *total_bases, int64_t *n_kmers);
+/* unitig i is d_bases[d_off[i] .. d_off[i+1]) and starts with the label of column d_first_col[i]; the pointers live as long
+ * as the handle (d_off: n_unitigs + 1 entries, d_first_col: n_unitigs) */
+int  sbwtgpu_unitigs_dev(const sbwtgpu_unitigs *u, const char **d_bases, const int64_t **d_off /* n+1 */,
+                         const int64_t **d_first_col /* n */);
+/* the same into host memory: bases[total_bases], off[n_unitigs + 1], first_col[n_unitigs] */
+int  sbwtgpu_unitigs_copy(const sbwtgpu_unitigs *u, char *bases, int64_t *off, int64_t *first_col /* may be NULL */);
+/* measurement aid (tools/unitig_bench.py): device-event times of the passes of the create call in ms -- [0] predecessors
+ * and marks, [1] real flags, [2] internal edges, [3] pointer jumping, [4] ids and offsets, [5] bases -- and the number of
+ * pointer-jumping rounds */
+int  sbwtgpu_unitigs_stats(const sbwtgpu_unitigs *u, double pass_ms[6], int64_t *jump_rounds);
+void sbwtgpu_unitigs_destroy(sbwtgpu_unitigs *u);
+
 #ifdef __cplusplus
 }
 #endif

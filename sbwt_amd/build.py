@@ -43,8 +43,8 @@ def _glob(d, exts):
 
 
 GPU_SRCS = [os.path.join(CSRC, f) for f in ("sbwt_search.hip", "sbwt_search_fused.hip", "sbwt_api_kernels.hip", "sbwt_derived.hip", "sbwt_build.hip", "sbwt_sort.hip",
-                                              "sbwt_format.hip", "sbwt_ms.hip", "sbwtgpu_capi.cpp")]
-GPU_DEPS = GPU_SRCS + [os.path.join(CSRC, f) for f in ("sbwt_device.h", "sbwt_kernels_common.h", "sbwt_scan.h", "sbwt_ms.h", "sbwt_search_fused_loop.inc")] + \
+                                              "sbwt_format.hip", "sbwt_ms.hip", "sbwt_unitigs.hip", "sbwtgpu_capi.cpp")]
+GPU_DEPS = GPU_SRCS + [os.path.join(CSRC, f) for f in ("sbwt_device.h", "sbwt_kernels_common.h", "sbwt_scan.h", "sbwt_ms.h", "sbwt_unitigs.h", "sbwt_search_fused_loop.inc")] + \
     [os.path.join(INC, "sbwtgpu.h")]
 MEGA_TEST_SHIFT = 12
 MEGA_TEST_LIB = os.path.join(LIB, "libsbwtgpu_mega%d.so" % MEGA_TEST_SHIFT)
@@ -99,9 +99,10 @@ def build_cli(force=False) -> str:
     os.makedirs(BIN, exist_ok=True)
     out = os.path.join(BIN, "sbwt")
     src = os.path.join(HOST, "sbwt_cli.cpp")
-    deps = [src, os.path.join(INC, "sbwtgpu.h"), os.path.join(LIB, "libsbwtgpu.so")] + _glob(HOST, (".hh",))
+    deps = [src, os.path.join(INC, "sbwtgpu.h"), os.path.join(INC, "sbwthost.h"), os.path.join(LIB, "libsbwtgpu.so"),
+            os.path.join(LIB, "libsbwthost.so")] + _glob(HOST, (".hh",))
     if force or _newer(out, deps):
-        _run([CXX, "-O3", "-std=c++17", "-pthread", "-Wall", "-o", out, src, "-L" + LIB, "-lsbwtgpu", "-lz",
+        _run([CXX, "-O3", "-std=c++17", "-pthread", "-Wall", "-o", out, src, "-L" + LIB, "-lsbwtgpu", "-lsbwthost", "-lz",
               "-Wl,-rpath,$ORIGIN/../lib", "-Wl,-rpath,/opt/rocm/lib"])
     return out
 

@@ -45,6 +45,8 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_search_text_batch", "sbwtgpu_search_text_stream", "sbwtgpu_free_host", "sbwtgpu_release_cached_buffers",
     "sbwtgpu_index_build_lcs", "sbwtgpu_index_get_lcs", "sbwtgpu_matching_statistics_batch", "sbwtgpu_ms_workspace_bytes",
     "sbwtgpu_matching_statistics_dev", "sbwtgpu_ms_workspace_stats",
+    "sbwtgpu_unitigs_create", "sbwtgpu_unitigs_info", "sbwtgpu_unitigs_dev", "sbwtgpu_unitigs_copy", "sbwtgpu_unitigs_stats",
+    "sbwtgpu_unitigs_destroy",
 ]
 
 
@@ -158,6 +160,13 @@ def lib() -> C.CDLL:
         L.sbwtgpu_ms_workspace_bytes.restype = i64
         L.sbwtgpu_matching_statistics_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp]
         L.sbwtgpu_ms_workspace_stats.argtypes = [vp, vp, C.POINTER(i64)]
+        L.sbwtgpu_unitigs_create.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_unitigs_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+        L.sbwtgpu_unitigs_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.sbwtgpu_unitigs_copy.argtypes = [vp, vp, vp, vp]
+        L.sbwtgpu_unitigs_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i64)]
+        L.sbwtgpu_unitigs_destroy.argtypes = [vp]
+        L.sbwtgpu_unitigs_destroy.restype = None
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -493,10 +502,71 @@ class Index:
         _check(lib().sbwtgpu_ms_workspace_stats(d_ws, stream, st))
         return dict(zip(("positions", "walked", "full", "contractions", "recomputes"), (int(x) for x in st)))
 
+    # ---- unitigs (include/sbwtgpu.h) ----
+    def unitigs_dev(self) -> "Unitigs":
+        """The unitigs of the index as a device-resident result (close() it, or let it go)."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_unitigs_create(self._h, C.byref(h)))
+        return Unitigs(h)
+
+    def unitigs(self):
+        """(bases: uint8[total], off: int64[n + 1], first_col: int64[n]): unitig i is bases[off[i]:off[i + 1]] and starts
+        with the label of column first_col[i]; ascending first_col."""
+        with self.unitigs_dev() as u:
+            return u.copy()
+
     def workspace_status(self, d_ws: int, stream: int = 0) -> int:
         st = C.c_int(0)
         _check(lib().sbwtgpu_workspace_status(d_ws, stream, C.byref(st)))
         return st.value
+
+
+class Unitigs:
+    """Owns an sbwtgpu_unitigs handle."""
+
+    def __init__(self, handle):
+        self._h = handle
+        n, total, nk = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _check(lib().sbwtgpu_unitigs_info(self._h, C.byref(n), C.byref(total), C.byref(nk)))
+        self.n_unitigs, self.total_bases, self.n_kmers = n.value, total.value, nk.value
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        if self._h:
+            lib().sbwtgpu_unitigs_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def dev_ptrs(self):
+        """(d_bases, d_off, d_first_col) as integers; valid until close()."""
+        b, o, f = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().sbwtgpu_unitigs_dev(self._h, C.byref(b), C.byref(o), C.byref(f)))
+        return b.value or 0, o.value or 0, f.value or 0
+
+    def copy(self):
+        bases = np.empty(self.total_bases, dtype=np.uint8)
+        off = np.empty(self.n_unitigs + 1, dtype=np.int64)
+        first_col = np.empty(self.n_unitigs, dtype=np.int64)
+        _check(lib().sbwtgpu_unitigs_copy(self._h, bases.ctypes.data, off.ctypes.data, first_col.ctypes.data))
+        return bases, off, first_col
+
+    def stats(self) -> dict:
+        """Device-event times of the passes (ms) and the number of pointer-jumping rounds."""
+        ms = (C.c_double * 6)()
+        r = C.c_int64(0)
+        _check(lib().sbwtgpu_unitigs_stats(self._h, ms, C.byref(r)))
+        names = ("pred_marks", "real_flags", "internal_edges", "pointer_jumping", "ids_offsets", "bases")
+        return {"pass_ms": dict(zip(names, (float(x) for x in ms))), "jump_rounds": int(r.value)}
 
 
 def kernel_times() -> list:

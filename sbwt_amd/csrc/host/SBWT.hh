@@ -455,6 +455,25 @@ public:
                                    int64_t *second) const {
         detail::gpu_check(sbwtgpu_matching_statistics_batch(need_device(), bases, read_off, n_reads, len, first, second));
     }
+    // the unitigs of the index (include/sbwtgpu.h): unitig i is bases[off[i] .. off[i+1]) and starts with the label of column
+    // first_col[i]; ascending first_col
+    struct Unitigs { std::vector<char> bases; std::vector<int64_t> off, first_col; };
+    Unitigs unitigs() const {
+        sbwtgpu_unitigs *u = nullptr;
+        detail::gpu_check(sbwtgpu_unitigs_create(need_device(), &u));
+        Unitigs r;
+        int64_t n = 0, total = 0;
+        int rc = sbwtgpu_unitigs_info(u, &n, &total, nullptr);
+        if (rc == SBWTGPU_OK) {
+            r.bases.resize((size_t)total);
+            r.off.resize((size_t)n + 1);
+            r.first_col.resize((size_t)n);
+            rc = sbwtgpu_unitigs_copy(u, r.bases.data(), r.off.data(), r.first_col.data());
+        }
+        sbwtgpu_unitigs_destroy(u);
+        detail::gpu_check(rc);
+        return r;
+    }
     // lcs[j]: the longest common suffix of the labels of columns j-1 and j ('$' never counts); lcs[0] = 0
     std::vector<uint8_t> get_lcs() const {
         std::vector<uint8_t> out((size_t)n_nodes);

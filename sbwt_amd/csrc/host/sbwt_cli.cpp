@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "SBWT.hh"
+#include "../../../include/sbwthost.h"
 
 using namespace sbwt;
 using std::string;
@@ -677,7 +678,51 @@ int matching_statistics_main(int argc, char **argv) {
     return 0;
 }
 
-const vector<string> commands = {"build", "search", "matching-statistics"};
+// sbwt dump-unitigs: the index turned back into sequence -- FASTA, one record per unitig in the order of the API (ascending
+// first column), the header the unitig's number
+int dump_unitigs_main(int argc, char **argv) {
+    set_log_level(LogLevel::MINOR);
+    Options opts({
+        {"out-file", 'o', true, "Output FASTA filename.", ""},
+        {"index-file", 'i', true, "Index input file.", ""},
+        {"gzip-output", 'z', false, "Writes output in gzipped form.", ""},
+        {"gpu", 0, true, "HIP device to run on.", "0"},
+        {"help", 'h', false, "Print usage", ""},
+    });
+    opts.parse(argc, argv);
+    if (argc == 1 || opts.count("help")) {
+        std::cerr << opts.help(argv[0], "Write the unitigs of the de Bruijn graph of the indexed k-mers as FASTA.") << std::endl;
+        exit(1);
+    }
+    const string indexfile = opts.get("index-file"), outfile = opts.get("out-file");
+    check_readable(indexfile);
+    check_writable(outfile);
+    set_default_device(atoi(opts.get("gpu").c_str()));
+    std::ifstream in(indexfile, std::ios::binary);
+    if (!in.good()) throw std::runtime_error("Error opening file: " + indexfile);
+    const string variant = load_string(in);
+    if (variant != "plain-matrix")
+        throw std::runtime_error("Error: only the plain-matrix variant is supported by the GPU path (got " + variant + ")");
+    plain_matrix_sbwt_t index;
+    index.load(in);
+    const plain_matrix_sbwt_t::Unitigs u = index.unitigs();
+    const int64_t n = (int64_t)u.first_col.size();
+    string text;
+    text.reserve(u.bases.size() + (size_t)n * 12);
+    for (int64_t i = 0; i < n; i++) {
+        text.push_back('>');
+        append_int(i, text);
+        text.push_back('\n');
+        text.append(u.bases.data() + u.off[(size_t)i], (size_t)(u.off[(size_t)i + 1] - u.off[(size_t)i]));
+        text.push_back('\n');
+    }
+    if (sbwthost_write_file(outfile.c_str(), text.data(), (int64_t)text.size(), opts.count("gzip-output") ? 1 : 0, 0) != 0)
+        throw std::runtime_error(string("Error writing ") + outfile + ": " + sbwthost_last_error());
+    write_log("Wrote " + std::to_string(n) + " unitigs, " + std::to_string(u.bases.size()) + " bases", LogLevel::MAJOR);
+    return 0;
+}
+
+const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs"};
 
 void print_help(char **argv) {
     std::cerr << "Available commands: " << std::endl;
@@ -707,6 +752,7 @@ int main(int argc, char **argv) {   // sbwt.cpp:19-57
             _exit(rc);
         }
         else if (command == "matching-statistics") return matching_statistics_main(argc, argv);
+        else if (command == "dump-unitigs") return dump_unitigs_main(argc, argv);
         else throw std::runtime_error("Invalid command: " + command);
     } catch (const std::runtime_error &e) {
         std::cerr << "Runtime error: " << e.what() << '\n';

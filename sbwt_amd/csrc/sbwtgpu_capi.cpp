@@ -20,6 +20,7 @@
 #include "../../include/sbwtgpu.h"
 #include "sbwt_device.h"
 #include "sbwt_ms.h"
+#include "sbwt_unitigs.h"
 
 namespace {
 
@@ -2631,6 +2632,88 @@ int sbwtgpu_matching_statistics_batch(const sbwtgpu_index *idx, const char *base
         HIP_TRY(hipMemcpyAsync(second + base0, dv + o_s, (size_t)total * 8, hipMemcpyDeviceToHost, st.s));
     }
     HIP_TRY(hipStreamSynchronize(st.s));
+    return SBWTGPU_OK;
+}
+
+// ---- unitigs (sbwt_unitigs.hip) ---------------------------------------------------------------------
+struct sbwtgpu_unitigs {
+    int device = 0;
+    int64_t k = 0;
+    SbwtUnitigRun run;
+};
+
+int sbwtgpu_unitigs_create(const sbwtgpu_index *idx, sbwtgpu_unitigs **out) {
+    if (!idx || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (idx->h.rank_only) return fail(SBWTGPU_ERR_INVALID_ARG, "%s", RANK_ONLY_MSG);
+    if (idx->h.k < 2) return fail(SBWTGPU_ERR_INVALID_ARG, "unitigs need k >= 2");
+    if (idx->h.n_nodes >= ((int64_t)1 << 32) - ((int64_t)1 << 24))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "unitigs: columns are 32-bit unsigned values (%lld columns)", (long long)idx->h.n_nodes);
+    DeviceGuard guard(idx->device);
+    sbwtgpu_unitigs *u = new (std::nothrow) sbwtgpu_unitigs();
+    if (!u) return fail(SBWTGPU_ERR_OOM, "out of host memory");
+    u->device = idx->device;
+    u->k = idx->h.k;
+    DevBuf scratch;
+    Stream st;
+    hipError_t e = scratch.alloc((size_t)sbwt_unitigs_scratch_bytes(idx->h.n_nodes));
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = sbwt_unitigs_run(idx->view(), idx->h.has_ssup || idx->h.ssup_derived, scratch.p, &u->run, st.s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        delete u;
+        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "unitigs: %s", hipGetErrorString(e));
+    }
+    const int64_t nk = u->run.total_bases - u->run.n_unitigs * (u->k - 1);
+    if (idx->h.n_kmers > 0 && nk != idx->h.n_kmers) {
+        sbwtgpu_unitigs_destroy(u);
+        return fail(SBWTGPU_ERR_INVALID_ARG, "unitigs: the index has %lld real columns, its n_kmers says %lld", (long long)nk,
+                    (long long)idx->h.n_kmers);
+    }
+    *out = u;
+    return SBWTGPU_OK;
+}
+
+void sbwtgpu_unitigs_destroy(sbwtgpu_unitigs *u) {
+    if (!u) return;
+    DeviceGuard guard(u->device);
+    if (u->run.d_bases) (void)hipFree(u->run.d_bases);
+    if (u->run.d_off) (void)hipFree(u->run.d_off);
+    if (u->run.d_first_col) (void)hipFree(u->run.d_first_col);
+    delete u;
+}
+
+int sbwtgpu_unitigs_info(const sbwtgpu_unitigs *u, int64_t *n_unitigs, int64_t *total_bases, int64_t *n_kmers) {
+    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    if (n_unitigs) *n_unitigs = u->run.n_unitigs;
+    if (total_bases) *total_bases = u->run.total_bases;
+    if (n_kmers) *n_kmers = u->run.total_bases - u->run.n_unitigs * (u->k - 1);
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_unitigs_dev(const sbwtgpu_unitigs *u, const char **d_bases, const int64_t **d_off, const int64_t **d_first_col) {
+    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    if (d_bases) *d_bases = u->run.d_bases;
+    if (d_off) *d_off = reinterpret_cast<const int64_t *>(u->run.d_off);
+    if (d_first_col) *d_first_col = reinterpret_cast<const int64_t *>(u->run.d_first_col);
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_unitigs_copy(const sbwtgpu_unitigs *u, char *bases, int64_t *off, int64_t *first_col) {
+    if (!u || !off || (!bases && u->run.total_bases > 0)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    DeviceGuard guard(u->device);
+    if (u->run.total_bases > 0) HIP_TRY(hipMemcpy(bases, u->run.d_bases, (size_t)u->run.total_bases, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(off, u->run.d_off, (size_t)(u->run.n_unitigs + 1) * 8, hipMemcpyDeviceToHost));
+    if (first_col && u->run.n_unitigs > 0)
+        HIP_TRY(hipMemcpy(first_col, u->run.d_first_col, (size_t)u->run.n_unitigs * 8, hipMemcpyDeviceToHost));
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_unitigs_stats(const sbwtgpu_unitigs *u, double pass_ms[6], int64_t *jump_rounds) {
+    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    if (pass_ms)
+        for (int i = 0; i < SBWT_UT_N_PASSES; i++) pass_ms[i] = (double)u->run.ms[i];
+    if (jump_rounds) *jump_rounds = u->run.jump_rounds;
     return SBWTGPU_OK;
 }
 
