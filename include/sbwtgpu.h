@@ -411,6 +411,45 @@ int  sbwtgpu_unitigs_copy(const sbwtgpu_unitigs *u, char *bases, int64_t *off, i
 int  sbwtgpu_unitigs_stats(const sbwtgpu_unitigs *u, double pass_ms[6], int64_t *jump_rounds);
 void sbwtgpu_unitigs_destroy(sbwtgpu_unitigs *u);
 
+/* ---- set operations on two indexes: union, intersection, difference, symmetric difference ----
+ * The columns of an index are its k-mers in sorted order, so two indexes combine without their input sequences and without
+ * a sort: the keys of the real columns of each (label extraction on the device), one merge under the operation's rule, and
+ * the part of the device builder that starts from sorted distinct k-mers.
+ *
+ * CONTRACT: the result is bit for bit what sbwtgpu_build_plain_matrix returns for the result set's k-mers given as n
+ * sequences of length k with add_revcomp = 0: rows, marks, n_nodes and n_kmers.  (So an empty result is what that call
+ * returns for no sequence at all: the root column alone.)  Release it with sbwtgpu_free_plain_matrix.
+ *
+ * Both handles must be on the same device and have the same k, 2 <= k <= 64 (the device builder's key: 64 or 128 bits);
+ * anything else is SBWTGPU_ERR_INVALID_ARG with a message naming the mismatch, as are rank-only indexes and indexes of
+ * 2^32 - 2^24 columns or more (columns are 32-bit unsigned as in the image).  a == b is allowed.  Neither index needs
+ * suffix-group marks: only the blocks and the C array are read, so every image level and layout is served.  Scratch: 37
+ * bytes per column of an index for k <= 32, 69 above, then about 34 (50) bytes per key of the two lists together; all of
+ * it is released before the call returns.  SBWTGPU_ERR_OOM leaves both indexes untouched and usable.
+ * The builder's host-side dummy limit applies unchanged: a result with n_nopred x k > 2^26 (n_nopred: its k-mers without a
+ * predecessor in it) is SBWTGPU_ERR_OOM -- intersections and differences of fragmented sets reach it sooner than genomes
+ * do -- and `info`, when given, still carries the counts and n_nopred then.
+ * Thread-safe on immutable handles like the query calls (a call owns its stream and its scratch). */
+#define SBWTGPU_SETOP_UNION 0
+#define SBWTGPU_SETOP_INTERSECTION 1
+#define SBWTGPU_SETOP_DIFFERENCE 2      /* a minus b */
+#define SBWTGPU_SETOP_SYMMETRIC_DIFFERENCE 3
+typedef struct {
+    int64_t n_a, n_b, n_both, n_either;   /* |A|, |B|, |A and B|, |A or B| */
+    int64_t n_result, n_nopred;           /* k-mers of the result; those without a predecessor in it */
+    double  pass_ms[4];                   /* keys of a, keys of b, merge+select, builder tail + columns */
+} sbwtgpu_setop_info;
+int  sbwtgpu_index_setop(const sbwtgpu_index *a, const sbwtgpu_index *b, int op, int build_streaming_support,
+                         sbwtgpu_plain_matrix_bits *out, sbwtgpu_setop_info *info /* may be NULL */);
+/* the four counts alone (Jaccard = n_both / n_either, containment = n_both / n_a): nothing is built; n_result and n_nopred
+ * are 0, pass_ms[3] is 0 */
+int  sbwtgpu_index_setop_counts(const sbwtgpu_index *a, const sbwtgpu_index *b, sbwtgpu_setop_info *info);
+/* The sorted keys themselves, for callers and tests: 8 (k <= 32) or 16 (32 < k <= 64) bytes per k-mer, little-endian,
+ * n_kmers of them, ascending = column order.  Character i of the k-mer (A, C, G, T = 0 .. 3) is at bits 2i of its key.
+ * *n_keys and *key_bytes are set whenever the extraction ran; cap_bytes < n_keys x key_bytes: SBWTGPU_ERR_INVALID_ARG and
+ * nothing is written to out_keys (out_keys = NULL with cap_bytes = 0 asks for the two numbers). */
+int  sbwtgpu_index_kmer_keys(const sbwtgpu_index *idx, void *out_keys, int64_t cap_bytes, int64_t *n_keys, int *key_bytes);
+
 #ifdef __cplusplus
 }
 #endif

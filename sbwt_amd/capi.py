@@ -47,7 +47,12 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_matching_statistics_dev", "sbwtgpu_ms_workspace_stats",
     "sbwtgpu_unitigs_create", "sbwtgpu_unitigs_info", "sbwtgpu_unitigs_dev", "sbwtgpu_unitigs_copy", "sbwtgpu_unitigs_stats",
     "sbwtgpu_unitigs_destroy",
+    "sbwtgpu_index_setop", "sbwtgpu_index_setop_counts", "sbwtgpu_index_kmer_keys",
 ]
+
+SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
+SETOPS = {"union": SETOP_UNION, "intersection": SETOP_INTERSECTION, "difference": SETOP_DIFFERENCE,
+          "symmetric-difference": SETOP_SYMMETRIC_DIFFERENCE}
 
 
 class SbwtGpuError(RuntimeError):
@@ -81,6 +86,16 @@ class PlainMatrixBitsC(C.Structure):
     _fields_ = [("n_nodes", C.c_int64), ("n_kmers", C.c_int64), ("k", C.c_int64),
                 ("A_bits", C.c_void_p), ("C_bits", C.c_void_p), ("G_bits", C.c_void_p), ("T_bits", C.c_void_p),
                 ("suffix_group_starts", C.c_void_p)]
+
+
+class SetopInfoC(C.Structure):
+    _fields_ = [("n_a", C.c_int64), ("n_b", C.c_int64), ("n_both", C.c_int64), ("n_either", C.c_int64),
+                ("n_result", C.c_int64), ("n_nopred", C.c_int64), ("pass_ms", C.c_double * 4)]
+
+    def as_dict(self) -> dict:
+        d = {f: int(getattr(self, f)) for f in ("n_a", "n_b", "n_both", "n_either", "n_result", "n_nopred")}
+        d["pass_ms"] = dict(zip(("keys_a", "keys_b", "merge_select", "tail_columns"), (float(x) for x in self.pass_ms)))
+        return d
 
 
 _lib: Optional[C.CDLL] = None
@@ -167,6 +182,9 @@ def lib() -> C.CDLL:
         L.sbwtgpu_unitigs_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i64)]
         L.sbwtgpu_unitigs_destroy.argtypes = [vp]
         L.sbwtgpu_unitigs_destroy.restype = None
+        L.sbwtgpu_index_setop.argtypes = [vp, vp, ci, ci, C.POINTER(PlainMatrixBitsC), C.POINTER(SetopInfoC)]
+        L.sbwtgpu_index_setop_counts.argtypes = [vp, vp, C.POINTER(SetopInfoC)]
+        L.sbwtgpu_index_kmer_keys.argtypes = [vp, vp, i64, C.POINTER(i64), C.POINTER(ci)]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -218,14 +236,8 @@ class BuiltBits:
         self.cols, self.ssup, self.n_nodes, self.n_kmers, self.k = cols, ssup, n_nodes, n_kmers, k
 
 
-def build_bits_gpu(seqs: Sequence[bytes], k: int, add_revcomp: bool = False, streaming_support: bool = True,
-                   device: int = 0) -> BuiltBits:
-    """sbwtgpu_build_plain_matrix: the plain-matrix SBWT columns of `seqs`, built on the GPU (2 <= k <= 64)."""
-    arr = (C.c_char_p * len(seqs))(*[bytes(s) for s in seqs])
-    lens = np.array([len(s) for s in seqs], dtype=np.int64)
-    out = PlainMatrixBitsC()
-    _check(lib().sbwtgpu_build_plain_matrix(arr, lens.ctypes.data, len(seqs), k, int(add_revcomp), int(streaming_support),
-                                            device, C.byref(out)))
+def _take_bits(out: PlainMatrixBitsC) -> BuiltBits:
+    """numpy copies of a sbwtgpu_plain_matrix_bits, which is released."""
     try:
         nw = (out.n_nodes + 63) // 64
 
@@ -236,6 +248,17 @@ def build_bits_gpu(seqs: Sequence[bytes], k: int, add_revcomp: bool = False, str
         return BuiltBits(cols, ssup, out.n_nodes, out.n_kmers, out.k)
     finally:
         lib().sbwtgpu_free_plain_matrix(C.byref(out))
+
+
+def build_bits_gpu(seqs: Sequence[bytes], k: int, add_revcomp: bool = False, streaming_support: bool = True,
+                   device: int = 0) -> BuiltBits:
+    """sbwtgpu_build_plain_matrix: the plain-matrix SBWT columns of `seqs`, built on the GPU (2 <= k <= 64)."""
+    arr = (C.c_char_p * len(seqs))(*[bytes(s) for s in seqs])
+    lens = np.array([len(s) for s in seqs], dtype=np.int64)
+    out = PlainMatrixBitsC()
+    _check(lib().sbwtgpu_build_plain_matrix(arr, lens.ctypes.data, len(seqs), k, int(add_revcomp), int(streaming_support),
+                                            device, C.byref(out)))
+    return _take_bits(out)
 
 
 class Index:
@@ -514,6 +537,42 @@ class Index:
         with the label of column first_col[i]; ascending first_col."""
         with self.unitigs_dev() as u:
             return u.copy()
+
+    # ---- set operations on two indexes (include/sbwtgpu.h) ----
+    def setop(self, other: "Index", op, streaming_support: bool = True):
+        """sbwtgpu_index_setop: (BuiltBits, info) of self `op` other; op is a SETOP_* value or a name of SETOPS.  A failed
+        call raises SbwtGpuError with the counts the call got to (n_nopred at the dummy limit) as its `info`."""
+        out, info = PlainMatrixBitsC(), SetopInfoC()
+        rc = lib().sbwtgpu_index_setop(self._h, other._h, SETOPS.get(op, op), int(streaming_support), C.byref(out), C.byref(info))
+        if rc != OK:
+            err = SbwtGpuError(rc, lib().sbwtgpu_last_error().decode(errors="replace"))
+            err.info = info.as_dict()
+            raise err
+        return _take_bits(out), info.as_dict()
+
+    def setop_counts(self, other: "Index") -> dict:
+        """|A|, |B|, |A and B|, |A or B| of the two indexes' k-mer sets, and jaccard / containment (of self in other)."""
+        info = SetopInfoC()
+        _check(lib().sbwtgpu_index_setop_counts(self._h, other._h, C.byref(info)))
+        d = info.as_dict()
+        d["jaccard"] = d["n_both"] / d["n_either"] if d["n_either"] else 1.0
+        d["containment"] = d["n_both"] / d["n_a"] if d["n_a"] else 1.0
+        return d
+
+    def kmer_keys(self) -> np.ndarray:
+        """The k-mers of the index as the builder's sorted keys (character i at bits 2i): uint64[n_kmers] for k <= 32, an
+        (n_kmers, 2) uint64 array of (low, high) words for 32 < k <= 64."""
+        n, kb = C.c_int64(0), C.c_int(0)
+        cap = max(self.n_kmers, 0) * (8 if self.k <= 32 else 16)
+        out = np.empty(cap // 8, dtype=np.uint64)
+        rc = lib().sbwtgpu_index_kmer_keys(self._h, out.ctypes.data if cap else None, cap, C.byref(n), C.byref(kb))
+        if rc in (OK, ERR_INVALID_ARG) and n.value * kb.value > cap:               # (an index made with n_kmers = 0: unknown)
+            cap = n.value * kb.value
+            out = np.empty(cap // 8, dtype=np.uint64)
+            rc = lib().sbwtgpu_index_kmer_keys(self._h, out.ctypes.data, cap, C.byref(n), C.byref(kb))
+        _check(rc)
+        out = out[: n.value * kb.value // 8]
+        return out if kb.value == 8 else out.reshape(n.value, 2)
 
     def workspace_status(self, d_ws: int, stream: int = 0) -> int:
         st = C.c_int(0)

@@ -474,6 +474,28 @@ public:
         detail::gpu_check(rc);
         return r;
     }
+    // Set operations on the k-mer sets of two indexes (include/sbwtgpu.h: SBWTGPU_SETOP_UNION, _INTERSECTION, _DIFFERENCE = a
+    // minus b, _SYMMETRIC_DIFFERENCE): the columns of the result, bit for bit what the builder gives for the result's k-mers.
+    // Both indexes on one device, the same k, 2 <= k <= 64.  `info` (optional) receives the counts and pass times.
+    static PlainMatrixBits set_operation(const SBWT &a, const SBWT &b, int op, bool streaming_support,
+                                         sbwtgpu_setop_info *info = nullptr) {
+        sbwtgpu_plain_matrix_bits r;
+        detail::gpu_check(sbwtgpu_index_setop(a.need_device(), b.need_device(), op, streaming_support ? 1 : 0, &r, info));
+        PlainMatrixBits out;
+        out.n_nodes = r.n_nodes; out.n_kmers = r.n_kmers; out.k = r.k;
+        const size_t nw = (size_t)((r.n_nodes + 63) / 64);
+        out.A.assign(r.A_bits, r.A_bits + nw); out.C.assign(r.C_bits, r.C_bits + nw);
+        out.G.assign(r.G_bits, r.G_bits + nw); out.T.assign(r.T_bits, r.T_bits + nw);
+        if (r.suffix_group_starts) out.ssup.assign(r.suffix_group_starts, r.suffix_group_starts + nw);
+        sbwtgpu_free_plain_matrix(&r);
+        return out;
+    }
+    // |A|, |B|, |A and B|, |A or B| alone: nothing is built
+    static sbwtgpu_setop_info set_operation_counts(const SBWT &a, const SBWT &b) {
+        sbwtgpu_setop_info info;
+        detail::gpu_check(sbwtgpu_index_setop_counts(a.need_device(), b.need_device(), &info));
+        return info;
+    }
     // lcs[j]: the longest common suffix of the labels of columns j-1 and j ('$' never counts); lcs[0] = 0
     std::vector<uint8_t> get_lcs() const {
         std::vector<uint8_t> out((size_t)n_nodes);

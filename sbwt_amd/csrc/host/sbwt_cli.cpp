@@ -722,7 +722,84 @@ int dump_unitigs_main(int argc, char **argv) {
     return 0;
 }
 
-const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs"};
+// sbwt set-op: two index files combined on the GPU without their input sequences -- the result is the index `sbwt build`
+// would write for the result's k-mers (same serialisation and precalc step as build_main)
+int set_op_main(int argc, char **argv) {
+    set_log_level(LogLevel::MAJOR);
+    Options opts({
+        {"index-a", 'a', true, "First index input file.", ""},
+        {"index-b", 'b', true, "Second index input file.", ""},
+        {"op", 0, true, "union, intersection, difference (a minus b) or symmetric-difference.", "union"},
+        {"out-file", 'o', true, "Output file for the resulting index.", ""},
+        {"no-streaming-support", 0, false, "Do not build the streaming query support bit vector.", ""},
+        {"precalc-length", 'p', true, "Precalculate SBWT intervals of strings of this length.", "8"},
+        {"counts-only", 0, false, "Write no index: print `n_a n_b n_both n_either` to stdout.", ""},
+        {"gpu", 0, true, "HIP device to run on.", "0"},
+        {"help", 'h', false, "Print usage", ""},
+    });
+    opts.parse(argc, argv);
+    if (argc == 1 || opts.count("help")) {
+        std::cerr << opts.help(argv[0], "Union, intersection or difference of the k-mer sets of two indexes, as an index.") << std::endl;
+        exit(1);
+    }
+    static const vector<string> names = {"union", "intersection", "difference", "symmetric-difference"};
+    const string opname = opts.get("op");
+    int op = -1;
+    for (size_t i = 0; i < names.size(); i++)
+        if (names[i] == opname) op = (int)i;
+    if (op < 0) throw std::runtime_error("Error: unknown set operation: " + opname);
+    const bool counts_only = opts.count("counts-only");
+    const string file_a = opts.get("index-a"), file_b = opts.get("index-b");
+    const string out_file = counts_only ? string() : opts.get("out-file");          // (--counts-only writes no file: no -o needed)
+    check_readable(file_a);
+    check_readable(file_b);
+    if (!counts_only) check_writable(out_file);
+    set_default_device(atoi(opts.get("gpu").c_str()));
+    plain_matrix_sbwt_t A, B;
+    for (int i = 0; i < 2; i++) {
+        const string &f = i ? file_b : file_a;
+        std::ifstream in(f, std::ios::binary);
+        if (!in.good()) throw std::runtime_error("Error opening file: " + f);
+        const string variant = load_string(in);
+        if (variant != "plain-matrix")
+            throw std::runtime_error("Error: only the plain-matrix variant is supported by the GPU path (got " + variant + ")");
+        (i ? B : A).load(in);
+    }
+    auto log_counts = [](const sbwtgpu_setop_info &c) {
+        write_log("k-mers: " + std::to_string(c.n_a) + " in a, " + std::to_string(c.n_b) + " in b, " + std::to_string(c.n_both) +
+                      " in both, " + std::to_string(c.n_either) + " in either; Jaccard index " +
+                      std::to_string(c.n_either ? (double)c.n_both / (double)c.n_either : 1.0),
+                  LogLevel::MAJOR);
+    };
+    if (counts_only) {
+        const sbwtgpu_setop_info c = plain_matrix_sbwt_t::set_operation_counts(A, B);
+        log_counts(c);
+        std::cout << c.n_a << " " << c.n_b << " " << c.n_both << " " << c.n_either << std::endl;
+        return 0;
+    }
+    const int64_t k = A.get_k();
+    int64_t precalc = atoll(opts.get("precalc-length").c_str());
+    if (precalc > k) {
+        write_log("Warning: precalc length " + std::to_string(precalc) + " is longer than k = " + std::to_string(k), LogLevel::MAJOR);
+        write_log("Setting precalc length to " + std::to_string(k), LogLevel::MAJOR);
+        precalc = k;
+    }
+    sbwtgpu_setop_info info;
+    PlainMatrixBits bits = plain_matrix_sbwt_t::set_operation(A, B, op, !opts.count("no-streaming-support"), &info);
+    log_counts(info);
+    plain_matrix_sbwt_t index(bits, 0);
+    write_log("The " + opname + " has " + std::to_string(index.number_of_kmers()) + " distinct k-mers, " +
+                  std::to_string(index.number_of_subsets()) + " subsets", LogLevel::MAJOR);
+    std::ofstream out(out_file, std::ios::binary);
+    if (!out.good()) throw std::runtime_error("Error opening file: " + out_file);
+    serialize_string("plain-matrix", out);
+    index.do_kmer_prefix_precalc(precalc);
+    index.serialize(out);
+    write_log("Wrote the index to " + out_file, LogLevel::MAJOR);
+    return 0;
+}
+
+const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "set-op"};
 
 void print_help(char **argv) {
     std::cerr << "Available commands: " << std::endl;
@@ -753,6 +830,7 @@ int main(int argc, char **argv) {   // sbwt.cpp:19-57
         }
         else if (command == "matching-statistics") return matching_statistics_main(argc, argv);
         else if (command == "dump-unitigs") return dump_unitigs_main(argc, argv);
+        else if (command == "set-op") return set_op_main(argc, argv);
         else throw std::runtime_error("Invalid command: " + command);
     } catch (const std::runtime_error &e) {
         std::cerr << "Runtime error: " << e.what() << '\n';

@@ -246,10 +246,58 @@ static void scan_i64(const i64 *in, i64 n, i64 *out, i64 *bsum, hipStream_t st) 
     hipLaunchKernelGGL(k_scan_apply, dim3(gb), dim3(256), 0, st, in, n, bsum, out);
 }
 
-// Device part of the builder.  Phase A: text (separator-joined) -> sorted distinct k-mers, suffix groups, edges, the
-// list of predecessor-less k-mers (returned to the host, which makes and sorts their dummy prefixes: few).  Phase B:
-// the columns.  All device memory is owned by SbwtBuildState.
+// Device part of the builder.  Phase A: text (separator-joined) -> sorted distinct k-mers; its TAIL, which starts from sorted
+// distinct keys and which the set operations (sbwt_setops.hip) call as well: suffix groups, edges, the list of
+// predecessor-less k-mers (returned to the host, which makes and sorts their dummy prefixes: few).  Phase B: the columns.
+// All device memory is owned by SbwtBuildState.
 #define BLD_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = e_; goto fail; } } while (0)
+
+// km: nk sorted distinct keys, a device allocation that S owns from here on (released by sbwt_build_release, also after a
+// failure); nk == 0: km may be null
+template <typename KT>
+static int build_tail(KT *km, i64 nk, int k, SbwtBuildState *S, hipStream_t st) {
+    hipError_t err = hipSuccess;
+    i64 *flag = nullptr, *pos = nullptr, *bsum = nullptr, *gstart = nullptr; KT *gsuf = nullptr;
+    i64 ng = 0, nn = 0;
+    S->k = k;
+    S->km = km;
+    if (nk > 0) {
+        BLD_TRY(hipMalloc((void **)&flag, (size_t)(nk + 1) * 8));
+        BLD_TRY(hipMalloc((void **)&pos, (size_t)(nk + 2) * 8));
+        BLD_TRY(hipMalloc((void **)&bsum, (size_t)((nk + 1023) / 1024 + 2) * 8));
+        // suffix groups
+        hipLaunchKernelGGL(k_bld_flag_first<KT>, dim3(grid_for(nk)), dim3(256), 0, st, km, nk, 2, flag);
+        scan_i64(flag, nk, pos, bsum, st);
+        BLD_TRY(hipMemcpyAsync(&ng, pos + nk, 8, hipMemcpyDeviceToHost, st));
+        BLD_TRY(hipStreamSynchronize(st));
+        BLD_TRY(hipMalloc((void **)&gstart, (size_t)ng * 8));
+        BLD_TRY(hipMalloc((void **)&gsuf, (size_t)ng * sizeof(KT)));
+        hipLaunchKernelGGL(k_bld_groups<KT>, dim3(grid_for(nk)), dim3(256), 0, st, km, flag, pos, nk, gstart, gsuf);
+        // predecessors and edges
+        BLD_TRY(hipMalloc((void **)&S->edges, (size_t)nk * 4));
+        BLD_TRY(hipMemsetAsync(S->edges, 0, (size_t)nk * 4, st));
+        hipLaunchKernelGGL(k_bld_pred<KT>, dim3(grid_for(nk)), dim3(256), 0, st, km, nk, k, gstart, gsuf, ng, S->edges, flag);
+        scan_i64(flag, nk, pos, bsum, st);
+        BLD_TRY(hipMemcpyAsync(&nn, pos + nk, 8, hipMemcpyDeviceToHost, st));
+        BLD_TRY(hipStreamSynchronize(st));
+        if (nn > 0) {
+            KT *np = nullptr;
+            BLD_TRY(hipMalloc((void **)&np, (size_t)nn * sizeof(KT)));
+            S->nopred_keys = np;
+            hipLaunchKernelGGL(k_bld_compact<KT>, dim3(grid_for(nk)), dim3(256), 0, st, km, flag, pos, nk, np);
+        }
+        BLD_TRY(hipStreamSynchronize(st));
+    }
+    S->nk = nk; S->ng = ng; S->n_nopred = nn;
+fail:
+    (void)hipFree(flag); (void)hipFree(pos); (void)hipFree(bsum); (void)hipFree(gstart); (void)hipFree(gsuf);
+    if (err != hipSuccess) { (void)hipGetLastError(); return err == hipErrorOutOfMemory ? -8 : -3; }
+    return 0;
+}
+int sbwt_build_from_keys(void *d_km, long long nk, int k, SbwtBuildState *S, hipStream_t st) {
+    S->key_bytes = k <= 32 ? 8 : 16;
+    return k <= 32 ? build_tail<u64>(static_cast<u64 *>(d_km), nk, k, S, st) : build_tail<u128>(static_cast<u128 *>(d_km), nk, k, S, st);
+}
 
 template <typename KT>
 static int build_phase_a(const char *h_text, long long n_text, int k, int rc, SbwtBuildState *S, hipStream_t st) {
@@ -258,12 +306,12 @@ static int build_phase_a(const char *h_text, long long n_text, int k, int rc, Sb
     const i64 n_groups = (n_text + 31) / 32 + 4;
     const i64 n_pos = n_text;                              // windows that run past the end meet zero validity bits
     const i64 cap = (rc ? 2 : 1) * n_text;
-    char *d_text = nullptr; uint4 *d_packed = nullptr; KT *keys = nullptr, *keys2 = nullptr; unsigned long long *d_cnt = nullptr;
-    i64 *flag = nullptr, *pos = nullptr, *bsum = nullptr, *gstart = nullptr; KT *gsuf = nullptr;
+    char *d_text = nullptr; uint4 *d_packed = nullptr; KT *keys = nullptr, *keys2 = nullptr, *km = nullptr; unsigned long long *d_cnt = nullptr;
+    i64 *flag = nullptr, *pos = nullptr, *bsum = nullptr;
     void *tmp = nullptr; size_t tmp_bytes = 0;
     SbwtWorkHeader *ws = nullptr;
     unsigned long long h_cnt = 0;
-    i64 nv = 0, nk = 0, ng = 0, nn = 0;
+    i64 nv = 0, nk = 0;
     BLD_TRY(hipMalloc((void **)&d_text, (size_t)n_text + 64));
     BLD_TRY(hipMalloc((void **)&d_packed, (size_t)n_groups * 16));
     BLD_TRY(hipMalloc((void **)&ws, sizeof(SbwtWorkHeader)));
@@ -295,41 +343,15 @@ static int build_phase_a(const char *h_text, long long n_text, int k, int rc, Sb
         scan_i64(flag, nv, pos, bsum, st);
         BLD_TRY(hipMemcpyAsync(&nk, pos + nv, 8, hipMemcpyDeviceToHost, st));
         BLD_TRY(hipStreamSynchronize(st));
-        KT *km = nullptr;
         BLD_TRY(hipMalloc((void **)&km, (size_t)nk * sizeof(KT)));
-        S->km = km;
         hipLaunchKernelGGL(k_bld_compact<KT>, dim3(grid_for(nv)), dim3(256), 0, st, keys2, flag, pos, nv, km);
         BLD_TRY(hipStreamSynchronize(st));
-        (void)hipFree(keys2); keys2 = nullptr;
-        // suffix groups
-        hipLaunchKernelGGL(k_bld_flag_first<KT>, dim3(grid_for(nk)), dim3(256), 0, st, km, nk, 2, flag);
-        scan_i64(flag, nk, pos, bsum, st);
-        BLD_TRY(hipMemcpyAsync(&ng, pos + nk, 8, hipMemcpyDeviceToHost, st));
-        BLD_TRY(hipStreamSynchronize(st));
-        BLD_TRY(hipMalloc((void **)&gstart, (size_t)ng * 8));
-        BLD_TRY(hipMalloc((void **)&gsuf, (size_t)ng * sizeof(KT)));
-        hipLaunchKernelGGL(k_bld_groups<KT>, dim3(grid_for(nk)), dim3(256), 0, st, km, flag, pos, nk, gstart, gsuf);
-        // predecessors and edges
-        BLD_TRY(hipMalloc((void **)&S->edges, (size_t)nk * 4));
-        BLD_TRY(hipMemsetAsync(S->edges, 0, (size_t)nk * 4, st));
-        hipLaunchKernelGGL(k_bld_pred<KT>, dim3(grid_for(nk)), dim3(256), 0, st, km, nk, k, gstart, gsuf, ng, S->edges, flag);
-        scan_i64(flag, nk, pos, bsum, st);
-        BLD_TRY(hipMemcpyAsync(&nn, pos + nk, 8, hipMemcpyDeviceToHost, st));
-        BLD_TRY(hipStreamSynchronize(st));
-        if (nn > 0) {
-            KT *np = nullptr;
-            BLD_TRY(hipMalloc((void **)&np, (size_t)nn * sizeof(KT)));
-            S->nopred_keys = np;
-            hipLaunchKernelGGL(k_bld_compact<KT>, dim3(grid_for(nk)), dim3(256), 0, st, km, flag, pos, nk, np);
-        }
-        BLD_TRY(hipStreamSynchronize(st));
     }
-    S->nk = nk; S->ng = ng; S->n_nopred = nn;
 fail:
     (void)hipFree(d_text); (void)hipFree(d_packed); (void)hipFree(ws); (void)hipFree(d_cnt); (void)hipFree(keys); (void)hipFree(keys2);
-    (void)hipFree(tmp); (void)hipFree(flag); (void)hipFree(pos); (void)hipFree(bsum); (void)hipFree(gstart); (void)hipFree(gsuf);
-    if (err != hipSuccess) { (void)hipGetLastError(); return err == hipErrorOutOfMemory ? -8 : -3; }
-    return 0;
+    (void)hipFree(tmp); (void)hipFree(flag); (void)hipFree(pos); (void)hipFree(bsum);
+    if (err != hipSuccess) { (void)hipFree(km); (void)hipGetLastError(); return err == hipErrorOutOfMemory ? -8 : -3; }
+    return build_tail<KT>(km, nk, k, S, st);
 }
 int sbwt_build_phase_a(const char *h_text, long long n_text, int k, int rc, SbwtBuildState *S, hipStream_t st) {
     S->key_bytes = k <= 32 ? 8 : 16;

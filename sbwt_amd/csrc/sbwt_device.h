@@ -289,6 +289,9 @@ struct SbwtBuildState {
     void *nopred_keys = nullptr;                 // the k-mers without a predecessor
 };
 int sbwt_build_phase_a(const char *h_text, long long n_text, int k, int rc, SbwtBuildState *S, hipStream_t st);
+// phase A's tail on its own: from nk sorted distinct keys on the device (8 bytes each for k <= 32, else 16; S takes the
+// allocation over, also when the call fails) to the same state phase A leaves -- what a set operation hands its result to
+int sbwt_build_from_keys(void *d_km, long long nk, int k, SbwtBuildState *S, hipStream_t st);
 int sbwt_build_copy_nopred(const SbwtBuildState *S, void *h_keys);
 int sbwt_build_phase_b(SbwtBuildState *S, const void *h_ddata, const unsigned *h_dedges, long long nd, int ssup,
                        unsigned long long *h_rows, hipStream_t st);

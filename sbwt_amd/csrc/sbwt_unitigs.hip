@@ -26,6 +26,7 @@
 // sector whether it carries one byte or four, so the array would add a 4-byte write and a 4-byte read per column on top of the
 // same number of scattered stores (and a search for the unitig of every output byte).
 #include "sbwt_kernels_common.h"
+#include "sbwt_colwalk.h"
 #include "sbwt_scan.h"
 #include "sbwt_unitigs.h"
 
@@ -34,25 +35,9 @@
 #define UT_RANKED 1u        //           { head, rank, -, UT_RANKED }
 #define UT_DUMMY 2u         //           not a real column
 
-__device__ __forceinline__ int ut_last_char(const SbwtIndexView &ix, i64 v) {
-    return (v >= ix.C[1]) + (v >= ix.C[2]) + (v >= ix.C[3]);
-}
 __device__ __forceinline__ bool ut_mark(const u64 *__restrict__ marks, i64 j) { return (marks[j >> 6] >> (j & 63)) & 1ull; }
-__device__ __forceinline__ unsigned char ut_level(int depth) { return (unsigned char)(depth % 254 + 1); }
-
 // ---- pass 1 ----
-template <bool MEGA>
-__global__ void __launch_bounds__(256) k_ut_pred(SbwtIndexView ix, unsigned *__restrict__ pred) {
-    const i64 u = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (u >= ix.n_nodes) return;
-    if (u == 0) pred[0] = 0;                                 // nothing enters the root
-    const uint4 *blk = ix.blocks + ((u >> 6) << 2);
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const uint4 q = blk[c];
-        if ((quad_bits(q) >> (u & 63)) & 1ull) pred[quad_rank<MEGA>(ix, q, u, c)] = (unsigned)u;
-    }
-}
+// (k_ut_pred: sbwt_colwalk.h)
 // the marks of the blocks: quads 0 and 1 hold the two halves of a block's word
 __global__ void __launch_bounds__(256) k_ut_marks_copy(SbwtIndexView ix, u64 *__restrict__ marks, i64 n_words) {
     const i64 b = (i64)blockIdx.x * 256 + threadIdx.x;
@@ -84,22 +69,7 @@ __global__ void __launch_bounds__(256) k_ut_marks_derive(SbwtIndexView ix, const
 }
 
 // ---- pass 2 ----
-// round r: the dummies of depth r hand level r + 1 to their children.  A level is stored modulo 254, which a child's one
-// depth makes unambiguous: a column that a later round takes for its own again only repeats the stores it made before.
-template <bool MEGA>
-__global__ void __launch_bounds__(256) k_ut_level(SbwtIndexView ix, unsigned char *__restrict__ lev, int r) {
-    const i64 u = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (u >= ix.n_nodes) return;
-    if (r == 0 && u == 0) lev[0] = ut_level(0);
-    if (u == 0 ? r % 254 != 0 : lev[u] != ut_level(r)) return;
-    const unsigned char next = ut_level(r + 1);
-    const uint4 *blk = ix.blocks + ((u >> 6) << 2);
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const uint4 q = blk[c];
-        if ((quad_bits(q) >> (u & 63)) & 1ull) lev[quad_rank<MEGA>(ix, q, u, c)] = next;
-    }
-}
+// (k_ut_level: sbwt_colwalk.h)
 
 // ---- pass 3 ----
 // is the one edge out of column p internal?  (p real, a group of its own, one set bit)

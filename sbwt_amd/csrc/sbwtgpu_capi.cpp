@@ -21,6 +21,7 @@
 #include "sbwt_device.h"
 #include "sbwt_ms.h"
 #include "sbwt_unitigs.h"
+#include "sbwt_setops.h"
 
 namespace {
 
@@ -2714,6 +2715,143 @@ int sbwtgpu_unitigs_stats(const sbwtgpu_unitigs *u, double pass_ms[6], int64_t *
     if (pass_ms)
         for (int i = 0; i < SBWT_UT_N_PASSES; i++) pass_ms[i] = (double)u->run.ms[i];
     if (jump_rounds) *jump_rounds = u->run.jump_rounds;
+    return SBWTGPU_OK;
+}
+
+// ---- set operations (sbwt_setops.hip) ---------------------------------------------------------------
+}  // extern "C"
+namespace {
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+// what the label extraction needs of an index: the unitig pass's conditions, and a key of 64 or 128 bits
+int setop_check_index(const sbwtgpu_index *idx, const char *who) {
+    if (idx->h.rank_only) return fail(SBWTGPU_ERR_INVALID_ARG, "%s", RANK_ONLY_MSG);
+    if (idx->h.k < 2 || idx->h.k > 64)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "%s: k = %lld, the keys of the device builder hold 2 <= k <= 64", who, (long long)idx->h.k);
+    if (idx->h.n_nodes >= ((int64_t)1 << 32) - ((int64_t)1 << 24))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "%s: columns are 32-bit unsigned values (%lld columns)", who, (long long)idx->h.n_nodes);
+    return SBWTGPU_OK;
+}
+int setop_check_pair(const sbwtgpu_index *a, const sbwtgpu_index *b, int op) {
+    if (!a || !b) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    if (op < SBWTGPU_SETOP_UNION || op > SBWTGPU_SETOP_SYMMETRIC_DIFFERENCE)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "set operation %d: 0 union, 1 intersection, 2 difference, 3 symmetric difference", op);
+    if (a->h.k != b->h.k)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "set operation: the indexes differ in k (%lld and %lld)", (long long)a->h.k, (long long)b->h.k);
+    if (a->device != b->device)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "set operation: the indexes are on different devices (%d and %d)", a->device, b->device);
+    int rc = setop_check_index(a, "set operation, a");
+    if (rc == SBWTGPU_OK && b != a) rc = setop_check_index(b, "set operation, b");
+    return rc;
+}
+int setop_hip_fail(hipError_t e, const char *what) {
+    (void)hipGetLastError();
+    return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "set operation, %s: %s", what, hipGetErrorString(e));
+}
+// keys of a, keys of b, merge + select.  With d_res: the result's keys (a device allocation the caller owns).
+int setop_merge(const sbwtgpu_index *a, const sbwtgpu_index *b, int op, hipStream_t st, void **d_res, sbwtgpu_setop_info *info) {
+    DevBuf ka, kb;
+    long long na = 0, nb = 0;
+    const int key_bytes = a->h.k <= 32 ? 8 : 16;
+    auto t0 = std::chrono::steady_clock::now();
+    hipError_t e = sbwt_setops_keys(a->view(), &ka.p, &na, st);
+    if (e != hipSuccess) return setop_hip_fail(e, "keys of a");
+    info->pass_ms[0] = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    if (b != a) {
+        e = sbwt_setops_keys(b->view(), &kb.p, &nb, st);
+        if (e != hipSuccess) return setop_hip_fail(e, "keys of b");
+    } else {
+        nb = na;
+    }
+    info->pass_ms[1] = ms_since(t0);
+    if (na + nb >= ((int64_t)1 << 32) - ((int64_t)1 << 24))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "set operation: %lld + %lld k-mers exceed the 2^32 work-items of one launch", na, nb);
+    t0 = std::chrono::steady_clock::now();
+    SbwtSetopCounts c;
+    e = sbwt_setops_merge(ka.p, na, b != a ? kb.p : ka.p, nb, key_bytes, op, d_res, &c, st);
+    if (e != hipSuccess) return setop_hip_fail(e, "merge");
+    info->pass_ms[2] = ms_since(t0);
+    info->n_a = c.n_a; info->n_b = c.n_b; info->n_both = c.n_both; info->n_either = c.n_either; info->n_result = c.n_result;
+    return SBWTGPU_OK;
+}
+}  // namespace
+extern "C" {
+
+int sbwtgpu_index_setop(const sbwtgpu_index *a, const sbwtgpu_index *b, int op, int build_streaming_support,
+                        sbwtgpu_plain_matrix_bits *out, sbwtgpu_setop_info *info) {
+    sbwtgpu_setop_info local;
+    if (!info) info = &local;
+    memset(info, 0, sizeof(*info));
+    if (!out) return fail(SBWTGPU_ERR_INVALID_ARG, "out is NULL");
+    memset(out, 0, sizeof(*out));
+    int rc = setop_check_pair(a, b, op);
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(a->device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", a->device);
+    Stream st;
+    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    const int64_t k = a->h.k;
+    void *d_res = nullptr;
+    rc = setop_merge(a, b, op, st.s, &d_res, info);
+    if (rc != SBWTGPU_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    SbwtBuildState S;
+    try {
+        const int ra = sbwt_build_from_keys(d_res, info->n_result, (int)k, &S, st.s);       // (S owns d_res now)
+        if (ra != 0) { sbwt_build_release(&S); return fail(ra == -8 ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "set operation: builder tail"); }
+        info->n_nopred = S.n_nopred;
+        if ((long long)S.n_nopred * (long long)k > (1ll << 26)) {
+            sbwt_build_release(&S);
+            return fail(SBWTGPU_ERR_OOM, "set operation: the result has %lld predecessor-less k-mers x k = %lld dummy records (limit 2^26; "
+                        "the dummies are expanded on the host).  Intersections and differences of fragmented sets reach this limit "
+                        "sooner than genomes do: dump the unitigs of both indexes and use the host builder",
+                        (long long)S.n_nopred, (long long)S.n_nopred * (long long)k);
+        }
+        rc = (k <= 32) ? build_columns_t<unsigned long long>(S, k, build_streaming_support, out)
+                       : build_columns_t<unsigned __int128>(S, k, build_streaming_support, out);
+    } catch (const std::bad_alloc &) {
+        sbwt_build_release(&S);
+        rc = fail(SBWTGPU_ERR_OOM, "out of host memory");
+    }
+    info->pass_ms[3] = ms_since(t0);
+    return rc;
+}
+
+int sbwtgpu_index_setop_counts(const sbwtgpu_index *a, const sbwtgpu_index *b, sbwtgpu_setop_info *info) {
+    if (!info) return fail(SBWTGPU_ERR_INVALID_ARG, "info is NULL");
+    memset(info, 0, sizeof(*info));
+    int rc = setop_check_pair(a, b, SBWTGPU_SETOP_UNION);
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(a->device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", a->device);
+    Stream st;
+    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    return setop_merge(a, b, SBWTGPU_SETOP_UNION, st.s, nullptr, info);
+}
+
+int sbwtgpu_index_kmer_keys(const sbwtgpu_index *idx, void *out_keys, int64_t cap_bytes, int64_t *n_keys, int *key_bytes) {
+    if (!idx) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    if (cap_bytes < 0 || (!out_keys && cap_bytes > 0)) return fail(SBWTGPU_ERR_INVALID_ARG, "out_keys is NULL");
+    int rc = setop_check_index(idx, "k-mer keys");
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(idx->device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", idx->device);
+    Stream st;
+    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    DevBuf keys;
+    long long n = 0;
+    const int kb = idx->h.k <= 32 ? 8 : 16;
+    hipError_t e = sbwt_setops_keys(idx->view(), &keys.p, &n, st.s);
+    if (e != hipSuccess) return setop_hip_fail(e, "keys");
+    if (n_keys) *n_keys = n;
+    if (key_bytes) *key_bytes = kb;
+    if (!out_keys && cap_bytes == 0) return SBWTGPU_OK;
+    if (cap_bytes < n * kb)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "k-mer keys: %lld keys of %d bytes need %lld bytes, cap_bytes is %lld", n, kb, n * kb,
+                    (long long)cap_bytes);
+    if (n > 0) HIP_TRY(hipMemcpy(out_keys, keys.p, (size_t)(n * kb), hipMemcpyDeviceToHost));
     return SBWTGPU_OK;
 }
 
