@@ -108,7 +108,12 @@ int         sbwtgpu_device_count(int *count);
  *   "debug"           kernel experiment bits (0 = product behaviour); fused kernel: 32 = no anchors / seeds / resumed compares,
  *                     64 = the k > 31 walk (F_CMP) for every k
  *   "poison_results"  1: every search first fills its result range with 0xA5, every matching-statistics call its len range
- *                        with 0xFF and its interval range with 0xA5 (parity tests)
+ *                        with 0xFF and its interval range with 0xA5, every read-hits call its records with 0xA5 (parity tests)
+ *   "read_hits_wave_min"    per-read hit profiles: reads of this many windows or more are reduced by a whole wave, shorter
+ *                        ones by one lane each (default 1024; < 1 restores the default)
+ *   "read_hits_chunk_bases" sbwtgpu_read_hits_batch cuts its batch into chunks of whole reads of at most this many bases (a
+ *                        chunk always takes one read); 0 (default) = 64 Mi
+ *   "read_hits_wide"     1: the read-hits calls take the int64 search route also on indexes of fewer than 2^31 columns (tests)
  *   "trans_ext", "trans_wide"   accepted and ignored (round-2 table formats)
  * Read when an index is CREATED (derived acceleration structures inside the device image; environment
  * variables of the same meaning: SBWTGPU_SPARSE_PRECALC, SBWTGPU_PROBE_FILTER, SBWTGPU_PATH_ORDER):
@@ -449,6 +454,48 @@ int  sbwtgpu_index_setop_counts(const sbwtgpu_index *a, const sbwtgpu_index *b, 
  * *n_keys and *key_bytes are set whenever the extraction ran; cap_bytes < n_keys x key_bytes: SBWTGPU_ERR_INVALID_ARG and
  * nothing is written to out_keys (out_keys = NULL with cap_bytes = 0 asks for the two numbers). */
 int  sbwtgpu_index_kmer_keys(const sbwtgpu_index *idx, void *out_keys, int64_t cap_bytes, int64_t *n_keys, int *key_bytes);
+
+/* ---- per-read hit profiles: counts, covered bases, longest run ----
+ * What a screen of reads against an index needs: a handful of numbers per read instead of one value per k-mer (16 bytes per
+ * read instead of 4 or 8 per window over PCIe and into the output file).
+ *
+ * Read r has L bases and m = max(0, L - k + 1) windows.
+ *   hits      strands = 1 (forward): hit[i] = 1 exactly where SBWT::search of window i is >= 0 -- the rule of
+ *             sbwtgpu_search_batch: any byte other than upper-case A/C/G/T in the window means no hit.
+ *             strands = 2 (either strand): hit[i] = forward hit, OR the reverse complement of window i is indexed.  The
+ *             complement is A<->T, C<->G on upper-case bytes only; a window holding any other byte is no hit on either strand.
+ *   record    four int32_t per read, in read order:
+ *             n_kmers       = m
+ *             n_found       = the sum of hit[i]
+ *             covered_bases = the size of the union over hits i of [i, i + k); equivalently the sum over hits i of
+ *                             min(k, next_hit(i) - i), with next_hit = +infinity for the last hit
+ *             longest_run   = the largest number of consecutive hits; the longest exact match of at least k bases is
+ *                             longest_run + k - 1 when longest_run > 0
+ *             A read with m = 0 gives {0, 0, 0, 0}.
+ * The search kernels are used as they are (int32 results below 2^31 columns, int64 above; the per-k-mer search semantics, with
+ * or without suffix-group marks); new kernels turn their results into one bit per window and the bits into records.  For
+ * strands = 2 the whole base buffer is reverse-complemented once and searched as a mirrored batch into the same result buffer.
+ * Rank-only indexes: SBWTGPU_ERR_INVALID_ARG.  The result does not depend on tuning, image level or chunking. */
+typedef struct { int32_t n_kmers, n_found, covered_bases, longest_run; } sbwtgpu_read_hits;
+/* Host buffers: read r = bases[read_off[r] .. read_off[r+1]), out[r] its record.  The batch is cut into chunks of whole reads
+ * (tuning "read_hits_chunk_bases"), so device memory is bounded whatever the batch size (a single read longer than the budget
+ * is a chunk of its own); only bases and offsets go to the device and only records come back.  Thread-safe on one handle like
+ * the search entry points.  A read of 2^31 bases or more: SBWTGPU_ERR_READ_TOO_LONG. */
+int     sbwtgpu_read_hits_batch(const sbwtgpu_index *idx, const char *bases, const int64_t *read_off, int64_t n_reads,
+                                int strands, sbwtgpu_read_hits *out);
+/* Device buffers, one pass over the batch, asynchronous on `stream`, never synchronises.  d_bases holds total_bases bases and
+ * d_read_off (n_reads + 1 entries, non-decreasing, d_read_off[n_reads] <= total_bases; d_read_off[0] need not be 0) are
+ * offsets into it, as for sbwtgpu_search_dev; the other preconditions are those of the "_dev" search calls, and n_reads < 2^31.
+ * d_out: n_reads records.  The workspace (16-byte aligned) holds the search workspace, the result buffer (8 bytes per base),
+ * the bit vector, the result offsets -- computed on the device from d_read_off and k -- and, for two strands, the mirrored
+ * bases and offsets: about 10.2 (11.2) bytes per base + 24 (40) per read.  Its size is non-decreasing in total_bases and in
+ * n_reads; a workspace that is too small is SBWTGPU_ERR_INVALID_ARG.  sbwtgpu_workspace_status on the workspace reports the
+ * status word of the call's last search.  Calls on different streams may run concurrently on one handle when each has its
+ * own workspace and records. */
+int64_t sbwtgpu_read_hits_workspace_bytes(int64_t total_bases, int64_t n_reads, int strands);
+int     sbwtgpu_read_hits_dev(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                              int64_t n_reads, int strands, sbwtgpu_read_hits *d_out, void *d_workspace,
+                              int64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

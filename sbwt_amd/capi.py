@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_unitigs_create", "sbwtgpu_unitigs_info", "sbwtgpu_unitigs_dev", "sbwtgpu_unitigs_copy", "sbwtgpu_unitigs_stats",
     "sbwtgpu_unitigs_destroy",
     "sbwtgpu_index_setop", "sbwtgpu_index_setop_counts", "sbwtgpu_index_kmer_keys",
+    "sbwtgpu_read_hits_batch", "sbwtgpu_read_hits_workspace_bytes", "sbwtgpu_read_hits_dev",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -185,6 +186,10 @@ def lib() -> C.CDLL:
         L.sbwtgpu_index_setop.argtypes = [vp, vp, ci, ci, C.POINTER(PlainMatrixBitsC), C.POINTER(SetopInfoC)]
         L.sbwtgpu_index_setop_counts.argtypes = [vp, vp, C.POINTER(SetopInfoC)]
         L.sbwtgpu_index_kmer_keys.argtypes = [vp, vp, i64, C.POINTER(i64), C.POINTER(ci)]
+        L.sbwtgpu_read_hits_batch.argtypes = [vp, vp, vp, i64, ci, vp]
+        L.sbwtgpu_read_hits_workspace_bytes.argtypes = [i64, i64, ci]
+        L.sbwtgpu_read_hits_workspace_bytes.restype = i64
+        L.sbwtgpu_read_hits_dev.argtypes = [vp, vp, i64, vp, i64, ci, vp, vp, i64, vp]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -574,6 +579,28 @@ class Index:
         out = out[: n.value * kb.value // 8]
         return out if kb.value == 8 else out.reshape(n.value, 2)
 
+    # ---- per-read hit profiles (include/sbwtgpu.h) ----
+    def read_hits(self, bases, read_off, both_strands: bool = False) -> np.ndarray:
+        """sbwtgpu_read_hits_batch: an (n_reads, 4) int32 array of (n_kmers, n_found, covered_bases, longest_run) per read."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        n = max(len(read_off) - 1, 0)
+        out = np.full((n, 4), -12345, dtype=np.int32)
+        _check(lib().sbwtgpu_read_hits_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n, 2 if both_strands else 1,
+                                             out.ctypes.data))
+        return out
+
+    def read_hits_reads(self, reads: Sequence[bytes], both_strands: bool = False) -> np.ndarray:
+        """The same for a list of byte strings."""
+        bases, off = concat_reads(reads)
+        return self.read_hits(bases, off, both_strands)
+
+    def read_hits_dev(self, d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_out: int, d_ws: int, ws_bytes: int,
+                      both_strands: bool = False, stream: int = 0):
+        """sbwtgpu_read_hits_dev (raw device pointers; d_out: n_reads records of four int32)."""
+        _check(lib().sbwtgpu_read_hits_dev(self._h, d_bases, total_bases, d_read_off, n_reads, 2 if both_strands else 1, d_out,
+                                           d_ws, ws_bytes, stream))
+
     def workspace_status(self, d_ws: int, stream: int = 0) -> int:
         st = C.c_int(0)
         _check(lib().sbwtgpu_workspace_status(d_ws, stream, C.byref(st)))
@@ -642,3 +669,7 @@ def search_workspace_bytes(total_bases: int) -> int:
 
 def ms_workspace_bytes(total_bases: int) -> int:
     return int(lib().sbwtgpu_ms_workspace_bytes(total_bases))
+
+
+def read_hits_workspace_bytes(total_bases: int, n_reads: int, both_strands: bool = False) -> int:
+    return int(lib().sbwtgpu_read_hits_workspace_bytes(total_bases, n_reads, 2 if both_strands else 1))

@@ -455,6 +455,11 @@ public:
                                    int64_t *second) const {
         detail::gpu_check(sbwtgpu_matching_statistics_batch(need_device(), bases, read_off, n_reads, len, first, second));
     }
+    // per-read hit profiles (include/sbwtgpu.h): out[r] = { n_kmers, n_found, covered_bases, longest_run } of read r;
+    // strands = 1: forward hits, 2: a window also hits when its reverse complement is indexed
+    void read_hits_batch(const char *bases, const int64_t *read_off, int64_t n_reads, int strands, sbwtgpu_read_hits *out) const {
+        detail::gpu_check(sbwtgpu_read_hits_batch(need_device(), bases, read_off, n_reads, strands, out));
+    }
     // the unitigs of the index (include/sbwtgpu.h): unitig i is bases[off[i] .. off[i+1]) and starts with the label of column
     // first_col[i]; ascending first_col
     struct Unitigs { std::vector<char> bases; std::vector<int64_t> off, first_col; };

@@ -678,6 +678,91 @@ int matching_statistics_main(int argc, char **argv) {
     return 0;
 }
 
+// sbwt read-hits: one line per read, `n_kmers n_found covered_bases longest_run` (include/sbwtgpu.h: the profile a screen of
+// reads against the index needs, 16 bytes per read from the GPU instead of a value per k-mer).  Batches go to the GPU one at a
+// time; the table is formatted on the host.
+int read_hits_main(int argc, char **argv) {
+    int64_t micros_start = cur_time_micros();
+    set_log_level(LogLevel::MINOR);
+    Options opts({
+        {"out-file", 'o', true, "Output filename (a list of output files if the query file is a .txt list).", ""},
+        {"index-file", 'i', true, "Index input file.", ""},
+        {"query-file", 'q', true,
+         "The query in FASTA or FASTQ format, possibly gzipped. If the file extension is .txt, this is interpreted as a "
+         "list of query files, one per line, and --out-file as a list of output files.", ""},
+        {"gzip-output", 'z', false, "Writes output in gzipped form.", ""},
+        {"both-strands", 0, false, "A k-mer also counts as found when its reverse complement is in the index.", ""},
+        {"gpu", 0, true, "HIP device to run on.", "0"},
+        {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
+        {"help", 'h', false, "Print usage", ""},
+    });
+    opts.parse(argc, argv);
+    if (argc == 1 || opts.count("help")) {
+        std::cerr << opts.help(argv[0], "Per read: k-mers, k-mers found in the index, bases they cover, longest run of found k-mers.") << std::endl;
+        exit(1);
+    }
+    const string indexfile = opts.get("index-file");
+    check_readable(indexfile);
+    const string queryfile = opts.get("query-file"), outfile = opts.get("out-file");
+    const bool multi_file = queryfile.size() >= 4 && queryfile.substr(queryfile.size() - 4) == ".txt";
+    const vector<string> input_files = multi_file ? readlines(queryfile) : vector<string>{queryfile};
+    const vector<string> output_files = multi_file ? readlines(outfile) : vector<string>{outfile};
+    for (const string &file : input_files) check_readable(file);
+    for (const string &file : output_files) check_writable(file);
+    if (input_files.size() != output_files.size())
+        throw std::runtime_error("Number of input and output files does not match (" + std::to_string(input_files.size()) +
+                                 " vs " + std::to_string(output_files.size()) + ")");
+    const bool gzip_output = opts.count("gzip-output");
+    const int strands = opts.count("both-strands") ? 2 : 1;
+    set_default_device(atoi(opts.get("gpu").c_str()));
+    int64_t batch_bases = atoll(opts.get("batch-bases").c_str());
+    if (batch_bases < 1) batch_bases = 1;
+
+    std::ifstream in(indexfile, std::ios::binary);
+    if (!in.good()) throw std::runtime_error("Error opening file: " + indexfile);
+    const string variant = load_string(in);
+    if (variant != "plain-matrix")
+        throw std::runtime_error("Error: only the plain-matrix variant is supported by the GPU search path (got " + variant + ")");
+    plain_matrix_sbwt_t index;
+    index.load(in);
+    int64_t total_reads = 0;
+    for (size_t f = 0; f < input_files.size(); f++) {
+        write_log("Running read-hits from input file " + input_files[f] + " to output file " + output_files[f], LogLevel::MAJOR);
+        seq_io::Reader reader(input_files[f]);
+        seq_io::Buffered_ofstream writer(output_files[f], gzip_output);
+        bool more = true;
+        vector<char> bases;
+        vector<int64_t> read_off;
+        vector<sbwtgpu_read_hits> rec;
+        string text;
+        while (more) {
+            bases.clear();
+            read_off.assign(1, 0);
+            more = reader.read_batch(bases, read_off, batch_bases);
+            const int64_t n_reads = (int64_t)read_off.size() - 1;
+            if (n_reads <= 0) continue;
+            rec.resize((size_t)n_reads);
+            index.read_hits_batch(bases.data(), read_off.data(), n_reads, strands, rec.data());
+            text.clear();
+            for (const sbwtgpu_read_hits &h : rec) {
+                append_int(h.n_kmers, text);
+                text.push_back(' ');
+                append_int(h.n_found, text);
+                text.push_back(' ');
+                append_int(h.covered_bases, text);
+                text.push_back(' ');
+                append_int(h.longest_run, text);
+                text.push_back('\n');
+            }
+            writer.write(text.data(), (int64_t)text.size());
+            total_reads += n_reads;
+        }
+    }
+    write_log("us/read end-to-end: " + std::to_string((double)(cur_time_micros() - micros_start) / (double)std::max<int64_t>(1, total_reads)),
+              LogLevel::MAJOR);
+    return 0;
+}
+
 // sbwt dump-unitigs: the index turned back into sequence -- FASTA, one record per unitig in the order of the API (ascending
 // first column), the header the unitig's number
 int dump_unitigs_main(int argc, char **argv) {
@@ -799,7 +884,7 @@ int set_op_main(int argc, char **argv) {
     return 0;
 }
 
-const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "set-op"};
+const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "set-op", "read-hits"};
 
 void print_help(char **argv) {
     std::cerr << "Available commands: " << std::endl;
@@ -831,6 +916,7 @@ int main(int argc, char **argv) {   // sbwt.cpp:19-57
         else if (command == "matching-statistics") return matching_statistics_main(argc, argv);
         else if (command == "dump-unitigs") return dump_unitigs_main(argc, argv);
         else if (command == "set-op") return set_op_main(argc, argv);
+        else if (command == "read-hits") return read_hits_main(argc, argv);
         else throw std::runtime_error("Invalid command: " + command);
     } catch (const std::runtime_error &e) {
         std::cerr << "Runtime error: " << e.what() << '\n';

@@ -22,6 +22,7 @@
 #include "sbwt_ms.h"
 #include "sbwt_unitigs.h"
 #include "sbwt_setops.h"
+#include "sbwt_readhits.h"
 
 namespace {
 
@@ -163,6 +164,11 @@ static int g_path_stitch_min = [] { const char *e = getenv("SBWTGPU_PATH_STITCH_
 // 100 for k <= 31 (round 5, one box: config 2 4.74 vs 4.90 ms, config 3 6.39 vs 6.54 ms -- the smaller table is no slower), 125 where
 // whole k-mers take two levels (k = 63: 4.18 ms at 125, 4.26 at 110, 4.29 at 100)
 static int g_sparse_buckets_pct = [] { const char *e = getenv("SBWTGPU_SPARSE_BUCKETS_PCT"); int v = e ? atoi(e) : 0; return v <= 0 ? 0 : v < 60 ? 60 : v > 400 ? 400 : v; }();
+// per-read hit profiles (sbwt_readhits.hip): reads of this many windows or more are reduced by a wave instead of a lane; the
+// host entry point's chunk budget in bases (0: 64 Mi); 1: int64 results on indexes that would take int32 (tests)
+static int g_rh_wave_min = SBWT_RH_WAVE_MIN;
+static int64_t g_rh_chunk_bases = 0;
+static int g_rh_wide = 0;
 static int g_sparse_depth = [] { const char *e = getenv("SBWTGPU_SPARSE_PRECALC"); return e ? atoi(e) : 31; }();
 
 struct sbwtgpu_index {
@@ -264,6 +270,9 @@ int sbwtgpu_set_tuning(const char *key, int64_t value) {
     if (!strcmp(key, "split_long")) { g_split_long = (int)value; return SBWTGPU_OK; }
     if (!strcmp(key, "path_stitch")) { g_path_stitch = (int)value; return SBWTGPU_OK; }   // indexes created afterwards
     if (!strcmp(key, "path_stitch_min")) { g_path_stitch_min = (int)value < 1 ? 1 : (int)value; return SBWTGPU_OK; }
+    if (!strcmp(key, "read_hits_wave_min")) { g_rh_wave_min = value < 1 ? SBWT_RH_WAVE_MIN : value > 0x7fffffff ? 0x7fffffff : (int)value; return SBWTGPU_OK; }
+    if (!strcmp(key, "read_hits_chunk_bases")) { g_rh_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
+    if (!strcmp(key, "read_hits_wide")) { g_rh_wide = (int)value; return SBWTGPU_OK; }
     if (!strcmp(key, "sparse_depth")) {      // takes effect for indexes created afterwards
         if (value < 0 || value > 31) return fail(SBWTGPU_ERR_INVALID_ARG, "sparse_depth must be in [0,31]");
         g_sparse_depth = (int)value;
@@ -2715,6 +2724,208 @@ int sbwtgpu_unitigs_stats(const sbwtgpu_unitigs *u, double pass_ms[6], int64_t *
     if (pass_ms)
         for (int i = 0; i < SBWT_UT_N_PASSES; i++) pass_ms[i] = (double)u->run.ms[i];
     if (jump_rounds) *jump_rounds = u->run.jump_rounds;
+    return SBWTGPU_OK;
+}
+
+// ---- per-read hit profiles (sbwt_readhits.hip) --------------------------------------------------------
+static_assert(sizeof(sbwtgpu_read_hits) == sizeof(SbwtReadHits), "the record of the ABI is the kernels' record");
+
+int64_t sbwtgpu_read_hits_workspace_bytes(int64_t total_bases, int64_t n_reads, int strands) {
+    if (total_bases < 0) total_bases = 0;
+    if (n_reads < 0) n_reads = 0;
+    return sbwt_rh_layout(sbwtgpu_search_workspace_bytes(total_bases), total_bases, n_reads, strands == 2 ? 2 : 1).total;
+}
+
+static int read_hits_check(const sbwtgpu_index *idx, int64_t n_reads, int strands) {
+    if (!idx) return fail(SBWTGPU_ERR_INVALID_ARG, "idx is NULL");
+    if (idx->h.rank_only) return fail(SBWTGPU_ERR_INVALID_ARG, "%s", RANK_ONLY_MSG);
+    if (strands != 1 && strands != 2) return fail(SBWTGPU_ERR_INVALID_ARG, "strands must be 1 (forward) or 2 (either strand), not %d", strands);
+    if (n_reads < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative n_reads");
+    if (n_reads >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_INVALID_ARG, "2^31 reads or more in one call: split the batch");
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_read_hits_dev(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                          int64_t n_reads, int strands, sbwtgpu_read_hits *d_out, void *d_ws, int64_t ws_bytes, void *stream) {
+    int rc = read_hits_check(idx, n_reads, strands);
+    if (rc != SBWTGPU_OK) return rc;
+    if (total_bases < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative size");
+    if (total_bases >= ((int64_t)1 << 36))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "more than 2^36 bases in one call: split the batch");
+    const int64_t need = sbwtgpu_read_hits_workspace_bytes(total_bases, n_reads, strands);
+    if (!d_ws || ws_bytes < need)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "workspace missing or too small (%lld < %lld)", (long long)ws_bytes, (long long)need);
+    if (((uintptr_t)d_ws & 15) != 0) return fail(SBWTGPU_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+    if (n_reads == 0) return SBWTGPU_OK;
+    if (!d_read_off || !d_out || (total_bases > 0 && !d_bases)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
+    DeviceGuard guard(idx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t search_ws = sbwtgpu_search_workspace_bytes(total_bases);
+    const SbwtRhLayout L = sbwt_rh_layout(search_ws, total_bases, n_reads, strands);
+    char *w = static_cast<char *>(d_ws);
+    SbwtRhHeader *hdr = reinterpret_cast<SbwtRhHeader *>(w + L.hdr);
+    int64_t *res = reinterpret_cast<int64_t *>(w + L.res);
+    unsigned long long *bits = reinterpret_cast<unsigned long long *>(w + L.bits);
+    long long *ooff = reinterpret_cast<long long *>(w + L.ooff);
+    // int32 results where the index allows them: half the bytes written and read back ("read_hits_wide": tests of the other)
+    const int wide = (idx->h.n_nodes >= ((int64_t)1 << 31) || g_rh_wide) ? 1 : 0;
+    const int k = (int)idx->h.k;
+    HIP_TRY(hipMemsetAsync(hdr, 0, sizeof(SbwtRhHeader), st));
+    if (g_poison) HIP_TRY(hipMemsetAsync(d_out, 0xA5, (size_t)n_reads * sizeof(sbwtgpu_read_hits), st));
+    sbwt_launch_rh_offsets(reinterpret_cast<const long long *>(d_read_off), n_reads, k, reinterpret_cast<long long *>(w + L.cnt),
+                           reinterpret_cast<long long *>(w + L.bsum), ooff, st);
+    // (a batch of fewer than k bases has no window: nothing to search and no bit to write -- the reducer reads no word of
+    // the bit vector for a read without windows -- and the records are zeros)
+    const bool any = total_bases >= k;
+    const SbwtWorkHeader *sws = reinterpret_cast<const SbwtWorkHeader *>(w);
+    if (any) {
+        t_out32 = wide ? 0 : 1;
+        rc = search_dev_common(idx, d_bases, total_bases, d_read_off, n_reads, res, reinterpret_cast<const int64_t *>(ooff), d_ws,
+                               search_ws, stream, 0);
+        t_out32 = 0;
+        if (rc != SBWTGPU_OK) return rc;
+        sbwt_launch_rh_bits(res, wide, ooff, n_reads, total_bases, 0, bits, sws, hdr, st);
+    }
+    if (strands == 2 && any) {
+        char *rcb = w + L.rc;
+        long long *roff2 = reinterpret_cast<long long *>(w + L.roff2), *ooff2 = reinterpret_cast<long long *>(w + L.ooff2);
+        sbwt_launch_rh_mirror(d_bases, total_bases, reinterpret_cast<const long long *>(d_read_off), ooff, n_reads, rcb, roff2, ooff2, st);
+        t_out32 = wide ? 0 : 1;
+        rc = search_dev_common(idx, rcb, total_bases, reinterpret_cast<const int64_t *>(roff2), n_reads, res,
+                               reinterpret_cast<const int64_t *>(ooff2), d_ws, search_ws, stream, 0);
+        t_out32 = 0;
+        if (rc != SBWTGPU_OK) return rc;
+        sbwt_launch_rh_bits(res, wide, ooff, n_reads, total_bases, 1, bits, sws, hdr, st);
+    }
+    sbwt_launch_rh_reduce(bits, ooff, n_reads, k, g_rh_wave_min, reinterpret_cast<SbwtReadHits *>(d_out), st);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
+    return SBWTGPU_OK;
+}
+
+// Host buffers: the batch is cut into chunks of whole reads of at most "read_hits_chunk_bases" bases (a chunk always takes
+// one read), two chunks in flight on the parked slots of the search pipeline.  Bases and offsets go down, records come back.
+int sbwtgpu_read_hits_batch(const sbwtgpu_index *idx, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
+                            sbwtgpu_read_hits *out) {
+    int rc = read_hits_check(idx, n_reads, strands);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_reads == 0) return SBWTGPU_OK;
+    if (!read_off || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    if (read_off[n_reads] > read_off[0] && !bases) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    const int64_t budget = g_rh_chunk_bases > 0 ? g_rh_chunk_bases : (int64_t)64 << 20, CH_READS = (int64_t)1 << 24;
+    std::vector<int64_t> cuts{0};
+    int64_t max_bases = 0, max_reads = 0;
+    try {
+        for (int64_t lo = 0, r = 0; r < n_reads; r++) {
+            const int64_t len = read_off[r + 1] - read_off[r];
+            if (len < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "read_off is not non-decreasing at read %lld", (long long)r);
+            if (len >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_READ_TOO_LONG, "read %lld has >= 2^31 bases", (long long)r);
+            if (r > lo && (read_off[r + 1] - read_off[lo] > budget || r - lo >= CH_READS)) {
+                cuts.push_back(r);
+                lo = r;
+            }
+            max_bases = std::max(max_bases, read_off[r + 1] - read_off[lo]);
+            max_reads = std::max(max_reads, r + 1 - lo);
+        }
+        cuts.push_back(n_reads);
+    } catch (const std::bad_alloc &) {
+        return fail(SBWTGPU_ERR_OOM, "out of host memory");
+    }
+    const int64_t n_chunks = (int64_t)cuts.size() - 1;
+    const bool pin_in = is_pinned(bases), pin_out = is_pinned(out);
+    const int64_t ws_bytes = sbwtgpu_read_hits_workspace_bytes(max_bases, max_reads, strands);
+    const int64_t need_in = a256(max_bases + 16) + a256((max_reads + 1) * 8);
+    const int64_t need_out = pin_out ? 0 : a256(max_reads * 16);
+    const int64_t need_dev = a256(max_bases + 16) + a256((max_reads + 1) * 8) + a256(max_reads * 16) + a256(ws_bytes);
+    DeviceGuard guard(idx->device);
+    PipeSlot S[2];
+    {
+        std::lock_guard<std::mutex> lock(g_pipe_mutex);
+        for (size_t i = 0; i < g_pipe_parked.size(); i++)
+            if (g_pipe_parked[i].device == idx->device) {
+                S[0] = g_pipe_parked[i].s[0];
+                S[1] = g_pipe_parked[i].s[1];
+                g_pipe_parked.erase(g_pipe_parked.begin() + (long)i);
+                break;
+            }
+    }
+    auto cleanup = [&]() { S[0].release(); S[1].release(); };
+    const int n_slots = n_chunks > 1 ? 2 : 1;
+    for (int q = 0; q < n_slots && rc == SBWTGPU_OK; q++) {
+        PipeSlot &P = S[q];
+        hipError_t e = hipSuccess;
+        if (!P.st) e = hipStreamCreateWithFlags(&P.st, hipStreamNonBlocking);
+        if (e == hipSuccess && !P.h_status) e = hipHostMalloc((void **)&P.h_status, 64, hipHostMallocDefault);
+        if (e == hipSuccess && P.cap_in < need_in) {
+            if (P.h_in) (void)hipHostFree(P.h_in);
+            P.h_in = nullptr; P.cap_in = 0;
+            if ((e = hipHostMalloc((void **)&P.h_in, (size_t)need_in, hipHostMallocDefault)) == hipSuccess) P.cap_in = need_in;
+        }
+        if (e == hipSuccess && P.cap_out < need_out) {
+            if (P.h_out) (void)hipHostFree(P.h_out);
+            P.h_out = nullptr; P.cap_out = 0;
+            if ((e = hipHostMalloc((void **)&P.h_out, (size_t)need_out, hipHostMallocDefault)) == hipSuccess) P.cap_out = need_out;
+        }
+        if (e == hipSuccess && P.cap_dev < need_dev) {
+            if (P.d_mem) (void)hipFree(P.d_mem);
+            P.d_mem = nullptr; P.cap_dev = 0;
+            if ((e = hipMalloc((void **)&P.d_mem, (size_t)need_dev)) == hipSuccess) P.cap_dev = need_dev;
+        }
+        if (e != hipSuccess)
+            rc = fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "read-hits buffers: %s", hipGetErrorString(e));
+    }
+    if (rc != SBWTGPU_OK) { (void)hipGetLastError(); cleanup(); return rc; }
+    int bug = 0;                    // the first nonzero device status of a chunk
+    const int64_t o_roff = a256(max_bases + 16), o_rec = o_roff + a256((max_reads + 1) * 8), o_ws = o_rec + a256(max_reads * 16);
+    auto submit = [&](int64_t c) -> int {
+        PipeSlot &P = S[c % n_slots];
+        const int64_t lo = cuts[(size_t)c], hi = cuts[(size_t)c + 1], nr = hi - lo, nb = read_off[hi] - read_off[lo];
+        int64_t *hro = (int64_t *)(P.h_in + a256(max_bases + 16));
+        for (int64_t r = 0; r <= nr; r++) hro[r] = read_off[lo + r] - read_off[lo];
+        const char *hb = bases + read_off[lo];
+        if (!pin_in && nb > 0) { parallel_memcpy(P.h_in, hb, (size_t)nb); hb = P.h_in; }
+        hipError_t e;
+        if ((nb > 0 && (e = hipMemcpyAsync(P.d_mem, hb, (size_t)nb, hipMemcpyHostToDevice, P.st)) != hipSuccess) ||
+            (e = hipMemcpyAsync(P.d_mem + o_roff, hro, (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, P.st)) != hipSuccess)
+            return fail(SBWTGPU_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
+        const int r2 = sbwtgpu_read_hits_dev(idx, P.d_mem, nb, (const int64_t *)(P.d_mem + o_roff), nr, strands,
+                                             (sbwtgpu_read_hits *)(P.d_mem + o_rec), P.d_mem + o_ws, ws_bytes, P.st);
+        if (r2 != SBWTGPU_OK) return r2;
+        const SbwtRhLayout L = sbwt_rh_layout(sbwtgpu_search_workspace_bytes(nb), nb, nr, strands);
+        char *target = pin_out ? (char *)(out + lo) : P.h_out;
+        if ((e = hipMemcpyAsync(target, P.d_mem + o_rec, (size_t)nr * 16, hipMemcpyDeviceToHost, P.st)) != hipSuccess ||
+            (e = hipMemcpyAsync(P.h_status, P.d_mem + o_ws + L.hdr, 4, hipMemcpyDeviceToHost, P.st)) != hipSuccess)
+            return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
+        return SBWTGPU_OK;
+    };
+    auto collect = [&](int64_t c) -> int {
+        PipeSlot &P = S[c % n_slots];
+        hipError_t e = hipStreamSynchronize(P.st);
+        if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "stream synchronize: %s", hipGetErrorString(e));
+        if (P.h_status[0] != 0 && bug == 0) bug = P.h_status[0];
+        const int64_t lo = cuts[(size_t)c], hi = cuts[(size_t)c + 1];
+        if (!pin_out) memcpy(out + lo, P.h_out, (size_t)(hi - lo) * 16);
+        return SBWTGPU_OK;
+    };
+    for (int64_t c = 0; c < n_chunks && rc == SBWTGPU_OK; c++) {
+        if (c >= 2) rc = collect(c - 2);
+        if (rc == SBWTGPU_OK) rc = submit(c);
+    }
+    for (int64_t c = std::max<int64_t>(0, n_chunks - 2); c < n_chunks && rc == SBWTGPU_OK; c++) rc = collect(c);
+    if (rc != SBWTGPU_OK) {
+        (void)hipDeviceSynchronize();
+        cleanup();
+        return rc;
+    }
+    {
+        std::lock_guard<std::mutex> lock(g_pipe_mutex);
+        ParkedPipe pp;
+        pp.device = idx->device;
+        pp.s[0] = S[0];
+        pp.s[1] = S[1];
+        g_pipe_parked.push_back(pp);
+    }
+    if (bug) return fail_status(bug);
     return SBWTGPU_OK;
 }
 
