@@ -99,40 +99,49 @@ struct DeviceGuard {
     }
 };
 
+template <typename T>
+inline T align256(T x) { return (x + 255) & ~(T)255; }
+
+// a knob's initial value: the environment variable when it is set, else the default
+int env_int(const char *name, int dflt) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+int64_t env_i64(const char *name, int64_t dflt) {
+    const char *e = getenv(name);
+    return e ? (int64_t)atoll(e) : dflt;
+}
+
 }  // namespace
 
 // tuning knobs (A/B experiments; defaults are the shipped configuration)
 // 0 = k_search (reference order), 1 = k_search_cert on the blocks, 4 = k_search_cert along the path order (two passes: encode +
 // search; 2 and 3, kernels of earlier rounds, mean 4 now), 5 = the fused route (k_search_fused + the general kernel behind it)
 static int tuning_variant() {
-    static int v = [] { const char *e = getenv("SBWTGPU_SEARCH_VARIANT"); return e ? atoi(e) : -1; }();
+    static int v = env_int("SBWTGPU_SEARCH_VARIANT", -1);
     return v;
 }
 static int g_variant_override = -1, g_probe_override = -1, g_debug = 0, g_derive_ssup = 1, g_kernel_events = 0;
-// the fused kernel with its lanes sorted by state ("fused_sort": 0 off, 1 on; env SBWTGPU_FUSED_SORT; sbwt_search_fused.hip)
 static int g_fused_table = 1;      // the fused route's ticket table for batches with many long reads ("fused_table")
-static int g_fused_sort = [] { const char *e = getenv("SBWTGPU_FUSED_SORT"); return e ? atoi(e) : SBWT_FUSED_SORT_DEFAULT; }();
+// the fused kernel with its lanes sorted by state ("fused_sort": 0 off, 1 on; env SBWTGPU_FUSED_SORT; sbwt_search_fused.hip)
+static int g_fused_sort = env_int("SBWTGPU_FUSED_SORT", SBWT_FUSED_SORT_DEFAULT);
 // set around a search call by the *_i32 entry points: the kernels of this call write int32 results (SbwtIndexView::out32)
 static thread_local int t_out32 = 0;
 static int64_t g_ev_count = 0;
-// depth of the sparse (hashed) prefix table built at index creation (capped at k and at 31 = one 62-bit key)
 // debug aid for the parity tests: fill the result range with a poison pattern before every search and every
 // matching-statistics call, so that a result the kernel never writes cannot inherit a correct value from an earlier launch
-static int g_poison = [] { const char *e = getenv("SBWTGPU_POISON_RESULTS"); return e ? atoi(e) : 0; }();
-static int g_probe_filter = [] { const char *e = getenv("SBWTGPU_PROBE_FILTER"); return e ? atoi(e) : 1; }();
-static int g_image_level = [] { const char *e = getenv("SBWTGPU_IMAGE_LEVEL"); return e ? atoi(e) : 0; }();
-static int64_t g_max_image_bytes = [] { const char *e = getenv("SBWTGPU_MAX_IMAGE_BYTES"); return e ? (int64_t)atoll(e) : (int64_t)0; }();
-static int g_sort_reads = [] { const char *e = getenv("SBWTGPU_SORT_READS"); return e ? atoi(e) : -1; }();   // -1 auto, 0 off, 1 on
+static int g_poison = env_int("SBWTGPU_POISON_RESULTS", 0);
+static int g_probe_filter = env_int("SBWTGPU_PROBE_FILTER", 1);
+static int g_image_level = env_int("SBWTGPU_IMAGE_LEVEL", 0);
+static int64_t g_max_image_bytes = env_i64("SBWTGPU_MAX_IMAGE_BYTES", 0);
+static int g_sort_reads = env_int("SBWTGPU_SORT_READS", -1);   // -1 auto, 0 off, 1 on
 static int g_force_mega = 0;    // tests: store every image's block counts relative to mega[c][0] (the dense rank-only layout)
-static int g_path_safe = [] { const char *e = getenv("SBWTGPU_PATH_SAFE"); return e ? atoi(e) : 2; }();   // 0 off, 1 narrow rule, 2 wide
-static int g_path_lookahead = [] { const char *e = getenv("SBWTGPU_PATH_LOOKAHEAD"); return e ? atoi(e) : 8; }();   // 0: the blind rule
-static int g_path_order = [] { const char *e = getenv("SBWTGPU_PATH_ORDER"); return e ? atoi(e) : 1; }();
-// the full image (path order, sparse table, filter) for indexes of 2^31 .. 2^32 - 2^24 columns with k <= 31 (round 5): columns
-// and positions as full 32-bit unsigned values, read by k_search_fused<false, false, BIG>.  0: such an index gets blocks +
-// dense table only, as before round 5 (23 G k-mers/s on 2.25 x 10^9 columns)
+static int g_path_safe = env_int("SBWTGPU_PATH_SAFE", 2);   // 0 off, 1 narrow rule, 2 wide
+static int g_path_lookahead = env_int("SBWTGPU_PATH_LOOKAHEAD", 8);   // 0: the blind rule
+static int g_path_order = env_int("SBWTGPU_PATH_ORDER", 1);
 // SBWTGPU_VERBOSE=1: index_create says on stderr which part of the image it is building and how long each took (a build of
 // 10^9 columns takes 10-30 s; a stall names its phase)
-static int g_verbose = [] { const char *e = getenv("SBWTGPU_VERBOSE"); return e ? atoi(e) : 0; }();
+static int g_verbose = env_int("SBWTGPU_VERBOSE", 0);
 struct PhaseLog {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     void operator()(const char *what) {
@@ -146,30 +155,34 @@ struct PhaseLog {
         t0 = t1;
     }
 };
-static int g_big_path = [] { const char *e = getenv("SBWTGPU_BIG_PATH"); return e ? atoi(e) : 1; }();
-// stitched chains (sbwt_derived.hip): 0 = vertex-disjoint paths only; the shortest stretch worth copying
+// the full image (path order, sparse table, filter) for indexes of 2^31 .. 2^32 - 2^24 columns with k <= 31 (round 5): columns
+// and positions as full 32-bit unsigned values, read by k_search_fused<false, false, BIG>.  0: such an index gets blocks +
+// dense table only, as before round 5 (23 G k-mers/s on 2.25 x 10^9 columns)
+static int g_big_path = env_int("SBWTGPU_BIG_PATH", 1);
 // long reads are cut into pieces on the device (SbwtPieceTab); 0: one lane per read whatever its length (tests)
-static int g_split_long = [] { const char *e = getenv("SBWTGPU_SPLIT_LONG"); return e ? atoi(e) : 1; }();
+static int g_split_long = env_int("SBWTGPU_SPLIT_LONG", 1);
 // batches of reads of different lengths through the fused kernel (it fetches their offsets); 0: only reads of one length
-static int g_fused_ragged = [] { const char *e = getenv("SBWTGPU_FUSED_RAGGED"); return e ? atoi(e) : 1; }();
+static int g_fused_ragged = env_int("SBWTGPU_FUSED_RAGGED", 1);
 // reads of more than 160 bases through the fused kernel as up to this many pieces of 160 bases (1: such reads go to the general
 // kernel).  -1 (default) = 3: for 31 < k <= 63 the fused kernel walks with F_CMP (250-base reads 115 -> 243 G k-mers/s, the
 // general kernel has neither bridges nor anchors there); for k <= 31 pieces and the two-pass route came out the same until
 // round 5 made the fused kernel's writer cheaper (250-base reads: 235 vs 228 G, lengths 80-250: 203 vs 200 G, NOTES.md)
-static int g_fused_pieces = [] { const char *e = getenv("SBWTGPU_FUSED_PIECES"); return e ? atoi(e) : -1; }();
-static int g_path_stitch = [] { const char *e = getenv("SBWTGPU_PATH_STITCH"); return e ? atoi(e) : 1; }();
-static int g_path_stitch_min = [] { const char *e = getenv("SBWTGPU_PATH_STITCH_MIN"); return e ? atoi(e) : 1; }();
+static int g_fused_pieces = env_int("SBWTGPU_FUSED_PIECES", -1);
+// stitched chains (sbwt_derived.hip): 0 = vertex-disjoint paths only; the shortest stretch worth copying
+static int g_path_stitch = env_int("SBWTGPU_PATH_STITCH", 1);
+static int g_path_stitch_min = env_int("SBWTGPU_PATH_STITCH_MIN", 1);
 // buckets of the sparse tables per 100 columns (two 16-byte entries each): 125 = 40 % of the slots in use (~6 % of the keys
 // overflow their bucket), 100 = 50 % (~10 %): 8 bytes per column against 0.1 more probes per read.  0 (default) = by the index:
 // 100 for k <= 31 (round 5, one box: config 2 4.74 vs 4.90 ms, config 3 6.39 vs 6.54 ms -- the smaller table is no slower), 125 where
 // whole k-mers take two levels (k = 63: 4.18 ms at 125, 4.26 at 110, 4.29 at 100)
-static int g_sparse_buckets_pct = [] { const char *e = getenv("SBWTGPU_SPARSE_BUCKETS_PCT"); int v = e ? atoi(e) : 0; return v <= 0 ? 0 : v < 60 ? 60 : v > 400 ? 400 : v; }();
+static int g_sparse_buckets_pct = [] { const int v = env_int("SBWTGPU_SPARSE_BUCKETS_PCT", 0); return v <= 0 ? 0 : v < 60 ? 60 : v > 400 ? 400 : v; }();
 // per-read hit profiles (sbwt_readhits.hip): reads of this many windows or more are reduced by a wave instead of a lane; the
 // host entry point's chunk budget in bases (0: 64 Mi); 1: int64 results on indexes that would take int32 (tests)
 static int g_rh_wave_min = SBWT_RH_WAVE_MIN;
 static int64_t g_rh_chunk_bases = 0;
 static int g_rh_wide = 0;
-static int g_sparse_depth = [] { const char *e = getenv("SBWTGPU_SPARSE_PRECALC"); return e ? atoi(e) : 31; }();
+// depth of the sparse (hashed) prefix table built at index creation (capped at k and at 31 = one 62-bit key)
+static int g_sparse_depth = env_int("SBWTGPU_SPARSE_PRECALC", 31);
 
 struct sbwtgpu_index {
     SbwtBlobHeader h;
@@ -292,9 +305,6 @@ int sbwtgpu_device_count(int *count) {
     *count = n;
     return SBWTGPU_OK;
 }
-
-static inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-static inline int64_t a256(int64_t x) { return align256(x); }
 
 // set while sbwtgpu_index_create retries without the derived structures after running out of device memory
 // Image levels: 0 = everything (path order, transition table, sparse table, probe filter: 139-168 bytes per column),
@@ -571,7 +581,7 @@ int sbwtgpu_index_create(const sbwtgpu_index_desc *d, int device, sbwtgpu_index 
     // costs 20-30 ms per GB on this driver once an allocation goes beyond what the process has had before (2.25 x 10^9 columns: 128 GB
     // for the path order and 108 GB for the sparse tables were 5.9 s of an 10.8 s image).  It is let go early only where the final
     // image does not fit beside it (2.25 x 10^9 columns at k = 32: 167 GB).  SBWTGPU_SCRATCH_ARENA=0: an allocation per phase, as before.
-    static const int use_arena = [] { const char *e = getenv("SBWTGPU_SCRATCH_ARENA"); return e ? atoi(e) : 1; }();
+    static const int use_arena = env_int("SBWTGPU_SCRATCH_ARENA", 1);
     void *arena = nullptr;
     size_t arena_bytes = 0;
     auto arena_drop = [&] { if (arena) (void)hipFree(arena); arena = nullptr; arena_bytes = 0; };
@@ -1340,6 +1350,7 @@ int sbwtgpu_workspace_stats(const void *d_ws, void *stream, int64_t stats[8]) {
 }
 
 // ---- host-buffer entry points --------------------------------------------------------------
+}  // extern "C"
 namespace {
 struct Stream {
     hipStream_t s = nullptr;
@@ -1393,17 +1404,109 @@ SmallSlot *small_slot(int device, size_t need) {
     t_slots.v.push_back(s);
     return &t_slots.v.back();
 }
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// One host-buffer call that is not pipelined: the caller lays its inputs, results and workspace out in one range of
+// `bytes` bytes (every part 256-byte aligned) and names the parts by their offsets.  A call that fits SLOT_CAP runs on the
+// thread's SmallSlot: in() copies into the pinned buffer, upload() is the ONE H2D copy, finish() the ONE D2H copy, the
+// ONE synchronise and the copies out to the caller.  A larger call gets a temporary stream and one device allocation,
+// and in() / out() copy straight between the caller's memory and the device: no host-side bounce.
+struct Staging {
+    std::vector<std::vector<int64_t>> kept;     // large calls: computed inputs, alive until the synchronise
+    Stream tmp_stream;
+    DevBuf tmp_dev;
+    SmallSlot *sl = nullptr;
+    char *dev = nullptr;
+    hipStream_t stream = nullptr;
+    size_t in_lo = SIZE_MAX, in_hi = 0, out_lo = SIZE_MAX, out_hi = 0;    // slot: the byte ranges of the two copies
+    struct Back { void *dst; size_t off, n; } back[4];
+    int n_back = 0;
+
+    int open(int device, size_t bytes) {       // (the current device must already be `device`)
+        sl = small_slot(device, bytes);
+        if (sl) { dev = sl->dev; stream = sl->stream; return SBWTGPU_OK; }
+        HIP_TRY(hipStreamCreateWithFlags(&tmp_stream.s, hipStreamNonBlocking));
+        HIP_TRY(tmp_dev.alloc(bytes));
+        dev = static_cast<char *>(tmp_dev.p);
+        stream = tmp_stream.s;
+        return SBWTGPU_OK;
+    }
+    template <typename T>
+    T *at(size_t off) const { return reinterpret_cast<T *>(dev + off); }
+    // n bytes of the caller's at src are the input at `off`
+    int in(size_t off, const void *src, size_t n) {
+        if (n == 0) return SBWTGPU_OK;
+        if (!sl) {
+            HIP_TRY(hipMemcpyAsync(dev + off, src, n, hipMemcpyHostToDevice, stream));
+            return SBWTGPU_OK;
+        }
+        if (src != sl->host + off) memcpy(sl->host + off, src, n);
+        in_lo = std::min(in_lo, off);
+        in_hi = std::max(in_hi, off + n);
+        return SBWTGPU_OK;
+    }
+    // the input at `off` is the n offsets src[0 .. n) rebased to start at 0 (device buffers start at their first base)
+    int in_rebased(size_t off, const int64_t *src, int64_t n) {
+        int64_t *o = nullptr;
+        if (sl) {
+            o = reinterpret_cast<int64_t *>(sl->host + off);
+        } else {
+            try {
+                kept.emplace_back((size_t)n);
+            } catch (const std::bad_alloc &) {
+                return fail(SBWTGPU_ERR_OOM, "out of host memory");
+            }
+            o = kept.back().data();
+        }
+        for (int64_t t = 0; t < n; t++) o[t] = src[t] - src[0];
+        return in(off, o, (size_t)n * 8);
+    }
+    int upload() {
+        if (sl && in_hi > in_lo) HIP_TRY(hipMemcpyAsync(dev + in_lo, sl->host + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, stream));
+        return SBWTGPU_OK;
+    }
+    // after the kernels: the n bytes at `off` are a result and go to dst (written by the time finish() returns)
+    int out(size_t off, void *dst, size_t n) {
+        if (n == 0) return SBWTGPU_OK;
+        if (!sl) {
+            HIP_TRY(hipMemcpyAsync(dst, dev + off, n, hipMemcpyDeviceToHost, stream));
+            return SBWTGPU_OK;
+        }
+        if (n_back == (int)(sizeof(back) / sizeof(back[0]))) return fail(SBWTGPU_ERR_HIP, "internal: too many results in one staged call");
+        back[n_back++] = Back{dst, off, n};
+        out_lo = std::min(out_lo, off);
+        out_hi = std::max(out_hi, off + n);
+        return SBWTGPU_OK;
+    }
+    int finish() {
+        if (sl && out_hi > out_lo) HIP_TRY(hipMemcpyAsync(sl->host + out_lo, dev + out_lo, out_hi - out_lo, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        for (int i = 0; i < n_back; i++) memcpy(back[i].dst, sl->host + back[i].off, back[i].n);
+        return SBWTGPU_OK;
+    }
+};
+#define STG_TRY(expr)                                                                          \
+    do {                                                                                       \
+        const int rc_ = (expr);                                                                \
+        if (rc_ != SBWTGPU_OK) return rc_;                                                     \
+    } while (0)
 }  // namespace
+extern "C" {
+
+// The length of read r as every host entry point checks it while it walks the offsets: not negative, below 2^31
+static inline int check_read_length(const int64_t *read_off, int64_t r) {
+    const int64_t len = read_off[r + 1] - read_off[r];
+    if (len < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "read_off is not non-decreasing at read %lld", (long long)r);
+    if (len >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_READ_TOO_LONG, "read %lld has >= 2^31 bases", (long long)r);
+    return SBWTGPU_OK;
+}
 
 // (*any_long: some read has more than 2 * PIECE k-mers -- the host entry points cut those into pieces, below)
 static int check_reads(const int64_t *read_off, const int64_t *out_off, int64_t n_reads, int64_t k, bool *any_long = nullptr) {
     int64_t longest = 0;
     for (int64_t r = 0; r < n_reads; r++) {
-        int64_t len = read_off[r + 1] - read_off[r];
-        if (len < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "read_off is not non-decreasing at read %lld", (long long)r);
-        if (len >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_READ_TOO_LONG, "read %lld has >= 2^31 bases", (long long)r);
-        int64_t m = len - k + 1;
+        const int rc = check_read_length(read_off, r);
+        if (rc != SBWTGPU_OK) return rc;
+        int64_t m = read_off[r + 1] - read_off[r] - k + 1;
         if (m < 0) m = 0;
         if (out_off[r + 1] - out_off[r] != m)
             return fail(SBWTGPU_ERR_INVALID_ARG, "out_off[%lld+1]-out_off[%lld] must be max(0,len-k+1) = %lld",
@@ -1471,13 +1574,34 @@ static inline int64_t pieces_bases_bound(int64_t len, int64_t k) {   // bytes ap
 // Buffers of the caller that are pinned (hipHostMalloc / hipHostRegister / torch pin_memory: hipPointerGetAttributes says
 // so) are the DMA's source and target themselves; pageable ones go through pinned staging buffers, copied by a few host
 // threads.  The rate is then PCIe's: 8 bytes of results per k-mer.
+}  // extern "C"
 namespace {
+// One slot of a pipeline: a stream, pinned staging buffers for what goes down and what comes back, a pinned status word
+// and one device allocation, which the entry point carves for its chunk.  Pinned and device buffers are expensive to
+// create (page pinning), so finished calls park their slots and later calls on the same device take them again, whichever
+// entry point parked them; ensure() grows only what is too small for the taker.
 struct PipeSlot {
     hipStream_t st = nullptr;
-    char *h_in = nullptr, *h_out = nullptr;     // pinned staging: bases | offsets; results (only for pageable callers)
-    int *h_status = nullptr;
+    char *h_in = nullptr, *h_out = nullptr;     // pinned staging: inputs; results (search: only for pageable callers)
+    int *h_status = nullptr;                    // pinned, 64 bytes: the chunk's device status (text: and its text length)
     char *d_mem = nullptr;
     int64_t cap_in = 0, cap_out = 0, cap_dev = 0;
+    hipError_t ensure(int64_t need_in, int64_t need_out, int64_t need_dev) {
+        hipError_t e = hipSuccess;
+        if (!st) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+        if (e == hipSuccess && !h_status) e = hipHostMalloc((void **)&h_status, 64, hipHostMallocDefault);
+        auto grow = [&e](char *&p, int64_t &cap, int64_t need, bool device) {
+            if (e != hipSuccess || cap >= need) return;
+            if (p) (void)(device ? hipFree(p) : hipHostFree(p));
+            p = nullptr; cap = 0;
+            e = device ? hipMalloc((void **)&p, (size_t)need) : hipHostMalloc((void **)&p, (size_t)need, hipHostMallocDefault);
+            if (e == hipSuccess) cap = need;
+        };
+        grow(h_in, cap_in, need_in, false);
+        grow(h_out, cap_out, need_out, false);
+        grow(d_mem, cap_dev, need_dev, true);
+        return e;
+    }
     void release() {
         if (st) (void)hipStreamDestroy(st);
         if (h_in) (void)hipHostFree(h_in);
@@ -1487,9 +1611,54 @@ struct PipeSlot {
         *this = PipeSlot();
     }
 };
-std::mutex g_pipe_mutex;
-struct ParkedPipe { int device; PipeSlot s[2]; };
-std::vector<ParkedPipe> g_pipe_parked;
+std::mutex g_park_mutex;
+struct Parked { int device; PipeSlot slot; };
+std::vector<Parked> g_parked;
+const size_t PARK_CAP = 8;                      // parked slots per device; a call that finishes beyond it frees its slots
+
+// n slots for a call on `device` (the current device), each grown to the call's needs: parked ones first, the most
+// recently parked first.  On failure nothing is left allocated.
+int take_slots(int device, PipeSlot *S, int n, int64_t need_in, int64_t need_out, int64_t need_dev, const char *what) {
+    {
+        std::lock_guard<std::mutex> lock(g_park_mutex);
+        int got = 0;
+        for (size_t i = g_parked.size(); i-- > 0 && got < n;)
+            if (g_parked[i].device == device) {
+                S[got++] = g_parked[i].slot;
+                g_parked.erase(g_parked.begin() + (long)i);
+            }
+    }
+    for (int q = 0; q < n; q++) {
+        const hipError_t e = S[q].ensure(need_in, need_out, need_dev);
+        if (e == hipSuccess) continue;
+        (void)hipGetLastError();
+        for (int r = 0; r < n; r++) S[r].release();
+        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+    }
+    return SBWTGPU_OK;
+}
+// The end of a call on its slots: parked for the next one, or, after an error, freed once the device is idle.
+void park_slots(int device, PipeSlot *S, int n, int rc) {
+    if (rc != SBWTGPU_OK) (void)hipDeviceSynchronize();
+    std::lock_guard<std::mutex> lock(g_park_mutex);
+    size_t there = 0;
+    for (const Parked &p : g_parked) there += p.device == device;
+    for (int q = 0; q < n; q++) {
+        if (rc == SBWTGPU_OK && there < PARK_CAP) { g_parked.push_back(Parked{device, S[q]}); there++; S[q] = PipeSlot(); }
+        else S[q].release();
+    }
+}
+// Two chunks in flight: chunk c is submitted once chunk c - 2 has been collected from the slot it takes
+template <typename Submit, typename Collect>
+int two_in_flight(int64_t n_chunks, Submit submit, Collect collect) {
+    int rc = SBWTGPU_OK;
+    for (int64_t c = 0; c < n_chunks && rc == SBWTGPU_OK; c++) {
+        if (c >= 2) rc = collect(c - 2);
+        if (rc == SBWTGPU_OK) rc = submit(c);
+    }
+    for (int64_t c = std::max<int64_t>(0, n_chunks - 2); c < n_chunks && rc == SBWTGPU_OK; c++) rc = collect(c);
+    return rc;
+}
 bool is_pinned(const void *p) {
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -1508,6 +1677,7 @@ void parallel_memcpy(char *dst, const char *src, size_t n) {
 }
 const int64_t PIPE_MIN = (int64_t)64 << 20;
 }  // namespace
+extern "C" {
 
 // ro / oo: nv + 1 offsets into src_bases / out (rebased to 0 or not: only ro[0], oo[0] and differences are used)
 // out32 != nullptr (and out == nullptr): the kernels write int32 results (SbwtIndexView::out32): half the bytes over PCIe
@@ -1516,7 +1686,7 @@ static int search_host_pipelined(const sbwtgpu_index *idx, const char *src_bases
     const int64_t vb = out32 ? 4 : 8;                   // bytes of a result on its way to the host
     const bool pin_in = is_pinned(src_bases), pin_out = is_pinned(out32 ? (const void *)out32 : (const void *)out);
     // chunks: results <= 512 MiB when they land in the caller's pinned memory, <= 128 MiB when they are staged
-    static const int64_t chunk_mb = [] { const char *e = getenv("SBWTGPU_PIPE_CHUNK_MB"); return e ? atoll(e) : 0ll; }();
+    static const int64_t chunk_mb = env_i64("SBWTGPU_PIPE_CHUNK_MB", 0);
     const int64_t CH_OUT = (chunk_mb > 0 ? chunk_mb : (pin_out ? (int64_t)512 : (int64_t)128)) << 20;
     std::vector<int64_t> cuts{0};
     int64_t max_bases = 0, max_reads = 0, max_vals = 0;
@@ -1537,56 +1707,22 @@ static int search_host_pipelined(const sbwtgpu_index *idx, const char *src_bases
     }
     const int64_t n_chunks = (int64_t)cuts.size() - 1;
     const int64_t ws_bytes = sbwtgpu_search_workspace_bytes(max_bases);
-    const int64_t need_in = a256(max_bases + 16) + 2 * a256((max_reads + 1) * 8);
-    const int64_t need_out = pin_out ? 0 : a256(max_vals * vb + 8);
-    const int64_t need_dev = a256(max_bases + 16) + 2 * a256((max_reads + 1) * 8) + a256(max_vals * 8 + 8) + a256(ws_bytes);
+    const int64_t need_in = align256(max_bases + 16) + 2 * align256((max_reads + 1) * 8);
+    const int64_t need_out = pin_out ? 0 : align256(max_vals * vb + 8);
+    const int64_t need_dev = align256(max_bases + 16) + 2 * align256((max_reads + 1) * 8) + align256(max_vals * 8 + 8) + align256(ws_bytes);
     DeviceGuard guard(idx->device);
     PipeSlot S[2];
-    {
-        std::lock_guard<std::mutex> lock(g_pipe_mutex);
-        for (size_t i = 0; i < g_pipe_parked.size(); i++)
-            if (g_pipe_parked[i].device == idx->device) {
-                S[0] = g_pipe_parked[i].s[0];
-                S[1] = g_pipe_parked[i].s[1];
-                g_pipe_parked.erase(g_pipe_parked.begin() + (long)i);
-                break;
-            }
-    }
-    int rc = SBWTGPU_OK;
-    auto cleanup = [&]() { S[0].release(); S[1].release(); };
-    for (int q = 0; q < 2 && rc == SBWTGPU_OK; q++) {
-        PipeSlot &P = S[q];
-        hipError_t e = hipSuccess;
-        if (!P.st) e = hipStreamCreateWithFlags(&P.st, hipStreamNonBlocking);
-        if (e == hipSuccess && !P.h_status) e = hipHostMalloc((void **)&P.h_status, 64, hipHostMallocDefault);
-        if (e == hipSuccess && P.cap_in < need_in) {
-            if (P.h_in) (void)hipHostFree(P.h_in);
-            P.h_in = nullptr; P.cap_in = 0;
-            if ((e = hipHostMalloc((void **)&P.h_in, (size_t)need_in, hipHostMallocDefault)) == hipSuccess) P.cap_in = need_in;
-        }
-        if (e == hipSuccess && P.cap_out < need_out) {
-            if (P.h_out) (void)hipHostFree(P.h_out);
-            P.h_out = nullptr; P.cap_out = 0;
-            if ((e = hipHostMalloc((void **)&P.h_out, (size_t)need_out, hipHostMallocDefault)) == hipSuccess) P.cap_out = need_out;
-        }
-        if (e == hipSuccess && P.cap_dev < need_dev) {
-            if (P.d_mem) (void)hipFree(P.d_mem);
-            P.d_mem = nullptr; P.cap_dev = 0;
-            if ((e = hipMalloc((void **)&P.d_mem, (size_t)need_dev)) == hipSuccess) P.cap_dev = need_dev;
-        }
-        if (e != hipSuccess)
-            rc = fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "pipeline buffers: %s", hipGetErrorString(e));
-    }
-    if (rc != SBWTGPU_OK) { (void)hipGetLastError(); cleanup(); return rc; }
+    int rc = take_slots(idx->device, S, 2, need_in, need_out, need_dev, "pipeline buffers");
+    if (rc != SBWTGPU_OK) return rc;
     int bug = 0;                    // the first nonzero device status of a chunk
     struct Carve { char *bases; int64_t *roff, *ooff, *out; char *ws; };
     auto carve = [&](PipeSlot &P) {
         Carve c;
         char *p = P.d_mem;
-        c.bases = p; p += a256(max_bases + 16);
-        c.roff = (int64_t *)p; p += a256((max_reads + 1) * 8);
-        c.ooff = (int64_t *)p; p += a256((max_reads + 1) * 8);
-        c.out = (int64_t *)p; p += a256(max_vals * 8 + 8);
+        c.bases = p; p += align256(max_bases + 16);
+        c.roff = (int64_t *)p; p += align256((max_reads + 1) * 8);
+        c.ooff = (int64_t *)p; p += align256((max_reads + 1) * 8);
+        c.out = (int64_t *)p; p += align256(max_vals * 8 + 8);
         c.ws = p;
         return c;
     };
@@ -1594,7 +1730,7 @@ static int search_host_pipelined(const sbwtgpu_index *idx, const char *src_bases
         PipeSlot &P = S[c & 1];
         const Carve d = carve(P);
         const int64_t lo = cuts[(size_t)c], hi = cuts[(size_t)c + 1], nr = hi - lo, nb = ro[hi] - ro[lo], nvals = oo[hi] - oo[lo];
-        int64_t *hro = (int64_t *)(P.h_in + a256(max_bases + 16)), *hoo = (int64_t *)((char *)hro + a256((max_reads + 1) * 8));
+        int64_t *hro = (int64_t *)(P.h_in + align256(max_bases + 16)), *hoo = (int64_t *)((char *)hro + align256((max_reads + 1) * 8));
         for (int64_t r = 0; r <= nr; r++) { hro[r] = ro[lo + r] - ro[lo]; hoo[r] = oo[lo + r] - oo[lo]; }
         const char *hb = src_bases + ro[lo];
         if (!pin_in) { memcpy(P.h_in, hb, (size_t)nb); hb = P.h_in; }
@@ -1623,24 +1759,9 @@ static int search_host_pipelined(const sbwtgpu_index *idx, const char *src_bases
         if (!pin_out) parallel_memcpy(out32 ? (char *)(out32 + oo[lo]) : (char *)(out + oo[lo]), P.h_out, (size_t)((oo[hi] - oo[lo]) * vb));
         return SBWTGPU_OK;
     };
-    for (int64_t c = 0; c < n_chunks && rc == SBWTGPU_OK; c++) {
-        if (c >= 2) rc = collect(c - 2);
-        if (rc == SBWTGPU_OK) rc = submit(c);
-    }
-    for (int64_t c = std::max<int64_t>(0, n_chunks - 2); c < n_chunks && rc == SBWTGPU_OK; c++) rc = collect(c);
-    if (rc != SBWTGPU_OK) {
-        (void)hipDeviceSynchronize();
-        cleanup();
-        return rc;
-    }
-    {
-        std::lock_guard<std::mutex> lock(g_pipe_mutex);
-        ParkedPipe pp;
-        pp.device = idx->device;
-        pp.s[0] = S[0];
-        pp.s[1] = S[1];
-        g_pipe_parked.push_back(pp);
-    }
+    rc = two_in_flight(n_chunks, submit, collect);
+    park_slots(idx->device, S, 2, rc);
+    if (rc != SBWTGPU_OK) return rc;
     if (bug) return fail_status(bug);
     return SBWTGPU_OK;
 }
@@ -1700,46 +1821,21 @@ static int search_host_common(const sbwtgpu_index *idx, const char *bases, const
         return search_host_pipelined(idx, src_bases, ro.data(), oo.data(), nv, out + out0, streaming);
     DeviceGuard guard(idx->device);
     const int64_t ws_bytes = sbwtgpu_search_workspace_bytes(vtotal);
-    {   // small call: layout [roff][ooff][bases] (in) | [out][workspace] (the D2H copy ends with the workspace header)
-        const size_t o_roff = 0, o_ooff = up256((size_t)(nv + 1) * 8), o_bases = o_ooff + up256((size_t)(nv + 1) * 8);
-        const size_t o_out = o_bases + up256((size_t)vtotal + 16), o_ws = o_out + up256((size_t)n_out * 8);
-        SmallSlot *sl = small_slot(idx->device, o_ws + (size_t)ws_bytes);
-        if (sl) {
-            memcpy(sl->host + o_roff, ro.data(), (size_t)(nv + 1) * 8);
-            memcpy(sl->host + o_ooff, oo.data(), (size_t)(nv + 1) * 8);
-            memcpy(sl->host + o_bases, src_bases, (size_t)vtotal);
-            HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, o_bases + (size_t)vtotal, hipMemcpyHostToDevice, sl->stream));
-            rc = search_dev_common(idx, sl->dev + o_bases, vtotal, (const int64_t *)(sl->dev + o_roff), nv,
-                                   (int64_t *)(sl->dev + o_out), (const int64_t *)(sl->dev + o_ooff), sl->dev + o_ws, ws_bytes,
-                                   sl->stream, streaming);
-            if (rc != SBWTGPU_OK) return rc;
-            const size_t back = (o_ws - o_out) + sizeof(SbwtWorkHeader);
-            HIP_TRY(hipMemcpyAsync(sl->host + o_out, sl->dev + o_out, back, hipMemcpyDeviceToHost, sl->stream));
-            HIP_TRY(hipStreamSynchronize(sl->stream));
-            memcpy(out + out0, sl->host + o_out, (size_t)n_out * 8);
-            const int status = reinterpret_cast<const SbwtWorkHeader *>(sl->host + o_ws)->status;
-            if (status != 0) return fail_status(status);
-            return SBWTGPU_OK;
-        }
-    }
-    Stream st;
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    DevBuf d_bases, d_roff, d_ooff, d_out, d_ws;
-    HIP_TRY(d_bases.alloc((size_t)vtotal + 16));
-    HIP_TRY(d_roff.alloc((size_t)(nv + 1) * 8));
-    HIP_TRY(d_ooff.alloc((size_t)(nv + 1) * 8));
-    HIP_TRY(d_out.alloc((size_t)n_out * 8));
-    HIP_TRY(d_ws.alloc((size_t)ws_bytes));
-    HIP_TRY(hipMemcpyAsync(d_bases.p, src_bases, (size_t)vtotal, hipMemcpyHostToDevice, st.s));
-    HIP_TRY(hipMemcpyAsync(d_roff.p, ro.data(), (size_t)(nv + 1) * 8, hipMemcpyHostToDevice, st.s));
-    HIP_TRY(hipMemcpyAsync(d_ooff.p, oo.data(), (size_t)(nv + 1) * 8, hipMemcpyHostToDevice, st.s));
-    rc = search_dev_common(idx, (const char *)d_bases.p, vtotal, (const int64_t *)d_roff.p, nv, (int64_t *)d_out.p,
-                           (const int64_t *)d_ooff.p, d_ws.p, ws_bytes, st.s, streaming);
-    if (rc != SBWTGPU_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out + out0, d_out.p, (size_t)n_out * 8, hipMemcpyDeviceToHost, st.s));
+    // layout [roff][ooff][bases] (in) | [out][workspace]: a small call's one D2H copy ends with the workspace header
+    const size_t o_roff = 0, o_ooff = align256((size_t)(nv + 1) * 8), o_bases = o_ooff + align256((size_t)(nv + 1) * 8);
+    const size_t o_out = o_bases + align256((size_t)vtotal + 16), o_ws = o_out + align256((size_t)n_out * 8);
+    Staging sg;
+    STG_TRY(sg.open(idx->device, o_ws + (size_t)ws_bytes));
+    STG_TRY(sg.in(o_roff, ro.data(), (size_t)(nv + 1) * 8));
+    STG_TRY(sg.in(o_ooff, oo.data(), (size_t)(nv + 1) * 8));
+    STG_TRY(sg.in(o_bases, src_bases, (size_t)vtotal));
+    STG_TRY(sg.upload());
+    STG_TRY(search_dev_common(idx, sg.at<const char>(o_bases), vtotal, sg.at<const int64_t>(o_roff), nv, sg.at<int64_t>(o_out),
+                              sg.at<const int64_t>(o_ooff), sg.at<char>(o_ws), ws_bytes, sg.stream, streaming));
     SbwtWorkHeader hdr;
-    HIP_TRY(hipMemcpyAsync(&hdr, d_ws.p, sizeof(hdr), hipMemcpyDeviceToHost, st.s));
-    HIP_TRY(hipStreamSynchronize(st.s));
+    STG_TRY(sg.out(o_out, out + out0, (size_t)n_out * 8));
+    STG_TRY(sg.out(o_ws, &hdr, sizeof(hdr)));
+    STG_TRY(sg.finish());
     if (hdr.status != 0) return fail_status(hdr.status);
     return SBWTGPU_OK;
 }
@@ -1803,34 +1899,16 @@ int sbwtgpu_rank_batch(const sbwtgpu_index *idx, const int64_t *pos, const char 
         if (pos[t] < 0 || pos[t] > idx->h.n_nodes)
             return fail(SBWTGPU_ERR_INVALID_ARG, "pos[%lld] = %lld outside [0, n_nodes]", (long long)t, (long long)pos[t]);
     DeviceGuard guard(idx->device);
-    {   // small call: [pos][sym] in, [out] back
-        const size_t o_sym = up256((size_t)n * 8), o_out = o_sym + up256((size_t)n);
-        SmallSlot *sl = small_slot(idx->device, o_out + (size_t)n * 8);
-        if (sl) {
-            memcpy(sl->host, pos, (size_t)n * 8);
-            memcpy(sl->host + o_sym, sym, (size_t)n);
-            HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, o_sym + (size_t)n, hipMemcpyHostToDevice, sl->stream));
-            int rc = sbwtgpu_rank_dev(idx, (const int64_t *)sl->dev, sl->dev + o_sym, n, (int64_t *)(sl->dev + o_out), sl->stream);
-            if (rc != SBWTGPU_OK) return rc;
-            HIP_TRY(hipMemcpyAsync(sl->host + o_out, sl->dev + o_out, (size_t)n * 8, hipMemcpyDeviceToHost, sl->stream));
-            HIP_TRY(hipStreamSynchronize(sl->stream));
-            memcpy(out, sl->host + o_out, (size_t)n * 8);
-            return SBWTGPU_OK;
-        }
-    }
-    Stream st;
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    DevBuf d_pos, d_sym, d_out;
-    HIP_TRY(d_pos.alloc((size_t)n * 8));
-    HIP_TRY(d_sym.alloc((size_t)n));
-    HIP_TRY(d_out.alloc((size_t)n * 8));
-    HIP_TRY(hipMemcpyAsync(d_pos.p, pos, (size_t)n * 8, hipMemcpyHostToDevice, st.s));
-    HIP_TRY(hipMemcpyAsync(d_sym.p, sym, (size_t)n, hipMemcpyHostToDevice, st.s));
-    int rc = sbwtgpu_rank_dev(idx, (const int64_t *)d_pos.p, (const char *)d_sym.p, n, (int64_t *)d_out.p, st.s);
-    if (rc != SBWTGPU_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out, d_out.p, (size_t)n * 8, hipMemcpyDeviceToHost, st.s));
-    HIP_TRY(hipStreamSynchronize(st.s));
-    return SBWTGPU_OK;
+    // [pos][sym] in, [out] back
+    const size_t o_sym = align256((size_t)n * 8), o_out = o_sym + align256((size_t)n);
+    Staging sg;
+    STG_TRY(sg.open(idx->device, o_out + (size_t)n * 8));
+    STG_TRY(sg.in(0, pos, (size_t)n * 8));
+    STG_TRY(sg.in(o_sym, sym, (size_t)n));
+    STG_TRY(sg.upload());
+    STG_TRY(sbwtgpu_rank_dev(idx, sg.at<const int64_t>(0), sg.at<const char>(o_sym), n, sg.at<int64_t>(o_out), sg.stream));
+    STG_TRY(sg.out(o_out, out, (size_t)n * 8));
+    return sg.finish();
 }
 
 int sbwtgpu_update_interval_batch(const sbwtgpu_index *idx, const char *bases, const int64_t *off, int64_t n,
@@ -1848,46 +1926,21 @@ int sbwtgpu_update_interval_batch(const sbwtgpu_index *idx, const char *bases, c
             return fail(SBWTGPU_ERR_INVALID_ARG, "interval %lld out of range", (long long)t);
     }
     DeviceGuard guard(idx->device);
-    {   // small call: [first][second] (in and back) [off][bases]
-        const size_t o_s = up256((size_t)n * 8), o_off = 2 * o_s, o_bases = o_off + up256((size_t)(n + 1) * 8);
-        SmallSlot *sl = small_slot(idx->device, o_bases + (size_t)total + 16);
-        if (sl) {
-            memcpy(sl->host, first, (size_t)n * 8);
-            memcpy(sl->host + o_s, second, (size_t)n * 8);
-            int64_t *o = reinterpret_cast<int64_t *>(sl->host + o_off);
-            for (int64_t t = 0; t <= n; t++) o[t] = off[t] - base0;
-            if (total) memcpy(sl->host + o_bases, bases + base0, (size_t)total);
-            HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, o_bases + (size_t)total, hipMemcpyHostToDevice, sl->stream));
-            sbwt_launch_update_interval(idx->view(), sl->dev + o_bases, (const long long *)(sl->dev + o_off), n,
-                                        (long long *)sl->dev, (long long *)(sl->dev + o_s), sl->stream);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(sl->host, sl->dev, o_s + (size_t)n * 8, hipMemcpyDeviceToHost, sl->stream));
-            HIP_TRY(hipStreamSynchronize(sl->stream));
-            memcpy(first, sl->host, (size_t)n * 8);
-            memcpy(second, sl->host + o_s, (size_t)n * 8);
-            return SBWTGPU_OK;
-        }
-    }
-    Stream st;
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    DevBuf d_bases, d_off, d_f, d_s;
-    HIP_TRY(d_bases.alloc((size_t)total + 16));
-    HIP_TRY(d_off.alloc((size_t)(n + 1) * 8));
-    HIP_TRY(d_f.alloc((size_t)n * 8));
-    HIP_TRY(d_s.alloc((size_t)n * 8));
-    std::vector<int64_t> o((size_t)n + 1);
-    for (int64_t t = 0; t <= n; t++) o[(size_t)t] = off[t] - base0;
-    if (total) HIP_TRY(hipMemcpyAsync(d_bases.p, bases + base0, (size_t)total, hipMemcpyHostToDevice, st.s));
-    HIP_TRY(hipMemcpyAsync(d_off.p, o.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st.s));
-    HIP_TRY(hipMemcpyAsync(d_f.p, first, (size_t)n * 8, hipMemcpyHostToDevice, st.s));
-    HIP_TRY(hipMemcpyAsync(d_s.p, second, (size_t)n * 8, hipMemcpyHostToDevice, st.s));
-    sbwt_launch_update_interval(idx->view(), (const char *)d_bases.p, (const long long *)d_off.p, n,
-                                (long long *)d_f.p, (long long *)d_s.p, st.s);
+    // [first][second] (in and back) [off][bases]
+    const size_t o_s = align256((size_t)n * 8), o_off = 2 * o_s, o_bases = o_off + align256((size_t)(n + 1) * 8);
+    Staging sg;
+    STG_TRY(sg.open(idx->device, o_bases + (size_t)total + 16));
+    STG_TRY(sg.in(0, first, (size_t)n * 8));
+    STG_TRY(sg.in(o_s, second, (size_t)n * 8));
+    STG_TRY(sg.in_rebased(o_off, off, n + 1));
+    STG_TRY(sg.in(o_bases, bases + base0, (size_t)total));
+    STG_TRY(sg.upload());
+    sbwt_launch_update_interval(idx->view(), sg.at<const char>(o_bases), sg.at<const long long>(o_off), n, sg.at<long long>(0),
+                                sg.at<long long>(o_s), sg.stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(first, d_f.p, (size_t)n * 8, hipMemcpyDeviceToHost, st.s));
-    HIP_TRY(hipMemcpyAsync(second, d_s.p, (size_t)n * 8, hipMemcpyDeviceToHost, st.s));
-    HIP_TRY(hipStreamSynchronize(st.s));
-    return SBWTGPU_OK;
+    STG_TRY(sg.out(0, first, (size_t)n * 8));
+    STG_TRY(sg.out(o_s, second, (size_t)n * 8));
+    return sg.finish();
 }
 
 int sbwtgpu_forward_batch(const sbwtgpu_index *idx, const int64_t *node, const char *sym, int64_t n, int64_t *out) {
@@ -1902,60 +1955,18 @@ int sbwtgpu_forward_batch(const sbwtgpu_index *idx, const int64_t *node, const c
         if (node[t] < 0 || node[t] >= idx->h.n_nodes)
             return fail(SBWTGPU_ERR_INVALID_ARG, "node[%lld] out of range", (long long)t);
     DeviceGuard guard(idx->device);
-    {   // small call: [node][sym] in, [out] back
-        const size_t o_sym = up256((size_t)n * 8), o_out = o_sym + up256((size_t)n);
-        SmallSlot *sl = small_slot(idx->device, o_out + (size_t)n * 8);
-        if (sl) {
-            memcpy(sl->host, node, (size_t)n * 8);
-            memcpy(sl->host + o_sym, sym, (size_t)n);
-            HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, o_sym + (size_t)n, hipMemcpyHostToDevice, sl->stream));
-            sbwt_launch_forward(idx->view(), (const long long *)sl->dev, sl->dev + o_sym, n, (long long *)(sl->dev + o_out),
-                                sl->stream);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(sl->host + o_out, sl->dev + o_out, (size_t)n * 8, hipMemcpyDeviceToHost, sl->stream));
-            HIP_TRY(hipStreamSynchronize(sl->stream));
-            memcpy(out, sl->host + o_out, (size_t)n * 8);
-            return SBWTGPU_OK;
-        }
-    }
-    Stream st;
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    DevBuf d_node, d_sym, d_out;
-    HIP_TRY(d_node.alloc((size_t)n * 8));
-    HIP_TRY(d_sym.alloc((size_t)n));
-    HIP_TRY(d_out.alloc((size_t)n * 8));
-    HIP_TRY(hipMemcpyAsync(d_node.p, node, (size_t)n * 8, hipMemcpyHostToDevice, st.s));
-    HIP_TRY(hipMemcpyAsync(d_sym.p, sym, (size_t)n, hipMemcpyHostToDevice, st.s));
-    sbwt_launch_forward(idx->view(), (const long long *)d_node.p, (const char *)d_sym.p, n, (long long *)d_out.p, st.s);
+    // [node][sym] in, [out] back
+    const size_t o_sym = align256((size_t)n * 8), o_out = o_sym + align256((size_t)n);
+    Staging sg;
+    STG_TRY(sg.open(idx->device, o_out + (size_t)n * 8));
+    STG_TRY(sg.in(0, node, (size_t)n * 8));
+    STG_TRY(sg.in(o_sym, sym, (size_t)n));
+    STG_TRY(sg.upload());
+    sbwt_launch_forward(idx->view(), sg.at<const long long>(0), sg.at<const char>(o_sym), n, sg.at<long long>(o_out), sg.stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, d_out.p, (size_t)n * 8, hipMemcpyDeviceToHost, st.s));
-    HIP_TRY(hipStreamSynchronize(st.s));
-    return SBWTGPU_OK;
+    STG_TRY(sg.out(o_out, out, (size_t)n * 8));
+    return sg.finish();
 }
-
-
-// One host-buffer call of the small API neighbours: inputs staged contiguously, one H2D, the kernel, one D2H.
-// `in` / `back` describe byte ranges of the staging buffer; small calls use the thread's slot, large ones a
-// temporary stream + device buffer.
-namespace {
-struct Staged {
-    SmallSlot *sl = nullptr;
-    Stream st;
-    DevBuf dbuf;
-    std::vector<char> hbuf;
-    char *host = nullptr, *dev = nullptr;
-    hipStream_t stream = nullptr;
-    int open(int device, size_t bytes) {
-        sl = small_slot(device, bytes);
-        if (sl) { host = sl->host; dev = sl->dev; stream = sl->stream; return SBWTGPU_OK; }
-        HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-        HIP_TRY(dbuf.alloc(bytes));
-        try { hbuf.resize(bytes); } catch (...) { return fail(SBWTGPU_ERR_OOM, "out of host memory"); }
-        host = hbuf.data(); dev = (char *)dbuf.p; stream = st.s;
-        return SBWTGPU_OK;
-    }
-};
-}  // namespace
 
 int sbwtgpu_partial_search_batch(const sbwtgpu_index *idx, const char *bases, const int64_t *off, int64_t n,
                                  int64_t *first, int64_t *second, int64_t *matched) {
@@ -1970,23 +1981,19 @@ int sbwtgpu_partial_search_batch(const sbwtgpu_index *idx, const char *bases, co
         if (off[t + 1] < off[t]) return fail(SBWTGPU_ERR_INVALID_ARG, "off is not non-decreasing");
     DeviceGuard guard(idx->device);
     // [first][second][matched] (back) [off][bases] (in)
-    const size_t o_s = up256((size_t)n * 8), o_m = 2 * o_s, o_off = 3 * o_s, o_bases = o_off + up256((size_t)(n + 1) * 8);
-    Staged sg;
-    int rc = sg.open(idx->device, o_bases + (size_t)total + 16);
-    if (rc != SBWTGPU_OK) return rc;
-    int64_t *o = reinterpret_cast<int64_t *>(sg.host + o_off);
-    for (int64_t t = 0; t <= n; t++) o[t] = off[t] - base0;
-    if (total) memcpy(sg.host + o_bases, bases + base0, (size_t)total);
-    HIP_TRY(hipMemcpyAsync(sg.dev + o_off, sg.host + o_off, (o_bases - o_off) + (size_t)total, hipMemcpyHostToDevice, sg.stream));
-    sbwt_launch_partial_search(idx->view(), sg.dev + o_bases, (const long long *)(sg.dev + o_off), n, (long long *)sg.dev,
-                               (long long *)(sg.dev + o_s), (long long *)(sg.dev + o_m), sg.stream);
+    const size_t o_s = align256((size_t)n * 8), o_m = 2 * o_s, o_off = 3 * o_s, o_bases = o_off + align256((size_t)(n + 1) * 8);
+    Staging sg;
+    STG_TRY(sg.open(idx->device, o_bases + (size_t)total + 16));
+    STG_TRY(sg.in_rebased(o_off, off, n + 1));
+    STG_TRY(sg.in(o_bases, bases + base0, (size_t)total));
+    STG_TRY(sg.upload());
+    sbwt_launch_partial_search(idx->view(), sg.at<const char>(o_bases), sg.at<const long long>(o_off), n, sg.at<long long>(0),
+                               sg.at<long long>(o_s), sg.at<long long>(o_m), sg.stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(sg.host, sg.dev, o_m + (size_t)n * 8, hipMemcpyDeviceToHost, sg.stream));
-    HIP_TRY(hipStreamSynchronize(sg.stream));
-    memcpy(first, sg.host, (size_t)n * 8);
-    memcpy(second, sg.host + o_s, (size_t)n * 8);
-    memcpy(matched, sg.host + o_m, (size_t)n * 8);
-    return SBWTGPU_OK;
+    STG_TRY(sg.out(0, first, (size_t)n * 8));
+    STG_TRY(sg.out(o_s, second, (size_t)n * 8));
+    STG_TRY(sg.out(o_m, matched, (size_t)n * 8));
+    return sg.finish();
 }
 
 int sbwtgpu_get_kmer_batch(const sbwtgpu_index *idx, const int64_t *colex_rank, int64_t n, char *out) {
@@ -2000,18 +2007,15 @@ int sbwtgpu_get_kmer_batch(const sbwtgpu_index *idx, const int64_t *colex_rank, 
             return fail(SBWTGPU_ERR_INVALID_ARG, "colex_rank[%lld] out of range", (long long)t);
     DeviceGuard guard(idx->device);
     const int64_t k = idx->h.k;
-    const size_t o_out = up256((size_t)n * 8);
-    Staged sg;
-    int rc = sg.open(idx->device, o_out + (size_t)(n * k) + 16);
-    if (rc != SBWTGPU_OK) return rc;
-    memcpy(sg.host, colex_rank, (size_t)n * 8);
-    HIP_TRY(hipMemcpyAsync(sg.dev, sg.host, (size_t)n * 8, hipMemcpyHostToDevice, sg.stream));
-    sbwt_launch_get_kmer(idx->view(), (const long long *)sg.dev, n, sg.dev + o_out, sg.stream);
+    const size_t o_out = align256((size_t)n * 8);
+    Staging sg;
+    STG_TRY(sg.open(idx->device, o_out + (size_t)(n * k) + 16));
+    STG_TRY(sg.in(0, colex_rank, (size_t)n * 8));
+    STG_TRY(sg.upload());
+    sbwt_launch_get_kmer(idx->view(), sg.at<const long long>(0), n, sg.at<char>(o_out), sg.stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(sg.host + o_out, sg.dev + o_out, (size_t)(n * k), hipMemcpyDeviceToHost, sg.stream));
-    HIP_TRY(hipStreamSynchronize(sg.stream));
-    memcpy(out, sg.host + o_out, (size_t)(n * k));
-    return SBWTGPU_OK;
+    STG_TRY(sg.out(o_out, out, (size_t)(n * k)));
+    return sg.finish();
 }
 
 int sbwtgpu_select_batch(const sbwtgpu_index *idx, const int64_t *j, const char *sym, int64_t n, int64_t *out) {
@@ -2027,20 +2031,17 @@ int sbwtgpu_select_batch(const sbwtgpu_index *idx, const int64_t *j, const char 
                         (long long)j[t], (long long)idx->h.row_ones[c], ch);
     }
     DeviceGuard guard(idx->device);
-    const size_t o_sym = up256((size_t)n * 8), o_out = o_sym + up256((size_t)n);
-    Staged sg;
-    int rc = sg.open(idx->device, o_out + (size_t)n * 8);
-    if (rc != SBWTGPU_OK) return rc;
-    memcpy(sg.host, j, (size_t)n * 8);
-    memcpy(sg.host + o_sym, sym, (size_t)n);
-    HIP_TRY(hipMemcpyAsync(sg.dev, sg.host, o_sym + (size_t)n, hipMemcpyHostToDevice, sg.stream));
+    const size_t o_sym = align256((size_t)n * 8), o_out = o_sym + align256((size_t)n);
+    Staging sg;
+    STG_TRY(sg.open(idx->device, o_out + (size_t)n * 8));
+    STG_TRY(sg.in(0, j, (size_t)n * 8));
+    STG_TRY(sg.in(o_sym, sym, (size_t)n));
+    STG_TRY(sg.upload());
     long long ones[4] = {idx->h.row_ones[0], idx->h.row_ones[1], idx->h.row_ones[2], idx->h.row_ones[3]};
-    sbwt_launch_select(idx->view(), (const long long *)sg.dev, sg.dev + o_sym, n, ones, (long long *)(sg.dev + o_out), sg.stream);
+    sbwt_launch_select(idx->view(), sg.at<const long long>(0), sg.at<const char>(o_sym), n, ones, sg.at<long long>(o_out), sg.stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(sg.host + o_out, sg.dev + o_out, (size_t)n * 8, hipMemcpyDeviceToHost, sg.stream));
-    HIP_TRY(hipStreamSynchronize(sg.stream));
-    memcpy(out, sg.host + o_out, (size_t)n * 8);
-    return SBWTGPU_OK;
+    STG_TRY(sg.out(o_out, out, (size_t)n * 8));
+    return sg.finish();
 }
 
 // ---- construction on the device ---------------------------------------------------
@@ -2185,76 +2186,12 @@ int sbwtgpu_format_results_dev(const sbwtgpu_index *idx, const int64_t *d_values
 
 void sbwtgpu_free_host(void *p) { free(p); }
 
-namespace {
-// one pipeline slot: a stream with its device buffers and pinned staging buffers
-struct Slot {
-    hipStream_t st = nullptr;
-    char *h_in = nullptr;            // pinned: bases | read_off | out_off
-    char *h_text = nullptr;          // pinned: formatted text
-    int64_t *h_total = nullptr;      // pinned: text length, status
-    char *d_mem = nullptr;           // one device allocation carved below
-    int64_t cap_bases = 0, cap_reads = 0, cap_vals = 0, cap_text = 0;
-    // carved device pointers
-    char *d_bases = nullptr; int64_t *d_roff = nullptr, *d_ooff = nullptr, *d_out = nullptr, *d_line = nullptr;
-    int64_t *d_vooff = nullptr;      // result offsets of the pieces (d_roff holds the pieces' base offsets)
-    int64_t cap_vreads = 0;          // pieces per chunk
-    char *d_ws = nullptr, *d_text = nullptr, *d_scr = nullptr;
-    int64_t ws_bytes = 0, scr_bytes = 0;
-    // the chunk in flight
-    int64_t n_reads = 0, n_vals = 0, text_len = 0;
-    bool busy = false;
-    void release() {
-        if (st) (void)hipStreamDestroy(st);
-        if (h_in) (void)hipHostFree(h_in);
-        if (h_text) (void)hipHostFree(h_text);
-        if (h_total) (void)hipHostFree(h_total);
-        if (d_mem) (void)hipFree(d_mem);
-        *this = Slot();
-    }
-};
-
-// Pinned + device buffers are expensive to create (page pinning), so finished calls park their slots
-// here and later calls on the same device reuse them when they are large enough.
-std::mutex g_slot_mutex;
-struct ParkedSlot { int device; Slot slot; };
-std::vector<ParkedSlot> g_parked;
-
-bool take_parked(int device, int64_t bases, int64_t reads, int64_t vals, int64_t text, Slot *out) {
-    std::lock_guard<std::mutex> lock(g_slot_mutex);
-    for (size_t i = 0; i < g_parked.size(); i++) {
-        Slot &S = g_parked[i].slot;
-        if (g_parked[i].device == device && S.cap_bases >= bases && S.cap_reads >= reads && S.cap_vals >= vals &&
-            S.cap_text >= text && S.ws_bytes >= sbwtgpu_search_workspace_bytes(S.cap_bases)) {   // (tuning may have changed it)
-            *out = S;
-            g_parked.erase(g_parked.begin() + (long)i);
-            return true;
-        }
-    }
-    return false;
-}
-void park(int device, Slot &S) {
-    std::lock_guard<std::mutex> lock(g_slot_mutex);
-    if (g_parked.size() >= 8) { S.release(); return; }
-    g_parked.push_back(ParkedSlot{device, S});
-    S = Slot();
-}
-}  // namespace
-
 void sbwtgpu_release_cached_buffers(void) {
     {
-        std::lock_guard<std::mutex> lock(g_pipe_mutex);
-        for (auto &pp : g_pipe_parked) { DeviceGuard guard(pp.device); pp.s[0].release(); pp.s[1].release(); }
-        g_pipe_parked.clear();
+        std::lock_guard<std::mutex> lock(g_park_mutex);
+        for (auto &p : g_parked) { DeviceGuard guard(p.device); p.slot.release(); }
+        g_parked.clear();
     }
-    std::lock_guard<std::mutex> lock(g_slot_mutex);
-    for (auto &ps : g_parked) {
-        int prev = -1;
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(ps.device);
-        ps.slot.release();
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-    g_parked.clear();
     for (auto &sl : t_slots.v) sl.release();            // the calling thread's small-call slots
     t_slots.v.clear();
 }
@@ -2278,9 +2215,9 @@ int sbwtgpu_search_text_stream(const sbwtgpu_index *idx, const char *bases, cons
         // vb / vr: bases and reads of the chunk after long reads are cut into pieces
         int64_t lo = 0, vals = 0, vb = 0, vr = 0;
         for (int64_t r = 0; r < n_reads; r++) {
-            int64_t len = read_off[r + 1] - read_off[r];
-            if (len < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "read_off is not non-decreasing at read %lld", (long long)r);
-            if (len >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_READ_TOO_LONG, "read %lld has >= 2^31 bases", (long long)r);
+            const int rc = check_read_length(read_off, r);
+            if (rc != SBWTGPU_OK) return rc;
+            const int64_t len = read_off[r + 1] - read_off[r];
             if (r > lo && (read_off[r + 1] - read_off[lo] > CH_BASES || r - lo >= CH_READS)) {
                 max_bases = std::max(max_bases, vb);
                 max_reads = std::max(max_reads, r - lo);
@@ -2306,59 +2243,45 @@ int sbwtgpu_search_text_stream(const sbwtgpu_index *idx, const char *bases, cons
     const int64_t n_chunks = (int64_t)cuts.size() - 1;
     if (n_chunks == 0) return SBWTGPU_OK;
     DeviceGuard guard(idx->device);
-    Slot slots[3];
-    int rc = SBWTGPU_OK;
-    auto cleanup = [&]() { slots[0].release(); slots[1].release(); slots[2].release(); };
-#define PIPE_TRY(expr)                                                                                     \
-    do {                                                                                                   \
-        hipError_t e_ = (expr);                                                                            \
-        if (e_ != hipSuccess) {                                                                            \
-            rc = fail(e_ == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "%s failed: %s", #expr, \
-                      hipGetErrorString(e_));                                                              \
-            cleanup();                                                                                     \
-            return rc;                                                                                     \
-        }                                                                                                  \
-    } while (0)
+    // a slot's pinned input: [bases][pieces' base offsets][pieces' result offsets][reads' result offsets]; its pinned output: the
+    // text; its device range: the same four, the reads' line offsets, the results, the search workspace, the text, the
+    // formatter's scratch.  (The workspace is sized by what sbwtgpu_search_workspace_bytes asks for NOW: tuning may have changed it.)
+    const int64_t cap_text = sbwtgpu_format_text_bound(idx, max_vals, max_reads);
+    const int64_t ws_bytes = sbwtgpu_search_workspace_bytes(max_bases), scr_bytes = sbwtgpu_format_scratch_bytes(max_reads);
+    const int64_t b_bases = align256(max_bases + 16), b_voff = align256((max_vreads + 1) * 8), b_off = align256((max_reads + 1) * 8);
     const int n_slots = n_chunks > 2 ? 3 : (int)n_chunks;
-    for (int s = 0; s < n_slots; s++) {
-        Slot &S = slots[s];
-        if (take_parked(idx->device, max_bases, max_reads, max_vals, sbwtgpu_format_text_bound(idx, max_vals, max_reads), &S) &&
-            S.cap_vreads >= max_vreads)
-            continue;
-        S.release();
-        S.cap_bases = max_bases; S.cap_reads = max_reads; S.cap_vals = max_vals; S.cap_vreads = max_vreads;
-        S.cap_text = sbwtgpu_format_text_bound(idx, max_vals, max_reads);
-        S.ws_bytes = sbwtgpu_search_workspace_bytes(max_bases);
-        S.scr_bytes = sbwtgpu_format_scratch_bytes(max_reads);
-        const int64_t in_bytes = a256(max_bases + 16) + 2 * a256((max_vreads + 1) * 8) + a256((max_reads + 1) * 8);
-        const int64_t dev_bytes = a256(max_bases + 16) + 2 * a256((max_vreads + 1) * 8) + 2 * a256((max_reads + 1) * 8) +
-                                  a256(max_vals * 8 + 8) + a256(S.ws_bytes) + a256(S.cap_text) + a256(S.scr_bytes);
-        PIPE_TRY(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
-        PIPE_TRY(hipHostMalloc((void **)&S.h_in, (size_t)in_bytes, hipHostMallocDefault));
-        PIPE_TRY(hipHostMalloc((void **)&S.h_text, (size_t)S.cap_text, hipHostMallocDefault));
-        PIPE_TRY(hipHostMalloc((void **)&S.h_total, 64, hipHostMallocDefault));
-        PIPE_TRY(hipMalloc((void **)&S.d_mem, (size_t)dev_bytes));
-        char *p = S.d_mem;
-        S.d_bases = p; p += a256(max_bases + 16);
-        S.d_roff = (int64_t *)p; p += a256((max_vreads + 1) * 8);
-        S.d_vooff = (int64_t *)p; p += a256((max_vreads + 1) * 8);
-        S.d_ooff = (int64_t *)p; p += a256((max_reads + 1) * 8);
-        S.d_line = (int64_t *)p; p += a256((max_reads + 1) * 8);
-        S.d_out = (int64_t *)p; p += a256(max_vals * 8 + 8);
-        S.d_ws = p; p += a256(S.ws_bytes);
-        S.d_text = p; p += a256(S.cap_text);
-        S.d_scr = p;
-    }
+    PipeSlot slots[3];
+    int rc = take_slots(idx->device, slots, n_slots, b_bases + 2 * b_voff + b_off, cap_text,
+                        b_bases + 2 * b_voff + 2 * b_off + align256(max_vals * 8 + 8) + align256(ws_bytes) + align256(cap_text) +
+                            align256(scr_bytes), "text pipeline buffers");
+    if (rc != SBWTGPU_OK) return rc;
+    struct Carve { char *bases; int64_t *roff, *vooff, *ooff, *line, *out; char *ws, *text, *scr; };
+    auto carve = [&](const PipeSlot &P) {
+        Carve c;
+        char *p = P.d_mem;
+        c.bases = p; p += b_bases;
+        c.roff = (int64_t *)p; p += b_voff;
+        c.vooff = (int64_t *)p; p += b_voff;           // result offsets of the pieces (roff holds the pieces' base offsets)
+        c.ooff = (int64_t *)p; p += b_off;
+        c.line = (int64_t *)p; p += b_off;
+        c.out = (int64_t *)p; p += align256(max_vals * 8 + 8);
+        c.ws = p; p += align256(ws_bytes);
+        c.text = p; p += align256(cap_text);
+        c.scr = p;
+        return c;
+    };
+    int64_t text_len[3] = {0, 0, 0};                   // of the chunk in flight on each slot
     int64_t total_queries = 0;
     int bug = 0;                    // the first nonzero device status of a chunk
     // enqueue everything of chunk c on its slot's stream up to the copy of the text length
     auto submit = [&](int64_t c) -> int {
-        Slot &S = slots[c % n_slots];
+        PipeSlot &S = slots[c % n_slots];
+        const Carve d = carve(S);
         const int64_t lo = cuts[(size_t)c], hi = cuts[(size_t)c + 1], nr = hi - lo;
         char *hb = S.h_in;
-        int64_t *hro = (int64_t *)(S.h_in + a256(S.cap_bases + 16));                    // pieces: base offsets
-        int64_t *hvo = (int64_t *)((char *)hro + a256((S.cap_vreads + 1) * 8));         // pieces: result offsets
-        int64_t *hoo = (int64_t *)((char *)hvo + a256((S.cap_vreads + 1) * 8));         // reads: result offsets
+        int64_t *hro = (int64_t *)(S.h_in + b_bases);                   // pieces: base offsets
+        int64_t *hvo = (int64_t *)((char *)hro + b_voff);               // pieces: result offsets
+        int64_t *hoo = (int64_t *)((char *)hvo + b_voff);               // reads: result offsets
         int64_t nb = 0, acc = 0, nv = 0;
         hoo[0] = 0;
         bool any_long = false;
@@ -2367,7 +2290,7 @@ int sbwtgpu_search_text_stream(const sbwtgpu_index *idx, const char *bases, cons
             // the usual chunk: no read long enough to be cut, pieces = reads -- one copy of the bases, offsets by a loop
             const int64_t b0 = read_off[lo];
             nb = read_off[hi] - b0;
-            if (nb > S.cap_bases || nr > S.cap_vreads) return fail(SBWTGPU_ERR_HIP, "internal: piece bound exceeded");
+            if (nb > max_bases || nr > max_vreads) return fail(SBWTGPU_ERR_HIP, "internal: piece bound exceeded");
             if (nb > 0) memcpy(hb, bases + b0, (size_t)nb);
             hro[0] = 0;
             hvo[0] = 0;
@@ -2388,49 +2311,47 @@ int sbwtgpu_search_text_stream(const sbwtgpu_index *idx, const char *bases, cons
                 hoo[r + 1] = acc;
             }
             nv = (int64_t)vro.size() - 1;
-            if (nv > S.cap_vreads || nb > S.cap_bases) return fail(SBWTGPU_ERR_HIP, "internal: piece bound exceeded");
+            if (nv > max_vreads || nb > max_bases) return fail(SBWTGPU_ERR_HIP, "internal: piece bound exceeded");
             memcpy(hro, vro.data(), (size_t)(nv + 1) * 8);
             memcpy(hvo, voo.data(), (size_t)(nv + 1) * 8);
         }
-        S.n_reads = nr;
-        S.n_vals = acc;
         total_queries += acc;
         hipError_t e;
-        if ((e = hipMemcpyAsync(S.d_bases, hb, (size_t)nb, hipMemcpyHostToDevice, S.st)) != hipSuccess ||
-            (e = hipMemcpyAsync(S.d_roff, hro, (size_t)(nv + 1) * 8, hipMemcpyHostToDevice, S.st)) != hipSuccess ||
-            (e = hipMemcpyAsync(S.d_vooff, hvo, (size_t)(nv + 1) * 8, hipMemcpyHostToDevice, S.st)) != hipSuccess ||
-            (e = hipMemcpyAsync(S.d_ooff, hoo, (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, S.st)) != hipSuccess)
+        if ((e = hipMemcpyAsync(d.bases, hb, (size_t)nb, hipMemcpyHostToDevice, S.st)) != hipSuccess ||
+            (e = hipMemcpyAsync(d.roff, hro, (size_t)(nv + 1) * 8, hipMemcpyHostToDevice, S.st)) != hipSuccess ||
+            (e = hipMemcpyAsync(d.vooff, hvo, (size_t)(nv + 1) * 8, hipMemcpyHostToDevice, S.st)) != hipSuccess ||
+            (e = hipMemcpyAsync(d.ooff, hoo, (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, S.st)) != hipSuccess)
             return fail(SBWTGPU_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
-        int r2 = search_dev_common(idx, S.d_bases, nb, S.d_roff, nv, S.d_out, S.d_vooff, S.d_ws, S.ws_bytes, S.st, streaming);
+        int r2 = search_dev_common(idx, d.bases, nb, d.roff, nv, d.out, d.vooff, d.ws, ws_bytes, S.st, streaming);
         if (r2 != SBWTGPU_OK) return r2;
-        r2 = sbwtgpu_format_results_dev(idx, S.d_out, S.d_ooff, nr, acc, S.d_text, S.cap_text, S.d_line, S.d_scr,
-                                        S.scr_bytes, S.st);
+        r2 = sbwtgpu_format_results_dev(idx, d.out, d.ooff, nr, acc, d.text, cap_text, d.line, d.scr, scr_bytes, S.st);
         if (r2 != SBWTGPU_OK) return r2;
-        if ((e = hipMemcpyAsync(&S.h_total[0], S.d_line + nr, 8, hipMemcpyDeviceToHost, S.st)) != hipSuccess ||
-            (e = hipMemcpyAsync(&S.h_total[1], S.d_ws + offsetof(SbwtWorkHeader, status), 4, hipMemcpyDeviceToHost, S.st)) != hipSuccess)
+        // the status word, and behind it (8-byte aligned) the length of the text
+        if ((e = hipMemcpyAsync(S.h_status + 2, d.line + nr, 8, hipMemcpyDeviceToHost, S.st)) != hipSuccess ||
+            (e = hipMemcpyAsync(S.h_status, d.ws + offsetof(SbwtWorkHeader, status), 4, hipMemcpyDeviceToHost, S.st)) != hipSuccess)
             return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
-        S.busy = true;
         return SBWTGPU_OK;
     };
     // wait for chunk c's kernels, then start the copy of its text
     auto fetch = [&](int64_t c) -> int {
-        Slot &S = slots[c % n_slots];
+        PipeSlot &S = slots[c % n_slots];
         hipError_t e = hipStreamSynchronize(S.st);
         if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "stream synchronize: %s", hipGetErrorString(e));
-        S.text_len = S.h_total[0];
-        if ((int)(S.h_total[1] & 0xffffffff) != 0 && bug == 0) bug = (int)(S.h_total[1] & 0xffffffff);
-        if (S.text_len < 0 || S.text_len > S.cap_text) return fail(SBWTGPU_ERR_HIP, "formatted text overflows its bound");
-        e = hipMemcpyAsync(S.h_text, S.d_text, (size_t)S.text_len, hipMemcpyDeviceToHost, S.st);
+        int64_t &len = text_len[c % n_slots];
+        memcpy(&len, S.h_status + 2, 8);
+        if (S.h_status[0] != 0 && bug == 0) bug = S.h_status[0];
+        if (len < 0 || len > cap_text) return fail(SBWTGPU_ERR_HIP, "formatted text overflows its bound");
+        e = hipMemcpyAsync(S.h_out, carve(S).text, (size_t)len, hipMemcpyDeviceToHost, S.st);
         if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
         return SBWTGPU_OK;
     };
     // wait for chunk c's text and hand it to the sink (straight out of the pinned staging buffer)
     auto collect = [&](int64_t c) -> int {
-        Slot &S = slots[c % n_slots];
+        PipeSlot &S = slots[c % n_slots];
         hipError_t e = hipStreamSynchronize(S.st);
         if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "stream synchronize: %s", hipGetErrorString(e));
-        if (S.text_len > 0 && sink(sink_ctx, S.h_text, S.text_len) != 0) return fail(SBWTGPU_ERR_INVALID_ARG, "the text sink reported an error");
-        S.busy = false;
+        const int64_t len = text_len[c % n_slots];
+        if (len > 0 && sink(sink_ctx, S.h_out, len) != 0) return fail(SBWTGPU_ERR_INVALID_ARG, "the text sink reported an error");
         return SBWTGPU_OK;
     };
     // Three slots: while the sink has chunk c-2's text (a write to a file takes several times longer than the GPU needs
@@ -2442,13 +2363,8 @@ int sbwtgpu_search_text_stream(const sbwtgpu_index *idx, const char *bases, cons
     }
     if (rc == SBWTGPU_OK) rc = fetch(n_chunks - 1);
     for (int64_t c = std::max<int64_t>(0, n_chunks - 2); c < n_chunks && rc == SBWTGPU_OK; c++) rc = collect(c);
-#undef PIPE_TRY
-    if (rc != SBWTGPU_OK) {
-        (void)hipDeviceSynchronize();
-        cleanup();
-        return rc;
-    }
-    for (int s2 = 0; s2 < n_slots; s2++) park(idx->device, slots[s2]);
+    park_slots(idx->device, slots, n_slots, rc);
+    if (rc != SBWTGPU_OK) return rc;
     if (bug) return fail_status(bug);
     if (n_queries) *n_queries = total_queries;
     return SBWTGPU_OK;
@@ -2608,41 +2524,31 @@ int sbwtgpu_matching_statistics_batch(const sbwtgpu_index *idx, const char *base
     if (n_reads < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative n_reads");
     if (n_reads == 0) return SBWTGPU_OK;
     if (!read_off) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    for (int64_t r = 0; r < n_reads; r++) {
-        const int64_t l = read_off[r + 1] - read_off[r];
-        if (l < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "read_off is not non-decreasing at read %lld", (long long)r);
-        if (l >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_READ_TOO_LONG, "read %lld has >= 2^31 bases", (long long)r);
-    }
+    for (int64_t r = 0; r < n_reads; r++)
+        if ((rc = check_read_length(read_off, r)) != SBWTGPU_OK) return rc;
     const int64_t base0 = read_off[0], total = read_off[n_reads] - base0;
     if (total == 0) return SBWTGPU_OK;
     if (!bases || !len) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
     DeviceGuard guard(idx->device);
-    Stream st;
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
     // [bases][read_off][len][first][second][workspace], every part 256-byte aligned
-    const size_t o_off = up256((size_t)total + 8), o_len = o_off + up256((size_t)(n_reads + 1) * 8),
-                 o_f = o_len + up256((size_t)total), o_s = o_f + (first ? up256((size_t)total * 8) : 0),
-                 o_ws = o_s + (first ? up256((size_t)total * 8) : 0), bytes = o_ws + (size_t)sbwtgpu_ms_workspace_bytes(total);
-    DevBuf d;
-    HIP_TRY(d.alloc(bytes));
-    char *dv = static_cast<char *>(d.p);
-    std::vector<int64_t> o;
-    try { o.resize((size_t)n_reads + 1); } catch (...) { return fail(SBWTGPU_ERR_OOM, "out of host memory"); }
-    for (int64_t r = 0; r <= n_reads; r++) o[(size_t)r] = read_off[r] - base0;
-    HIP_TRY(hipMemcpyAsync(dv, bases + base0, (size_t)total, hipMemcpyHostToDevice, st.s));
-    HIP_TRY(hipMemcpyAsync(dv + o_off, o.data(), (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st.s));
-    rc = sbwtgpu_matching_statistics_dev(idx, dv, total, reinterpret_cast<const int64_t *>(dv + o_off), n_reads,
-                                         reinterpret_cast<uint8_t *>(dv + o_len), first ? reinterpret_cast<int64_t *>(dv + o_f) : nullptr,
-                                         first ? reinterpret_cast<int64_t *>(dv + o_s) : nullptr, dv + o_ws,
-                                         sbwtgpu_ms_workspace_bytes(total), st.s);
-    if (rc != SBWTGPU_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(len + base0, dv + o_len, (size_t)total, hipMemcpyDeviceToHost, st.s));
+    const size_t o_off = align256((size_t)total + 8), o_len = o_off + align256((size_t)(n_reads + 1) * 8),
+                 o_f = o_len + align256((size_t)total), o_s = o_f + (first ? align256((size_t)total * 8) : 0),
+                 o_ws = o_s + (first ? align256((size_t)total * 8) : 0);
+    const int64_t ws_bytes = sbwtgpu_ms_workspace_bytes(total);
+    Staging sg;
+    STG_TRY(sg.open(idx->device, o_ws + (size_t)ws_bytes));
+    STG_TRY(sg.in(0, bases + base0, (size_t)total));
+    STG_TRY(sg.in_rebased(o_off, read_off, n_reads + 1));
+    STG_TRY(sg.upload());
+    STG_TRY(sbwtgpu_matching_statistics_dev(idx, sg.at<const char>(0), total, sg.at<const int64_t>(o_off), n_reads, sg.at<uint8_t>(o_len),
+                                            first ? sg.at<int64_t>(o_f) : nullptr, first ? sg.at<int64_t>(o_s) : nullptr,
+                                            sg.at<char>(o_ws), ws_bytes, sg.stream));
+    STG_TRY(sg.out(o_len, len + base0, (size_t)total));
     if (first) {
-        HIP_TRY(hipMemcpyAsync(first + base0, dv + o_f, (size_t)total * 8, hipMemcpyDeviceToHost, st.s));
-        HIP_TRY(hipMemcpyAsync(second + base0, dv + o_s, (size_t)total * 8, hipMemcpyDeviceToHost, st.s));
+        STG_TRY(sg.out(o_f, first + base0, (size_t)total * 8));
+        STG_TRY(sg.out(o_s, second + base0, (size_t)total * 8));
     }
-    HIP_TRY(hipStreamSynchronize(st.s));
-    return SBWTGPU_OK;
+    return sg.finish();
 }
 
 // ---- unitigs (sbwt_unitigs.hip) ---------------------------------------------------------------------
@@ -2817,9 +2723,7 @@ int sbwtgpu_read_hits_batch(const sbwtgpu_index *idx, const char *bases, const i
     int64_t max_bases = 0, max_reads = 0;
     try {
         for (int64_t lo = 0, r = 0; r < n_reads; r++) {
-            const int64_t len = read_off[r + 1] - read_off[r];
-            if (len < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "read_off is not non-decreasing at read %lld", (long long)r);
-            if (len >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_READ_TOO_LONG, "read %lld has >= 2^31 bases", (long long)r);
+            if ((rc = check_read_length(read_off, r)) != SBWTGPU_OK) return rc;
             if (r > lo && (read_off[r + 1] - read_off[lo] > budget || r - lo >= CH_READS)) {
                 cuts.push_back(r);
                 lo = r;
@@ -2834,53 +2738,19 @@ int sbwtgpu_read_hits_batch(const sbwtgpu_index *idx, const char *bases, const i
     const int64_t n_chunks = (int64_t)cuts.size() - 1;
     const bool pin_in = is_pinned(bases), pin_out = is_pinned(out);
     const int64_t ws_bytes = sbwtgpu_read_hits_workspace_bytes(max_bases, max_reads, strands);
-    const int64_t need_in = a256(max_bases + 16) + a256((max_reads + 1) * 8);
-    const int64_t need_out = pin_out ? 0 : a256(max_reads * 16);
-    const int64_t need_dev = a256(max_bases + 16) + a256((max_reads + 1) * 8) + a256(max_reads * 16) + a256(ws_bytes);
+    const int64_t need_in = align256(max_bases + 16) + align256((max_reads + 1) * 8);
+    const int64_t need_out = pin_out ? 0 : align256(max_reads * 16);
+    const int64_t need_dev = align256(max_bases + 16) + align256((max_reads + 1) * 8) + align256(max_reads * 16) + align256(ws_bytes);
     DeviceGuard guard(idx->device);
-    PipeSlot S[2];
-    {
-        std::lock_guard<std::mutex> lock(g_pipe_mutex);
-        for (size_t i = 0; i < g_pipe_parked.size(); i++)
-            if (g_pipe_parked[i].device == idx->device) {
-                S[0] = g_pipe_parked[i].s[0];
-                S[1] = g_pipe_parked[i].s[1];
-                g_pipe_parked.erase(g_pipe_parked.begin() + (long)i);
-                break;
-            }
-    }
-    auto cleanup = [&]() { S[0].release(); S[1].release(); };
     const int n_slots = n_chunks > 1 ? 2 : 1;
-    for (int q = 0; q < n_slots && rc == SBWTGPU_OK; q++) {
-        PipeSlot &P = S[q];
-        hipError_t e = hipSuccess;
-        if (!P.st) e = hipStreamCreateWithFlags(&P.st, hipStreamNonBlocking);
-        if (e == hipSuccess && !P.h_status) e = hipHostMalloc((void **)&P.h_status, 64, hipHostMallocDefault);
-        if (e == hipSuccess && P.cap_in < need_in) {
-            if (P.h_in) (void)hipHostFree(P.h_in);
-            P.h_in = nullptr; P.cap_in = 0;
-            if ((e = hipHostMalloc((void **)&P.h_in, (size_t)need_in, hipHostMallocDefault)) == hipSuccess) P.cap_in = need_in;
-        }
-        if (e == hipSuccess && P.cap_out < need_out) {
-            if (P.h_out) (void)hipHostFree(P.h_out);
-            P.h_out = nullptr; P.cap_out = 0;
-            if ((e = hipHostMalloc((void **)&P.h_out, (size_t)need_out, hipHostMallocDefault)) == hipSuccess) P.cap_out = need_out;
-        }
-        if (e == hipSuccess && P.cap_dev < need_dev) {
-            if (P.d_mem) (void)hipFree(P.d_mem);
-            P.d_mem = nullptr; P.cap_dev = 0;
-            if ((e = hipMalloc((void **)&P.d_mem, (size_t)need_dev)) == hipSuccess) P.cap_dev = need_dev;
-        }
-        if (e != hipSuccess)
-            rc = fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "read-hits buffers: %s", hipGetErrorString(e));
-    }
-    if (rc != SBWTGPU_OK) { (void)hipGetLastError(); cleanup(); return rc; }
+    PipeSlot S[2];
+    if ((rc = take_slots(idx->device, S, n_slots, need_in, need_out, need_dev, "read-hits buffers")) != SBWTGPU_OK) return rc;
     int bug = 0;                    // the first nonzero device status of a chunk
-    const int64_t o_roff = a256(max_bases + 16), o_rec = o_roff + a256((max_reads + 1) * 8), o_ws = o_rec + a256(max_reads * 16);
+    const int64_t o_roff = align256(max_bases + 16), o_rec = o_roff + align256((max_reads + 1) * 8), o_ws = o_rec + align256(max_reads * 16);
     auto submit = [&](int64_t c) -> int {
         PipeSlot &P = S[c % n_slots];
         const int64_t lo = cuts[(size_t)c], hi = cuts[(size_t)c + 1], nr = hi - lo, nb = read_off[hi] - read_off[lo];
-        int64_t *hro = (int64_t *)(P.h_in + a256(max_bases + 16));
+        int64_t *hro = (int64_t *)(P.h_in + align256(max_bases + 16));
         for (int64_t r = 0; r <= nr; r++) hro[r] = read_off[lo + r] - read_off[lo];
         const char *hb = bases + read_off[lo];
         if (!pin_in && nb > 0) { parallel_memcpy(P.h_in, hb, (size_t)nb); hb = P.h_in; }
@@ -2907,24 +2777,9 @@ int sbwtgpu_read_hits_batch(const sbwtgpu_index *idx, const char *bases, const i
         if (!pin_out) memcpy(out + lo, P.h_out, (size_t)(hi - lo) * 16);
         return SBWTGPU_OK;
     };
-    for (int64_t c = 0; c < n_chunks && rc == SBWTGPU_OK; c++) {
-        if (c >= 2) rc = collect(c - 2);
-        if (rc == SBWTGPU_OK) rc = submit(c);
-    }
-    for (int64_t c = std::max<int64_t>(0, n_chunks - 2); c < n_chunks && rc == SBWTGPU_OK; c++) rc = collect(c);
-    if (rc != SBWTGPU_OK) {
-        (void)hipDeviceSynchronize();
-        cleanup();
-        return rc;
-    }
-    {
-        std::lock_guard<std::mutex> lock(g_pipe_mutex);
-        ParkedPipe pp;
-        pp.device = idx->device;
-        pp.s[0] = S[0];
-        pp.s[1] = S[1];
-        g_pipe_parked.push_back(pp);
-    }
+    rc = two_in_flight(n_chunks, submit, collect);
+    park_slots(idx->device, S, n_slots, rc);
+    if (rc != SBWTGPU_OK) return rc;
     if (bug) return fail_status(bug);
     return SBWTGPU_OK;
 }

@@ -305,3 +305,166 @@ def test_int32_results_on_the_device_every_route(gpu, k, streaming):
                 assert bool((d32[n_out:] == 77).all()), variant
     finally:
         capi.set_tuning("poison_results", 0)
+
+
+# ---- the host-buffer staging layer: every call on both sides of the 1 MiB small-call slot, and the one parking lot ----
+RANK_SYMS = np.frombuffer(b"ACGTNacgt$\x00\xff", dtype=np.uint8)
+
+
+@pytest.fixture(scope="module")
+def case_idx(case):
+    genomes, orc = case
+    return genomes, orc, gpu_index_from_oracle(orc)
+
+
+def _queries(g, n, rng, starts=None, lo=8, hi=40):
+    """n strings of lo..hi genome bases (from `starts` on), some with a substitution, an N or in lower case; a few empty or
+    non-ACGT ones."""
+    if starts is None:
+        starts = rng.integers(0, len(g) - 100, size=n)
+    lens = rng.integers(lo, hi + 1, size=n)
+    kind = rng.random(n)
+    qs = []
+    for s, L, r in zip(starts, lens, kind):
+        q = g[s:s + L].tobytes()
+        if r < 0.3:
+            q = bytearray(q)
+            q[int(rng.integers(0, L))] = ord("ACGT"[int(rng.integers(0, 4))])
+        elif r < 0.4:
+            q = bytearray(q)
+            q[int(rng.integers(0, L))] = ord("N")
+        elif r < 0.5:
+            q = q.lower()
+        qs.append(bytes(q))
+    for i, q in zip(rng.integers(0, n, size=5), (b"", b"N", b"a", b"$", b"")):
+        qs[int(i)] = q
+    qs[0], qs[-1] = b"", g[:hi].tobytes()
+    return qs
+
+
+def _slot_case(name, genomes, orc, n, seed):
+    """(arguments of Index.<name>, got -> list of arrays, want(items) -> list of arrays) for a batch of n items."""
+    rng = np.random.default_rng(seed)
+    g, nn, k = genomes[0], orc.n_nodes, orc.k
+    as_list = lambda got: [np.asarray(a) for a in (got if isinstance(got, tuple) else (got,))]
+    if name == "rank":
+        pos = rng.integers(0, nn + 1, size=n)
+        pos[0], pos[-1] = nn, 0
+        sym = rng.choice(RANK_SYMS, size=n)
+        return (pos, sym), as_list, lambda it: [orc.batch_rank(pos[it], sym[it], 1)[0]]
+    if name == "forward":
+        node = rng.integers(0, nn, size=n)
+        node[0], node[-1] = 0, nn - 1
+        sym = rng.choice(np.frombuffer(b"ACGTN", dtype=np.uint8), size=n)
+        return (node, sym), as_list, lambda it: [np.array([orc.forward(int(node[i]), bytes([int(sym[i])])) for i in it])]
+    if name == "select":
+        # select inverts rank on set bits (the identity of test_get_kmer_and_select); non-ACGT -> 0
+        words = orc.columns()
+        ones = [np.flatnonzero(np.unpackbits(words[c].view(np.uint8), bitorder="little")[:nn]) for c in range(4)]
+        row = rng.integers(0, 5, size=n)                       # 4: a symbol without a row
+        row[:8] = [0, 0, 1, 1, 2, 2, 3, 3]
+        j = np.array([int(rng.integers(1, len(ones[c]) + 1)) if c < 4 else 5 for c in row])
+        j[:8] = [1, len(ones[0]), 1, len(ones[1]), 1, len(ones[2]), 1, len(ones[3])]      # first and last one of every row
+        sym = np.where(row < 4, np.frombuffer(b"ACGTN", dtype=np.uint8)[row], rng.choice(np.frombuffer(b"N$", dtype=np.uint8), size=n))
+        return (j, sym), as_list, lambda it: [np.array([ones[row[i]][j[i] - 1] if row[i] < 4 else 0 for i in it])]
+    if name == "get_kmers":
+        cols = rng.integers(0, nn, size=n)
+        cols[:5] = [0, 1, 2, nn - 1, nn - 2]
+        return (cols,), as_list, lambda it: [np.array([np.frombuffer(orc.get_kmer(int(cols[i])), dtype=np.uint8) for i in it])]
+    st = rng.integers(0, len(g) - 100, size=n)
+    l0 = rng.integers(0, 13, size=n)
+    qs = _queries(g, n, rng, st + l0 if name == "update_interval" else None)
+    bases, off = capi.concat_reads(qs)
+    if name == "partial_search":
+        def want(it):
+            w = [orc.partial_search(qs[i]) for i in it]
+            return [np.array([x[0][0] for x in w]), np.array([x[0][1] for x in w]), np.array([x[1] for x in w])]
+        return (bases, off), as_list, want
+    assert name == "update_interval"
+    # starting intervals: those of the 0-12 genome bases in front of the query, one in 30 is (-1, -1)
+    dead = rng.random(n) < 1 / 30
+    start = [(-1, -1) if d else orc.update_interval(g[s:s + L].tobytes(), 0, nn - 1) for s, L, d in zip(st, l0, dead)]
+    first, second = (np.array([x[j] for x in start], dtype=np.int64) for j in (0, 1))
+
+    def want_ui(it):
+        w = [orc.update_interval(qs[i], int(first[i]), int(second[i])) for i in it]
+        return [np.array([x[0] for x in w]), np.array([x[1] for x in w])]
+    return (bases, off, first, second), as_list, want_ui
+
+
+@pytest.mark.parametrize("name,n_large", [("rank", 70_000), ("forward", 70_000), ("select", 70_000), ("get_kmers", 40_000),
+                                          ("update_interval", 40_000), ("partial_search", 40_000)])
+def test_calls_on_both_sides_of_the_slot(gpu, case_idx, name, n_large):
+    """Each one-call entry point with a batch that fits the thread's 1 MiB slot (n = 1000: every item checked) and one that
+    cannot (n_large: 2000 sampled items and the first and the last), against the CPU oracle: the large call, a small call
+    right after it, and the small call again after sbwtgpu_release_cached_buffers()."""
+    genomes, orc, idx = case_idx
+    call = getattr(idx, name)
+
+    def check(args, as_list, want, items, label):
+        got = as_list(call(*args))
+        exp = want(items)
+        assert len(got) == len(exp)
+        for a, b in zip(got, exp):
+            assert np.array_equal(a[items], b), (name, label)
+
+    args, as_list, want = _slot_case(name, genomes, orc, n_large, 100)
+    rng = np.random.default_rng(7)
+    sample = np.unique(np.concatenate([[0, n_large - 1], rng.integers(0, n_large, size=2500)]))
+    assert len(sample) >= 2002
+    check(args, as_list, want, sample, "large")
+    small = _slot_case(name, genomes, orc, 1000, 101)
+    check(*small, np.arange(1000), "small after large")
+    capi.lib().sbwtgpu_release_cached_buffers()
+    check(*small, np.arange(1000), "small after release")
+
+
+@pytest.mark.parametrize("n_reads,read_len", [(20, 100), (3000, 150), (3600, 150)])
+def test_matching_statistics_through_the_staging_helper(gpu, case_idx, n_reads, read_len):
+    """sbwtgpu_matching_statistics_batch on the small-call slot (20 reads of 100 bases) and beyond it (3000 reads of 150 bases
+    with intervals: 7.6 MB; the lengths alone, 0.9 MB, still fit; those of 3600 reads, 540 kB of bases + 540 kB of lengths +
+    29 kB of offsets, do not), with and without intervals, against the oracle at every position.  read_off is a view that
+    starts at read 3 of a larger batch: the results land at slot b of bases[b], and nothing in front of read_off[0] is
+    written."""
+    genomes, orc, idx = case_idx
+    bases, off = synth.sample_reads(genomes, n_reads + 3, read_len, 0.02, 1000 + n_reads)
+    for j, ch in enumerate((ord("N"), ord("a"), 0xFF)):
+        bases = synth.inject(bases, max(n_reads // 4, 3), ch, 50 + j)
+    view = off[3:]
+    b0 = int(view[0])
+    assert b0 == 3 * read_len
+    wl, wf, ws, _ = orc.matching_statistics(bases, view)
+    ln, f, s = idx.matching_statistics(bases, view)
+    only = idx.matching_statistics(bases, view, intervals=False)
+    for got, want, name in ((ln, wl, "len"), (f, wf, "first"), (s, ws, "second"), (only, wl, "len only")):
+        assert got.shape == want.shape and np.array_equal(got[b0:], want[b0:]), name
+    assert not ln[:b0].any() and not only[:b0].any() and (f[:b0] == -12345).all() and (s[:b0] == -12345).all()
+
+
+def test_one_parking_lot(gpu, case_idx):
+    """The pipelined search, the chunked read_hits call and the text stream take their slots from one parking lot: each
+    gives what it gave the first time when it runs on slots another entry point parked (smaller or larger than it needs),
+    and on fresh ones after sbwtgpu_release_cached_buffers()."""
+    genomes, orc, idx = case_idx
+    bases, off = synth.sample_reads(genomes, 200_000, 150, 0.01, 9)          # 200 000 x 120 x 8 B = 192 MB of results: pipelined
+    bases = synth.inject(bases, 50, ord("N"), 2)
+    n_text, n_hits = 120_000, 3000                                           # 18 M bases: three text chunks; 450 k bases: five chunks
+
+    def search():
+        return idx.streaming_search(bases, off)[0]
+
+    def hits():
+        capi.set_tuning("read_hits_chunk_bases", 100_000)
+        try:
+            return idx.read_hits(bases[:off[n_hits]], off[:n_hits + 1])
+        finally:
+            capi.set_tuning("read_hits_chunk_bases", 0)
+
+    def text():
+        return idx.search_text(bases[:off[n_text]], off[:n_text + 1])
+
+    first = [search(), hits(), text()]
+    assert (first[0][:120] == orc.streaming_search(bases[:150].tobytes())).all() and first[2][1] == n_text * 120
+    capi.lib().sbwtgpu_release_cached_buffers()
+    again = [text(), hits(), search()][::-1]
+    assert np.array_equal(again[0], first[0]) and np.array_equal(again[1], first[1]) and again[2] == first[2]
