@@ -83,6 +83,31 @@ class IndexInfo(C.Structure):
     ]
 
 
+class ImageHeader(C.Structure):
+    """SbwtBlobHeader (csrc/sbwt_device.h): what sbwtgpu_index_export_header hands out, field for field.  Read-only view for
+    tests and tools that need to know which structures an image holds (Index.image_header())."""
+    _fields_ = [
+        ("magic", C.c_uint64),
+        ("n_nodes", C.c_int64), ("n_kmers", C.c_int64), ("k", C.c_int64), ("p_file", C.c_int64), ("p_dev", C.c_int64),
+        ("C", C.c_int64 * 4),
+        ("n_blocks", C.c_int64), ("n_mega", C.c_int64),
+        ("off_blocks", C.c_int64), ("off_ptab", C.c_int64), ("off_ftab", C.c_int64), ("off_mega", C.c_int64),
+        ("blob_bytes", C.c_int64),
+        ("has_ssup", C.c_int32), ("rank_only", C.c_int32), ("ssup_derived", C.c_int32), ("p_sparse", C.c_int32),
+        ("off_stab", C.c_int64),
+        ("big_layout", C.c_int32), ("has_path", C.c_int32),
+        ("off_col", C.c_int64), ("off_pos", C.c_int64), ("off_pq", C.c_int64), ("off_trans", C.c_int64),
+        ("stab_pos", C.c_int32), ("p_filter", C.c_int32),
+        ("off_pfil", C.c_int64),
+        ("log2f", C.c_int32), ("has_safe", C.c_int32), ("force_mega", C.c_int32),
+        ("n_tslots", C.c_int64), ("n_sb", C.c_int64), ("n_pos", C.c_int64), ("n_trans", C.c_int64),
+        ("n_paths", C.c_int64), ("n_branch", C.c_int64), ("image_level", C.c_int64),
+        ("row_ones", C.c_int64 * 4),
+        ("log2b2_unused", C.c_int32),
+        ("n_sb2", C.c_int64), ("off_stab2", C.c_int64), ("path_lookahead", C.c_int64),
+    ]
+
+
 class PlainMatrixBitsC(C.Structure):
     _fields_ = [("n_nodes", C.c_int64), ("n_kmers", C.c_int64), ("k", C.c_int64),
                 ("A_bits", C.c_void_p), ("C_bits", C.c_void_p), ("G_bits", C.c_void_p), ("T_bits", C.c_void_p),
@@ -326,6 +351,13 @@ class Index:
         buf = C.create_string_buffer(n.value)
         _check(lib().sbwtgpu_index_export_header(self._h, buf, n.value, C.byref(n)))
         return buf.raw[: n.value]
+
+    def image_header(self) -> ImageHeader:
+        """The exported header as a structure: has_path, p_sparse, n_sb2 (0 = no second-level table), p_dev, p_file, ..."""
+        raw = self.export_header()
+        if len(raw) != C.sizeof(ImageHeader):
+            raise SbwtGpuError(ERR_INVALID_ARG, "ImageHeader has %d bytes, the library's header %d" % (C.sizeof(ImageHeader), len(raw)))
+        return ImageHeader.from_buffer_copy(raw)
 
     def blob(self):
         p, n = C.c_void_p(), C.c_int64(0)

@@ -87,6 +87,7 @@ struct SbwtIndexView {
 };
 
 // Position-independent description of a blob (what index_export_header hands out).
+// (sbwt_amd/capi.py mirrors it field for field as ImageHeader: change the two together)
 struct SbwtBlobHeader {
     uint64_t magic;                 // 'SBWTGPU3'
     int64_t n_nodes, n_kmers, k, p_file, p_dev;

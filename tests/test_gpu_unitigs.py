@@ -259,7 +259,7 @@ def test_long_pure_cycle(gpu):
     check_round_trip(bits, b, o, k)
 
 
-@pytest.mark.parametrize("k", [65, 72, 80])
+@pytest.mark.parametrize("k", [65, 72, 80, 128, 255])
 def test_round_trip_long_k_host_builder(gpu, k):
     rng = random.Random(k)
     seqs = ["".join(rng.choice("ACGT") for _ in range(rng.randint(k, 400))) for _ in range(6)]

@@ -1,7 +1,8 @@
 """GPU fuzz: random indexes (k, genome shapes with repeats / related strains / tiny alphabets) and random reads
 (substitutions, N, lower case, ragged lengths, long reads); every route (5 fused, 4 two-pass path kernel, 1 blocks) must
 equal the reference-order kernel (variant 0) bit for bit, and a sample must equal the oracle.
-Usage: python tools/fuzz_gpu.py [seconds]   (SEED=n);   tests/test_gpu_fuzz.py runs fuzz() under the driver's -m gpu suite"""
+Usage: python tools/fuzz_gpu.py [seconds] [k,k,...]   (SEED=n; the list replaces the k the cases draw from, e.g. 64,65,96,128,255);
+tests/test_gpu_fuzz.py and tests/test_gpu_long_k.py run fuzz() under the driver's -m gpu suite"""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,23 +44,30 @@ def reset_tuning():
     capi.set_tuning("path_stitch", 1); capi.set_tuning("path_stitch_min", 1)
 
 
-def fuzz(budget, seed, max_cases=None):
+K_CHOICES = [4, 7, 12, 16, 21, 30, 31, 32, 33, 40, 63]
+
+
+def fuzz(budget, seed, max_cases=None, k_choices=None, stats=None, oracle_every=10):
     """Runs random cases for `budget` seconds (or max_cases); returns the number of cases.  Raises FuzzMismatch with a
-    description of the first difference."""
+    description of the first difference.  k_choices: the k a case draws from (default K_CHOICES; a list of the same length
+    or not, the draws that follow are those of the generator).  stats: a dict that receives "compared" (cases that got as far as
+    comparing the routes) and "oracle" (those that were also held against the oracle: the first of every `oracle_every`
+    cases, where the index has fewer than 400 000 columns)."""
     try:
-        return _fuzz(budget, seed, max_cases)
+        return _fuzz(budget, seed, max_cases, K_CHOICES if k_choices is None else list(k_choices), {} if stats is None else stats, oracle_every)
     finally:
         reset_tuning()
 
 
-def _fuzz(budget, seed, max_cases):
+def _fuzz(budget, seed, max_cases, k_choices, stats, oracle_every):
+    stats.update(compared=0, oracle=0)
     capi.set_tuning("poison_results", 1)
     t_end = time.time() + budget
     case = 0
     rng = np.random.default_rng(seed)
     while time.time() < t_end and (max_cases is None or case < max_cases):
         case += 1
-        k = int(rng.choice([4, 7, 12, 16, 21, 30, 31, 32, 33, 40, 63]))
+        k = int(rng.choice(k_choices))
         shape = int(rng.integers(0, 5))
         glen = int(rng.integers(2_000, 120_000))
         g0 = synth.random_genome(glen, int(rng.integers(1, 1 << 30)))
@@ -165,7 +173,9 @@ def _fuzz(budget, seed, max_cases):
                 explain(a, ref[0]); raise FuzzMismatch("MISMATCH streaming %s seed %d case %d k %d shape %d ssup %s rc %s" % (key, seed, case, k, shape, ssup, rc))
             if not np.array_equal(b, ref[1]):
                 explain(b, ref[1]); raise FuzzMismatch("MISMATCH search %s seed %d case %d k %d shape %d ssup %s rc %s" % (key, seed, case, k, shape, ssup, rc))
-        if case % 10 == 1 and bits.n_nodes < 400_000:     # the oracle on a sample
+        stats["compared"] += 1
+        if case % oracle_every == 1 % oracle_every and bits.n_nodes < 400_000:     # the oracle on a sample
+            stats["oracle"] += 1
             orc = OracleIndex.from_bits(bits.cols[0], bits.cols[1], bits.cols[2], bits.cols[3], bits.ssup if ssup else None,
                                         bits.n_nodes, k, bits.n_kmers, 0)
             for r in range(min(nr, 40)):
@@ -181,7 +191,8 @@ def _fuzz(budget, seed, max_cases):
 if __name__ == "__main__":
     budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
     try:
-        n = fuzz(budget, int(os.environ.get("SEED", 1)))
+        ks = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else None
+        n = fuzz(budget, int(os.environ.get("SEED", 1)), k_choices=ks)
     except FuzzMismatch as ex:
         print(ex)
         sys.exit(1)
