@@ -80,12 +80,26 @@ def key_of(kmer: str) -> int:
 
 
 def packed_keys(kmers: Iterable[str], k: int) -> np.ndarray:
-    """The sorted keys as sbwtgpu_index_kmer_keys returns them: uint64[n] for k <= 32, (n, 2) uint64 (low, high) above."""
-    keys = sorted(key_of(w) for w in kmers)
-    m = (1 << 64) - 1
+    """The sorted keys as sbwtgpu_index_kmer_keys returns them: uint64[n] for k <= 32, (n, 2) uint64 (low, high) above.
+    (key_of for every k-mer, in numpy: sets of 10^5 k-mers take a moment instead of seconds.)"""
+    kmers = list(kmers)
+    n = len(kmers)
+    if n == 0:
+        return np.zeros(0 if k <= 32 else (0, 2), dtype=np.uint64)
+    lut = np.zeros(256, dtype=np.uint64)
+    for c, v in CODE.items():
+        lut[ord(c)] = v
+    codes = lut[np.frombuffer("".join(kmers).encode(), dtype=np.uint8).reshape(n, k)]
+    lo, hi = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    for i in range(k):
+        if i < 32:
+            lo |= codes[:, i] << np.uint64(2 * i)
+        else:
+            hi |= codes[:, i] << np.uint64(2 * (i - 32))
+    order = np.lexsort((lo, hi))
     if k <= 32:
-        return np.array(keys, dtype=np.uint64).reshape(len(keys))
-    return np.array([[v & m, v >> 64] for v in keys], dtype=np.uint64).reshape(len(keys), 2)
+        return lo[order]
+    return np.stack([lo[order], hi[order]], axis=1)
 
 
 def same_bits(a, b) -> bool:

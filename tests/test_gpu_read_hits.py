@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from bruteforce import BruteSBWT
-from read_hits_brute import format_table, profile_of_hits, profiles, revcomp
+from read_hits_brute import format_table, profile_of_hits, profiles, reduce_hits, revcomp
 from sbwt_amd import capi, hostlib, synth
 
 pytestmark = pytest.mark.gpu
@@ -91,33 +91,6 @@ def test_random_small_indexes(gpu, k, ssup):
         rc = trial == 1
         idx = make_index(seqs, k, rc, ssup)
         check_against_brute(idx, BruteSBWT(seqs, k, rc), probe_reads(seqs, k, rng), (k, ssup, trial))
-
-
-# ---- a numpy reduction of search results: the sum-of-min form, reads as segments of one array ----
-def reduce_hits(hit, oo, k):
-    """(n_reads, 4) records from the hit flags of all windows (read r: hit[oo[r]:oo[r + 1]])."""
-    n = len(oo) - 1
-    W = int(oo[-1])
-    m = np.diff(oo)
-    out = np.zeros((n, 4), dtype=np.int64)
-    out[:, 0] = m
-    if W == 0:
-        return out.astype(np.int32)
-    h = hit.astype(np.int64)
-    pos = np.arange(W, dtype=np.int64)
-    start = np.repeat(oo[:-1], m)                                 # first window of the read of every window
-    cs = np.concatenate([[0], np.cumsum(h)])
-    out[:, 1] = cs[oo[1:]] - cs[oo[:-1]]
-    last0 = np.maximum.accumulate(np.where(h == 0, pos, -1))      # last miss at or before p
-    run = h * (pos - np.maximum(last0, start - 1))                # hits in a row that end at p
-    lasthit = np.maximum.accumulate(np.where(h == 1, pos, -1))
-    prev = np.concatenate([[-1], lasthit[:-1]])                   # last hit before p
-    add = h * np.where(prev >= start, np.minimum(k, pos - prev), k)
-    ca = np.concatenate([[0], np.cumsum(add)])
-    out[:, 2] = ca[oo[1:]] - ca[oo[:-1]]
-    ne = np.nonzero(m > 0)[0]
-    out[ne, 3] = np.maximum.reduceat(run, oo[ne])
-    return out.astype(np.int32)
 
 
 def mirrored_hits(idx, bases, off):

@@ -12,6 +12,7 @@ import pytest
 
 from bruteforce import BruteSBWT
 from unitig_brute import brute_unitigs, flatten
+from unitig_numpy import graph, key_set
 from sbwt_amd import capi, hostlib, synth
 
 pytestmark = pytest.mark.gpu
@@ -271,17 +272,6 @@ def test_round_trip_long_k_host_builder(gpu, k):
         check_round_trip(bits, b, o, k, host=True)
 
 
-def pack(genome, k):
-    """every k-mer of an ACGT array as a 2k-bit integer (k <= 31), first base in the highest bits"""
-    code = np.zeros(256, dtype=np.uint64)
-    code[np.frombuffer(b"ACGT", dtype=np.uint8)] = np.arange(4, dtype=np.uint64)
-    c = code[genome]
-    v = np.zeros(len(genome) - k + 1, dtype=np.uint64)
-    for j in range(k):
-        v = (v << np.uint64(2)) | c[j:j + len(v)]
-    return v
-
-
 def test_moderate_scale(gpu):
     k = 31
     genomes = synth.coli3_like(700_000, 0.01)
@@ -295,24 +285,11 @@ def test_moderate_scale(gpu):
     assert np.all(f[1:] > f[:-1])
     check_permutation(idx, bits, b, o, f, k)
     check_round_trip(bits, b, o, k)
-    # the start rule over packed 62-bit k-mers: x is a start unless it has exactly one in-neighbour whose out-degree is 1
-    K = np.unique(np.concatenate([pack(g, k) for g in genomes] + [pack(synth.revcomp(g), k) for g in genomes]))
+    # the start rule over packed 62-bit k-mers (tests/unitig_numpy.py): x is a start unless it has exactly one in-neighbour
+    # whose out-degree is 1
+    K = key_set(list(genomes) + [synth.revcomp(g) for g in genomes], k)
     assert len(K) == bits.n_kmers
-    mask = np.uint64((1 << (2 * k)) - 1)
-
-    def find(q):
-        i = np.minimum(np.searchsorted(K, q), len(K) - 1)
-        return i, K[i] == q
-    outdeg = np.zeros(len(K), dtype=np.int64)
-    for d in range(4):
-        outdeg += find(((K << np.uint64(2)) & mask) | np.uint64(d))[1]
-    indeg = np.zeros(len(K), dtype=np.int64)
-    pred_outdeg = np.zeros(len(K), dtype=np.int64)       # out-degree of the in-neighbours, summed
-    for c in range(4):
-        i, hp = find((K >> np.uint64(2)) | (np.uint64(c) << np.uint64(2 * (k - 1))))
-        indeg += hp
-        pred_outdeg += np.where(hp, outdeg[i], 0)
-    n_starts = int(np.sum(~((indeg == 1) & (pred_outdeg == 1))))
+    n_starts = int(graph(K, k)[1].sum())
     # (a pure cycle would add a unitig without a start: three random genomes hold none)
     assert len(f) == n_starts
 

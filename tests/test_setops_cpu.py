@@ -111,6 +111,7 @@ def test_key_format_orders_kmers_like_columns(k):
     assert len({key_of(w) for w in kmers}) == len(kmers)
     P = packed_keys(kmers, k)
     assert P.dtype == np.uint64 and P.shape == ((len(kmers),) if k <= 32 else (len(kmers), 2))
+    assert [int(x) if k <= 32 else int(x[0]) | (int(x[1]) << 64) for x in P] == [key_of(w) for w in real]
     w = real[-1]
     got = int(P[-1]) if k <= 32 else int(P[-1, 0]) | (int(P[-1, 1]) << 64)
     assert got == key_of(w) and got < (1 << (2 * k))
