@@ -114,6 +114,8 @@ int         sbwtgpu_device_count(int *count);
  *   "read_hits_chunk_bases" sbwtgpu_read_hits_batch cuts its batch into chunks of whole reads of at most this many bases (a
  *                        chunk always takes one read); 0 (default) = 64 Mi
  *   "read_hits_wide"     1: the read-hits calls take the int64 search route also on indexes of fewer than 2^31 columns (tests)
+ *   "pseudoalign_chunk_bases" sbwtgpu_pseudoalign_batch and sbwtgpu_colors_add_batch cut their batch into chunks of whole reads
+ *                        of at most this many bases (a chunk always takes one read); 0 (default) = 64 Mi
  *   "trans_ext", "trans_wide"   accepted and ignored (round-2 table formats)
  * Read when an index is CREATED (derived acceleration structures inside the device image; environment
  * variables of the same meaning: SBWTGPU_SPARSE_PRECALC, SBWTGPU_PROBE_FILTER, SBWTGPU_PATH_ORDER):
@@ -496,6 +498,81 @@ int64_t sbwtgpu_read_hits_workspace_bytes(int64_t total_bases, int64_t n_reads, 
 int     sbwtgpu_read_hits_dev(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
                               int64_t n_reads, int strands, sbwtgpu_read_hits *d_out, void *d_workspace,
                               int64_t workspace_bytes, void *stream);
+
+/* ---- colours and pseudoalignment: which of the indexed references hold a k-mer or a read ----
+ * One index over N references (strains of a pan-genome) and one search answer "which references hold this read", instead of
+ * N indexes, N searches of the same reads and a join.
+ *
+ * Colour matrix.  An index of n columns carries n little-endian uint64_t rows and n_colors colours, 1 <= n_colors <= 64.
+ *   - Bit c of row j is set exactly when column j is a real column whose k-mer was given for colour c.
+ *   - Dummy columns and bits >= n_colors are always 0.
+ *   - More than 64 colours (W words per row) is out of scope.
+ * Colouring.  add(color c, sequences, strands):
+ *   - Every window of every sequence is searched with the rule of sbwtgpu_search_batch: upper-case ACGT only; any other byte
+ *     in the window means no hit.
+ *   - A hit on column j sets bit c of row j.
+ *   - strands = 2 also searches the reverse complement of every window and sets bit c on that column too.  This is needed
+ *     for indexes built with reverse complements.  The complement rule is read-hits' rule.
+ *   - Windows that the index lacks are skipped and counted.
+ *   - The call returns n_windows and n_hit_windows.  For two strands, a window counts once if either strand hit.
+ *   - Adding is idempotent and order-independent.
+ * Colour set of a window.
+ *   - S_i is the row of the window's column, or 0 if the window is not found.
+ *   - With strands = 2, S_i is the row of the forward hit OR the row of the reverse-complement hit; a missing hit
+ *     contributes 0.
+ *   - A found window with S_i = 0 counts as not found.
+ * Record per read: { uint64_t colors; int32_t n_kmers; int32_t n_found; }, 16 bytes.
+ *   - n_kmers = m = max(0, L - k + 1).
+ *   - n_found = the number of windows i with S_i != 0.
+ *   - count_c = the number of windows i with bit c set in S_i.
+ *   - Let D = n_found when denominator = 0 and D = m when denominator = 1.
+ *   - Bit c of colors is set exactly when D > 0 and count_c x 1 000 000 >= threshold_ppm x D, in 64-bit integer arithmetic,
+ *     1 <= threshold_ppm <= 1 000 000.  No floating point anywhere.
+ *   - threshold_ppm = 1 000 000 with denominator = 0 is the classical intersection over the found k-mers.
+ *   - m = 0 gives {0, 0, 0}.
+ * Optional counts output: n_reads x n_colors int32_t, counts[r x n_colors + c] = count_c.
+ * Refusals, each SBWTGPU_ERR_INVALID_ARG with a message naming the cause: rank-only indexes; indexes of 2^31 columns or more
+ * (the int32 search results are the only route); n_colors outside 1..64; color >= n_colors; a threshold or denominator out of
+ * range; a colours object used with an index of another n_nodes or k (an object is bound to its index when it is created;
+ * callers that load rows from a file compare the file's n_columns and k with the index first, as the CLI and the Python
+ * binding do).
+ *
+ * Memory and ownership: sbwtgpu_colors_create allocates 8 bytes per column on the index's device and zeroes them, or uploads
+ * rows_or_null (n_nodes rows) after clearing bits >= n_colors and the rows of dummy columns.  The index must outlive the
+ * colours object.  SBWTGPU_ERR_OOM leaves the index untouched and usable.
+ * Concurrency: the queries (pseudoalign_batch / _dev, info, copy) are thread-safe on one index and one colours object.
+ * sbwtgpu_colors_add_batch changes the object and must not run concurrently with anything else on the same object. */
+typedef struct sbwtgpu_colors sbwtgpu_colors;
+typedef struct { int64_t n_columns, k; int32_t n_colors; int64_t n_colored_columns; int64_t per_color[64]; } sbwtgpu_colors_info_t;
+typedef struct { uint64_t colors; int32_t n_kmers, n_found; } sbwtgpu_pseudoalignment;
+
+int  sbwtgpu_colors_create(const sbwtgpu_index *idx, int n_colors, const uint64_t *rows_or_null, sbwtgpu_colors **out);
+void sbwtgpu_colors_destroy(sbwtgpu_colors *c);
+/* Host buffers, as sbwtgpu_read_hits_batch takes them: sequence r = bases[read_off[r] .. read_off[r+1]).  Chunked by whole
+ * reads (tuning "pseudoalign_chunk_bases", default 64 Mi) on the parked pipeline slots; only bases and offsets go down.
+ * n_windows / n_hit_windows may be NULL.  A sequence of 2^31 bases or more: SBWTGPU_ERR_READ_TOO_LONG. */
+int  sbwtgpu_colors_add_batch(sbwtgpu_colors *c, int color, const char *bases, const int64_t *read_off, int64_t n_reads,
+                              int strands, int64_t *n_windows, int64_t *n_hit_windows);
+/* coloured columns (rows that are not 0) in total and per colour, counted on the device */
+int  sbwtgpu_colors_info(const sbwtgpu_colors *c, sbwtgpu_colors_info_t *info);
+/* the n_columns rows into host memory / the device array itself (valid as long as the object) */
+int  sbwtgpu_colors_copy(const sbwtgpu_colors *c, uint64_t *rows_out);
+int  sbwtgpu_colors_dev(const sbwtgpu_colors *c, const uint64_t **d_rows);
+/* Host buffers: out[r] the record of read r, counts_or_null the counts.  Chunked like sbwtgpu_colors_add_batch; only records,
+ * and counts if asked for, come back.  The result does not depend on tuning, image level or chunking. */
+int  sbwtgpu_pseudoalign_batch(const sbwtgpu_colors *c, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
+                               int threshold_ppm, int denominator, sbwtgpu_pseudoalignment *out, int32_t *counts_or_null);
+/* Device buffers, asynchronous on `stream`, never synchronises; the preconditions of sbwtgpu_read_hits_dev (d_read_off[0] need
+ * not be 0; n_reads < 2^31).  d_out: n_reads records, 8-byte aligned; d_counts_or_null: n_reads x n_colors int32.  The
+ * workspace (16-byte aligned) holds the search workspace first -- sbwtgpu_workspace_status reports the status word of the
+ * call's last search -- then the int32 results, the result offsets and, for two strands, the mirrored bases, offsets and
+ * results: about 5.1 (10.2) bytes per base + 24 (40) per read.  Its size is non-decreasing in total_bases and in n_reads; a
+ * workspace that is too small is SBWTGPU_ERR_INVALID_ARG. */
+int64_t sbwtgpu_pseudoalign_workspace_bytes(int64_t total_bases, int64_t n_reads, int strands);
+int  sbwtgpu_pseudoalign_dev(const sbwtgpu_colors *c, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                             int64_t n_reads, int strands, int threshold_ppm, int denominator,
+                             sbwtgpu_pseudoalignment *d_out, int32_t *d_counts_or_null,
+                             void *d_workspace, int64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,14 @@ int  sbwthost_write_file(const char *path, const char *data, int64_t n, int gzip
  * path go to the GPU -- this entry point exists so that the directory's arithmetic is tested where there is no GPU.) */
 int  sbwthost_rank_batch(const uint64_t *bits, int64_t n_bits, const int64_t *pos, int64_t n, int64_t *out);
 
+/* Colour files (the colour matrix of include/sbwtgpu.h beside its index file): 8 bytes "SBWTCOL1"; int64 n_columns, n_colors,
+ * k; then n_columns little-endian uint64 rows.  The read is a two-call pattern: rows_or_null = NULL gives the three sizes,
+ * a second call with room for rows_cap >= n_columns rows fills them.  A truncated file, a wrong magic and n_colors outside
+ * 1 .. 64 are errors with a message. */
+int  sbwthost_colors_write(const char *path, const uint64_t *rows, int64_t n_columns, int64_t n_colors, int64_t k);
+int  sbwthost_colors_read(const char *path, int64_t *n_columns, int64_t *n_colors, int64_t *k, uint64_t *rows_or_null,
+                          int64_t rows_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,8 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_unitigs_destroy",
     "sbwtgpu_index_setop", "sbwtgpu_index_setop_counts", "sbwtgpu_index_kmer_keys",
     "sbwtgpu_read_hits_batch", "sbwtgpu_read_hits_workspace_bytes", "sbwtgpu_read_hits_dev",
+    "sbwtgpu_colors_create", "sbwtgpu_colors_destroy", "sbwtgpu_colors_add_batch", "sbwtgpu_colors_info", "sbwtgpu_colors_copy",
+    "sbwtgpu_colors_dev", "sbwtgpu_pseudoalign_batch", "sbwtgpu_pseudoalign_workspace_bytes", "sbwtgpu_pseudoalign_dev",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -123,6 +125,14 @@ class SetopInfoC(C.Structure):
         d["pass_ms"] = dict(zip(("keys_a", "keys_b", "merge_select", "tail_columns"), (float(x) for x in self.pass_ms)))
         return d
 
+
+class ColorsInfoC(C.Structure):
+    _fields_ = [("n_columns", C.c_int64), ("k", C.c_int64), ("n_colors", C.c_int32), ("n_colored_columns", C.c_int64),
+                ("per_color", C.c_int64 * 64)]
+
+
+# a read's pseudoalignment record (sbwtgpu_pseudoalignment): 16 bytes
+PSEUDOALIGNMENT_DTYPE = np.dtype([("colors", np.uint64), ("n_kmers", np.int32), ("n_found", np.int32)])
 
 _lib: Optional[C.CDLL] = None
 
@@ -215,6 +225,17 @@ def lib() -> C.CDLL:
         L.sbwtgpu_read_hits_workspace_bytes.argtypes = [i64, i64, ci]
         L.sbwtgpu_read_hits_workspace_bytes.restype = i64
         L.sbwtgpu_read_hits_dev.argtypes = [vp, vp, i64, vp, i64, ci, vp, vp, i64, vp]
+        L.sbwtgpu_colors_create.argtypes = [vp, ci, vp, C.POINTER(vp)]
+        L.sbwtgpu_colors_destroy.argtypes = [vp]
+        L.sbwtgpu_colors_destroy.restype = None
+        L.sbwtgpu_colors_add_batch.argtypes = [vp, ci, vp, vp, i64, ci, C.POINTER(i64), C.POINTER(i64)]
+        L.sbwtgpu_colors_info.argtypes = [vp, C.POINTER(ColorsInfoC)]
+        L.sbwtgpu_colors_copy.argtypes = [vp, vp]
+        L.sbwtgpu_colors_dev.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_pseudoalign_batch.argtypes = [vp, vp, vp, i64, ci, ci, ci, vp, vp]
+        L.sbwtgpu_pseudoalign_workspace_bytes.argtypes = [i64, i64, ci]
+        L.sbwtgpu_pseudoalign_workspace_bytes.restype = i64
+        L.sbwtgpu_pseudoalign_dev.argtypes = [vp, vp, i64, vp, i64, ci, ci, ci, vp, vp, vp, i64, vp]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -687,6 +708,114 @@ class Unitigs:
         return {"pass_ms": dict(zip(names, (float(x) for x in ms))), "jump_rounds": int(r.value)}
 
 
+class Colors:
+    """Owns an sbwtgpu_colors handle: the colour matrix of an index (one uint64 row per column, bit c = reference c holds the
+    column's k-mer) and pseudoalignment over it.  The index must stay alive as long as the object (it is kept referenced)."""
+
+    def __init__(self, handle, index: Index, n_colors: int):
+        self._h = handle
+        self.index, self.n_colors = index, n_colors
+
+    @classmethod
+    def create(cls, index: Index, n_colors: int) -> "Colors":
+        """An empty matrix of n_colors colours (1 .. 64)."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_colors_create(index.handle, n_colors, None, C.byref(h)))
+        return cls(h, index, n_colors)
+
+    @classmethod
+    def from_rows(cls, index: Index, rows, n_colors: int, k: Optional[int] = None) -> "Colors":
+        """A matrix from its rows (Colors.rows(), or hostlib.colors_read with its k): bits >= n_colors and the rows of dummy
+        columns are cleared.  Rows of another index -- another number of columns, another k -- are refused."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        if rows.ndim != 1 or len(rows) != index.n_nodes or (k is not None and k != index.k):
+            raise SbwtGpuError(ERR_INVALID_ARG, "colours of %d columns at k = %s used with an index of %d columns at k = %d"
+                               % (rows.size, "?" if k is None else k, index.n_nodes, index.k))
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_colors_create(index.handle, n_colors, rows.ctypes.data, C.byref(h)))
+        return cls(h, index, n_colors)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        if self._h:
+            lib().sbwtgpu_colors_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def add_sequences(self, color: int, bases, read_off, both_strands: bool = False):
+        """sbwtgpu_colors_add_batch: colours every k-mer of the sequences that the index holds; (n_windows, n_hit_windows).
+        Not to be run concurrently with anything else on this object."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        nw, nh = C.c_int64(0), C.c_int64(0)
+        _check(lib().sbwtgpu_colors_add_batch(self._h, color, bases.ctypes.data, read_off.ctypes.data, max(len(read_off) - 1, 0),
+                                              2 if both_strands else 1, C.byref(nw), C.byref(nh)))
+        return nw.value, nh.value
+
+    def add_reads(self, color: int, reads: Sequence[bytes], both_strands: bool = False):
+        """The same for a list of byte strings."""
+        bases, off = concat_reads(reads)
+        return self.add_sequences(color, bases, off, both_strands)
+
+    def rows(self) -> np.ndarray:
+        out = np.empty(self.index.n_nodes, dtype=np.uint64)
+        _check(lib().sbwtgpu_colors_copy(self._h, out.ctypes.data))
+        return out
+
+    def rows_dev(self) -> int:
+        p = C.c_void_p()
+        _check(lib().sbwtgpu_colors_dev(self._h, C.byref(p)))
+        return p.value or 0
+
+    def info(self) -> dict:
+        """n_columns, k, n_colors, n_colored_columns and per_color (n_colors counts of coloured columns)."""
+        ci = ColorsInfoC()
+        _check(lib().sbwtgpu_colors_info(self._h, C.byref(ci)))
+        return {"n_columns": ci.n_columns, "k": ci.k, "n_colors": ci.n_colors, "n_colored_columns": ci.n_colored_columns,
+                "per_color": [int(ci.per_color[c]) for c in range(ci.n_colors)]}
+
+    def pseudoalign(self, bases, read_off, both_strands: bool = False, threshold_ppm: int = 1_000_000, denominator: int = 0,
+                    counts: bool = False):
+        """sbwtgpu_pseudoalign_batch: a record array (PSEUDOALIGNMENT_DTYPE: colors, n_kmers, n_found) of n_reads entries;
+        with counts=True also the (n_reads, n_colors) int32 array of count_c."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        n = max(len(read_off) - 1, 0)
+        out = np.zeros(n, dtype=PSEUDOALIGNMENT_DTYPE)
+        out["n_kmers"] = -12345
+        cnt = np.full((n, self.n_colors), -12345, dtype=np.int32) if counts else None
+        _check(lib().sbwtgpu_pseudoalign_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n, 2 if both_strands else 1,
+                                               threshold_ppm, denominator, out.ctypes.data, cnt.ctypes.data if counts else None))
+        return (out, cnt) if counts else out
+
+    def pseudoalign_reads(self, reads: Sequence[bytes], both_strands: bool = False, threshold_ppm: int = 1_000_000,
+                          denominator: int = 0, counts: bool = False):
+        """The same for a list of byte strings."""
+        bases, off = concat_reads(reads)
+        return self.pseudoalign(bases, off, both_strands, threshold_ppm, denominator, counts)
+
+    def pseudoalign_dev(self, d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_out: int, d_counts: int, d_ws: int,
+                        ws_bytes: int, both_strands: bool = False, threshold_ppm: int = 1_000_000, denominator: int = 0,
+                        stream: int = 0):
+        """sbwtgpu_pseudoalign_dev (raw device pointers; d_out: n_reads records of 16 bytes; d_counts = 0: no counts)."""
+        _check(lib().sbwtgpu_pseudoalign_dev(self._h, d_bases, total_bases, d_read_off, n_reads, 2 if both_strands else 1,
+                                             threshold_ppm, denominator, d_out, d_counts or None, d_ws, ws_bytes, stream))
+
+
 def kernel_times() -> list:
     """Durations (ms) of the dominant kernel of the search calls since set_tuning("kernel_events", 1)."""
     buf = (C.c_double * 256)()
@@ -705,3 +834,7 @@ def ms_workspace_bytes(total_bases: int) -> int:
 
 def read_hits_workspace_bytes(total_bases: int, n_reads: int, both_strands: bool = False) -> int:
     return int(lib().sbwtgpu_read_hits_workspace_bytes(total_bases, n_reads, 2 if both_strands else 1))
+
+
+def pseudoalign_workspace_bytes(total_bases: int, n_reads: int, both_strands: bool = False) -> int:
+    return int(lib().sbwtgpu_pseudoalign_workspace_bytes(total_bases, n_reads, 2 if both_strands else 1))

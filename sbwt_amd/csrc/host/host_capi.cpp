@@ -223,4 +223,52 @@ int sbwthost_rank_batch(const uint64_t *bits, int64_t n_bits, const int64_t *pos
     }
 }
 
+// ---- colour files: "SBWTCOL1", int64 n_columns, n_colors, k, then n_columns little-endian uint64 rows ----
+static const char COLORS_MAGIC[8] = {'S', 'B', 'W', 'T', 'C', 'O', 'L', '1'};
+
+int sbwthost_colors_write(const char *path, const uint64_t *rows, int64_t n_columns, int64_t n_colors, int64_t k) {
+    if (!path || n_columns < 0 || (n_columns > 0 && !rows)) return fail("invalid argument");
+    if (n_colors < 1 || n_colors > 64) return fail("Error: n_colors must be in 1 .. 64, not %lld", (long long)n_colors);
+    std::ofstream out(path, std::ios::binary);
+    if (!out.good()) return fail("Error opening file: %s", path);
+    const int64_t head[3] = {n_columns, n_colors, k};
+    out.write(COLORS_MAGIC, 8);
+    out.write(reinterpret_cast<const char *>(head), 24);
+    if (n_columns > 0) out.write(reinterpret_cast<const char *>(rows), (std::streamsize)(n_columns * 8));
+    out.flush();
+    if (!out.good()) return fail("Error writing to file %s", path);
+    return 0;
+}
+
+int sbwthost_colors_read(const char *path, int64_t *n_columns, int64_t *n_colors, int64_t *k, uint64_t *rows_or_null,
+                         int64_t rows_cap) {
+    if (!path) return fail("invalid argument");
+    std::ifstream in(path, std::ios::binary);
+    if (!in.good()) return fail("Error opening file: %s", path);
+    char magic[8];
+    int64_t head[3];
+    in.read(magic, 8);
+    if (in.gcount() != 8) return fail("Error: colour file %s is truncated (no magic)", path);
+    if (memcmp(magic, COLORS_MAGIC, 8) != 0) return fail("Error: %s is not a colour file (wrong magic, SBWTCOL1 expected)", path);
+    in.read(reinterpret_cast<char *>(head), 24);
+    if (in.gcount() != 24) return fail("Error: colour file %s is truncated (header)", path);
+    if (head[1] < 1 || head[1] > 64) return fail("Error: colour file %s: n_colors = %lld is outside 1 .. 64", path, (long long)head[1]);
+    if (head[0] < 0 || head[0] > ((int64_t)1 << 56)) return fail("Error: colour file %s: n_columns = %lld", path, (long long)head[0]);
+    in.seekg(0, std::ios::end);
+    const int64_t size = (int64_t)in.tellg(), want = 32 + head[0] * 8;
+    if (size < want)
+        return fail("Error: colour file %s is truncated (%lld bytes, %lld columns need %lld)", path, (long long)size, (long long)head[0],
+                    (long long)want);
+    if (size > want) return fail("Error: colour file %s has %lld bytes after its %lld rows", path, (long long)(size - want), (long long)head[0]);
+    if (n_columns) *n_columns = head[0];
+    if (n_colors) *n_colors = head[1];
+    if (k) *k = head[2];
+    if (!rows_or_null) return 0;
+    if (rows_cap < head[0]) return fail("Error: room for %lld rows, the colour file holds %lld", (long long)rows_cap, (long long)head[0]);
+    in.seekg(32, std::ios::beg);
+    if (head[0] > 0) in.read(reinterpret_cast<char *>(rows_or_null), (std::streamsize)(head[0] * 8));
+    if (!in.good()) return fail("Error reading %s", path);
+    return 0;
+}
+
 }  // extern "C"

@@ -5,6 +5,10 @@
 //   sbwt search -o <out> -i <index> -q <query> [-z]        (sbwt_search.cpp:151-157)
 //   sbwt matching-statistics -i <index> -q <query> -o <out> [-z] [--intervals]
 //               k-bounded matching statistics: one line per read, one token per base ("d", or "d,first,second")
+//   sbwt build-colors -i <index> -r <refs.txt> -o <colours> [--both-strands]
+//               one colour per listed reference file, set on the columns of the index's k-mers that the file holds
+//   sbwt pseudoalign -i <index> -c <colours> -q <query> -o <out> [-z] [--threshold 0.7] [--all-kmers] [--both-strands]
+//               one line per read: its number, then the colours that hold it
 //   sbwt build  -i <in> -o <index> -k <k> [-p <precalc>] [--add-reverse-complements]
 //               [--no-streaming-support] [-t <threads>]      (subset of sbwt_build.cpp:40-55)
 // Extra, GPU-only flags of `search` (defaults keep the reference behaviour and output):
@@ -884,7 +888,198 @@ int set_op_main(int argc, char **argv) {
     return 0;
 }
 
-const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "set-op", "read-hits"};
+// ---- colours and pseudoalignment (include/sbwtgpu.h) ----
+// `--threshold` as parts per million, from its decimal text and without floating point: "0.7" -> 700000, "1" -> 1000000.
+// Digits (at least one), optionally '.' and digits; what comes after the sixth decimal must be zeros; 0 < value <= 1.
+int64_t parse_threshold_ppm(const string &s) {
+    const size_t dot = s.find('.');
+    const string ip = s.substr(0, dot), fp = dot == string::npos ? string() : s.substr(dot + 1);
+    bool ok = !ip.empty() && ip.size() <= 9 && (dot == string::npos || !fp.empty());
+    for (char ch : ip + fp) ok = ok && ch >= '0' && ch <= '9';
+    int64_t ppm = 0;
+    if (ok) {
+        ppm = atoll(ip.c_str()) * 1000000;
+        int64_t scale = 100000;
+        for (size_t i = 0; i < fp.size(); i++) {
+            if (i < 6) { ppm += (fp[i] - '0') * scale; scale /= 10; }
+            else if (fp[i] != '0') ok = false;
+        }
+    }
+    if (!ok || ppm < 1 || ppm > 1000000)
+        throw std::runtime_error("Error: --threshold must be a decimal number in (0, 1] with at most six decimals, not '" + s + "'");
+    return ppm;
+}
+
+void colors_check(int rc) {
+    if (rc != SBWTGPU_OK) throw std::runtime_error(string("Error: ") + sbwtgpu_last_error());
+}
+struct ColorsHandle {
+    sbwtgpu_colors *h = nullptr;
+    ~ColorsHandle() { sbwtgpu_colors_destroy(h); }
+};
+
+void load_plain_matrix(const string &indexfile, plain_matrix_sbwt_t &index) {
+    std::ifstream in(indexfile, std::ios::binary);
+    if (!in.good()) throw std::runtime_error("Error opening file: " + indexfile);
+    const string variant = load_string(in);
+    if (variant != "plain-matrix")
+        throw std::runtime_error("Error: only the plain-matrix variant is supported by the GPU path (got " + variant + ")");
+    index.load(in);
+}
+
+// sbwt build-colors: refs.txt holds one sequence file per line, colour = 0-based line number (at most 64); every file's k-mers
+// that the index holds get the file's colour
+int build_colors_main(int argc, char **argv) {
+    set_log_level(LogLevel::MINOR);
+    Options opts({
+        {"index-file", 'i', true, "Index input file.", ""},
+        {"refs", 'r', true, "A list of sequence files (FASTA or FASTQ, possibly gzipped), one per line: the colour of a file is its 0-based line number. At most 64 lines.", ""},
+        {"out-file", 'o', true, "Output colour file.", ""},
+        {"both-strands", 0, false, "Also colour the reverse complement of every k-mer (for indexes built with reverse complements).", ""},
+        {"gpu", 0, true, "HIP device to run on.", "0"},
+        {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
+        {"help", 'h', false, "Print usage", ""},
+    });
+    opts.parse(argc, argv);
+    if (argc == 1 || opts.count("help")) {
+        std::cerr << opts.help(argv[0], "Colour the k-mers of an index by the reference files that hold them.") << std::endl;
+        exit(1);
+    }
+    const string indexfile = opts.get("index-file"), refsfile = opts.get("refs"), outfile = opts.get("out-file");
+    check_readable(indexfile);
+    check_readable(refsfile);
+    const vector<string> refs = readlines(refsfile);
+    if (refs.empty() || refs.size() > 64)
+        throw std::runtime_error("Error: " + refsfile + " lists " + std::to_string(refs.size()) + " files; a colour file holds 1 to 64 colours");
+    for (const string &file : refs) check_readable(file);
+    check_writable(outfile);
+    const int strands = opts.count("both-strands") ? 2 : 1;
+    set_default_device(atoi(opts.get("gpu").c_str()));
+    int64_t batch_bases = atoll(opts.get("batch-bases").c_str());
+    if (batch_bases < 1) batch_bases = 1;
+    plain_matrix_sbwt_t index;
+    load_plain_matrix(indexfile, index);
+    ColorsHandle col;
+    colors_check(sbwtgpu_colors_create(index.device_handle(), (int)refs.size(), nullptr, &col.h));
+    vector<int64_t> windows(refs.size(), 0), hit_windows(refs.size(), 0);
+    for (size_t c = 0; c < refs.size(); c++) {
+        seq_io::Reader reader(refs[c]);
+        bool more = true;
+        vector<char> bases;
+        vector<int64_t> read_off;
+        while (more) {
+            bases.clear();
+            read_off.assign(1, 0);
+            more = reader.read_batch(bases, read_off, batch_bases);
+            const int64_t n_reads = (int64_t)read_off.size() - 1;
+            if (n_reads <= 0) continue;
+            int64_t w = 0, h = 0;
+            colors_check(sbwtgpu_colors_add_batch(col.h, (int)c, bases.data(), read_off.data(), n_reads, strands, &w, &h));
+            windows[c] += w;
+            hit_windows[c] += h;
+        }
+    }
+    sbwtgpu_colors_info_t info;
+    colors_check(sbwtgpu_colors_info(col.h, &info));
+    for (size_t c = 0; c < refs.size(); c++)
+        std::cout << "colour " << c << ": " << windows[c] << " windows, " << hit_windows[c] << " hit windows, " << info.per_color[c]
+                  << " coloured columns" << std::endl;
+    vector<uint64_t> rows((size_t)info.n_columns);
+    colors_check(sbwtgpu_colors_copy(col.h, rows.data()));
+    if (sbwthost_colors_write(outfile.c_str(), rows.data(), info.n_columns, info.n_colors, info.k) != 0)
+        throw std::runtime_error(sbwthost_last_error());
+    write_log("Wrote " + std::to_string(info.n_colors) + " colours of " + std::to_string(info.n_colored_columns) + " coloured columns to " + outfile,
+              LogLevel::MAJOR);
+    return 0;
+}
+
+// sbwt pseudoalign: one line per read in input order -- the read's 0-based number, then the ids of its colours, ascending,
+// separated by single spaces
+int pseudoalign_main(int argc, char **argv) {
+    int64_t micros_start = cur_time_micros();
+    set_log_level(LogLevel::MINOR);
+    Options opts({
+        {"out-file", 'o', true, "Output filename.", ""},
+        {"index-file", 'i', true, "Index input file.", ""},
+        {"colors-file", 'c', true, "Colour file of the index (sbwt build-colors).", ""},
+        {"query-file", 'q', true, "The query in FASTA or FASTQ format, possibly gzipped.", ""},
+        {"gzip-output", 'z', false, "Writes output in gzipped form.", ""},
+        {"threshold", 0, true, "A colour is reported when at least this fraction of the read's k-mers carries it.", "1.0"},
+        {"all-kmers", 0, false, "The fraction is taken of all k-mers of the read instead of the k-mers found in the index.", ""},
+        {"both-strands", 0, false, "A k-mer also carries the colours of its reverse complement.", ""},
+        {"gpu", 0, true, "HIP device to run on.", "0"},
+        {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
+        {"help", 'h', false, "Print usage", ""},
+    });
+    opts.parse(argc, argv);
+    if (argc == 1 || opts.count("help")) {
+        std::cerr << opts.help(argv[0], "Per read: the references (colours) that hold it.") << std::endl;
+        exit(1);
+    }
+    const string indexfile = opts.get("index-file"), colorsfile = opts.get("colors-file");
+    const string queryfile = opts.get("query-file"), outfile = opts.get("out-file");
+    check_readable(indexfile);
+    check_readable(colorsfile);
+    check_readable(queryfile);
+    check_writable(outfile);
+    const int threshold_ppm = (int)parse_threshold_ppm(opts.get("threshold"));
+    const int denominator = opts.count("all-kmers") ? 1 : 0;
+    const int strands = opts.count("both-strands") ? 2 : 1;
+    const bool gzip_output = opts.count("gzip-output");
+    set_default_device(atoi(opts.get("gpu").c_str()));
+    int64_t batch_bases = atoll(opts.get("batch-bases").c_str());
+    if (batch_bases < 1) batch_bases = 1;
+    plain_matrix_sbwt_t index;
+    load_plain_matrix(indexfile, index);
+    int64_t n_columns = 0, n_colors = 0, ck = 0;
+    if (sbwthost_colors_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, nullptr, 0) != 0) throw std::runtime_error(sbwthost_last_error());
+    if (n_columns != index.number_of_subsets() || ck != index.get_k())
+        throw std::runtime_error("Error: " + colorsfile + " colours an index of " + std::to_string(n_columns) + " columns at k = " +
+                                 std::to_string(ck) + ", " + indexfile + " has " + std::to_string(index.number_of_subsets()) +
+                                 " columns at k = " + std::to_string(index.get_k()));
+    ColorsHandle col;
+    {
+        vector<uint64_t> rows((size_t)n_columns);
+        if (sbwthost_colors_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, rows.data(), n_columns) != 0)
+            throw std::runtime_error(sbwthost_last_error());
+        colors_check(sbwtgpu_colors_create(index.device_handle(), (int)n_colors, rows.data(), &col.h));
+    }
+    write_log("Running pseudoalignment from input file " + queryfile + " to output file " + outfile, LogLevel::MAJOR);
+    seq_io::Reader reader(queryfile);
+    seq_io::Buffered_ofstream writer(outfile, gzip_output);
+    bool more = true;
+    vector<char> bases;
+    vector<int64_t> read_off;
+    vector<sbwtgpu_pseudoalignment> rec;
+    string text;
+    int64_t total_reads = 0;
+    while (more) {
+        bases.clear();
+        read_off.assign(1, 0);
+        more = reader.read_batch(bases, read_off, batch_bases);
+        const int64_t n_reads = (int64_t)read_off.size() - 1;
+        if (n_reads <= 0) continue;
+        rec.resize((size_t)n_reads);
+        colors_check(sbwtgpu_pseudoalign_batch(col.h, bases.data(), read_off.data(), n_reads, strands, threshold_ppm, denominator,
+                                               rec.data(), nullptr));
+        text.clear();
+        for (const sbwtgpu_pseudoalignment &p : rec) {
+            append_int(total_reads++, text);
+            for (int c = 0; c < 64; c++)
+                if ((p.colors >> c) & 1) {
+                    text.push_back(' ');
+                    append_int(c, text);
+                }
+            text.push_back('\n');
+        }
+        writer.write(text.data(), (int64_t)text.size());
+    }
+    write_log("us/read end-to-end: " + std::to_string((double)(cur_time_micros() - micros_start) / (double)std::max<int64_t>(1, total_reads)),
+              LogLevel::MAJOR);
+    return 0;
+}
+
+const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "set-op", "read-hits", "build-colors", "pseudoalign"};
 
 void print_help(char **argv) {
     std::cerr << "Available commands: " << std::endl;
@@ -917,6 +1112,8 @@ int main(int argc, char **argv) {   // sbwt.cpp:19-57
         else if (command == "dump-unitigs") return dump_unitigs_main(argc, argv);
         else if (command == "set-op") return set_op_main(argc, argv);
         else if (command == "read-hits") return read_hits_main(argc, argv);
+        else if (command == "build-colors") return build_colors_main(argc, argv);
+        else if (command == "pseudoalign") return pseudoalign_main(argc, argv);
         else throw std::runtime_error("Invalid command: " + command);
     } catch (const std::runtime_error &e) {
         std::cerr << "Runtime error: " << e.what() << '\n';

@@ -23,6 +23,7 @@
 #include "sbwt_unitigs.h"
 #include "sbwt_setops.h"
 #include "sbwt_readhits.h"
+#include "sbwt_colors.h"
 
 namespace {
 
@@ -181,6 +182,7 @@ static int g_sparse_buckets_pct = [] { const int v = env_int("SBWTGPU_SPARSE_BUC
 static int g_rh_wave_min = SBWT_RH_WAVE_MIN;
 static int64_t g_rh_chunk_bases = 0;
 static int g_rh_wide = 0;
+static int64_t g_pa_chunk_bases = 0;      // "pseudoalign_chunk_bases": 0 = the default of 64 Mi
 // depth of the sparse (hashed) prefix table built at index creation (capped at k and at 31 = one 62-bit key)
 static int g_sparse_depth = env_int("SBWTGPU_SPARSE_PRECALC", 31);
 
@@ -286,6 +288,7 @@ int sbwtgpu_set_tuning(const char *key, int64_t value) {
     if (!strcmp(key, "read_hits_wave_min")) { g_rh_wave_min = value < 1 ? SBWT_RH_WAVE_MIN : value > 0x7fffffff ? 0x7fffffff : (int)value; return SBWTGPU_OK; }
     if (!strcmp(key, "read_hits_chunk_bases")) { g_rh_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "read_hits_wide")) { g_rh_wide = (int)value; return SBWTGPU_OK; }
+    if (!strcmp(key, "pseudoalign_chunk_bases")) { g_pa_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "sparse_depth")) {      // takes effect for indexes created afterwards
         if (value < 0 || value > 31) return fail(SBWTGPU_ERR_INVALID_ARG, "sparse_depth must be in [0,31]");
         g_sparse_depth = (int)value;
@@ -2782,6 +2785,324 @@ int sbwtgpu_read_hits_batch(const sbwtgpu_index *idx, const char *bases, const i
     if (rc != SBWTGPU_OK) return rc;
     if (bug) return fail_status(bug);
     return SBWTGPU_OK;
+}
+
+// ---- colours and pseudoalignment (sbwt_colors.hip) ----------------------------------------------------
+static_assert(sizeof(sbwtgpu_pseudoalignment) == sizeof(SbwtPseudoalignment), "the record of the ABI is the kernels' record");
+
+struct sbwtgpu_colors {
+    const sbwtgpu_index *idx = nullptr;
+    int device = 0;
+    int64_t n_nodes = 0, k = 0;
+    int n_colors = 0;
+    unsigned long long *d_rows = nullptr;
+};
+
+static int colors_check_index(const sbwtgpu_index *idx) {
+    if (idx->h.n_nodes >= ((int64_t)1 << 31))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "colours: the index has %lld columns, the colour layer reads int32 search results (fewer than 2^31 columns)",
+                    (long long)idx->h.n_nodes);
+    if (idx->h.rank_only) return fail(SBWTGPU_ERR_INVALID_ARG, "%s", RANK_ONLY_MSG);
+    return SBWTGPU_OK;
+}
+// the object and the index it was made for still agree (a colours object is bound to its index at creation)
+static int colors_check(const sbwtgpu_colors *c) {
+    if (!c || !c->idx) return fail(SBWTGPU_ERR_INVALID_ARG, "colours object is NULL");
+    if (c->idx->h.n_nodes != c->n_nodes || c->idx->h.k != c->k)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "colours of %lld columns at k = %lld used with an index of %lld columns at k = %lld",
+                    (long long)c->n_nodes, (long long)c->k, (long long)c->idx->h.n_nodes, (long long)c->idx->h.k);
+    return colors_check_index(c->idx);
+}
+static int colors_check_batch(int64_t n_reads, int strands) {
+    if (strands != 1 && strands != 2) return fail(SBWTGPU_ERR_INVALID_ARG, "strands must be 1 (forward) or 2 (either strand), not %d", strands);
+    if (n_reads < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative n_reads");
+    if (n_reads >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_INVALID_ARG, "2^31 reads or more in one call: split the batch");
+    return SBWTGPU_OK;
+}
+static int colors_check_query(int threshold_ppm, int denominator) {
+    if (threshold_ppm < 1 || threshold_ppm > 1000000)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "threshold_ppm must be in 1 .. 1000000, not %d", threshold_ppm);
+    if (denominator != 0 && denominator != 1)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "denominator must be 0 (the found k-mers) or 1 (all k-mers), not %d", denominator);
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_colors_create(const sbwtgpu_index *idx, int n_colors, const uint64_t *rows_or_null, sbwtgpu_colors **out) {
+    if (!idx || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    int rc = colors_check_index(idx);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_colors < 1 || n_colors > 64)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "n_colors must be in 1 .. 64, not %d (more than 64 colours are out of scope)", n_colors);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", idx->device);
+    sbwtgpu_colors *c = new (std::nothrow) sbwtgpu_colors();
+    if (!c) return fail(SBWTGPU_ERR_OOM, "out of host memory");
+    c->idx = idx;
+    c->device = idx->device;
+    c->n_nodes = idx->h.n_nodes;
+    c->k = idx->h.k;
+    c->n_colors = n_colors;
+    const size_t bytes = (size_t)c->n_nodes * 8;
+    Stream st;
+    hipError_t e = hipMalloc((void **)&c->d_rows, bytes ? bytes : 16);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
+    if (e == hipSuccess && !rows_or_null) e = hipMemsetAsync(c->d_rows, 0, bytes, st.s);
+    if (e == hipSuccess && rows_or_null) e = hipMemcpyAsync(c->d_rows, rows_or_null, bytes, hipMemcpyHostToDevice, st.s);
+    if (e == hipSuccess) e = rows_or_null ? sbwt_colors_clean(idx->view(), c->d_rows, n_colors, st.s) : hipStreamSynchronize(st.s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        sbwtgpu_colors_destroy(c);
+        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "colours: %s", hipGetErrorString(e));
+    }
+    *out = c;
+    return SBWTGPU_OK;
+}
+
+void sbwtgpu_colors_destroy(sbwtgpu_colors *c) {
+    if (!c) return;
+    DeviceGuard guard(c->device);
+    if (c->d_rows) (void)hipFree(c->d_rows);
+    delete c;
+}
+
+int sbwtgpu_colors_info(const sbwtgpu_colors *c, sbwtgpu_colors_info_t *info) {
+    if (!c || !info) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    memset(info, 0, sizeof(*info));
+    info->n_columns = c->n_nodes;
+    info->k = c->k;
+    info->n_colors = c->n_colors;
+    DeviceGuard guard(c->device);
+    DevBuf stats;
+    Stream st;
+    unsigned long long h[65];
+    HIP_TRY(stats.alloc(sizeof(h)));
+    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    HIP_TRY(hipMemsetAsync(stats.p, 0, sizeof(h), st.s));
+    sbwt_launch_col_stats(c->d_rows, c->n_nodes, static_cast<unsigned long long *>(stats.p), st.s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h, stats.p, sizeof(h), hipMemcpyDeviceToHost, st.s));
+    HIP_TRY(hipStreamSynchronize(st.s));
+    for (int i = 0; i < 64; i++) info->per_color[i] = (int64_t)h[i];
+    info->n_colored_columns = (int64_t)h[64];
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_colors_copy(const sbwtgpu_colors *c, uint64_t *rows_out) {
+    if (!c || !rows_out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    DeviceGuard guard(c->device);
+    HIP_TRY(hipMemcpy(rows_out, c->d_rows, (size_t)c->n_nodes * 8, hipMemcpyDeviceToHost));
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_colors_dev(const sbwtgpu_colors *c, const uint64_t **d_rows) {
+    if (!c || !d_rows) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *d_rows = reinterpret_cast<const uint64_t *>(c->d_rows);
+    return SBWTGPU_OK;
+}
+
+int64_t sbwtgpu_pseudoalign_workspace_bytes(int64_t total_bases, int64_t n_reads, int strands) {
+    if (total_bases < 0) total_bases = 0;
+    if (n_reads < 0) n_reads = 0;
+    return sbwt_pa_layout(sbwtgpu_search_workspace_bytes(total_bases), total_bases, n_reads, strands == 2 ? 2 : 1).total;
+}
+
+// What colouring and the query share: the result offsets, the int32 search of the batch and, for two strands, of the mirrored
+// batch into the second result buffer; `tail` enqueues what turns the results into bits or records (res2: NULL with one strand,
+// and for a batch without any window, whose result buffers nobody wrote).
+}  // extern "C"
+template <typename Tail>
+static int colors_dev_common(const sbwtgpu_colors *c, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                             int64_t n_reads, int strands, void *d_ws, int64_t ws_bytes, void *stream, Tail tail) {
+    if (total_bases < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative size");
+    if (total_bases >= ((int64_t)1 << 36))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "more than 2^36 bases in one call: split the batch");
+    const int64_t need = sbwtgpu_pseudoalign_workspace_bytes(total_bases, n_reads, strands);
+    if (!d_ws || ws_bytes < need)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "workspace missing or too small (%lld < %lld)", (long long)ws_bytes, (long long)need);
+    if (((uintptr_t)d_ws & 15) != 0) return fail(SBWTGPU_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+    if (n_reads == 0) return SBWTGPU_OK;
+    if (!d_read_off || (total_bases > 0 && !d_bases)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
+    const sbwtgpu_index *idx = c->idx;
+    DeviceGuard guard(idx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t search_ws = sbwtgpu_search_workspace_bytes(total_bases);
+    const SbwtPaLayout L = sbwt_pa_layout(search_ws, total_bases, n_reads, strands);
+    char *w = static_cast<char *>(d_ws);
+    SbwtPaHeader *hdr = reinterpret_cast<SbwtPaHeader *>(w + L.hdr);
+    int *res = reinterpret_cast<int *>(w + L.res);
+    long long *ooff = reinterpret_cast<long long *>(w + L.ooff);
+    const int k = (int)idx->h.k;
+    HIP_TRY(hipMemsetAsync(hdr, 0, sizeof(SbwtPaHeader), st));
+    sbwt_launch_rh_offsets(reinterpret_cast<const long long *>(d_read_off), n_reads, k, reinterpret_cast<long long *>(w + L.cnt),
+                           reinterpret_cast<long long *>(w + L.bsum), ooff, st);
+    // (a batch of fewer than k bases has no window: nothing to search, and `tail` reads no result)
+    const bool any = total_bases >= k;
+    const SbwtWorkHeader *sws = reinterpret_cast<const SbwtWorkHeader *>(w);
+    int *res2 = nullptr;
+    int rc;
+    if (any) {
+        t_out32 = 1;
+        rc = search_dev_common(idx, d_bases, total_bases, d_read_off, n_reads, reinterpret_cast<int64_t *>(res),
+                               reinterpret_cast<const int64_t *>(ooff), d_ws, search_ws, stream, 0);
+        t_out32 = 0;
+        if (rc != SBWTGPU_OK) return rc;
+        sbwt_launch_pa_note_status(sws, hdr, st);
+    }
+    if (strands == 2 && any) {
+        res2 = reinterpret_cast<int *>(w + L.res2);
+        char *rcb = w + L.rc;
+        long long *roff2 = reinterpret_cast<long long *>(w + L.roff2), *ooff2 = reinterpret_cast<long long *>(w + L.ooff2);
+        sbwt_launch_rh_mirror(d_bases, total_bases, reinterpret_cast<const long long *>(d_read_off), ooff, n_reads, rcb, roff2, ooff2, st);
+        t_out32 = 1;
+        rc = search_dev_common(idx, rcb, total_bases, reinterpret_cast<const int64_t *>(roff2), n_reads, reinterpret_cast<int64_t *>(res2),
+                               reinterpret_cast<const int64_t *>(ooff2), d_ws, search_ws, stream, 0);
+        t_out32 = 0;
+        if (rc != SBWTGPU_OK) return rc;
+        sbwt_launch_pa_note_status(sws, hdr, st);
+    }
+    tail(res, res2, ooff, hdr, st);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
+    return SBWTGPU_OK;
+}
+extern "C" {
+
+int sbwtgpu_pseudoalign_dev(const sbwtgpu_colors *c, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                            int64_t n_reads, int strands, int threshold_ppm, int denominator, sbwtgpu_pseudoalignment *d_out,
+                            int32_t *d_counts_or_null, void *d_ws, int64_t ws_bytes, void *stream) {
+    int rc = colors_check(c);
+    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_reads > 0 && !d_out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
+    return colors_dev_common(c, d_bases, total_bases, d_read_off, n_reads, strands, d_ws, ws_bytes, stream,
+                             [&](const int *res, const int *res2, const long long *ooff, SbwtPaHeader *, hipStream_t st) {
+                                 sbwt_launch_pa_reduce(res, res2, ooff, n_reads, c->d_rows, c->n_nodes, c->n_colors, threshold_ppm,
+                                                       denominator, reinterpret_cast<SbwtPseudoalignment *>(d_out), d_counts_or_null, st);
+                             });
+}
+
+// Host buffers, for colouring (out == NULL: bit `color` is set, *n_hit the windows with a hit) and for the query alike: the batch
+// is cut into chunks of whole reads of at most "pseudoalign_chunk_bases" bases (a chunk always takes one read), two chunks in
+// flight on the parked slots of the search pipeline.  Bases and offsets go down; records, and counts if asked for, come back.
+static int colors_host_batch(const sbwtgpu_colors *c, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
+                             int color, int threshold_ppm, int denominator, sbwtgpu_pseudoalignment *out, int32_t *counts,
+                             int64_t *n_windows, int64_t *n_hit) {
+    const sbwtgpu_index *idx = c->idx;
+    if (n_windows) *n_windows = 0;
+    if (n_hit) *n_hit = 0;
+    if (n_reads == 0) return SBWTGPU_OK;
+    if (!read_off) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    if (read_off[n_reads] > read_off[0] && !bases) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    const int64_t budget = g_pa_chunk_bases > 0 ? g_pa_chunk_bases : (int64_t)64 << 20, CH_READS = (int64_t)1 << 24;
+    const int64_t nc = c->n_colors, k = c->k;
+    std::vector<int64_t> cuts{0};
+    int64_t max_bases = 0, max_reads = 0, windows = 0;
+    int rc;
+    try {
+        for (int64_t lo = 0, r = 0; r < n_reads; r++) {
+            if ((rc = check_read_length(read_off, r)) != SBWTGPU_OK) return rc;
+            if (r > lo && (read_off[r + 1] - read_off[lo] > budget || r - lo >= CH_READS)) {
+                cuts.push_back(r);
+                lo = r;
+            }
+            max_bases = std::max(max_bases, read_off[r + 1] - read_off[lo]);
+            max_reads = std::max(max_reads, r + 1 - lo);
+            windows += std::max<int64_t>(0, read_off[r + 1] - read_off[r] - k + 1);
+        }
+        cuts.push_back(n_reads);
+    } catch (const std::bad_alloc &) {
+        return fail(SBWTGPU_ERR_OOM, "out of host memory");
+    }
+    const int64_t n_chunks = (int64_t)cuts.size() - 1;
+    const bool pin_in = is_pinned(bases);
+    const int64_t ws_bytes = sbwtgpu_pseudoalign_workspace_bytes(max_bases, max_reads, strands);
+    const int64_t b_rec = out ? align256(max_reads * 16) : 0, b_cnt = counts ? align256(max_reads * nc * 4) : 0;
+    const int64_t need_in = align256(max_bases + 16) + align256((max_reads + 1) * 8);
+    const int64_t need_out = b_rec + b_cnt;
+    const int64_t need_dev = align256(max_bases + 16) + align256((max_reads + 1) * 8) + b_rec + b_cnt + align256(ws_bytes);
+    DeviceGuard guard(idx->device);
+    const int n_slots = n_chunks > 1 ? 2 : 1;
+    PipeSlot S[2];
+    if ((rc = take_slots(idx->device, S, n_slots, need_in, need_out, need_dev, "pseudoalignment buffers")) != SBWTGPU_OK) return rc;
+    int bug = 0;                    // the first nonzero device status of a chunk
+    int64_t hits = 0;
+    const int64_t o_roff = align256(max_bases + 16), o_rec = o_roff + align256((max_reads + 1) * 8), o_cnt = o_rec + b_rec,
+                  o_ws = o_cnt + b_cnt;
+    auto submit = [&](int64_t ch) -> int {
+        PipeSlot &P = S[ch % n_slots];
+        const int64_t lo = cuts[(size_t)ch], hi = cuts[(size_t)ch + 1], nr = hi - lo, nb = read_off[hi] - read_off[lo];
+        int64_t *hro = (int64_t *)(P.h_in + align256(max_bases + 16));
+        for (int64_t r = 0; r <= nr; r++) hro[r] = read_off[lo + r] - read_off[lo];
+        const char *hb = bases + read_off[lo];
+        if (!pin_in && nb > 0) { parallel_memcpy(P.h_in, hb, (size_t)nb); hb = P.h_in; }
+        hipError_t e;
+        if ((nb > 0 && (e = hipMemcpyAsync(P.d_mem, hb, (size_t)nb, hipMemcpyHostToDevice, P.st)) != hipSuccess) ||
+            (e = hipMemcpyAsync(P.d_mem + o_roff, hro, (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, P.st)) != hipSuccess)
+            return fail(SBWTGPU_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
+        int r2;
+        const int64_t *d_roff = (const int64_t *)(P.d_mem + o_roff);
+        if (out) {
+            r2 = sbwtgpu_pseudoalign_dev(c, P.d_mem, nb, d_roff, nr, strands, threshold_ppm, denominator,
+                                         (sbwtgpu_pseudoalignment *)(P.d_mem + o_rec), counts ? (int32_t *)(P.d_mem + o_cnt) : nullptr,
+                                         P.d_mem + o_ws, ws_bytes, P.st);
+        } else {
+            r2 = colors_dev_common(c, P.d_mem, nb, d_roff, nr, strands, P.d_mem + o_ws, ws_bytes, P.st,
+                                   [&](const int *res, const int *res2, const long long *ooff, SbwtPaHeader *hdr, hipStream_t st) {
+                                       sbwt_launch_col_mark(res, res2, ooff, nr, nb, c->d_rows, c->n_nodes, color, 1, hdr, st);
+                                       if (res2) sbwt_launch_col_mark(res2, nullptr, ooff, nr, nb, c->d_rows, c->n_nodes, color, 0, hdr, st);
+                                   });
+        }
+        if (r2 != SBWTGPU_OK) return r2;
+        const SbwtPaLayout L = sbwt_pa_layout(sbwtgpu_search_workspace_bytes(nb), nb, nr, strands);
+        if ((out && (e = hipMemcpyAsync(P.h_out, P.d_mem + o_rec, (size_t)nr * 16, hipMemcpyDeviceToHost, P.st)) != hipSuccess) ||
+            (counts && nr * nc > 0 &&
+             (e = hipMemcpyAsync(P.h_out + b_rec, P.d_mem + o_cnt, (size_t)(nr * nc) * 4, hipMemcpyDeviceToHost, P.st)) != hipSuccess) ||
+            (e = hipMemcpyAsync(P.h_status, P.d_mem + o_ws + L.hdr, 16, hipMemcpyDeviceToHost, P.st)) != hipSuccess)
+            return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
+        return SBWTGPU_OK;
+    };
+    auto collect = [&](int64_t ch) -> int {
+        PipeSlot &P = S[ch % n_slots];
+        hipError_t e = hipStreamSynchronize(P.st);
+        if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "stream synchronize: %s", hipGetErrorString(e));
+        if (P.h_status[0] != 0 && bug == 0) bug = P.h_status[0];
+        unsigned long long nh;
+        memcpy(&nh, P.h_status + 2, 8);                  // (SbwtPaHeader::n_hit)
+        hits += (int64_t)nh;
+        const int64_t lo = cuts[(size_t)ch], hi = cuts[(size_t)ch + 1];
+        if (out) memcpy(out + lo, P.h_out, (size_t)(hi - lo) * 16);
+        if (counts && (hi - lo) * nc > 0) memcpy(counts + lo * nc, P.h_out + b_rec, (size_t)((hi - lo) * nc) * 4);
+        return SBWTGPU_OK;
+    };
+    rc = two_in_flight(n_chunks, submit, collect);
+    park_slots(idx->device, S, n_slots, rc);
+    if (rc != SBWTGPU_OK) return rc;
+    if (bug) return fail_status(bug);
+    if (n_windows) *n_windows = windows;
+    if (n_hit) *n_hit = hits;
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_colors_add_batch(sbwtgpu_colors *c, int color, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
+                             int64_t *n_windows, int64_t *n_hit_windows) {
+    int rc = colors_check(c);
+    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc != SBWTGPU_OK) return rc;
+    if (color < 0 || color >= c->n_colors)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "color %d is out of range: the colours object has %d colours", color, c->n_colors);
+    return colors_host_batch(c, bases, read_off, n_reads, strands, color, 0, 0, nullptr, nullptr, n_windows, n_hit_windows);
+}
+
+int sbwtgpu_pseudoalign_batch(const sbwtgpu_colors *c, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
+                              int threshold_ppm, int denominator, sbwtgpu_pseudoalignment *out, int32_t *counts_or_null) {
+    int rc = colors_check(c);
+    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_reads > 0 && !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    return colors_host_batch(c, bases, read_off, n_reads, strands, 0, threshold_ppm, denominator, out, counts_or_null, nullptr, nullptr);
 }
 
 // ---- set operations (sbwt_setops.hip) ---------------------------------------------------------------

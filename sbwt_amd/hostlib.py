@@ -16,7 +16,7 @@ EXPORTED_SYMBOLS = [
     "sbwthost_last_error", "sbwthost_build", "sbwthost_bits_free", "sbwthost_bits_info", "sbwthost_bits_words",
     "sbwthost_file_write", "sbwthost_file_read", "sbwthost_file_free", "sbwthost_file_info",
     "sbwthost_file_words", "sbwthost_file_precalc", "sbwthost_read_sequences", "sbwthost_read_sequences_chunked", "sbwthost_free", "sbwthost_write_file",
-    "sbwthost_rank_batch",
+    "sbwthost_rank_batch", "sbwthost_colors_write", "sbwthost_colors_read",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -53,6 +53,8 @@ def lib() -> C.CDLL:
     L.sbwthost_free.restype = None
     L.sbwthost_write_file.argtypes = [C.c_char_p, C.c_char_p, i64, ci, ci]
     L.sbwthost_rank_batch.argtypes = [vp, i64, vp, i64, vp]
+    L.sbwthost_colors_write.argtypes = [C.c_char_p, vp, i64, i64, i64]
+    L.sbwthost_colors_read.argtypes = [C.c_char_p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp, i64]
     _lib = L
     return L
 
@@ -179,3 +181,22 @@ def rank_batch(bits: np.ndarray, n_bits: int, pos) -> np.ndarray:
     if lib().sbwthost_rank_batch(bits.ctypes.data, n_bits, pos.ctypes.data, len(pos), out.ctypes.data) != 0:
         raise RuntimeError(_err())
     return out
+
+
+def colors_write(path: str, rows, n_colors: int, k: int) -> None:
+    """Writes a colour matrix (one uint64 row per column of its index) as a colour file (include/sbwthost.h)."""
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    if lib().sbwthost_colors_write(path.encode(), rows.ctypes.data if len(rows) else None, len(rows), n_colors, k) != 0:
+        raise RuntimeError(_err())
+
+
+def colors_read(path: str):
+    """(rows uint64[n_columns], n_colors, k) of a colour file."""
+    L = lib()
+    n, nc, k = C.c_int64(), C.c_int64(), C.c_int64()
+    if L.sbwthost_colors_read(path.encode(), C.byref(n), C.byref(nc), C.byref(k), None, 0) != 0:
+        raise RuntimeError(_err())
+    rows = np.zeros(n.value, dtype=np.uint64)
+    if L.sbwthost_colors_read(path.encode(), C.byref(n), C.byref(nc), C.byref(k), rows.ctypes.data if n.value else None, n.value) != 0:
+        raise RuntimeError(_err())
+    return rows, nc.value, k.value
