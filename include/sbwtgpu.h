@@ -506,7 +506,7 @@ int     sbwtgpu_read_hits_dev(const sbwtgpu_index *idx, const char *d_bases, int
  * Colour matrix.  An index of n columns carries n little-endian uint64_t rows and n_colors colours, 1 <= n_colors <= 64.
  *   - Bit c of row j is set exactly when column j is a real column whose k-mer was given for colour c.
  *   - Dummy columns and bits >= n_colors are always 0.
- *   - More than 64 colours (W words per row) is out of scope.
+ *   - More than 64 colours: the wide calls below (rows of W words, up to SBWTGPU_MAX_COLORS colours).
  * Colouring.  add(color c, sequences, strands):
  *   - Every window of every sequence is searched with the rule of sbwtgpu_search_batch: upper-case ACGT only; any other byte
  *     in the window means no hit.
@@ -532,7 +532,7 @@ int     sbwtgpu_read_hits_dev(const sbwtgpu_index *idx, const char *d_bases, int
  *   - m = 0 gives {0, 0, 0}.
  * Optional counts output: n_reads x n_colors int32_t, counts[r x n_colors + c] = count_c.
  * Refusals, each SBWTGPU_ERR_INVALID_ARG with a message naming the cause: rank-only indexes; indexes of 2^31 columns or more
- * (the int32 search results are the only route); n_colors outside 1..64; color >= n_colors; a threshold or denominator out of
+ * (the int32 search results are the only route); n_colors outside 1..64 (1..4096 for the wide create); color >= n_colors; a threshold or denominator out of
  * range; a colours object used with an index of another n_nodes or k (an object is bound to its index when it is created;
  * callers that load rows from a file compare the file's n_columns and k with the index first, as the CLI and the Python
  * binding do).
@@ -573,6 +573,53 @@ int  sbwtgpu_pseudoalign_dev(const sbwtgpu_colors *c, const char *d_bases, int64
                              int64_t n_reads, int strands, int threshold_ppm, int denominator,
                              sbwtgpu_pseudoalignment *d_out, int32_t *d_counts_or_null,
                              void *d_workspace, int64_t workspace_bytes, void *stream);
+
+/* ---- wide colour matrices: more than 64 references ----
+ * A wide matrix of an index of n columns is n x W little-endian uint64_t words, row-major, W = ceil(n_colors / 64),
+ * 1 <= n_colors <= SBWTGPU_MAX_COLORS.  Word w of column j is at rows[j * W + w].
+ *   - Colour c is bit c & 63 of word c >> 6.
+ *   - Bit c of row j is set exactly when column j is a real column whose k-mer was given for colour c.
+ *   - Dummy columns are all zero.
+ *   - Bits >= n_colors in the last word are zero.
+ *   - With W = 1 this is the matrix above.
+ * Colouring is add(c, sequences, strands) above, unchanged.
+ * The colour set S_i of a window is the W-word row of its column.  With two strands it is the word-wise OR of the two rows.
+ * It is all zero when nothing is found.  A found window whose row is zero in every word counts as not found.
+ * A read's result is three things:
+ *   - n_kmers = m = max(0, L - k + 1).
+ *   - n_found = #{i : S_i != 0}.
+ *   - W words of colors.
+ * Bit c of colors is set exactly when D > 0 and count_c x 1 000 000 >= threshold_ppm x D, in 64-bit integers.  D is n_found
+ * when denominator = 0 and m when denominator = 1.  This is the same rule as above, with no floating point.
+ * The optional counts output is n_reads x n_colors int32.
+ * For n_colors <= 64 the wide calls return exactly what the calls above return.
+ *
+ * One object type serves both: sbwtgpu_colors_add_batch, _copy (n x W words), _dev and _destroy work on any colours object,
+ * and every wide call works on an object of sbwtgpu_colors_create.  sbwtgpu_colors_info, sbwtgpu_pseudoalign_batch and
+ * sbwtgpu_pseudoalign_dev refuse an object of more than 64 colours (SBWTGPU_ERR_INVALID_ARG, the message names the wide call):
+ * their 16-byte record and per_color[64] cannot hold more.  The refusals, ownership and concurrency rules above carry over;
+ * SBWTGPU_ERR_OOM for the n x W x 8 bytes leaves the index usable. */
+#define SBWTGPU_MAX_COLORS 4096
+typedef struct { int32_t n_kmers, n_found; } sbwtgpu_read_found;
+
+int  sbwtgpu_colors_create_wide(const sbwtgpu_index *idx, int n_colors /* 1..4096 */, const uint64_t *rows_or_null /* n_nodes x W */,
+                                sbwtgpu_colors **out);
+int  sbwtgpu_colors_words(const sbwtgpu_colors *c);            /* W */
+/* every output may be NULL; per_color: n_colors entries */
+int  sbwtgpu_colors_info_wide(const sbwtgpu_colors *c, int64_t *n_columns, int64_t *k, int32_t *n_colors, int64_t *n_colored_columns,
+                              int64_t *per_color);
+/* Host buffers: out[r] = {n_kmers, n_found} of read r, colors_out its W words (n_reads x W), counts_or_null n_reads x n_colors.
+ * Chunked like sbwtgpu_pseudoalign_batch: 8 + 8 W bytes per read come back, and 4 n_colors more with counts.  The result does not
+ * depend on tuning, image level or chunking. */
+int  sbwtgpu_pseudoalign_wide_batch(const sbwtgpu_colors *c, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
+                                    int threshold_ppm, int denominator, sbwtgpu_read_found *out, uint64_t *colors_out,
+                                    int32_t *counts_or_null);
+/* Device buffers, as sbwtgpu_pseudoalign_dev: the same preconditions, the same workspace (sbwtgpu_pseudoalign_workspace_bytes does
+ * not depend on the colours) with the same layout.  d_out: n_reads records of 8 bytes; d_colors: n_reads x W words. */
+int  sbwtgpu_pseudoalign_wide_dev(const sbwtgpu_colors *c, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                                  int64_t n_reads, int strands, int threshold_ppm, int denominator,
+                                  sbwtgpu_read_found *d_out, uint64_t *d_colors, int32_t *d_counts_or_null,
+                                  void *d_workspace, int64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -64,6 +64,15 @@ int  sbwthost_rank_batch(const uint64_t *bits, int64_t n_bits, const int64_t *po
 int  sbwthost_colors_write(const char *path, const uint64_t *rows, int64_t n_columns, int64_t n_colors, int64_t k);
 int  sbwthost_colors_read(const char *path, int64_t *n_columns, int64_t *n_colors, int64_t *k, uint64_t *rows_or_null,
                           int64_t rows_cap);
+/* Wide colour files (more than 64 colours): 8 bytes "SBWTCOL2"; int64 n_columns, n_colors, k, words_per_row; then
+ * n_columns x words_per_row little-endian uint64 words, row-major (word w of column j at j * words_per_row + w).
+ * 1 <= n_colors <= 4096 and words_per_row = ceil(n_colors / 64).  The read is the same two-call pattern (words_cap counts
+ * words: room for n_columns x words_per_row) and also reads an "SBWTCOL1" file, as words_per_row = 1.  A truncated file, an
+ * unknown magic, n_colors outside 1 .. 4096 and another words_per_row are errors with a message.  sbwthost_colors_read
+ * refuses "SBWTCOL2" files. */
+int  sbwthost_colors_write_wide(const char *path, const uint64_t *rows, int64_t n_columns, int64_t n_colors, int64_t k);
+int  sbwthost_colors_read_wide(const char *path, int64_t *n_columns, int64_t *n_colors, int64_t *k, int64_t *words_per_row,
+                               uint64_t *rows_or_null, int64_t words_cap);
 
 #ifdef __cplusplus
 }

@@ -51,6 +51,8 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_read_hits_batch", "sbwtgpu_read_hits_workspace_bytes", "sbwtgpu_read_hits_dev",
     "sbwtgpu_colors_create", "sbwtgpu_colors_destroy", "sbwtgpu_colors_add_batch", "sbwtgpu_colors_info", "sbwtgpu_colors_copy",
     "sbwtgpu_colors_dev", "sbwtgpu_pseudoalign_batch", "sbwtgpu_pseudoalign_workspace_bytes", "sbwtgpu_pseudoalign_dev",
+    "sbwtgpu_colors_create_wide", "sbwtgpu_colors_words", "sbwtgpu_colors_info_wide", "sbwtgpu_pseudoalign_wide_batch",
+    "sbwtgpu_pseudoalign_wide_dev",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -133,6 +135,9 @@ class ColorsInfoC(C.Structure):
 
 # a read's pseudoalignment record (sbwtgpu_pseudoalignment): 16 bytes
 PSEUDOALIGNMENT_DTYPE = np.dtype([("colors", np.uint64), ("n_kmers", np.int32), ("n_found", np.int32)])
+# a read's record over a wide colour matrix (sbwtgpu_read_found): 8 bytes, its colours are W words of their own
+READ_FOUND_DTYPE = np.dtype([("n_kmers", np.int32), ("n_found", np.int32)])
+MAX_COLORS = 4096
 
 _lib: Optional[C.CDLL] = None
 
@@ -236,6 +241,11 @@ def lib() -> C.CDLL:
         L.sbwtgpu_pseudoalign_workspace_bytes.argtypes = [i64, i64, ci]
         L.sbwtgpu_pseudoalign_workspace_bytes.restype = i64
         L.sbwtgpu_pseudoalign_dev.argtypes = [vp, vp, i64, vp, i64, ci, ci, ci, vp, vp, vp, i64, vp]
+        L.sbwtgpu_colors_create_wide.argtypes = [vp, ci, vp, C.POINTER(vp)]
+        L.sbwtgpu_colors_words.argtypes = [vp]
+        L.sbwtgpu_colors_info_wide.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_int32), C.POINTER(i64), vp]
+        L.sbwtgpu_pseudoalign_wide_batch.argtypes = [vp, vp, vp, i64, ci, ci, ci, vp, vp, vp]
+        L.sbwtgpu_pseudoalign_wide_dev.argtypes = [vp, vp, i64, vp, i64, ci, ci, ci, vp, vp, vp, vp, i64, vp]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -814,6 +824,78 @@ class Colors:
         """sbwtgpu_pseudoalign_dev (raw device pointers; d_out: n_reads records of 16 bytes; d_counts = 0: no counts)."""
         _check(lib().sbwtgpu_pseudoalign_dev(self._h, d_bases, total_bases, d_read_off, n_reads, 2 if both_strands else 1,
                                              threshold_ppm, denominator, d_out, d_counts or None, d_ws, ws_bytes, stream))
+
+
+class WideColors(Colors):
+    """A colour matrix of up to MAX_COLORS colours: W = ceil(n_colors / 64) uint64 words per column, colour c is bit c & 63 of
+    word c >> 6 (include/sbwtgpu.h, "wide colour matrices").  Colouring (add_sequences, add_reads), rows_dev and close are
+    Colors'; rows, info and the queries are the wide calls, which give for n_colors <= 64 what Colors gives."""
+
+    def __init__(self, handle, index: Index, n_colors: int):
+        super().__init__(handle, index, n_colors)
+        self.words = int(lib().sbwtgpu_colors_words(handle))
+
+    @classmethod
+    def create(cls, index: Index, n_colors: int) -> "WideColors":
+        """An empty matrix of n_colors colours (1 .. MAX_COLORS)."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_colors_create_wide(index.handle, n_colors, None, C.byref(h)))
+        return cls(h, index, n_colors)
+
+    @classmethod
+    def from_rows(cls, index: Index, rows, n_colors: int, k: Optional[int] = None) -> "WideColors":
+        """A matrix from its (n_nodes, W) words (WideColors.rows(), or hostlib.colors_read_wide with its k): bits >= n_colors
+        and the rows of dummy columns are cleared.  Rows of another shape, another index or another k are refused."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        if not 1 <= n_colors <= MAX_COLORS:
+            raise SbwtGpuError(ERR_INVALID_ARG, "n_colors must be in 1 .. %d, not %d" % (MAX_COLORS, n_colors))
+        words = (n_colors + 63) // 64
+        if rows.ndim != 2 or rows.shape != (index.n_nodes, words) or (k is not None and k != index.k):
+            raise SbwtGpuError(ERR_INVALID_ARG, "colours of shape %s at k = %s used with an index of %d columns at k = %d, %d words a row"
+                               % (rows.shape, "?" if k is None else k, index.n_nodes, index.k, words))
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_colors_create_wide(index.handle, n_colors, rows.ctypes.data, C.byref(h)))
+        return cls(h, index, n_colors)
+
+    add = Colors.add_sequences
+
+    def rows(self) -> np.ndarray:
+        """(n_nodes, W) uint64"""
+        out = np.empty((self.index.n_nodes, self.words), dtype=np.uint64)
+        _check(lib().sbwtgpu_colors_copy(self._h, out.ctypes.data))
+        return out
+
+    def info(self) -> dict:
+        """n_columns, k, n_colors, words, n_colored_columns and per_color (n_colors counts of coloured columns)."""
+        n, k, nc, ncc = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64()
+        per = np.zeros(self.n_colors, dtype=np.int64)
+        _check(lib().sbwtgpu_colors_info_wide(self._h, C.byref(n), C.byref(k), C.byref(nc), C.byref(ncc), per.ctypes.data))
+        return {"n_columns": n.value, "k": k.value, "n_colors": nc.value, "words": self.words, "n_colored_columns": ncc.value,
+                "per_color": [int(x) for x in per]}
+
+    def pseudoalign(self, bases, read_off, both_strands: bool = False, threshold_ppm: int = 1_000_000, denominator: int = 0,
+                    counts: bool = False):
+        """sbwtgpu_pseudoalign_wide_batch: (records, colors) -- a READ_FOUND_DTYPE array of n_reads entries and the (n_reads, W)
+        uint64 colour words; with counts=True also the (n_reads, n_colors) int32 array of count_c."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        n = max(len(read_off) - 1, 0)
+        out = np.zeros(n, dtype=READ_FOUND_DTYPE)
+        out["n_kmers"] = -12345
+        col = np.zeros((n, self.words), dtype=np.uint64)
+        cnt = np.full((n, self.n_colors), -12345, dtype=np.int32) if counts else None
+        _check(lib().sbwtgpu_pseudoalign_wide_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n, 2 if both_strands else 1,
+                                                    threshold_ppm, denominator, out.ctypes.data, col.ctypes.data,
+                                                    cnt.ctypes.data if counts else None))
+        return (out, col, cnt) if counts else (out, col)
+
+    def pseudoalign_dev(self, d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_out: int, d_colors: int, d_counts: int,
+                        d_ws: int, ws_bytes: int, both_strands: bool = False, threshold_ppm: int = 1_000_000, denominator: int = 0,
+                        stream: int = 0):
+        """sbwtgpu_pseudoalign_wide_dev (raw device pointers; d_out: n_reads records of 8 bytes; d_colors: n_reads x W words;
+        d_counts = 0: no counts)."""
+        _check(lib().sbwtgpu_pseudoalign_wide_dev(self._h, d_bases, total_bases, d_read_off, n_reads, 2 if both_strands else 1,
+                                                  threshold_ppm, denominator, d_out, d_colors, d_counts or None, d_ws, ws_bytes, stream))
 
 
 def kernel_times() -> list:

@@ -271,4 +271,64 @@ int sbwthost_colors_read(const char *path, int64_t *n_columns, int64_t *n_colors
     return 0;
 }
 
+// ---- wide colour files: "SBWTCOL2", int64 n_columns, n_colors, k, words_per_row, then n_columns x words_per_row words ----
+static const char COLORS_MAGIC_WIDE[8] = {'S', 'B', 'W', 'T', 'C', 'O', 'L', '2'};
+
+int sbwthost_colors_write_wide(const char *path, const uint64_t *rows, int64_t n_columns, int64_t n_colors, int64_t k) {
+    if (!path || n_columns < 0 || (n_columns > 0 && !rows)) return fail("invalid argument");
+    if (n_colors < 1 || n_colors > 4096) return fail("Error: n_colors must be in 1 .. 4096, not %lld", (long long)n_colors);
+    std::ofstream out(path, std::ios::binary);
+    if (!out.good()) return fail("Error opening file: %s", path);
+    const int64_t words = (n_colors + 63) / 64;
+    const int64_t head[4] = {n_columns, n_colors, k, words};
+    out.write(COLORS_MAGIC_WIDE, 8);
+    out.write(reinterpret_cast<const char *>(head), 32);
+    if (n_columns > 0) out.write(reinterpret_cast<const char *>(rows), (std::streamsize)(n_columns * words * 8));
+    out.flush();
+    if (!out.good()) return fail("Error writing to file %s", path);
+    return 0;
+}
+
+int sbwthost_colors_read_wide(const char *path, int64_t *n_columns, int64_t *n_colors, int64_t *k, int64_t *words_per_row,
+                              uint64_t *rows_or_null, int64_t words_cap) {
+    if (!path) return fail("invalid argument");
+    std::ifstream in(path, std::ios::binary);
+    if (!in.good()) return fail("Error opening file: %s", path);
+    char magic[8];
+    int64_t head[4];
+    in.read(magic, 8);
+    if (in.gcount() != 8) return fail("Error: colour file %s is truncated (no magic)", path);
+    const bool wide = memcmp(magic, COLORS_MAGIC_WIDE, 8) == 0;
+    if (!wide && memcmp(magic, COLORS_MAGIC, 8) != 0)
+        return fail("Error: %s is not a colour file (unknown magic, SBWTCOL1 or SBWTCOL2 expected)", path);
+    const int64_t head_bytes = wide ? 32 : 24;
+    in.read(reinterpret_cast<char *>(head), head_bytes);
+    if (in.gcount() != head_bytes) return fail("Error: colour file %s is truncated (header)", path);
+    const int64_t max_colors = wide ? 4096 : 64;
+    if (head[1] < 1 || head[1] > max_colors)
+        return fail("Error: colour file %s: n_colors = %lld is outside 1 .. %lld", path, (long long)head[1], (long long)max_colors);
+    const int64_t words = (head[1] + 63) / 64;
+    if (wide && head[3] != words)
+        return fail("Error: colour file %s: words_per_row = %lld, %lld colours need %lld", path, (long long)head[3], (long long)head[1],
+                    (long long)words);
+    if (head[0] < 0 || head[0] > ((int64_t)1 << 50)) return fail("Error: colour file %s: n_columns = %lld", path, (long long)head[0]);
+    in.seekg(0, std::ios::end);
+    const int64_t size = (int64_t)in.tellg(), start = 8 + head_bytes, want = start + head[0] * words * 8;
+    if (size < want)
+        return fail("Error: colour file %s is truncated (%lld bytes, %lld columns of %lld words need %lld)", path, (long long)size,
+                    (long long)head[0], (long long)words, (long long)want);
+    if (size > want) return fail("Error: colour file %s has %lld bytes after its %lld rows", path, (long long)(size - want), (long long)head[0]);
+    if (n_columns) *n_columns = head[0];
+    if (n_colors) *n_colors = head[1];
+    if (k) *k = head[2];
+    if (words_per_row) *words_per_row = words;
+    if (!rows_or_null) return 0;
+    if (words_cap < head[0] * words)
+        return fail("Error: room for %lld words, the colour file holds %lld", (long long)words_cap, (long long)(head[0] * words));
+    in.seekg(start, std::ios::beg);
+    if (head[0] > 0) in.read(reinterpret_cast<char *>(rows_or_null), (std::streamsize)(head[0] * words * 8));
+    if (!in.good()) return fail("Error reading %s", path);
+    return 0;
+}
+
 }  // extern "C"

@@ -5,8 +5,9 @@
 //   sbwt search -o <out> -i <index> -q <query> [-z]        (sbwt_search.cpp:151-157)
 //   sbwt matching-statistics -i <index> -q <query> -o <out> [-z] [--intervals]
 //               k-bounded matching statistics: one line per read, one token per base ("d", or "d,first,second")
-//   sbwt build-colors -i <index> -r <refs.txt> -o <colours> [--both-strands]
+//   sbwt build-colors -i <index> -r <refs.txt> -o <colours> [--both-strands] [--wide]
 //               one colour per listed reference file, set on the columns of the index's k-mers that the file holds
+//               (--wide: up to 4096 files, a colour file of several words per column)
 //   sbwt pseudoalign -i <index> -c <colours> -q <query> -o <out> [-z] [--threshold 0.7] [--all-kmers] [--both-strands]
 //               one line per read: its number, then the colours that hold it
 //   sbwt build  -i <in> -o <index> -k <k> [-p <precalc>] [--add-reverse-complements]
@@ -927,8 +928,8 @@ void load_plain_matrix(const string &indexfile, plain_matrix_sbwt_t &index) {
     index.load(in);
 }
 
-// sbwt build-colors: refs.txt holds one sequence file per line, colour = 0-based line number (at most 64); every file's k-mers
-// that the index holds get the file's colour
+// sbwt build-colors: refs.txt holds one sequence file per line, colour = 0-based line number (at most 64, with --wide at most
+// 4096 and an "SBWTCOL2" colour file whatever the number); every file's k-mers that the index holds get the file's colour
 int build_colors_main(int argc, char **argv) {
     set_log_level(LogLevel::MINOR);
     Options opts({
@@ -936,6 +937,7 @@ int build_colors_main(int argc, char **argv) {
         {"refs", 'r', true, "A list of sequence files (FASTA or FASTQ, possibly gzipped), one per line: the colour of a file is its 0-based line number. At most 64 lines.", ""},
         {"out-file", 'o', true, "Output colour file.", ""},
         {"both-strands", 0, false, "Also colour the reverse complement of every k-mer (for indexes built with reverse complements).", ""},
+        {"wide", 0, false, "Up to 4096 lines in the list; writes a wide colour file (several 64-bit words per column).", ""},
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
@@ -949,8 +951,13 @@ int build_colors_main(int argc, char **argv) {
     check_readable(indexfile);
     check_readable(refsfile);
     const vector<string> refs = readlines(refsfile);
-    if (refs.empty() || refs.size() > 64)
-        throw std::runtime_error("Error: " + refsfile + " lists " + std::to_string(refs.size()) + " files; a colour file holds 1 to 64 colours");
+    const bool wide = opts.count("wide");
+    if (wide && (refs.empty() || refs.size() > SBWTGPU_MAX_COLORS))
+        throw std::runtime_error("Error: " + refsfile + " lists " + std::to_string(refs.size()) + " files; a wide colour file holds 1 to " +
+                                 std::to_string(SBWTGPU_MAX_COLORS) + " colours");
+    if (!wide && (refs.empty() || refs.size() > 64))
+        throw std::runtime_error("Error: " + refsfile + " lists " + std::to_string(refs.size()) +
+                                 " files; a colour file holds 1 to 64 colours (use --wide for more)");
     for (const string &file : refs) check_readable(file);
     check_writable(outfile);
     const int strands = opts.count("both-strands") ? 2 : 1;
@@ -960,7 +967,8 @@ int build_colors_main(int argc, char **argv) {
     plain_matrix_sbwt_t index;
     load_plain_matrix(indexfile, index);
     ColorsHandle col;
-    colors_check(sbwtgpu_colors_create(index.device_handle(), (int)refs.size(), nullptr, &col.h));
+    if (wide) colors_check(sbwtgpu_colors_create_wide(index.device_handle(), (int)refs.size(), nullptr, &col.h));
+    else colors_check(sbwtgpu_colors_create(index.device_handle(), (int)refs.size(), nullptr, &col.h));
     vector<int64_t> windows(refs.size(), 0), hit_windows(refs.size(), 0);
     for (size_t c = 0; c < refs.size(); c++) {
         seq_io::Reader reader(refs[c]);
@@ -979,16 +987,26 @@ int build_colors_main(int argc, char **argv) {
             hit_windows[c] += h;
         }
     }
-    sbwtgpu_colors_info_t info;
-    colors_check(sbwtgpu_colors_info(col.h, &info));
+    int64_t n_columns = 0, ck = 0, n_colored = 0;
+    int32_t n_colors = 0;
+    vector<int64_t> per_color(refs.size(), 0);
+    if (wide) {
+        colors_check(sbwtgpu_colors_info_wide(col.h, &n_columns, &ck, &n_colors, &n_colored, per_color.data()));
+    } else {
+        sbwtgpu_colors_info_t info;
+        colors_check(sbwtgpu_colors_info(col.h, &info));
+        n_columns = info.n_columns, ck = info.k, n_colors = info.n_colors, n_colored = info.n_colored_columns;
+        std::copy(info.per_color, info.per_color + refs.size(), per_color.begin());
+    }
     for (size_t c = 0; c < refs.size(); c++)
-        std::cout << "colour " << c << ": " << windows[c] << " windows, " << hit_windows[c] << " hit windows, " << info.per_color[c]
+        std::cout << "colour " << c << ": " << windows[c] << " windows, " << hit_windows[c] << " hit windows, " << per_color[c]
                   << " coloured columns" << std::endl;
-    vector<uint64_t> rows((size_t)info.n_columns);
+    vector<uint64_t> rows((size_t)n_columns * (size_t)sbwtgpu_colors_words(col.h));
     colors_check(sbwtgpu_colors_copy(col.h, rows.data()));
-    if (sbwthost_colors_write(outfile.c_str(), rows.data(), info.n_columns, info.n_colors, info.k) != 0)
+    if ((wide ? sbwthost_colors_write_wide(outfile.c_str(), rows.data(), n_columns, n_colors, ck)
+              : sbwthost_colors_write(outfile.c_str(), rows.data(), n_columns, n_colors, ck)) != 0)
         throw std::runtime_error(sbwthost_last_error());
-    write_log("Wrote " + std::to_string(info.n_colors) + " colours of " + std::to_string(info.n_colored_columns) + " coloured columns to " + outfile,
+    write_log("Wrote " + std::to_string(n_colors) + " colours of " + std::to_string(n_colored) + " coloured columns to " + outfile,
               LogLevel::MAJOR);
     return 0;
 }
@@ -1031,18 +1049,30 @@ int pseudoalign_main(int argc, char **argv) {
     if (batch_bases < 1) batch_bases = 1;
     plain_matrix_sbwt_t index;
     load_plain_matrix(indexfile, index);
-    int64_t n_columns = 0, n_colors = 0, ck = 0;
-    if (sbwthost_colors_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, nullptr, 0) != 0) throw std::runtime_error(sbwthost_last_error());
+    // the colour file's magic says which calls it goes through: "SBWTCOL2" the wide ones, anything else where it always went
+    bool wide = false;
+    {
+        std::ifstream in(colorsfile, std::ios::binary);
+        char magic[8] = {0};
+        in.read(magic, 8);
+        wide = in.gcount() == 8 && memcmp(magic, "SBWTCOL2", 8) == 0;
+    }
+    int64_t n_columns = 0, n_colors = 0, ck = 0, words = 1;
+    if ((wide ? sbwthost_colors_read_wide(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, nullptr, 0)
+              : sbwthost_colors_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, nullptr, 0)) != 0)
+        throw std::runtime_error(sbwthost_last_error());
     if (n_columns != index.number_of_subsets() || ck != index.get_k())
         throw std::runtime_error("Error: " + colorsfile + " colours an index of " + std::to_string(n_columns) + " columns at k = " +
                                  std::to_string(ck) + ", " + indexfile + " has " + std::to_string(index.number_of_subsets()) +
                                  " columns at k = " + std::to_string(index.get_k()));
     ColorsHandle col;
     {
-        vector<uint64_t> rows((size_t)n_columns);
-        if (sbwthost_colors_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, rows.data(), n_columns) != 0)
+        vector<uint64_t> rows((size_t)(n_columns * words));
+        if ((wide ? sbwthost_colors_read_wide(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, rows.data(), n_columns * words)
+                  : sbwthost_colors_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, rows.data(), n_columns)) != 0)
             throw std::runtime_error(sbwthost_last_error());
-        colors_check(sbwtgpu_colors_create(index.device_handle(), (int)n_colors, rows.data(), &col.h));
+        if (wide) colors_check(sbwtgpu_colors_create_wide(index.device_handle(), (int)n_colors, rows.data(), &col.h));
+        else colors_check(sbwtgpu_colors_create(index.device_handle(), (int)n_colors, rows.data(), &col.h));
     }
     write_log("Running pseudoalignment from input file " + queryfile + " to output file " + outfile, LogLevel::MAJOR);
     seq_io::Reader reader(queryfile);
@@ -1051,6 +1081,8 @@ int pseudoalign_main(int argc, char **argv) {
     vector<char> bases;
     vector<int64_t> read_off;
     vector<sbwtgpu_pseudoalignment> rec;
+    vector<sbwtgpu_read_found> wrec;
+    vector<uint64_t> wcol;
     string text;
     int64_t total_reads = 0;
     while (more) {
@@ -1059,18 +1091,35 @@ int pseudoalign_main(int argc, char **argv) {
         more = reader.read_batch(bases, read_off, batch_bases);
         const int64_t n_reads = (int64_t)read_off.size() - 1;
         if (n_reads <= 0) continue;
-        rec.resize((size_t)n_reads);
-        colors_check(sbwtgpu_pseudoalign_batch(col.h, bases.data(), read_off.data(), n_reads, strands, threshold_ppm, denominator,
-                                               rec.data(), nullptr));
         text.clear();
-        for (const sbwtgpu_pseudoalignment &p : rec) {
-            append_int(total_reads++, text);
-            for (int c = 0; c < 64; c++)
-                if ((p.colors >> c) & 1) {
-                    text.push_back(' ');
-                    append_int(c, text);
+        if (wide) {
+            wrec.resize((size_t)n_reads);
+            wcol.resize((size_t)(n_reads * words));
+            colors_check(sbwtgpu_pseudoalign_wide_batch(col.h, bases.data(), read_off.data(), n_reads, strands, threshold_ppm, denominator,
+                                                        wrec.data(), wcol.data(), nullptr));
+            for (int64_t r = 0; r < n_reads; r++) {
+                append_int(total_reads++, text);
+                for (int64_t w = 0; w < words; w++) {
+                    for (uint64_t left = wcol[(size_t)(r * words + w)]; left; left &= left - 1) {
+                        text.push_back(' ');
+                        append_int(w * 64 + __builtin_ctzll(left), text);
+                    }
                 }
-            text.push_back('\n');
+                text.push_back('\n');
+            }
+        } else {
+            rec.resize((size_t)n_reads);
+            colors_check(sbwtgpu_pseudoalign_batch(col.h, bases.data(), read_off.data(), n_reads, strands, threshold_ppm, denominator,
+                                                   rec.data(), nullptr));
+            for (const sbwtgpu_pseudoalignment &p : rec) {
+                append_int(total_reads++, text);
+                for (int c = 0; c < 64; c++)
+                    if ((p.colors >> c) & 1) {
+                        text.push_back(' ');
+                        append_int(c, text);
+                    }
+                text.push_back('\n');
+            }
         }
         writer.write(text.data(), (int64_t)text.size());
     }

@@ -6,6 +6,9 @@
 // the record of a read (sbwtgpu_pseudoalignment of include/sbwtgpu.h)
 struct SbwtPseudoalignment { unsigned long long colors; int n_kmers, n_found; };
 static_assert(sizeof(SbwtPseudoalignment) == 16, "a read's record is 16 bytes");
+// the record of a read over a wide matrix (sbwtgpu_read_found): its colours are `words` words of their own
+struct SbwtReadFound { int n_kmers, n_found; };
+static_assert(sizeof(SbwtReadFound) == 8, "a read's wide record is 8 bytes");
 
 // Where the parts of a pseudoalignment (and colouring) workspace lie, in bytes from its start (every part 256-byte aligned).
 // The search workspace comes first, so the search's status word is where sbwtgpu_workspace_status looks for it.
@@ -34,16 +37,20 @@ SbwtPaLayout sbwt_pa_layout(long long search_ws_bytes, long long total_bases, lo
 // hdr->status = the search's status word unless an earlier search of the call left one (one thread, after each search)
 void sbwt_launch_pa_note_status(const SbwtWorkHeader *search_ws, SbwtPaHeader *hdr, hipStream_t stream);
 
-// Bit `color` of rows[res[i]] is set for every result res[i] >= 0 of the W = d_out_off[n_reads] results (max_results bounds W for
+// The matrix: n_nodes x words 64-bit words, row-major; colour c is bit c & 63 of word c >> 6 (words = 1: one word per column).
+// Bit `color` of row res[i] is set for every result res[i] >= 0 of the W = d_out_off[n_reads] results (max_results bounds W for
 // the grid).  count != 0: hdr->n_hit += the number of i with res[i] >= 0 or, when d_other is given, other[W - 1 - i] >= 0 (the
 // mirrored batch's result of the same window).
 void sbwt_launch_col_mark(const int *d_res, const int *d_other, const long long *d_out_off, long long n_reads, long long max_results,
-                          unsigned long long *d_rows, long long n_nodes, int color, int count, SbwtPaHeader *hdr, hipStream_t stream);
+                          unsigned long long *d_rows, long long n_nodes, int words, int color, int count, SbwtPaHeader *hdr,
+                          hipStream_t stream);
 
-// d_stats[c] = rows with bit c set (c < 64), d_stats[64] = rows that are not 0; the caller zeroes the 65 entries first
-void sbwt_launch_col_stats(const unsigned long long *d_rows, long long n_nodes, unsigned long long *d_stats, hipStream_t stream);
+// d_stats[c] = rows with bit c set (c < 64 words), d_stats[64 words] = rows that are not 0 in some word; the caller zeroes the
+// 64 words + 1 entries first
+void sbwt_launch_col_stats(const unsigned long long *d_rows, long long n_nodes, int words, unsigned long long *d_stats,
+                           hipStream_t stream);
 
-// An uploaded matrix made to obey the definition: bits >= n_colors and the rows of dummy columns (k-1 rounds down the dummy tree
+// An uploaded matrix (of ceil(n_colors / 64) words per row) made to obey the definition: bits >= n_colors and the rows of dummy columns (k-1 rounds down the dummy tree
 // from the root: sbwt_colwalk.h) are cleared.  Scratch of one byte per column, freed before it returns; synchronises `stream`.
 hipError_t sbwt_colors_clean(const SbwtIndexView &ix, unsigned long long *d_rows, int n_colors, hipStream_t stream);
 
@@ -52,3 +59,9 @@ hipError_t sbwt_colors_clean(const SbwtIndexView &ix, unsigned long long *d_rows
 void sbwt_launch_pa_reduce(const int *d_res, const int *d_res2, const long long *d_out_off, long long n_reads,
                            const unsigned long long *d_rows, long long n_nodes, int n_colors, int threshold_ppm, int denominator,
                            SbwtPseudoalignment *d_out, int *d_counts, hipStream_t stream);
+
+// The same over rows of `words` words: d_out[r] = {n_kmers, n_found}, d_colors: n_reads x words, d_counts (may be NULL): n_reads x
+// n_colors int32.  Dynamic LDS: 4 waves x (words - 1) x 64 int32 (none for words = 1, 63 KiB for 64).
+void sbwt_launch_pa_reduce_wide(const int *d_res, const int *d_res2, const long long *d_out_off, long long n_reads,
+                                const unsigned long long *d_rows, long long n_nodes, int words, int n_colors, int threshold_ppm,
+                                int denominator, SbwtReadFound *d_out, unsigned long long *d_colors, int *d_counts, hipStream_t stream);

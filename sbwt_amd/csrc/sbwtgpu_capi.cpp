@@ -2789,12 +2789,14 @@ int sbwtgpu_read_hits_batch(const sbwtgpu_index *idx, const char *bases, const i
 
 // ---- colours and pseudoalignment (sbwt_colors.hip) ----------------------------------------------------
 static_assert(sizeof(sbwtgpu_pseudoalignment) == sizeof(SbwtPseudoalignment), "the record of the ABI is the kernels' record");
+static_assert(sizeof(sbwtgpu_read_found) == sizeof(SbwtReadFound), "the wide record of the ABI is the kernels' record");
 
 struct sbwtgpu_colors {
     const sbwtgpu_index *idx = nullptr;
     int device = 0;
     int64_t n_nodes = 0, k = 0;
     int n_colors = 0;
+    int words = 1;                      // 64-bit words per row: ceil(n_colors / 64)
     unsigned long long *d_rows = nullptr;
 };
 
@@ -2827,13 +2829,8 @@ static int colors_check_query(int threshold_ppm, int denominator) {
     return SBWTGPU_OK;
 }
 
-int sbwtgpu_colors_create(const sbwtgpu_index *idx, int n_colors, const uint64_t *rows_or_null, sbwtgpu_colors **out) {
-    if (!idx || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    int rc = colors_check_index(idx);
-    if (rc != SBWTGPU_OK) return rc;
-    if (n_colors < 1 || n_colors > 64)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "n_colors must be in 1 .. 64, not %d (more than 64 colours are out of scope)", n_colors);
+// what both creates do once n_colors has passed their own bound
+static int colors_create_checked(const sbwtgpu_index *idx, int n_colors, const uint64_t *rows_or_null, sbwtgpu_colors **out) {
     DeviceGuard guard(idx->device);
     if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", idx->device);
     sbwtgpu_colors *c = new (std::nothrow) sbwtgpu_colors();
@@ -2843,7 +2840,8 @@ int sbwtgpu_colors_create(const sbwtgpu_index *idx, int n_colors, const uint64_t
     c->n_nodes = idx->h.n_nodes;
     c->k = idx->h.k;
     c->n_colors = n_colors;
-    const size_t bytes = (size_t)c->n_nodes * 8;
+    c->words = (n_colors + 63) / 64;
+    const size_t bytes = (size_t)c->n_nodes * (size_t)c->words * 8;
     Stream st;
     hipError_t e = hipMalloc((void **)&c->d_rows, bytes ? bytes : 16);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
@@ -2859,6 +2857,30 @@ int sbwtgpu_colors_create(const sbwtgpu_index *idx, int n_colors, const uint64_t
     return SBWTGPU_OK;
 }
 
+int sbwtgpu_colors_create(const sbwtgpu_index *idx, int n_colors, const uint64_t *rows_or_null, sbwtgpu_colors **out) {
+    if (!idx || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    int rc = colors_check_index(idx);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_colors < 1 || n_colors > 64)
+        return fail(SBWTGPU_ERR_INVALID_ARG,
+                    "n_colors must be in 1 .. 64, not %d (more than 64 colours are out of scope here: sbwtgpu_colors_create_wide takes up to %d)",
+                    n_colors, SBWTGPU_MAX_COLORS);
+    return colors_create_checked(idx, n_colors, rows_or_null, out);
+}
+
+int sbwtgpu_colors_create_wide(const sbwtgpu_index *idx, int n_colors, const uint64_t *rows_or_null, sbwtgpu_colors **out) {
+    if (!idx || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    int rc = colors_check_index(idx);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_colors < 1 || n_colors > SBWTGPU_MAX_COLORS)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "n_colors must be in 1 .. %d, not %d", SBWTGPU_MAX_COLORS, n_colors);
+    return colors_create_checked(idx, n_colors, rows_or_null, out);
+}
+
+int sbwtgpu_colors_words(const sbwtgpu_colors *c) { return c ? c->words : 0; }
+
 void sbwtgpu_colors_destroy(sbwtgpu_colors *c) {
     if (!c) return;
     DeviceGuard guard(c->device);
@@ -2866,32 +2888,59 @@ void sbwtgpu_colors_destroy(sbwtgpu_colors *c) {
     delete c;
 }
 
-int sbwtgpu_colors_info(const sbwtgpu_colors *c, sbwtgpu_colors_info_t *info) {
-    if (!c || !info) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    memset(info, 0, sizeof(*info));
-    info->n_columns = c->n_nodes;
-    info->k = c->k;
-    info->n_colors = c->n_colors;
+// h: 64 words + 1 entries -- the coloured columns per colour, then those of any colour
+static int colors_stats(const sbwtgpu_colors *c, unsigned long long *h) {
+    const size_t bytes = ((size_t)c->words * 64 + 1) * 8;
     DeviceGuard guard(c->device);
     DevBuf stats;
     Stream st;
-    unsigned long long h[65];
-    HIP_TRY(stats.alloc(sizeof(h)));
+    HIP_TRY(stats.alloc(bytes));
     HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    HIP_TRY(hipMemsetAsync(stats.p, 0, sizeof(h), st.s));
-    sbwt_launch_col_stats(c->d_rows, c->n_nodes, static_cast<unsigned long long *>(stats.p), st.s);
+    HIP_TRY(hipMemsetAsync(stats.p, 0, bytes, st.s));
+    sbwt_launch_col_stats(c->d_rows, c->n_nodes, c->words, static_cast<unsigned long long *>(stats.p), st.s);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h, stats.p, sizeof(h), hipMemcpyDeviceToHost, st.s));
+    HIP_TRY(hipMemcpyAsync(h, stats.p, bytes, hipMemcpyDeviceToHost, st.s));
     HIP_TRY(hipStreamSynchronize(st.s));
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_colors_info(const sbwtgpu_colors *c, sbwtgpu_colors_info_t *info) {
+    if (!c || !info) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    memset(info, 0, sizeof(*info));
+    if (c->n_colors > 64)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "the colours object has %d colours, sbwtgpu_colors_info_t holds 64: use sbwtgpu_colors_info_wide",
+                    c->n_colors);
+    info->n_columns = c->n_nodes;
+    info->k = c->k;
+    info->n_colors = c->n_colors;
+    unsigned long long h[65];
+    const int rc = colors_stats(c, h);
+    if (rc != SBWTGPU_OK) return rc;
     for (int i = 0; i < 64; i++) info->per_color[i] = (int64_t)h[i];
     info->n_colored_columns = (int64_t)h[64];
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_colors_info_wide(const sbwtgpu_colors *c, int64_t *n_columns, int64_t *k, int32_t *n_colors, int64_t *n_colored_columns,
+                             int64_t *per_color) {
+    if (!c) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    if (n_columns) *n_columns = c->n_nodes;
+    if (k) *k = c->k;
+    if (n_colors) *n_colors = c->n_colors;
+    if (!n_colored_columns && !per_color) return SBWTGPU_OK;
+    unsigned long long h[SBWTGPU_MAX_COLORS + 1];
+    const int rc = colors_stats(c, h);
+    if (rc != SBWTGPU_OK) return rc;
+    if (per_color)
+        for (int i = 0; i < c->n_colors; i++) per_color[i] = (int64_t)h[i];
+    if (n_colored_columns) *n_colored_columns = (int64_t)h[(size_t)c->words * 64];
     return SBWTGPU_OK;
 }
 
 int sbwtgpu_colors_copy(const sbwtgpu_colors *c, uint64_t *rows_out) {
     if (!c || !rows_out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
     DeviceGuard guard(c->device);
-    HIP_TRY(hipMemcpy(rows_out, c->d_rows, (size_t)c->n_nodes * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rows_out, c->d_rows, (size_t)c->n_nodes * (size_t)c->words * 8, hipMemcpyDeviceToHost));
     return SBWTGPU_OK;
 }
 
@@ -2975,6 +3024,9 @@ int sbwtgpu_pseudoalign_dev(const sbwtgpu_colors *c, const char *d_bases, int64_
     if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
     if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
     if (rc != SBWTGPU_OK) return rc;
+    if (c->n_colors > 64)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "the colours object has %d colours, a 16-byte record holds 64: use sbwtgpu_pseudoalign_wide_dev",
+                    c->n_colors);
     if (n_reads > 0 && !d_out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
     return colors_dev_common(c, d_bases, total_bases, d_read_off, n_reads, strands, d_ws, ws_bytes, stream,
                              [&](const int *res, const int *res2, const long long *ooff, SbwtPaHeader *, hipStream_t st) {
@@ -2983,11 +3035,30 @@ int sbwtgpu_pseudoalign_dev(const sbwtgpu_colors *c, const char *d_bases, int64_
                              });
 }
 
+int sbwtgpu_pseudoalign_wide_dev(const sbwtgpu_colors *c, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                                 int64_t n_reads, int strands, int threshold_ppm, int denominator, sbwtgpu_read_found *d_out,
+                                 uint64_t *d_colors, int32_t *d_counts_or_null, void *d_ws, int64_t ws_bytes, void *stream) {
+    int rc = colors_check(c);
+    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_reads > 0 && (!d_out || !d_colors)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
+    return colors_dev_common(c, d_bases, total_bases, d_read_off, n_reads, strands, d_ws, ws_bytes, stream,
+                             [&](const int *res, const int *res2, const long long *ooff, SbwtPaHeader *, hipStream_t st) {
+                                 sbwt_launch_pa_reduce_wide(res, res2, ooff, n_reads, c->d_rows, c->n_nodes, c->words, c->n_colors,
+                                                            threshold_ppm, denominator, reinterpret_cast<SbwtReadFound *>(d_out),
+                                                            reinterpret_cast<unsigned long long *>(d_colors), d_counts_or_null, st);
+                             });
+}
+
 // Host buffers, for colouring (out == NULL: bit `color` is set, *n_hit the windows with a hit) and for the query alike: the batch
 // is cut into chunks of whole reads of at most "pseudoalign_chunk_bases" bases (a chunk always takes one read), two chunks in
 // flight on the parked slots of the search pipeline.  Bases and offsets go down; records, and counts if asked for, come back.
+// wide_colors != NULL: the wide query -- `out` holds 8-byte records (sbwtgpu_read_found) and wide_colors the reads' colour
+// words, 8 + 8 words bytes per read instead of 16; a chunk then also ends where its results would outgrow what 2^24 reads of
+// 64 colours with counts bring back.
 static int colors_host_batch(const sbwtgpu_colors *c, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
-                             int color, int threshold_ppm, int denominator, sbwtgpu_pseudoalignment *out, int32_t *counts,
+                             int color, int threshold_ppm, int denominator, void *out, uint64_t *wide_colors, int32_t *counts,
                              int64_t *n_windows, int64_t *n_hit) {
     const sbwtgpu_index *idx = c->idx;
     if (n_windows) *n_windows = 0;
@@ -2995,8 +3066,10 @@ static int colors_host_batch(const sbwtgpu_colors *c, const char *bases, const i
     if (n_reads == 0) return SBWTGPU_OK;
     if (!read_off) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
     if (read_off[n_reads] > read_off[0] && !bases) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    const int64_t budget = g_pa_chunk_bases > 0 ? g_pa_chunk_bases : (int64_t)64 << 20, CH_READS = (int64_t)1 << 24;
-    const int64_t nc = c->n_colors, k = c->k;
+    const int64_t nc = c->n_colors, k = c->k, nw = c->words;
+    const int64_t rec_bytes = wide_colors ? 8 : 16, per_read = rec_bytes + (wide_colors ? 8 * nw : 0) + (counts ? 4 * nc : 0);
+    const int64_t budget = g_pa_chunk_bases > 0 ? g_pa_chunk_bases : (int64_t)64 << 20;
+    const int64_t CH_READS = std::min((int64_t)1 << 24, std::max<int64_t>(1, (((int64_t)1 << 24) * 272) / per_read));
     std::vector<int64_t> cuts{0};
     int64_t max_bases = 0, max_reads = 0, windows = 0;
     int rc;
@@ -3018,18 +3091,19 @@ static int colors_host_batch(const sbwtgpu_colors *c, const char *bases, const i
     const int64_t n_chunks = (int64_t)cuts.size() - 1;
     const bool pin_in = is_pinned(bases);
     const int64_t ws_bytes = sbwtgpu_pseudoalign_workspace_bytes(max_bases, max_reads, strands);
-    const int64_t b_rec = out ? align256(max_reads * 16) : 0, b_cnt = counts ? align256(max_reads * nc * 4) : 0;
+    const int64_t b_rec = out ? align256(max_reads * rec_bytes) : 0, b_col = wide_colors ? align256(max_reads * nw * 8) : 0,
+                  b_cnt = counts ? align256(max_reads * nc * 4) : 0;
     const int64_t need_in = align256(max_bases + 16) + align256((max_reads + 1) * 8);
-    const int64_t need_out = b_rec + b_cnt;
-    const int64_t need_dev = align256(max_bases + 16) + align256((max_reads + 1) * 8) + b_rec + b_cnt + align256(ws_bytes);
+    const int64_t need_out = b_rec + b_col + b_cnt;
+    const int64_t need_dev = align256(max_bases + 16) + align256((max_reads + 1) * 8) + b_rec + b_col + b_cnt + align256(ws_bytes);
     DeviceGuard guard(idx->device);
     const int n_slots = n_chunks > 1 ? 2 : 1;
     PipeSlot S[2];
     if ((rc = take_slots(idx->device, S, n_slots, need_in, need_out, need_dev, "pseudoalignment buffers")) != SBWTGPU_OK) return rc;
     int bug = 0;                    // the first nonzero device status of a chunk
     int64_t hits = 0;
-    const int64_t o_roff = align256(max_bases + 16), o_rec = o_roff + align256((max_reads + 1) * 8), o_cnt = o_rec + b_rec,
-                  o_ws = o_cnt + b_cnt;
+    const int64_t o_roff = align256(max_bases + 16), o_rec = o_roff + align256((max_reads + 1) * 8), o_col = o_rec + b_rec,
+                  o_cnt = o_col + b_col, o_ws = o_cnt + b_cnt;
     auto submit = [&](int64_t ch) -> int {
         PipeSlot &P = S[ch % n_slots];
         const int64_t lo = cuts[(size_t)ch], hi = cuts[(size_t)ch + 1], nr = hi - lo, nb = read_off[hi] - read_off[lo];
@@ -3043,22 +3117,29 @@ static int colors_host_batch(const sbwtgpu_colors *c, const char *bases, const i
             return fail(SBWTGPU_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
         int r2;
         const int64_t *d_roff = (const int64_t *)(P.d_mem + o_roff);
-        if (out) {
+        if (wide_colors) {
+            r2 = sbwtgpu_pseudoalign_wide_dev(c, P.d_mem, nb, d_roff, nr, strands, threshold_ppm, denominator,
+                                              (sbwtgpu_read_found *)(P.d_mem + o_rec), (uint64_t *)(P.d_mem + o_col),
+                                              counts ? (int32_t *)(P.d_mem + o_cnt) : nullptr, P.d_mem + o_ws, ws_bytes, P.st);
+        } else if (out) {
             r2 = sbwtgpu_pseudoalign_dev(c, P.d_mem, nb, d_roff, nr, strands, threshold_ppm, denominator,
                                          (sbwtgpu_pseudoalignment *)(P.d_mem + o_rec), counts ? (int32_t *)(P.d_mem + o_cnt) : nullptr,
                                          P.d_mem + o_ws, ws_bytes, P.st);
         } else {
             r2 = colors_dev_common(c, P.d_mem, nb, d_roff, nr, strands, P.d_mem + o_ws, ws_bytes, P.st,
                                    [&](const int *res, const int *res2, const long long *ooff, SbwtPaHeader *hdr, hipStream_t st) {
-                                       sbwt_launch_col_mark(res, res2, ooff, nr, nb, c->d_rows, c->n_nodes, color, 1, hdr, st);
-                                       if (res2) sbwt_launch_col_mark(res2, nullptr, ooff, nr, nb, c->d_rows, c->n_nodes, color, 0, hdr, st);
+                                       sbwt_launch_col_mark(res, res2, ooff, nr, nb, c->d_rows, c->n_nodes, c->words, color, 1, hdr, st);
+                                       if (res2)
+                                           sbwt_launch_col_mark(res2, nullptr, ooff, nr, nb, c->d_rows, c->n_nodes, c->words, color, 0, hdr, st);
                                    });
         }
         if (r2 != SBWTGPU_OK) return r2;
         const SbwtPaLayout L = sbwt_pa_layout(sbwtgpu_search_workspace_bytes(nb), nb, nr, strands);
-        if ((out && (e = hipMemcpyAsync(P.h_out, P.d_mem + o_rec, (size_t)nr * 16, hipMemcpyDeviceToHost, P.st)) != hipSuccess) ||
+        if ((out && (e = hipMemcpyAsync(P.h_out, P.d_mem + o_rec, (size_t)(nr * rec_bytes), hipMemcpyDeviceToHost, P.st)) != hipSuccess) ||
+            (wide_colors &&
+             (e = hipMemcpyAsync(P.h_out + b_rec, P.d_mem + o_col, (size_t)(nr * nw) * 8, hipMemcpyDeviceToHost, P.st)) != hipSuccess) ||
             (counts && nr * nc > 0 &&
-             (e = hipMemcpyAsync(P.h_out + b_rec, P.d_mem + o_cnt, (size_t)(nr * nc) * 4, hipMemcpyDeviceToHost, P.st)) != hipSuccess) ||
+             (e = hipMemcpyAsync(P.h_out + b_rec + b_col, P.d_mem + o_cnt, (size_t)(nr * nc) * 4, hipMemcpyDeviceToHost, P.st)) != hipSuccess) ||
             (e = hipMemcpyAsync(P.h_status, P.d_mem + o_ws + L.hdr, 16, hipMemcpyDeviceToHost, P.st)) != hipSuccess)
             return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
         return SBWTGPU_OK;
@@ -3072,8 +3153,9 @@ static int colors_host_batch(const sbwtgpu_colors *c, const char *bases, const i
         memcpy(&nh, P.h_status + 2, 8);                  // (SbwtPaHeader::n_hit)
         hits += (int64_t)nh;
         const int64_t lo = cuts[(size_t)ch], hi = cuts[(size_t)ch + 1];
-        if (out) memcpy(out + lo, P.h_out, (size_t)(hi - lo) * 16);
-        if (counts && (hi - lo) * nc > 0) memcpy(counts + lo * nc, P.h_out + b_rec, (size_t)((hi - lo) * nc) * 4);
+        if (out) memcpy((char *)out + lo * rec_bytes, P.h_out, (size_t)((hi - lo) * rec_bytes));
+        if (wide_colors) memcpy(wide_colors + lo * nw, P.h_out + b_rec, (size_t)((hi - lo) * nw) * 8);
+        if (counts && (hi - lo) * nc > 0) memcpy(counts + lo * nc, P.h_out + b_rec + b_col, (size_t)((hi - lo) * nc) * 4);
         return SBWTGPU_OK;
     };
     rc = two_in_flight(n_chunks, submit, collect);
@@ -3092,7 +3174,7 @@ int sbwtgpu_colors_add_batch(sbwtgpu_colors *c, int color, const char *bases, co
     if (rc != SBWTGPU_OK) return rc;
     if (color < 0 || color >= c->n_colors)
         return fail(SBWTGPU_ERR_INVALID_ARG, "color %d is out of range: the colours object has %d colours", color, c->n_colors);
-    return colors_host_batch(c, bases, read_off, n_reads, strands, color, 0, 0, nullptr, nullptr, n_windows, n_hit_windows);
+    return colors_host_batch(c, bases, read_off, n_reads, strands, color, 0, 0, nullptr, nullptr, nullptr, n_windows, n_hit_windows);
 }
 
 int sbwtgpu_pseudoalign_batch(const sbwtgpu_colors *c, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
@@ -3101,8 +3183,24 @@ int sbwtgpu_pseudoalign_batch(const sbwtgpu_colors *c, const char *bases, const 
     if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
     if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
     if (rc != SBWTGPU_OK) return rc;
+    if (c->n_colors > 64)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "the colours object has %d colours, a 16-byte record holds 64: use sbwtgpu_pseudoalign_wide_batch",
+                    c->n_colors);
     if (n_reads > 0 && !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    return colors_host_batch(c, bases, read_off, n_reads, strands, 0, threshold_ppm, denominator, out, counts_or_null, nullptr, nullptr);
+    return colors_host_batch(c, bases, read_off, n_reads, strands, 0, threshold_ppm, denominator, out, nullptr, counts_or_null, nullptr,
+                             nullptr);
+}
+
+int sbwtgpu_pseudoalign_wide_batch(const sbwtgpu_colors *c, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
+                                   int threshold_ppm, int denominator, sbwtgpu_read_found *out, uint64_t *colors_out,
+                                   int32_t *counts_or_null) {
+    int rc = colors_check(c);
+    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_reads > 0 && (!out || !colors_out)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    return colors_host_batch(c, bases, read_off, n_reads, strands, 0, threshold_ppm, denominator, out, colors_out, counts_or_null,
+                             nullptr, nullptr);
 }
 
 // ---- set operations (sbwt_setops.hip) ---------------------------------------------------------------

@@ -17,6 +17,7 @@ EXPORTED_SYMBOLS = [
     "sbwthost_file_write", "sbwthost_file_read", "sbwthost_file_free", "sbwthost_file_info",
     "sbwthost_file_words", "sbwthost_file_precalc", "sbwthost_read_sequences", "sbwthost_read_sequences_chunked", "sbwthost_free", "sbwthost_write_file",
     "sbwthost_rank_batch", "sbwthost_colors_write", "sbwthost_colors_read",
+    "sbwthost_colors_write_wide", "sbwthost_colors_read_wide",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -55,6 +56,8 @@ def lib() -> C.CDLL:
     L.sbwthost_rank_batch.argtypes = [vp, i64, vp, i64, vp]
     L.sbwthost_colors_write.argtypes = [C.c_char_p, vp, i64, i64, i64]
     L.sbwthost_colors_read.argtypes = [C.c_char_p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp, i64]
+    L.sbwthost_colors_write_wide.argtypes = [C.c_char_p, vp, i64, i64, i64]
+    L.sbwthost_colors_read_wide.argtypes = [C.c_char_p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp, i64]
     _lib = L
     return L
 
@@ -198,5 +201,28 @@ def colors_read(path: str):
         raise RuntimeError(_err())
     rows = np.zeros(n.value, dtype=np.uint64)
     if L.sbwthost_colors_read(path.encode(), C.byref(n), C.byref(nc), C.byref(k), rows.ctypes.data if n.value else None, n.value) != 0:
+        raise RuntimeError(_err())
+    return rows, nc.value, k.value
+
+
+def colors_write_wide(path: str, rows, n_colors: int, k: int) -> None:
+    """Writes a wide colour matrix ((n_columns, ceil(n_colors / 64)) uint64 words) as an "SBWTCOL2" file (include/sbwthost.h)."""
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    words = (n_colors + 63) // 64
+    if rows.ndim != 2 or (1 <= n_colors <= 4096 and rows.shape[1] != words):
+        raise RuntimeError("rows of shape %s, %d colours need %d words a row" % (rows.shape, n_colors, words))
+    if lib().sbwthost_colors_write_wide(path.encode(), rows.ctypes.data if rows.size else None, rows.shape[0], n_colors, k) != 0:
+        raise RuntimeError(_err())
+
+
+def colors_read_wide(path: str):
+    """(rows uint64[n_columns, words_per_row], n_colors, k) of an "SBWTCOL2" or "SBWTCOL1" colour file."""
+    L = lib()
+    n, nc, k, w = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    if L.sbwthost_colors_read_wide(path.encode(), C.byref(n), C.byref(nc), C.byref(k), C.byref(w), None, 0) != 0:
+        raise RuntimeError(_err())
+    rows = np.zeros((n.value, w.value), dtype=np.uint64)
+    if L.sbwthost_colors_read_wide(path.encode(), C.byref(n), C.byref(nc), C.byref(k), C.byref(w), rows.ctypes.data if rows.size else None,
+                                   rows.size) != 0:
         raise RuntimeError(_err())
     return rows, nc.value, k.value

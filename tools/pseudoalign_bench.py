@@ -7,7 +7,11 @@ Prints one JSON line:
   host     pseudoalign_batch from pageable host buffers on --host-reads reads, and colors_add_batch per strain: host clock
            around the (synchronous) call
 
-  python tools/pseudoalign_bench.py [--reads N] [--host-reads N] [--steps 7] [--warmup 2]
+  wide     (--wide, instead of the above) the wide call beside the 64-colour call on the same batch: the three strains as
+           colours 0, 70 and 130 of 192 (3 words a row), as colours 0, 1 and 2 of 64 through the wide call, and through the
+           64-colour call; the three calls alternate, device events around each, medians of --steps
+
+  python tools/pseudoalign_bench.py [--reads N] [--host-reads N] [--steps 7] [--warmup 2] [--wide]
 Kernel names and times: run it under `rocprofv3 --kernel-trace --stats -d DIR -- python tools/pseudoalign_bench.py ...`."""
 import argparse
 import json
@@ -29,6 +33,7 @@ def main():
     ap.add_argument("--steps", type=int, default=7)
     ap.add_argument("--host-steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--wide", action="store_true")
     args = ap.parse_args()
     import torch
     import bench
@@ -41,6 +46,9 @@ def main():
     idx = capi.Index.create(bits.cols[0], bits.cols[1], bits.cols[2], bits.cols[3], bits.ssup, bits.n_nodes, k, bits.n_kmers, 0)
     del bits
     res = {"config": 2, "k": k, "n_nodes": idx.n_nodes, "image_level": idx.image_level, "n_colors": len(genomes)}
+    if args.wide:
+        print(json.dumps(wide_leg(args, torch, bench, capi, genomes, idx, k, dev, res)))
+        return
 
     # ---- colouring: one strain per colour, each genome one sequence ----
     col = capi.Colors.create(idx, len(genomes))
@@ -140,6 +148,76 @@ def main():
                                          "G_kmers_per_s": round(hW / med / 1e6, 2), "result_bytes": 16 * hn,
                                          "n_found": int(hrec["n_found"].sum(dtype=np.int64))}}
     print(json.dumps(res))
+
+
+def wide_leg(args, torch, bench, capi, genomes, idx, k, dev, res):
+    """The same reads through sbwtgpu_pseudoalign_dev (64 colours), sbwtgpu_pseudoalign_wide_dev at 64 colours (1 word a row) and
+    at 192 colours (3 words a row, the strains on colours 0, 70 and 130: one per word)."""
+    wide_ids = (0, 70, 130)
+    objs = {"narrow64": (capi.Colors.create(idx, 64), (0, 1, 2)), "wide64": (capi.WideColors.create(idx, 64), (0, 1, 2)),
+            "wide192": (capi.WideColors.create(idx, 192), wide_ids)}
+    for name, (col, ids) in objs.items():
+        for c, g in zip(ids, genomes):
+            col.add_sequences(c, g, np.array([0, len(g)], dtype=np.int64))
+    res["wide_colors"] = {name: {"n_colors": col.n_colors, "words": getattr(col, "words", 1), "strain_colors": list(ids),
+                                 "rows_bytes": 8 * idx.n_nodes * getattr(col, "words", 1)} for name, (col, ids) in objs.items()}
+    stream = torch.cuda.current_stream(dev)
+    n, L = args.reads, bench.READ_LEN
+    bases_t = bench.gpu_reads(genomes, n, 12345, dev)
+    T = bases_t.numel()
+    off_t = torch.arange(n + 1, dtype=torch.int64, device=dev) * L
+    W = n * (L - k + 1)
+    res.update({"reads": n, "read_len": L, "kmers": W})
+    rows = {}
+    for both in (False, True):
+        need = capi.pseudoalign_workspace_bytes(T, n, both)
+        pws = torch.zeros(need, dtype=torch.uint8, device=dev)
+        rec16 = torch.empty((n, 2), dtype=torch.int64, device=dev)
+        rec8 = torch.empty(n, dtype=torch.int64, device=dev)
+        colw = {name: torch.empty((n, getattr(col, "words", 1)), dtype=torch.int64, device=dev) for name, (col, _) in objs.items()}
+        calls = {
+            "narrow64": lambda: objs["narrow64"][0].pseudoalign_dev(bases_t.data_ptr(), T, off_t.data_ptr(), n, rec16.data_ptr(), 0,
+                                                                    pws.data_ptr(), need, both, 1_000_000, 0, stream.cuda_stream)}
+        for name in ("wide64", "wide192"):
+            calls[name] = (lambda name=name: objs[name][0].pseudoalign_dev(bases_t.data_ptr(), T, off_t.data_ptr(), n, rec8.data_ptr(),
+                                                                          colw[name].data_ptr(), 0, pws.data_ptr(), need, both,
+                                                                          1_000_000, 0, stream.cuda_stream))
+        times = {name: [] for name in calls}
+        found, sets = {}, {}
+        for s in range(args.warmup + args.steps):               # the three calls alternate
+            for name, call in calls.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                call()
+                e1.record(stream)
+                e1.synchronize()
+                if s >= args.warmup:
+                    times[name].append(e0.elapsed_time(e1))
+                if s == 0:                                      # what each call found: the three must agree
+                    if name == "narrow64":
+                        h = rec16.cpu().numpy().view(capi.PSEUDOALIGNMENT_DTYPE).reshape(n)
+                        found[name], words = h["n_found"].copy(), h["colors"].reshape(n, 1)
+                    else:
+                        found[name] = rec8.cpu().numpy().view(capi.READ_FOUND_DTYPE).reshape(n)["n_found"].copy()
+                        words = colw[name].cpu().numpy().view(np.uint64)
+                    ids = objs[name][1]
+                    sets[name] = np.stack([(words[:, c >> 6] >> np.uint64(c & 63)) & np.uint64(1) for c in ids], axis=1)
+        for name in ("wide64", "wide192"):
+            if not (np.array_equal(found[name], found["narrow64"]) and np.array_equal(sets[name], sets["narrow64"])):
+                raise SystemExit("%s and the 64-colour call disagree" % name)
+        for name, t in times.items():
+            med = float(np.median(t))
+            rows["%s_strands%d" % (name, 2 if both else 1)] = {
+                "median_ms": round(med, 3), "min_ms": round(min(t), 3), "max_ms": round(max(t), 3), "calls": len(t),
+                "G_kmers_per_s": round(W / med / 1e6, 2), "n_found": int(found[name].sum(dtype=np.int64)),
+                "result_bytes": n * (16 if name == "narrow64" else 8 + 8 * objs[name][0].words)}
+        for name in ("wide64", "wide192"):
+            rows["%s_over_narrow64_strands%d" % (name, 2 if both else 1)] = round(
+                rows["%s_strands%d" % (name, 2 if both else 1)]["median_ms"] / rows["narrow64_strands%d" % (2 if both else 1)]["median_ms"], 3)
+        del pws, rec16, rec8, colw
+    rows["results_agree"] = True
+    res["wide"] = rows
+    return res
 
 
 if __name__ == "__main__":
