@@ -114,8 +114,8 @@ int         sbwtgpu_device_count(int *count);
  *   "read_hits_chunk_bases" sbwtgpu_read_hits_batch cuts its batch into chunks of whole reads of at most this many bases (a
  *                        chunk always takes one read); 0 (default) = 64 Mi
  *   "read_hits_wide"     1: the read-hits calls take the int64 search route also on indexes of fewer than 2^31 columns (tests)
- *   "pseudoalign_chunk_bases" sbwtgpu_pseudoalign_batch and sbwtgpu_colors_add_batch cut their batch into chunks of whole reads
- *                        of at most this many bases (a chunk always takes one read); 0 (default) = 64 Mi
+ *   "pseudoalign_chunk_bases" sbwtgpu_pseudoalign_batch (_wide_batch, _sets_batch) and sbwtgpu_colors_add_batch cut their batch
+ *                        into chunks of whole reads of at most this many bases (a chunk always takes one read); 0 (default) = 64 Mi
  *   "trans_ext", "trans_wide"   accepted and ignored (round-2 table formats)
  * Read when an index is CREATED (derived acceleration structures inside the device image; environment
  * variables of the same meaning: SBWTGPU_SPARSE_PRECALC, SBWTGPU_PROBE_FILTER, SBWTGPU_PATH_ORDER):
@@ -617,6 +617,62 @@ int  sbwtgpu_pseudoalign_wide_batch(const sbwtgpu_colors *c, const char *bases, 
 /* Device buffers, as sbwtgpu_pseudoalign_dev: the same preconditions, the same workspace (sbwtgpu_pseudoalign_workspace_bytes does
  * not depend on the colours) with the same layout.  d_out: n_reads records of 8 bytes; d_colors: n_reads x W words. */
 int  sbwtgpu_pseudoalign_wide_dev(const sbwtgpu_colors *c, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                                  int64_t n_reads, int strands, int threshold_ppm, int denominator,
+                                  sbwtgpu_read_found *d_out, uint64_t *d_colors, int32_t *d_counts_or_null,
+                                  void *d_workspace, int64_t workspace_bytes, void *stream);
+
+/* ---- colour sets: one id per column and a table of the distinct rows ----
+ * A colour-set object of an index of n columns (n < 2^31) with n_colors in 1 .. SBWTGPU_MAX_COLORS and
+ * W = ceil(n_colors / 64) holds
+ *   - ids: n uint32_t;
+ *   - n_sets >= 1;
+ *   - table: n_sets x W little-endian uint64_t, row-major.
+ * It MEANS the wide matrix rows[j * W + w] = table[ids[j] * W + w].
+ * Invariants, checked on every way in:
+ *   - Row 0 of the table is all zero.
+ *   - No other row is all zero, so a column is coloured exactly when ids[j] != 0.
+ *   - No bit >= n_colors is set.
+ *   - Every id is < n_sets.
+ *   - Dummy columns have id 0.
+ * Duplicate rows and unused rows are allowed in an uploaded object: queries stay correct and lose only the fast path.
+ * Canonical form (what sbwtgpu_colorsets_compress produces and the files written by the CLI hold):
+ *   - The distinct non-zero rows of the matrix are numbered 1, 2, ... in the order of the smallest column that carries them.
+ *   - Row 0 is the empty set.
+ *   - n_sets = 1 + the number of distinct non-zero rows.
+ * Two runs of compress give identical bytes.
+ * Query results: records, colour words and counts are exactly those of the wide calls above on the matrix the object means --
+ * one and two strands, threshold_ppm, denominator, optional counts, and a found window with an empty set counting as not found.
+ *
+ * Memory: 4 bytes per column and 8 W bytes per distinct set on the index's device.  compress needs, while it runs and beside
+ * its result, 13 bytes per column (the slots of a hash table of 2 n + 1 uint32, one flag byte and one uint32 of their scan) and
+ * a few KiB; create and info need one byte per column while they run.  The index must outlive the object; the colours object
+ * given to compress is unchanged and may be destroyed afterwards.
+ * Refusals (SBWTGPU_ERR_INVALID_ARG with a message that names the cause): those of the colour calls above (rank-only indexes,
+ * 2^31 columns or more, ranges, an object of another index, NULL pointers) and, for create, every broken invariant but the
+ * dummy columns' ids, which it sets to 0.  SBWTGPU_ERR_OOM leaves index and inputs usable.
+ * Concurrency: the queries (pseudoalign_sets_batch / _dev, expand, info, copy) are thread-safe on one object. */
+typedef struct sbwtgpu_colorsets sbwtgpu_colorsets;
+
+/* any colours object, W = 1 included */
+int  sbwtgpu_colorsets_compress(const sbwtgpu_colors *c, sbwtgpu_colorsets **out);
+/* ids: n_nodes entries; table: n_sets x W words.  The checks run on the device. */
+int  sbwtgpu_colorsets_create(const sbwtgpu_index *idx, int n_colors, const uint32_t *ids, int64_t n_sets, const uint64_t *table,
+                              sbwtgpu_colorsets **out);
+/* the wide colours object it means (of sbwtgpu_colors_create_wide; destroy it with sbwtgpu_colors_destroy) */
+int  sbwtgpu_colorsets_expand(const sbwtgpu_colorsets *s, sbwtgpu_colors **out);
+void sbwtgpu_colorsets_destroy(sbwtgpu_colorsets *s);
+/* every output may be NULL; device_bytes = 4 n_columns + 8 words n_sets */
+int  sbwtgpu_colorsets_info(const sbwtgpu_colorsets *s, int64_t *n_columns, int64_t *k, int32_t *n_colors, int32_t *words,
+                            int64_t *n_sets, int64_t *n_colored_columns, int64_t *device_bytes);
+/* ids_out: n_columns entries, table_out: n_sets x W words; either may be NULL */
+int  sbwtgpu_colorsets_copy(const sbwtgpu_colorsets *s, uint32_t *ids_out, uint64_t *table_out);
+int  sbwtgpu_colorsets_dev(const sbwtgpu_colorsets *s, const uint32_t **d_ids, const uint64_t **d_table);
+/* sbwtgpu_pseudoalign_wide_batch and _dev with a colour-set object in the place of the colours object: the same arguments,
+ * outputs, chunking ("pseudoalign_chunk_bases") and workspace (sbwtgpu_pseudoalign_workspace_bytes, the same layout). */
+int  sbwtgpu_pseudoalign_sets_batch(const sbwtgpu_colorsets *s, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
+                                    int threshold_ppm, int denominator, sbwtgpu_read_found *out, uint64_t *colors_out,
+                                    int32_t *counts_or_null);
+int  sbwtgpu_pseudoalign_sets_dev(const sbwtgpu_colorsets *s, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
                                   int64_t n_reads, int strands, int threshold_ppm, int denominator,
                                   sbwtgpu_read_found *d_out, uint64_t *d_colors, int32_t *d_counts_or_null,
                                   void *d_workspace, int64_t workspace_bytes, void *stream);

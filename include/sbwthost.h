@@ -73,6 +73,20 @@ int  sbwthost_colors_read(const char *path, int64_t *n_columns, int64_t *n_color
 int  sbwthost_colors_write_wide(const char *path, const uint64_t *rows, int64_t n_columns, int64_t n_colors, int64_t k);
 int  sbwthost_colors_read_wide(const char *path, int64_t *n_columns, int64_t *n_colors, int64_t *k, int64_t *words_per_row,
                                uint64_t *rows_or_null, int64_t words_cap);
+/* Colour-set files (the colour-set object of include/sbwtgpu.h: one id per column and a table of the distinct rows): 8 bytes
+ * "SBWTCOL3"; int64 n_columns, n_colors, k, words_per_row, n_sets; then n_columns little-endian uint32 ids, zero-padded to a
+ * multiple of 8 bytes; then n_sets x words_per_row little-endian uint64 words, row-major.  The read is the two-call pattern:
+ * with ids_or_null = table_or_null = NULL it gives the five sizes, a second call with room for ids_cap >= n_columns ids and
+ * table_words_cap >= n_sets x words_per_row words fills them.  Both calls check the header's ranges (1 <= n_colors <= 4096,
+ * words_per_row = ceil(n_colors / 64), n_columns < 2^31, 1 <= n_sets < 2^32), the exact file size and every invariant of the
+ * object but the ids of dummy columns, which only the index knows: ids below n_sets, row 0 of the table zero, no other row
+ * zero, no bit >= n_colors.  Truncation, a wrong magic and any violation are errors with a message; the writer refuses the
+ * same violations.  sbwthost_colors_read and sbwthost_colors_read_wide refuse "SBWTCOL3" files as they refuse any unknown
+ * magic. */
+int  sbwthost_colorsets_write(const char *path, const uint32_t *ids, const uint64_t *table, int64_t n_columns, int64_t n_colors,
+                              int64_t k, int64_t n_sets);
+int  sbwthost_colorsets_read(const char *path, int64_t *n_columns, int64_t *n_colors, int64_t *k, int64_t *words_per_row,
+                             int64_t *n_sets, uint32_t *ids_or_null, int64_t ids_cap, uint64_t *table_or_null, int64_t table_words_cap);
 
 #ifdef __cplusplus
 }

@@ -53,6 +53,9 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_colors_dev", "sbwtgpu_pseudoalign_batch", "sbwtgpu_pseudoalign_workspace_bytes", "sbwtgpu_pseudoalign_dev",
     "sbwtgpu_colors_create_wide", "sbwtgpu_colors_words", "sbwtgpu_colors_info_wide", "sbwtgpu_pseudoalign_wide_batch",
     "sbwtgpu_pseudoalign_wide_dev",
+    "sbwtgpu_colorsets_compress", "sbwtgpu_colorsets_create", "sbwtgpu_colorsets_expand", "sbwtgpu_colorsets_destroy",
+    "sbwtgpu_colorsets_info", "sbwtgpu_colorsets_copy", "sbwtgpu_colorsets_dev", "sbwtgpu_pseudoalign_sets_batch",
+    "sbwtgpu_pseudoalign_sets_dev",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -246,6 +249,17 @@ def lib() -> C.CDLL:
         L.sbwtgpu_colors_info_wide.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_int32), C.POINTER(i64), vp]
         L.sbwtgpu_pseudoalign_wide_batch.argtypes = [vp, vp, vp, i64, ci, ci, ci, vp, vp, vp]
         L.sbwtgpu_pseudoalign_wide_dev.argtypes = [vp, vp, i64, vp, i64, ci, ci, ci, vp, vp, vp, vp, i64, vp]
+        L.sbwtgpu_colorsets_compress.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_colorsets_create.argtypes = [vp, ci, vp, i64, vp, C.POINTER(vp)]
+        L.sbwtgpu_colorsets_expand.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_colorsets_destroy.argtypes = [vp]
+        L.sbwtgpu_colorsets_destroy.restype = None
+        L.sbwtgpu_colorsets_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(i64),
+                                             C.POINTER(i64), C.POINTER(i64)]
+        L.sbwtgpu_colorsets_copy.argtypes = [vp, vp, vp]
+        L.sbwtgpu_colorsets_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        L.sbwtgpu_pseudoalign_sets_batch.argtypes = [vp, vp, vp, i64, ci, ci, ci, vp, vp, vp]
+        L.sbwtgpu_pseudoalign_sets_dev.argtypes = [vp, vp, i64, vp, i64, ci, ci, ci, vp, vp, vp, vp, i64, vp]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -895,6 +909,121 @@ class WideColors(Colors):
         """sbwtgpu_pseudoalign_wide_dev (raw device pointers; d_out: n_reads records of 8 bytes; d_colors: n_reads x W words;
         d_counts = 0: no counts)."""
         _check(lib().sbwtgpu_pseudoalign_wide_dev(self._h, d_bases, total_bases, d_read_off, n_reads, 2 if both_strands else 1,
+                                                  threshold_ppm, denominator, d_out, d_colors, d_counts or None, d_ws, ws_bytes, stream))
+
+
+class ColorSets:
+    """Owns an sbwtgpu_colorsets handle: the deduplicated colour sets of an index -- one uint32 id per column and a table of the
+    distinct rows of W = ceil(n_colors / 64) words (include/sbwtgpu.h, "colour sets").  It means the wide matrix
+    table[ids[j]]; the queries return what WideColors' return on that matrix.  The index is kept referenced."""
+
+    def __init__(self, handle, index: Index):
+        self._h = handle
+        self.index = index
+        info = self.info()
+        self.n_colors, self.words, self.n_sets = info["n_colors"], info["words"], info["n_sets"]
+
+    @classmethod
+    def from_colors(cls, colors: Colors) -> "ColorSets":
+        """sbwtgpu_colorsets_compress: the canonical form of any colours object, which stays as it is."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_colorsets_compress(colors.handle, C.byref(h)))
+        return cls(h, colors.index)
+
+    @classmethod
+    def from_arrays(cls, index: Index, n_colors: int, ids, table, k: Optional[int] = None) -> "ColorSets":
+        """sbwtgpu_colorsets_create from ids (n_nodes uint32) and table ((n_sets, W) uint64; ColorSets.copy(), or
+        hostlib.colorsets_read with its k): the ids of dummy columns are set to 0, every other broken invariant is refused."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        table = np.ascontiguousarray(table, dtype=np.uint64)
+        if not 1 <= n_colors <= MAX_COLORS:
+            raise SbwtGpuError(ERR_INVALID_ARG, "n_colors must be in 1 .. %d, not %d" % (MAX_COLORS, n_colors))
+        words = (n_colors + 63) // 64
+        if ids.ndim != 1 or len(ids) != index.n_nodes or (k is not None and k != index.k):
+            raise SbwtGpuError(ERR_INVALID_ARG, "colour sets of %d columns at k = %s used with an index of %d columns at k = %d"
+                               % (ids.size, "?" if k is None else k, index.n_nodes, index.k))
+        if table.ndim != 2 or table.shape[1] != words or table.shape[0] < 1:
+            raise SbwtGpuError(ERR_INVALID_ARG, "a table of shape %s, %d colours need at least one row of %d words"
+                               % (table.shape, n_colors, words))
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_colorsets_create(index.handle, n_colors, ids.ctypes.data, table.shape[0], table.ctypes.data, C.byref(h)))
+        return cls(h, index)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        if self._h:
+            lib().sbwtgpu_colorsets_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self) -> dict:
+        """n_columns, k, n_colors, words, n_sets, n_colored_columns and device_bytes."""
+        n, k, ns, ncc, db = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        nc, w = C.c_int32(), C.c_int32()
+        _check(lib().sbwtgpu_colorsets_info(self._h, C.byref(n), C.byref(k), C.byref(nc), C.byref(w), C.byref(ns), C.byref(ncc),
+                                            C.byref(db)))
+        return {"n_columns": n.value, "k": k.value, "n_colors": nc.value, "words": w.value, "n_sets": ns.value,
+                "n_colored_columns": ncc.value, "device_bytes": db.value}
+
+    def copy(self):
+        """(ids uint32[n_nodes], table uint64[n_sets, W])"""
+        ids = np.empty(self.index.n_nodes, dtype=np.uint32)
+        table = np.empty((self.n_sets, self.words), dtype=np.uint64)
+        _check(lib().sbwtgpu_colorsets_copy(self._h, ids.ctypes.data, table.ctypes.data))
+        return ids, table
+
+    def dev_ptrs(self):
+        """(d_ids, d_table) raw device pointers"""
+        a, b = C.c_void_p(), C.c_void_p()
+        _check(lib().sbwtgpu_colorsets_dev(self._h, C.byref(a), C.byref(b)))
+        return a.value or 0, b.value or 0
+
+    def expand(self) -> "WideColors":
+        """sbwtgpu_colorsets_expand: the wide colours object this one means."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_colorsets_expand(self._h, C.byref(h)))
+        return WideColors(h, self.index, self.n_colors)
+
+    def pseudoalign(self, bases, read_off, both_strands: bool = False, threshold_ppm: int = 1_000_000, denominator: int = 0,
+                    counts: bool = False):
+        """sbwtgpu_pseudoalign_sets_batch: what WideColors.pseudoalign returns -- (records, colors[, counts])."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        n = max(len(read_off) - 1, 0)
+        out = np.zeros(n, dtype=READ_FOUND_DTYPE)
+        out["n_kmers"] = -12345
+        col = np.zeros((n, self.words), dtype=np.uint64)
+        cnt = np.full((n, self.n_colors), -12345, dtype=np.int32) if counts else None
+        _check(lib().sbwtgpu_pseudoalign_sets_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n, 2 if both_strands else 1,
+                                                    threshold_ppm, denominator, out.ctypes.data, col.ctypes.data,
+                                                    cnt.ctypes.data if counts else None))
+        return (out, col, cnt) if counts else (out, col)
+
+    def pseudoalign_reads(self, reads: Sequence[bytes], both_strands: bool = False, threshold_ppm: int = 1_000_000,
+                          denominator: int = 0, counts: bool = False):
+        """The same for a list of byte strings."""
+        bases, off = concat_reads(reads)
+        return self.pseudoalign(bases, off, both_strands, threshold_ppm, denominator, counts)
+
+    def pseudoalign_dev(self, d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_out: int, d_colors: int, d_counts: int,
+                        d_ws: int, ws_bytes: int, both_strands: bool = False, threshold_ppm: int = 1_000_000, denominator: int = 0,
+                        stream: int = 0):
+        """sbwtgpu_pseudoalign_sets_dev (raw device pointers, as WideColors.pseudoalign_dev)."""
+        _check(lib().sbwtgpu_pseudoalign_sets_dev(self._h, d_bases, total_bases, d_read_off, n_reads, 2 if both_strands else 1,
                                                   threshold_ppm, denominator, d_out, d_colors, d_counts or None, d_ws, ws_bytes, stream))
 
 

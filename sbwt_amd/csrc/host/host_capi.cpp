@@ -1,6 +1,7 @@
 // host_capi.cpp -- implementation of include/sbwthost.h (GPU-free host helpers).
 #include "../../../include/sbwthost.h"
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -328,6 +329,130 @@ int sbwthost_colors_read_wide(const char *path, int64_t *n_columns, int64_t *n_c
     in.seekg(start, std::ios::beg);
     if (head[0] > 0) in.read(reinterpret_cast<char *>(rows_or_null), (std::streamsize)(head[0] * words * 8));
     if (!in.good()) return fail("Error reading %s", path);
+    return 0;
+}
+
+// ---- colour-set files: "SBWTCOL3", int64 n_columns, n_colors, k, words_per_row, n_sets, then n_columns uint32 ids zero-padded
+// to a multiple of 8 bytes, then n_sets x words_per_row words ----
+static const char COLORS_MAGIC_SETS[8] = {'S', 'B', 'W', 'T', 'C', 'O', 'L', '3'};
+
+// the invariants a file can be held to (include/sbwtgpu.h, "colour sets"): ids below n_sets; row 0 zero, no other row zero, no
+// bit >= n_colors.  NULL when they hold, else the message in `msg`.
+static const char *colorsets_violation(const uint32_t *ids, int64_t n_ids, int64_t first_col, const uint64_t *table, int64_t n_rows,
+                                       int64_t first_row, int64_t n_sets, int64_t n_colors, int64_t words, char *msg, size_t cap) {
+    for (int64_t j = 0; j < n_ids; j++)
+        if ((int64_t)ids[j] >= n_sets) {
+            snprintf(msg, cap, "the id %lld of column %lld is not below n_sets = %lld", (long long)ids[j], (long long)(first_col + j),
+                     (long long)n_sets);
+            return msg;
+        }
+    const uint64_t keep = (n_colors & 63) == 0 ? ~0ull : ((1ull << (n_colors & 63)) - 1ull);
+    for (int64_t r = 0; r < n_rows; r++) {
+        const uint64_t *row = table + r * words;
+        uint64_t any = 0;
+        for (int64_t w = 0; w < words; w++) any |= row[w];
+        if (first_row + r == 0 && any) { snprintf(msg, cap, "row 0 of the table is not all zero"); return msg; }
+        if (first_row + r != 0 && !any) {
+            snprintf(msg, cap, "row %lld of the table is all zero (only row 0 may be)", (long long)(first_row + r));
+            return msg;
+        }
+        if (row[words - 1] & ~keep) {
+            snprintf(msg, cap, "row %lld of the table has a bit >= n_colors = %lld", (long long)(first_row + r), (long long)n_colors);
+            return msg;
+        }
+    }
+    return nullptr;
+}
+
+int sbwthost_colorsets_write(const char *path, const uint32_t *ids, const uint64_t *table, int64_t n_columns, int64_t n_colors,
+                             int64_t k, int64_t n_sets) {
+    if (!path || n_columns < 0 || (n_columns > 0 && !ids) || !table) return fail("invalid argument");
+    if (n_colors < 1 || n_colors > 4096) return fail("Error: n_colors must be in 1 .. 4096, not %lld", (long long)n_colors);
+    if (n_columns >= ((int64_t)1 << 31)) return fail("Error: colour sets hold fewer than 2^31 columns, not %lld", (long long)n_columns);
+    if (n_sets < 1 || n_sets > 0xFFFFFFFFll) return fail("Error: n_sets must be in 1 .. 2^32 - 1, not %lld", (long long)n_sets);
+    const int64_t words = (n_colors + 63) / 64;
+    char msg[160];
+    if (colorsets_violation(ids, n_columns, 0, table, n_sets, 0, n_sets, n_colors, words, msg, sizeof msg))
+        return fail("Error: colour sets for %s: %s", path, msg);
+    std::ofstream out(path, std::ios::binary);
+    if (!out.good()) return fail("Error opening file: %s", path);
+    const int64_t head[5] = {n_columns, n_colors, k, words, n_sets};
+    const char pad[8] = {0};
+    out.write(COLORS_MAGIC_SETS, 8);
+    out.write(reinterpret_cast<const char *>(head), 40);
+    if (n_columns > 0) out.write(reinterpret_cast<const char *>(ids), (std::streamsize)(n_columns * 4));
+    if (n_columns & 1) out.write(pad, 4);
+    out.write(reinterpret_cast<const char *>(table), (std::streamsize)(n_sets * words * 8));
+    out.flush();
+    if (!out.good()) return fail("Error writing to file %s", path);
+    return 0;
+}
+
+int sbwthost_colorsets_read(const char *path, int64_t *n_columns, int64_t *n_colors, int64_t *k, int64_t *words_per_row, int64_t *n_sets,
+                            uint32_t *ids_or_null, int64_t ids_cap, uint64_t *table_or_null, int64_t table_words_cap) {
+    if (!path) return fail("invalid argument");
+    std::ifstream in(path, std::ios::binary);
+    if (!in.good()) return fail("Error opening file: %s", path);
+    char magic[8];
+    int64_t head[5];
+    in.read(magic, 8);
+    if (in.gcount() != 8) return fail("Error: colour file %s is truncated (no magic)", path);
+    if (memcmp(magic, COLORS_MAGIC_SETS, 8) != 0) return fail("Error: %s is not a colour-set file (wrong magic, SBWTCOL3 expected)", path);
+    in.read(reinterpret_cast<char *>(head), 40);
+    if (in.gcount() != 40) return fail("Error: colour file %s is truncated (header)", path);
+    const int64_t n = head[0], nc = head[1], ns = head[4];
+    if (nc < 1 || nc > 4096) return fail("Error: colour file %s: n_colors = %lld is outside 1 .. 4096", path, (long long)nc);
+    const int64_t words = (nc + 63) / 64;
+    if (head[3] != words)
+        return fail("Error: colour file %s: words_per_row = %lld, %lld colours need %lld", path, (long long)head[3], (long long)nc,
+                    (long long)words);
+    if (n < 0 || n >= ((int64_t)1 << 31)) return fail("Error: colour file %s: n_columns = %lld is outside 0 .. 2^31 - 1", path, (long long)n);
+    if (ns < 1 || ns > 0xFFFFFFFFll) return fail("Error: colour file %s: n_sets = %lld is outside 1 .. 2^32 - 1", path, (long long)ns);
+    in.seekg(0, std::ios::end);
+    const int64_t size = (int64_t)in.tellg(), id_bytes = (n * 4 + 7) & ~(int64_t)7, want = 48 + id_bytes + ns * words * 8;
+    if (size < want)
+        return fail("Error: colour file %s is truncated (%lld bytes, %lld ids and %lld sets of %lld words need %lld)", path, (long long)size,
+                    (long long)n, (long long)ns, (long long)words, (long long)want);
+    if (size > want) return fail("Error: colour file %s has %lld bytes after its table", path, (long long)(size - want));
+    if (ids_or_null && ids_cap < n) return fail("Error: room for %lld ids, the colour file holds %lld", (long long)ids_cap, (long long)n);
+    if (table_or_null && table_words_cap < ns * words)
+        return fail("Error: room for %lld words, the colour file's table holds %lld", (long long)table_words_cap, (long long)(ns * words));
+    // ids and table go through a buffer piece by piece (or straight into the caller's arrays) and are checked on the way
+    in.seekg(48, std::ios::beg);
+    char msg[160];
+    try {
+        const int64_t PIECE = (int64_t)1 << 20;
+        std::vector<uint32_t> ibuf(ids_or_null ? 0 : (size_t)std::min(n, PIECE));
+        for (int64_t lo = 0; lo < n; lo += PIECE) {
+            const int64_t m = std::min(PIECE, n - lo);
+            uint32_t *dst = ids_or_null ? ids_or_null + lo : ibuf.data();
+            in.read(reinterpret_cast<char *>(dst), (std::streamsize)(m * 4));
+            if (!in.good()) return fail("Error reading %s", path);
+            if (colorsets_violation(dst, m, lo, nullptr, 0, 0, ns, nc, words, msg, sizeof msg)) return fail("Error: colour file %s: %s", path, msg);
+        }
+        if (n & 1) {
+            uint32_t pad = 0;
+            in.read(reinterpret_cast<char *>(&pad), 4);
+            if (!in.good()) return fail("Error reading %s", path);
+            if (pad != 0) return fail("Error: colour file %s: the padding after the ids is not zero", path);
+        }
+        const int64_t ROWS = std::max<int64_t>(1, PIECE / words);
+        std::vector<uint64_t> tbuf(table_or_null ? 0 : (size_t)(std::min(ns, ROWS) * words));
+        for (int64_t lo = 0; lo < ns; lo += ROWS) {
+            const int64_t m = std::min(ROWS, ns - lo);
+            uint64_t *dst = table_or_null ? table_or_null + lo * words : tbuf.data();
+            in.read(reinterpret_cast<char *>(dst), (std::streamsize)(m * words * 8));
+            if (!in.good()) return fail("Error reading %s", path);
+            if (colorsets_violation(nullptr, 0, 0, dst, m, lo, ns, nc, words, msg, sizeof msg)) return fail("Error: colour file %s: %s", path, msg);
+        }
+    } catch (const std::bad_alloc &) {
+        return fail("out of memory");
+    }
+    if (n_columns) *n_columns = n;
+    if (n_colors) *n_colors = nc;
+    if (k) *k = head[2];
+    if (words_per_row) *words_per_row = words;
+    if (n_sets) *n_sets = ns;
     return 0;
 }
 

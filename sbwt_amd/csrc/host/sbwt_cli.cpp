@@ -5,9 +5,12 @@
 //   sbwt search -o <out> -i <index> -q <query> [-z]        (sbwt_search.cpp:151-157)
 //   sbwt matching-statistics -i <index> -q <query> -o <out> [-z] [--intervals]
 //               k-bounded matching statistics: one line per read, one token per base ("d", or "d,first,second")
-//   sbwt build-colors -i <index> -r <refs.txt> -o <colours> [--both-strands] [--wide]
+//   sbwt build-colors -i <index> -r <refs.txt> -o <colours> [--both-strands] [--wide | --compress]
 //               one colour per listed reference file, set on the columns of the index's k-mers that the file holds
-//               (--wide: up to 4096 files, a colour file of several words per column)
+//               (--wide: up to 4096 files, a colour file of several words per column; --compress: up to 4096 files, a
+//               colour-set file of one id per column and the distinct colour sets)
+//   sbwt compress-colors -i <index> -c <colours> -o <colour sets>
+//               the colour-set file of a colour file written with or without --wide
 //   sbwt pseudoalign -i <index> -c <colours> -q <query> -o <out> [-z] [--threshold 0.7] [--all-kmers] [--both-strands]
 //               one line per read: its number, then the colours that hold it
 //   sbwt build  -i <in> -o <index> -k <k> [-p <precalc>] [--add-reverse-complements]
@@ -918,6 +921,35 @@ struct ColorsHandle {
     sbwtgpu_colors *h = nullptr;
     ~ColorsHandle() { sbwtgpu_colors_destroy(h); }
 };
+struct ColorSetsHandle {
+    sbwtgpu_colorsets *h = nullptr;
+    ~ColorSetsHandle() { sbwtgpu_colorsets_destroy(h); }
+};
+
+// the first 8 bytes of a colour file say which calls it goes through
+bool file_has_magic(const string &file, const char *magic) {
+    std::ifstream in(file, std::ios::binary);
+    char got[8] = {0};
+    in.read(got, 8);
+    return in.gcount() == 8 && memcmp(got, magic, 8) == 0;
+}
+
+// compresses a colours object (sbwtgpu_colorsets_compress: the canonical form) and writes it as an "SBWTCOL3" file
+void compress_and_write(const sbwtgpu_colors *col, const string &outfile) {
+    ColorSetsHandle sets;
+    colors_check(sbwtgpu_colorsets_compress(col, &sets.h));
+    int64_t n_columns = 0, ck = 0, n_sets = 0, n_colored = 0, bytes = 0;
+    int32_t n_colors = 0, words = 0;
+    colors_check(sbwtgpu_colorsets_info(sets.h, &n_columns, &ck, &n_colors, &words, &n_sets, &n_colored, &bytes));
+    vector<uint32_t> ids((size_t)n_columns);
+    vector<uint64_t> table((size_t)(n_sets * words));
+    colors_check(sbwtgpu_colorsets_copy(sets.h, ids.data(), table.data()));
+    if (sbwthost_colorsets_write(outfile.c_str(), ids.data(), table.data(), n_columns, n_colors, ck, n_sets) != 0)
+        throw std::runtime_error(sbwthost_last_error());
+    write_log("Wrote " + std::to_string(n_sets) + " colour sets of " + std::to_string(n_colors) + " colours over " +
+                  std::to_string(n_colored) + " coloured columns (" + std::to_string(bytes) + " bytes on the device) to " + outfile,
+              LogLevel::MAJOR);
+}
 
 void load_plain_matrix(const string &indexfile, plain_matrix_sbwt_t &index) {
     std::ifstream in(indexfile, std::ios::binary);
@@ -938,6 +970,7 @@ int build_colors_main(int argc, char **argv) {
         {"out-file", 'o', true, "Output colour file.", ""},
         {"both-strands", 0, false, "Also colour the reverse complement of every k-mer (for indexes built with reverse complements).", ""},
         {"wide", 0, false, "Up to 4096 lines in the list; writes a wide colour file (several 64-bit words per column).", ""},
+        {"compress", 0, false, "Up to 4096 lines in the list; writes a colour-set file (one id per column and the distinct colour sets).", ""},
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
@@ -951,7 +984,8 @@ int build_colors_main(int argc, char **argv) {
     check_readable(indexfile);
     check_readable(refsfile);
     const vector<string> refs = readlines(refsfile);
-    const bool wide = opts.count("wide");
+    const bool compress = opts.count("compress");
+    const bool wide = opts.count("wide") || compress;
     if (wide && (refs.empty() || refs.size() > SBWTGPU_MAX_COLORS))
         throw std::runtime_error("Error: " + refsfile + " lists " + std::to_string(refs.size()) + " files; a wide colour file holds 1 to " +
                                  std::to_string(SBWTGPU_MAX_COLORS) + " colours");
@@ -1001,6 +1035,10 @@ int build_colors_main(int argc, char **argv) {
     for (size_t c = 0; c < refs.size(); c++)
         std::cout << "colour " << c << ": " << windows[c] << " windows, " << hit_windows[c] << " hit windows, " << per_color[c]
                   << " coloured columns" << std::endl;
+    if (compress) {
+        compress_and_write(col.h, outfile);
+        return 0;
+    }
     vector<uint64_t> rows((size_t)n_columns * (size_t)sbwtgpu_colors_words(col.h));
     colors_check(sbwtgpu_colors_copy(col.h, rows.data()));
     if ((wide ? sbwthost_colors_write_wide(outfile.c_str(), rows.data(), n_columns, n_colors, ck)
@@ -1008,6 +1046,47 @@ int build_colors_main(int argc, char **argv) {
         throw std::runtime_error(sbwthost_last_error());
     write_log("Wrote " + std::to_string(n_colors) + " colours of " + std::to_string(n_colored) + " coloured columns to " + outfile,
               LogLevel::MAJOR);
+    return 0;
+}
+
+// sbwt compress-colors: an "SBWTCOL1" or "SBWTCOL2" colour file of the index -> the "SBWTCOL3" file that
+// `sbwt build-colors --compress` writes for the same colouring
+int compress_colors_main(int argc, char **argv) {
+    set_log_level(LogLevel::MINOR);
+    Options opts({
+        {"index-file", 'i', true, "Index input file.", ""},
+        {"colors-file", 'c', true, "Colour file of the index (sbwt build-colors, with or without --wide).", ""},
+        {"out-file", 'o', true, "Output colour-set file.", ""},
+        {"gpu", 0, true, "HIP device to run on.", "0"},
+        {"help", 'h', false, "Print usage", ""},
+    });
+    opts.parse(argc, argv);
+    if (argc == 1 || opts.count("help")) {
+        std::cerr << opts.help(argv[0], "Deduplicate the colour sets of a colour file: one id per column and a table of the distinct sets.") << std::endl;
+        exit(1);
+    }
+    const string indexfile = opts.get("index-file"), colorsfile = opts.get("colors-file"), outfile = opts.get("out-file");
+    check_readable(indexfile);
+    check_readable(colorsfile);
+    check_writable(outfile);
+    set_default_device(atoi(opts.get("gpu").c_str()));
+    plain_matrix_sbwt_t index;
+    load_plain_matrix(indexfile, index);
+    int64_t n_columns = 0, n_colors = 0, ck = 0, words = 1;
+    if (sbwthost_colors_read_wide(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, nullptr, 0) != 0)
+        throw std::runtime_error(sbwthost_last_error());
+    if (n_columns != index.number_of_subsets() || ck != index.get_k())
+        throw std::runtime_error("Error: " + colorsfile + " colours an index of " + std::to_string(n_columns) + " columns at k = " +
+                                 std::to_string(ck) + ", " + indexfile + " has " + std::to_string(index.number_of_subsets()) +
+                                 " columns at k = " + std::to_string(index.get_k()));
+    ColorsHandle col;
+    {
+        vector<uint64_t> rows((size_t)(n_columns * words));
+        if (sbwthost_colors_read_wide(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, rows.data(), n_columns * words) != 0)
+            throw std::runtime_error(sbwthost_last_error());
+        colors_check(sbwtgpu_colors_create_wide(index.device_handle(), (int)n_colors, rows.data(), &col.h));
+    }
+    compress_and_write(col.h, outfile);
     return 0;
 }
 
@@ -1049,16 +1128,13 @@ int pseudoalign_main(int argc, char **argv) {
     if (batch_bases < 1) batch_bases = 1;
     plain_matrix_sbwt_t index;
     load_plain_matrix(indexfile, index);
-    // the colour file's magic says which calls it goes through: "SBWTCOL2" the wide ones, anything else where it always went
-    bool wide = false;
-    {
-        std::ifstream in(colorsfile, std::ios::binary);
-        char magic[8] = {0};
-        in.read(magic, 8);
-        wide = in.gcount() == 8 && memcmp(magic, "SBWTCOL2", 8) == 0;
-    }
-    int64_t n_columns = 0, n_colors = 0, ck = 0, words = 1;
-    if ((wide ? sbwthost_colors_read_wide(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, nullptr, 0)
+    // the colour file's magic says which calls it goes through: "SBWTCOL2" the wide ones, "SBWTCOL3" the colour-set ones
+    // (whose records are the wide ones'), anything else where it always went
+    const bool sets = file_has_magic(colorsfile, "SBWTCOL3");
+    const bool wide = sets || file_has_magic(colorsfile, "SBWTCOL2");
+    int64_t n_columns = 0, n_colors = 0, ck = 0, words = 1, n_sets = 0;
+    if (sets ? sbwthost_colorsets_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, &n_sets, nullptr, 0, nullptr, 0) != 0 :
+        (wide ? sbwthost_colors_read_wide(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, nullptr, 0)
               : sbwthost_colors_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, nullptr, 0)) != 0)
         throw std::runtime_error(sbwthost_last_error());
     if (n_columns != index.number_of_subsets() || ck != index.get_k())
@@ -1066,7 +1142,15 @@ int pseudoalign_main(int argc, char **argv) {
                                  std::to_string(ck) + ", " + indexfile + " has " + std::to_string(index.number_of_subsets()) +
                                  " columns at k = " + std::to_string(index.get_k()));
     ColorsHandle col;
-    {
+    ColorSetsHandle cset;
+    if (sets) {
+        vector<uint32_t> ids((size_t)n_columns);
+        vector<uint64_t> table((size_t)(n_sets * words));
+        if (sbwthost_colorsets_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, &n_sets, ids.data(), n_columns, table.data(),
+                                    n_sets * words) != 0)
+            throw std::runtime_error(sbwthost_last_error());
+        colors_check(sbwtgpu_colorsets_create(index.device_handle(), (int)n_colors, ids.data(), n_sets, table.data(), &cset.h));
+    } else {
         vector<uint64_t> rows((size_t)(n_columns * words));
         if ((wide ? sbwthost_colors_read_wide(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, rows.data(), n_columns * words)
                   : sbwthost_colors_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, rows.data(), n_columns)) != 0)
@@ -1095,8 +1179,12 @@ int pseudoalign_main(int argc, char **argv) {
         if (wide) {
             wrec.resize((size_t)n_reads);
             wcol.resize((size_t)(n_reads * words));
-            colors_check(sbwtgpu_pseudoalign_wide_batch(col.h, bases.data(), read_off.data(), n_reads, strands, threshold_ppm, denominator,
-                                                        wrec.data(), wcol.data(), nullptr));
+            if (sets)
+                colors_check(sbwtgpu_pseudoalign_sets_batch(cset.h, bases.data(), read_off.data(), n_reads, strands, threshold_ppm,
+                                                            denominator, wrec.data(), wcol.data(), nullptr));
+            else
+                colors_check(sbwtgpu_pseudoalign_wide_batch(col.h, bases.data(), read_off.data(), n_reads, strands, threshold_ppm,
+                                                            denominator, wrec.data(), wcol.data(), nullptr));
             for (int64_t r = 0; r < n_reads; r++) {
                 append_int(total_reads++, text);
                 for (int64_t w = 0; w < words; w++) {
@@ -1128,7 +1216,7 @@ int pseudoalign_main(int argc, char **argv) {
     return 0;
 }
 
-const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "set-op", "read-hits", "build-colors", "pseudoalign"};
+const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "set-op", "read-hits", "build-colors", "compress-colors", "pseudoalign"};
 
 void print_help(char **argv) {
     std::cerr << "Available commands: " << std::endl;
@@ -1162,6 +1250,7 @@ int main(int argc, char **argv) {   // sbwt.cpp:19-57
         else if (command == "set-op") return set_op_main(argc, argv);
         else if (command == "read-hits") return read_hits_main(argc, argv);
         else if (command == "build-colors") return build_colors_main(argc, argv);
+        else if (command == "compress-colors") return compress_colors_main(argc, argv);
         else if (command == "pseudoalign") return pseudoalign_main(argc, argv);
         else throw std::runtime_error("Invalid command: " + command);
     } catch (const std::runtime_error &e) {

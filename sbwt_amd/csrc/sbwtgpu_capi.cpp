@@ -24,6 +24,7 @@
 #include "sbwt_setops.h"
 #include "sbwt_readhits.h"
 #include "sbwt_colors.h"
+#include "sbwt_colorsets.h"
 
 namespace {
 
@@ -2799,6 +2800,13 @@ struct sbwtgpu_colors {
     int words = 1;                      // 64-bit words per row: ceil(n_colors / 64)
     unsigned long long *d_rows = nullptr;
 };
+// deduplicated colour sets (sbwt_colorsets.hip): `base` binds the object to its index as a colours object is bound (no rows)
+struct sbwtgpu_colorsets {
+    sbwtgpu_colors base;
+    int64_t n_sets = 0, n_colored = 0;
+    unsigned *d_ids = nullptr;
+    unsigned long long *d_table = nullptr;
+};
 
 static int colors_check_index(const sbwtgpu_index *idx) {
     if (idx->h.n_nodes >= ((int64_t)1 << 31))
@@ -3056,10 +3064,10 @@ int sbwtgpu_pseudoalign_wide_dev(const sbwtgpu_colors *c, const char *d_bases, i
 // flight on the parked slots of the search pipeline.  Bases and offsets go down; records, and counts if asked for, come back.
 // wide_colors != NULL: the wide query -- `out` holds 8-byte records (sbwtgpu_read_found) and wide_colors the reads' colour
 // words, 8 + 8 words bytes per read instead of 16; a chunk then also ends where its results would outgrow what 2^24 reads of
-// 64 colours with counts bring back.
+// 64 colours with counts bring back.  sets != NULL: the wide query over a colour-set object, whose `base` is c.
 static int colors_host_batch(const sbwtgpu_colors *c, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
                              int color, int threshold_ppm, int denominator, void *out, uint64_t *wide_colors, int32_t *counts,
-                             int64_t *n_windows, int64_t *n_hit) {
+                             int64_t *n_windows, int64_t *n_hit, const sbwtgpu_colorsets *sets = nullptr) {
     const sbwtgpu_index *idx = c->idx;
     if (n_windows) *n_windows = 0;
     if (n_hit) *n_hit = 0;
@@ -3117,7 +3125,11 @@ static int colors_host_batch(const sbwtgpu_colors *c, const char *bases, const i
             return fail(SBWTGPU_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
         int r2;
         const int64_t *d_roff = (const int64_t *)(P.d_mem + o_roff);
-        if (wide_colors) {
+        if (sets) {
+            r2 = sbwtgpu_pseudoalign_sets_dev(sets, P.d_mem, nb, d_roff, nr, strands, threshold_ppm, denominator,
+                                              (sbwtgpu_read_found *)(P.d_mem + o_rec), (uint64_t *)(P.d_mem + o_col),
+                                              counts ? (int32_t *)(P.d_mem + o_cnt) : nullptr, P.d_mem + o_ws, ws_bytes, P.st);
+        } else if (wide_colors) {
             r2 = sbwtgpu_pseudoalign_wide_dev(c, P.d_mem, nb, d_roff, nr, strands, threshold_ppm, denominator,
                                               (sbwtgpu_read_found *)(P.d_mem + o_rec), (uint64_t *)(P.d_mem + o_col),
                                               counts ? (int32_t *)(P.d_mem + o_cnt) : nullptr, P.d_mem + o_ws, ws_bytes, P.st);
@@ -3201,6 +3213,200 @@ int sbwtgpu_pseudoalign_wide_batch(const sbwtgpu_colors *c, const char *bases, c
     if (n_reads > 0 && (!out || !colors_out)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
     return colors_host_batch(c, bases, read_off, n_reads, strands, 0, threshold_ppm, denominator, out, colors_out, counts_or_null,
                              nullptr, nullptr);
+}
+
+// ---- deduplicated colour sets (sbwt_colorsets.hip) -----------------------------------------------------
+static int colorsets_check(const sbwtgpu_colorsets *s) {
+    if (!s) return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set object is NULL");
+    return colors_check(&s->base);
+}
+
+static sbwtgpu_colorsets *colorsets_new(const sbwtgpu_index *idx, int n_colors) {
+    sbwtgpu_colorsets *s = new (std::nothrow) sbwtgpu_colorsets();
+    if (!s) return nullptr;
+    s->base.idx = idx;
+    s->base.device = idx->device;
+    s->base.n_nodes = idx->h.n_nodes;
+    s->base.k = idx->h.k;
+    s->base.n_colors = n_colors;
+    s->base.words = (n_colors + 63) / 64;
+    return s;
+}
+
+// n_colored = the ids that are not 0
+static hipError_t colorsets_count(sbwtgpu_colorsets *s, hipStream_t st) {
+    DevBuf count;
+    unsigned long long h = 0;
+    hipError_t e = count.alloc(8);
+    if (e == hipSuccess) e = hipMemsetAsync(count.p, 0, 8, st);
+    if (e == hipSuccess) {
+        sbwt_launch_cs_count(s->d_ids, s->base.n_nodes, static_cast<unsigned long long *>(count.p), st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, count.p, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    s->n_colored = (int64_t)h;
+    return e;
+}
+
+static int colorsets_hip_failed(sbwtgpu_colorsets *s, hipError_t e) {
+    (void)hipGetLastError();
+    sbwtgpu_colorsets_destroy(s);
+    return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "colour sets: %s", hipGetErrorString(e));
+}
+
+int sbwtgpu_colorsets_compress(const sbwtgpu_colors *c, sbwtgpu_colorsets **out) {
+    if (!c || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    const int rc = colors_check(c);
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(c->device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", c->device);
+    sbwtgpu_colorsets *s = colorsets_new(c->idx, c->n_colors);
+    if (!s) return fail(SBWTGPU_ERR_OOM, "out of host memory");
+    Stream st;
+    long long n_sets = 0;
+    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = sbwt_colorsets_compress(c->d_rows, c->n_nodes, c->words, &s->d_ids, &s->d_table, &n_sets, st.s);
+    s->n_sets = n_sets;
+    if (e == hipSuccess) e = colorsets_count(s, st.s);
+    if (e != hipSuccess) return colorsets_hip_failed(s, e);
+    *out = s;
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_colorsets_create(const sbwtgpu_index *idx, int n_colors, const uint32_t *ids, int64_t n_sets, const uint64_t *table,
+                             sbwtgpu_colorsets **out) {
+    if (!idx || !out || !ids || !table) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    const int rc = colors_check_index(idx);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_colors < 1 || n_colors > SBWTGPU_MAX_COLORS)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "n_colors must be in 1 .. %d, not %d", SBWTGPU_MAX_COLORS, n_colors);
+    if (n_sets < 1 || n_sets > (int64_t)0xFFFFFFFFll)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "n_sets must be in 1 .. 2^32 - 1, not %lld (row 0, the empty set, is always there)", (long long)n_sets);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", idx->device);
+    sbwtgpu_colorsets *s = colorsets_new(idx, n_colors);
+    if (!s) return fail(SBWTGPU_ERR_OOM, "out of host memory");
+    s->n_sets = n_sets;
+    const size_t id_bytes = (size_t)s->base.n_nodes * 4, table_bytes = (size_t)n_sets * (size_t)s->base.words * 8;
+    Stream st;
+    unsigned long long report[2] = {~0ull, ~0ull};
+    hipError_t e = hipMalloc((void **)&s->d_ids, id_bytes + 16);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_table, table_bytes);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_ids, ids, id_bytes, hipMemcpyHostToDevice, st.s);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_table, table, table_bytes, hipMemcpyHostToDevice, st.s);
+    if (e == hipSuccess) e = sbwt_colorsets_validate(idx->view(), s->d_ids, s->d_table, n_sets, n_colors, report, st.s);
+    if (e == hipSuccess && report[0] == ~0ull && report[1] == ~0ull) e = colorsets_count(s, st.s);
+    if (e != hipSuccess) return colorsets_hip_failed(s, e);
+    if (report[1] != ~0ull || report[0] != ~0ull) {
+        sbwtgpu_colorsets_destroy(s);
+        const long long row = (long long)(report[1] >> 8);
+        if (report[1] == ~0ull)
+            return fail(SBWTGPU_ERR_INVALID_ARG, "colour sets: the id of column %lld is not below n_sets = %lld", (long long)report[0],
+                        (long long)n_sets);
+        switch ((int)(report[1] & 255)) {
+        case SBWT_CS_ROW0_NOT_ZERO:
+            return fail(SBWTGPU_ERR_INVALID_ARG, "colour sets: row 0 of the table is not all zero (id 0 is the empty set)");
+        case SBWT_CS_ZERO_ROW:
+            return fail(SBWTGPU_ERR_INVALID_ARG, "colour sets: row %lld of the table is all zero (only row 0 may be)", row);
+        default:
+            return fail(SBWTGPU_ERR_INVALID_ARG, "colour sets: row %lld of the table has a bit >= n_colors = %d", row, n_colors);
+        }
+    }
+    *out = s;
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_colorsets_expand(const sbwtgpu_colorsets *s, sbwtgpu_colors **out) {
+    if (!s || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    int rc = colorsets_check(s);
+    if (rc != SBWTGPU_OK) return rc;
+    sbwtgpu_colors *c = nullptr;
+    if ((rc = colors_create_checked(s->base.idx, s->base.n_colors, nullptr, &c)) != SBWTGPU_OK) return rc;
+    DeviceGuard guard(s->base.device);
+    Stream st;
+    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
+    if (e == hipSuccess) {
+        sbwt_launch_cs_expand(s->d_ids, s->d_table, s->base.n_nodes, s->base.words, c->d_rows, st.s);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st.s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        sbwtgpu_colors_destroy(c);
+        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "colour sets: %s", hipGetErrorString(e));
+    }
+    *out = c;
+    return SBWTGPU_OK;
+}
+
+void sbwtgpu_colorsets_destroy(sbwtgpu_colorsets *s) {
+    if (!s) return;
+    DeviceGuard guard(s->base.device);
+    if (s->d_ids) (void)hipFree(s->d_ids);
+    if (s->d_table) (void)hipFree(s->d_table);
+    delete s;
+}
+
+int sbwtgpu_colorsets_info(const sbwtgpu_colorsets *s, int64_t *n_columns, int64_t *k, int32_t *n_colors, int32_t *words, int64_t *n_sets,
+                           int64_t *n_colored_columns, int64_t *device_bytes) {
+    if (!s) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    if (n_columns) *n_columns = s->base.n_nodes;
+    if (k) *k = s->base.k;
+    if (n_colors) *n_colors = s->base.n_colors;
+    if (words) *words = s->base.words;
+    if (n_sets) *n_sets = s->n_sets;
+    if (n_colored_columns) *n_colored_columns = s->n_colored;
+    if (device_bytes) *device_bytes = s->base.n_nodes * 4 + s->n_sets * (int64_t)s->base.words * 8;
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_colorsets_copy(const sbwtgpu_colorsets *s, uint32_t *ids_out, uint64_t *table_out) {
+    if (!s) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    DeviceGuard guard(s->base.device);
+    if (ids_out && s->base.n_nodes > 0) HIP_TRY(hipMemcpy(ids_out, s->d_ids, (size_t)s->base.n_nodes * 4, hipMemcpyDeviceToHost));
+    if (table_out) HIP_TRY(hipMemcpy(table_out, s->d_table, (size_t)s->n_sets * (size_t)s->base.words * 8, hipMemcpyDeviceToHost));
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_colorsets_dev(const sbwtgpu_colorsets *s, const uint32_t **d_ids, const uint64_t **d_table) {
+    if (!s) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    if (d_ids) *d_ids = reinterpret_cast<const uint32_t *>(s->d_ids);
+    if (d_table) *d_table = reinterpret_cast<const uint64_t *>(s->d_table);
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_pseudoalign_sets_dev(const sbwtgpu_colorsets *s, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                                 int64_t n_reads, int strands, int threshold_ppm, int denominator, sbwtgpu_read_found *d_out,
+                                 uint64_t *d_colors, int32_t *d_counts_or_null, void *d_ws, int64_t ws_bytes, void *stream) {
+    int rc = colorsets_check(s);
+    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_reads > 0 && (!d_out || !d_colors)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
+    const sbwtgpu_colors *c = &s->base;
+    return colors_dev_common(c, d_bases, total_bases, d_read_off, n_reads, strands, d_ws, ws_bytes, stream,
+                             [&](const int *res, const int *res2, const long long *ooff, SbwtPaHeader *, hipStream_t st) {
+                                 sbwt_launch_pa_reduce_sets(res, res2, ooff, n_reads, s->d_ids, s->d_table, c->n_nodes, s->n_sets, c->words,
+                                                            c->n_colors, threshold_ppm, denominator, reinterpret_cast<SbwtReadFound *>(d_out),
+                                                            reinterpret_cast<unsigned long long *>(d_colors), d_counts_or_null, st);
+                             });
+}
+
+int sbwtgpu_pseudoalign_sets_batch(const sbwtgpu_colorsets *s, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
+                                   int threshold_ppm, int denominator, sbwtgpu_read_found *out, uint64_t *colors_out,
+                                   int32_t *counts_or_null) {
+    int rc = colorsets_check(s);
+    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_reads > 0 && (!out || !colors_out)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    return colors_host_batch(&s->base, bases, read_off, n_reads, strands, 0, threshold_ppm, denominator, out, colors_out, counts_or_null,
+                             nullptr, nullptr, s);
 }
 
 // ---- set operations (sbwt_setops.hip) ---------------------------------------------------------------

@@ -17,7 +17,7 @@ EXPORTED_SYMBOLS = [
     "sbwthost_file_write", "sbwthost_file_read", "sbwthost_file_free", "sbwthost_file_info",
     "sbwthost_file_words", "sbwthost_file_precalc", "sbwthost_read_sequences", "sbwthost_read_sequences_chunked", "sbwthost_free", "sbwthost_write_file",
     "sbwthost_rank_batch", "sbwthost_colors_write", "sbwthost_colors_read",
-    "sbwthost_colors_write_wide", "sbwthost_colors_read_wide",
+    "sbwthost_colors_write_wide", "sbwthost_colors_read_wide", "sbwthost_colorsets_write", "sbwthost_colorsets_read",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -58,6 +58,9 @@ def lib() -> C.CDLL:
     L.sbwthost_colors_read.argtypes = [C.c_char_p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp, i64]
     L.sbwthost_colors_write_wide.argtypes = [C.c_char_p, vp, i64, i64, i64]
     L.sbwthost_colors_read_wide.argtypes = [C.c_char_p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp, i64]
+    L.sbwthost_colorsets_write.argtypes = [C.c_char_p, vp, vp, i64, i64, i64, i64]
+    L.sbwthost_colorsets_read.argtypes = [C.c_char_p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
+                                          vp, i64, vp, i64]
     _lib = L
     return L
 
@@ -226,3 +229,30 @@ def colors_read_wide(path: str):
                                    rows.size) != 0:
         raise RuntimeError(_err())
     return rows, nc.value, k.value
+
+
+def colorsets_write(path: str, ids, table, n_colors: int, k: int) -> None:
+    """Writes a colour-set object (ids uint32[n_columns], table uint64[n_sets, ceil(n_colors / 64)]) as an "SBWTCOL3" file
+    (include/sbwthost.h); an object that breaks an invariant is refused."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    table = np.ascontiguousarray(table, dtype=np.uint64)
+    words = (n_colors + 63) // 64
+    if ids.ndim != 1 or table.ndim != 2 or (1 <= n_colors <= 4096 and table.shape[1] != words):
+        raise RuntimeError("ids of shape %s and a table of shape %s, %d colours need %d words a row" % (ids.shape, table.shape, n_colors, words))
+    if lib().sbwthost_colorsets_write(path.encode(), ids.ctypes.data if len(ids) else None, table.ctypes.data if table.size else None,
+                                      len(ids), n_colors, k, table.shape[0]) != 0:
+        raise RuntimeError(_err())
+
+
+def colorsets_read(path: str):
+    """(ids uint32[n_columns], table uint64[n_sets, words_per_row], n_colors, k) of an "SBWTCOL3" colour-set file."""
+    L = lib()
+    n, nc, k, w, ns = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    sizes = (C.byref(n), C.byref(nc), C.byref(k), C.byref(w), C.byref(ns))
+    if L.sbwthost_colorsets_read(path.encode(), *sizes, None, 0, None, 0) != 0:
+        raise RuntimeError(_err())
+    ids = np.empty(n.value, dtype=np.uint32)
+    table = np.empty((ns.value, w.value), dtype=np.uint64)
+    if L.sbwthost_colorsets_read(path.encode(), *sizes, ids.ctypes.data if n.value else None, n.value, table.ctypes.data, table.size) != 0:
+        raise RuntimeError(_err())
+    return ids, table, nc.value, k.value

@@ -11,7 +11,13 @@ Prints one JSON line:
            colours 0, 70 and 130 of 192 (3 words a row), as colours 0, 1 and 2 of 64 through the wide call, and through the
            64-colour call; the three calls alternate, device events around each, medians of --steps
 
-  python tools/pseudoalign_bench.py [--reads N] [--host-reads N] [--steps 7] [--warmup 2] [--wide]
+  sets     (--sets, instead of the above) colour-set objects beside the wide objects they were compressed from: the 64-colour
+           call, wide and sets at 64 colours, at 192 (the strains on colours 0, 70, 130) and at 4096 (colours 0, 2000, 4095: the
+           6.5 GB matrix is built, compressed, then timed); the seven calls alternate, device events around each, median and
+           min-max of --steps; compress time, n_sets and device bytes per object; the gate of DESIGN.md section 15 at 192 and
+           4096 colours: median(sets) <= median(wide) + (max - min of that wide call's timings)
+
+  python tools/pseudoalign_bench.py [--reads N] [--host-reads N] [--steps 7] [--warmup 2] [--wide | --sets]
 Kernel names and times: run it under `rocprofv3 --kernel-trace --stats -d DIR -- python tools/pseudoalign_bench.py ...`."""
 import argparse
 import json
@@ -34,6 +40,7 @@ def main():
     ap.add_argument("--host-steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--wide", action="store_true")
+    ap.add_argument("--sets", action="store_true")
     args = ap.parse_args()
     import torch
     import bench
@@ -48,6 +55,9 @@ def main():
     res = {"config": 2, "k": k, "n_nodes": idx.n_nodes, "image_level": idx.image_level, "n_colors": len(genomes)}
     if args.wide:
         print(json.dumps(wide_leg(args, torch, bench, capi, genomes, idx, k, dev, res)))
+        return
+    if args.sets:
+        print(json.dumps(sets_leg(args, torch, bench, capi, genomes, idx, k, dev, res)))
         return
 
     # ---- colouring: one strain per colour, each genome one sequence ----
@@ -217,6 +227,94 @@ def wide_leg(args, torch, bench, capi, genomes, idx, k, dev, res):
         del pws, rec16, rec8, colw
     rows["results_agree"] = True
     res["wide"] = rows
+    return res
+
+
+def sets_leg(args, torch, bench, capi, genomes, idx, k, dev, res):
+    """The same reads through sbwtgpu_pseudoalign_dev (64 colours), and through sbwtgpu_pseudoalign_wide_dev and
+    sbwtgpu_pseudoalign_sets_dev at 64, 192 and 4096 colours, each colour-set object compressed from the wide object beside it."""
+    strain_colors = {64: (0, 1, 2), 192: (0, 70, 130), 4096: (0, 2000, 4095)}
+    objs = {"narrow64": (capi.Colors.create(idx, 64), strain_colors[64])}
+    res["objects"] = {}
+    for nc, ids in strain_colors.items():
+        wide = capi.WideColors.create(idx, nc)
+        for c, g in zip(ids, genomes):
+            wide.add_sequences(c, g, np.array([0, len(g)], dtype=np.int64))
+        if nc == 64:
+            for c, g in zip(ids, genomes):
+                objs["narrow64"][0].add_sequences(c, g, np.array([0, len(g)], dtype=np.int64))
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        sets = capi.ColorSets.from_colors(wide)                   # (synchronous: the host clock covers the whole call)
+        compress_ms = (time.perf_counter() - t0) * 1e3
+        info = sets.info()
+        objs["wide%d" % nc], objs["sets%d" % nc] = (wide, ids), (sets, ids)
+        res["objects"][str(nc)] = {"n_colors": nc, "words": wide.words, "strain_colors": list(ids), "wide_bytes": 8 * idx.n_nodes * wide.words,
+                                   "sets_bytes": info["device_bytes"], "n_sets": info["n_sets"], "n_colored_columns": info["n_colored_columns"],
+                                   "compress_ms": round(compress_ms, 3)}
+    stream = torch.cuda.current_stream(dev)
+    n, L = args.reads, bench.READ_LEN
+    bases_t = bench.gpu_reads(genomes, n, 12345, dev)
+    T = bases_t.numel()
+    off_t = torch.arange(n + 1, dtype=torch.int64, device=dev) * L
+    W = n * (L - k + 1)
+    res.update({"reads": n, "read_len": L, "kmers": W})
+    rows, gate = {}, {}
+    rec16 = torch.empty((n, 2), dtype=torch.int64, device=dev)
+    rec8 = torch.empty(n, dtype=torch.int64, device=dev)
+    colw = {words: torch.empty((n, words), dtype=torch.int64, device=dev) for words in (1, 3, 64)}     # (shared by the calls of a width)
+    for both in (False, True):
+        st = 2 if both else 1
+        need = capi.pseudoalign_workspace_bytes(T, n, both)
+        pws = torch.zeros(need, dtype=torch.uint8, device=dev)
+        calls = {"narrow64": lambda: objs["narrow64"][0].pseudoalign_dev(bases_t.data_ptr(), T, off_t.data_ptr(), n, rec16.data_ptr(), 0,
+                                                                        pws.data_ptr(), need, both, 1_000_000, 0, stream.cuda_stream)}
+        for name in objs:
+            if name != "narrow64":
+                calls[name] = (lambda name=name: objs[name][0].pseudoalign_dev(
+                    bases_t.data_ptr(), T, off_t.data_ptr(), n, rec8.data_ptr(), colw[objs[name][0].words].data_ptr(), 0, pws.data_ptr(), need,
+                    both, 1_000_000, 0, stream.cuda_stream))
+        times = {name: [] for name in calls}
+        found, strain_sets = {}, {}
+        for s in range(args.warmup + args.steps):               # the seven calls alternate
+            for name, call in calls.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                call()
+                e1.record(stream)
+                e1.synchronize()
+                if s >= args.warmup:
+                    times[name].append(e0.elapsed_time(e1))
+                if s == 0:                                      # what each call found: all must agree
+                    if name == "narrow64":
+                        h = rec16.cpu().numpy().view(capi.PSEUDOALIGNMENT_DTYPE).reshape(n)
+                        found[name], words = h["n_found"].copy(), h["colors"].reshape(n, 1)
+                    else:
+                        found[name] = rec8.cpu().numpy().view(capi.READ_FOUND_DTYPE).reshape(n)["n_found"].copy()
+                        words = colw[objs[name][0].words].cpu().numpy().view(np.uint64)
+                    strain_sets[name] = np.stack([(words[:, c >> 6] >> np.uint64(c & 63)) & np.uint64(1) for c in objs[name][1]], axis=1)
+                    del words
+        for name in calls:
+            if not (np.array_equal(found[name], found["narrow64"]) and np.array_equal(strain_sets[name], strain_sets["narrow64"])):
+                raise SystemExit("%s and the 64-colour call disagree" % name)
+        for name, t in times.items():
+            med = float(np.median(t))
+            rows["%s_strands%d" % (name, st)] = {
+                "median_ms": round(med, 3), "min_ms": round(min(t), 3), "max_ms": round(max(t), 3), "calls": len(t),
+                "G_kmers_per_s": round(W / med / 1e6, 2), "n_found": int(found[name].sum(dtype=np.int64))}
+        for nc in strain_colors:
+            wide, sets = rows["wide%d_strands%d" % (nc, st)], rows["sets%d_strands%d" % (nc, st)]
+            rows["sets%d_over_wide%d_strands%d" % (nc, nc, st)] = round(sets["median_ms"] / wide["median_ms"], 3)
+            if nc != 64:                                        # (at 64 colours only reported)
+                bound = wide["median_ms"] + (wide["max_ms"] - wide["min_ms"])
+                gate["%d_strands%d" % (nc, st)] = {"sets_median_ms": sets["median_ms"], "wide_median_ms": wide["median_ms"],
+                                                   "wide_spread_ms": round(wide["max_ms"] - wide["min_ms"], 3), "bound_ms": round(bound, 3),
+                                                   "passed": bool(sets["median_ms"] <= bound)}
+        del pws
+    rows["results_agree"] = True
+    res["sets"] = rows
+    res["gate"] = gate
+    res["gate_passed"] = all(g["passed"] for g in gate.values())
     return res
 
 
