@@ -677,6 +677,49 @@ int  sbwtgpu_pseudoalign_sets_dev(const sbwtgpu_colorsets *s, const char *d_base
                                   sbwtgpu_read_found *d_out, uint64_t *d_colors, int32_t *d_counts_or_null,
                                   void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- colour sets built one colour at a time: the builder ----
+ * sbwtgpu_colors_create_wide -> sbwtgpu_colors_add_batch x N -> sbwtgpu_colorsets_compress holds an n x W x 8-byte matrix on the
+ * device before the 4-byte ids come out.  A colour-set BUILDER takes the same adds and holds only the object it is making.
+ * It is bound to one index of n columns (n < 2^31, not rank-only) and one n_colors in 1 .. SBWTGPU_MAX_COLORS;
+ * W = ceil(n_colors / 64) is fixed for its life.  Each colour is NEW, OPEN (at most one at a time) or CLOSED.
+ * add_batch:
+ *   - It is sbwtgpu_colors_add_batch in every respect but the target: the same search rule, strands, meaning of n_windows and
+ *     n_hit_windows, chunking by "pseudoalign_chunk_bases" on the parked pipeline slots, and SBWTGPU_ERR_READ_TOO_LONG.
+ *   - A hit on column j MARKS j for `color`.  If `color` is open, the marks accumulate.  If another colour is open, that
+ *     colour is closed first and `color` opens.
+ *   - A closed colour is refused (SBWTGPU_ERR_INVALID_ARG): the sequences of one colour must come in consecutive calls.
+ *   - Closing a colour c merges its marks: every marked column's set becomes its old set + {c}.
+ *   - Within an open colour, adding is idempotent and order-independent.  Colours may be opened in any order, and colours
+ *     may be left out.
+ * finish:
+ *   - It closes the open colour and returns a colour-set object in canonical form: byte for byte what
+ *     sbwtgpu_colorsets_compress returns for a wide object coloured by the same adds.
+ *   - The builder is consumed: every later call but destroy is refused.
+ * info:
+ *   - Before finish, it reports the state as of the last closed colour.  per_color[c] is the number of columns marked when c
+ *     was closed, and 0 for new or open colours.  n_colored_columns counts columns with a non-empty set.  device_bytes is
+ *     what the builder holds now.
+ * Memory: 4 n bytes of ids, n / 8 of marks (in 64-bit words) and cap x (8 W + 4) bytes for a table of cap rows with their
+ * column counts; cap starts at 64 rows and doubles when the sets outgrow it (a new allocation, a device copy, a free).
+ * While a colour is closed: 4 bytes per set.  While finish runs: 1 + 4 bytes per column, 4 per set and the result's table.
+ * Refusals (SBWTGPU_ERR_INVALID_ARG with a message that names the cause): those of the colour calls (a rank-only index, an
+ * index of 2^31 columns or more, n_colors, color or strands out of range, NULL pointers).  SBWTGPU_ERR_OOM or SBWTGPU_ERR_HIP --
+ * when the table grows, for one -- leaves the index usable and the builder broken: every later call but destroy then returns
+ * SBWTGPU_ERR_INVALID_ARG with "builder is broken".
+ * Concurrency: a builder is not thread-safe.  The index must outlive it. */
+typedef struct sbwtgpu_colorsets_builder sbwtgpu_colorsets_builder;
+
+int  sbwtgpu_colorsets_builder_create(const sbwtgpu_index *idx, int n_colors, sbwtgpu_colorsets_builder **out);
+int  sbwtgpu_colorsets_builder_add_batch(sbwtgpu_colorsets_builder *b, int color, const char *bases, const int64_t *read_off,
+                                         int64_t n_reads, int strands, int64_t *n_windows, int64_t *n_hit_windows);
+/* every output may be NULL; per_color: n_colors entries */
+int  sbwtgpu_colorsets_builder_info(const sbwtgpu_colorsets_builder *b, int64_t *n_columns, int64_t *k, int32_t *n_colors,
+                                    int32_t *words, int64_t *n_sets, int64_t *n_colored_columns, int64_t *per_color,
+                                    int64_t *device_bytes);
+/* the object is independent of the builder (destroy it with sbwtgpu_colorsets_destroy) */
+int  sbwtgpu_colorsets_builder_finish(sbwtgpu_colorsets_builder *b, sbwtgpu_colorsets **out);
+void sbwtgpu_colorsets_builder_destroy(sbwtgpu_colorsets_builder *b);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,8 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_colorsets_compress", "sbwtgpu_colorsets_create", "sbwtgpu_colorsets_expand", "sbwtgpu_colorsets_destroy",
     "sbwtgpu_colorsets_info", "sbwtgpu_colorsets_copy", "sbwtgpu_colorsets_dev", "sbwtgpu_pseudoalign_sets_batch",
     "sbwtgpu_pseudoalign_sets_dev",
+    "sbwtgpu_colorsets_builder_create", "sbwtgpu_colorsets_builder_add_batch", "sbwtgpu_colorsets_builder_info",
+    "sbwtgpu_colorsets_builder_finish", "sbwtgpu_colorsets_builder_destroy",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -260,6 +262,13 @@ def lib() -> C.CDLL:
         L.sbwtgpu_colorsets_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         L.sbwtgpu_pseudoalign_sets_batch.argtypes = [vp, vp, vp, i64, ci, ci, ci, vp, vp, vp]
         L.sbwtgpu_pseudoalign_sets_dev.argtypes = [vp, vp, i64, vp, i64, ci, ci, ci, vp, vp, vp, vp, i64, vp]
+        L.sbwtgpu_colorsets_builder_create.argtypes = [vp, ci, C.POINTER(vp)]
+        L.sbwtgpu_colorsets_builder_add_batch.argtypes = [vp, ci, vp, vp, i64, ci, C.POINTER(i64), C.POINTER(i64)]
+        L.sbwtgpu_colorsets_builder_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                     C.POINTER(i64), C.POINTER(i64), vp, C.POINTER(i64)]
+        L.sbwtgpu_colorsets_builder_finish.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_colorsets_builder_destroy.argtypes = [vp]
+        L.sbwtgpu_colorsets_builder_destroy.restype = None
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -1025,6 +1034,78 @@ class ColorSets:
         """sbwtgpu_pseudoalign_sets_dev (raw device pointers, as WideColors.pseudoalign_dev)."""
         _check(lib().sbwtgpu_pseudoalign_sets_dev(self._h, d_bases, total_bases, d_read_off, n_reads, 2 if both_strands else 1,
                                                   threshold_ppm, denominator, d_out, d_colors, d_counts or None, d_ws, ws_bytes, stream))
+
+
+class ColorSetsBuilder:
+    """Owns an sbwtgpu_colorsets_builder handle: colour sets made one colour at a time, without the wide matrix
+    (include/sbwtgpu.h, "the builder").  The sequences of one colour come in consecutive add calls; finish() gives the
+    ColorSets that ColorSets.from_colors gives for a WideColors coloured by the same adds, and consumes the builder.  Not
+    thread-safe.  The index is kept referenced."""
+
+    def __init__(self, handle, index: Index, n_colors: int):
+        self._h = handle
+        self.index, self.n_colors = index, n_colors
+        self.words = (n_colors + 63) // 64
+
+    @classmethod
+    def create(cls, index: Index, n_colors: int) -> "ColorSetsBuilder":
+        """An empty builder of n_colors colours (1 .. MAX_COLORS)."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_colorsets_builder_create(index.handle, n_colors, C.byref(h)))
+        return cls(h, index, n_colors)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        if self._h:
+            lib().sbwtgpu_colorsets_builder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def add_sequences(self, color: int, bases, read_off, both_strands: bool = False):
+        """sbwtgpu_colorsets_builder_add_batch: marks every k-mer of the sequences that the index holds for `color`, which
+        opens (closing the colour that was open); (n_windows, n_hit_windows)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        nw, nh = C.c_int64(0), C.c_int64(0)
+        _check(lib().sbwtgpu_colorsets_builder_add_batch(self._h, color, bases.ctypes.data, read_off.ctypes.data,
+                                                         max(len(read_off) - 1, 0), 2 if both_strands else 1, C.byref(nw), C.byref(nh)))
+        return nw.value, nh.value
+
+    def add_reads(self, color: int, reads: Sequence[bytes], both_strands: bool = False):
+        """The same for a list of byte strings."""
+        bases, off = concat_reads(reads)
+        return self.add_sequences(color, bases, off, both_strands)
+
+    def info(self) -> dict:
+        """The state as of the last closed colour: n_columns, k, n_colors, words, n_sets, n_colored_columns, per_color (the
+        columns marked when a colour was closed; 0 for new and open colours) and device_bytes."""
+        n, k, ns, ncc, db = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        nc, w = C.c_int32(), C.c_int32()
+        per = np.zeros(self.n_colors, dtype=np.int64)
+        _check(lib().sbwtgpu_colorsets_builder_info(self._h, C.byref(n), C.byref(k), C.byref(nc), C.byref(w), C.byref(ns), C.byref(ncc),
+                                                    per.ctypes.data, C.byref(db)))
+        return {"n_columns": n.value, "k": k.value, "n_colors": nc.value, "words": w.value, "n_sets": ns.value,
+                "n_colored_columns": ncc.value, "per_color": [int(x) for x in per], "device_bytes": db.value}
+
+    def finish(self) -> ColorSets:
+        """sbwtgpu_colorsets_builder_finish: closes the open colour and returns the canonical colour-set object."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_colorsets_builder_finish(self._h, C.byref(h)))
+        return ColorSets(h, self.index)
 
 
 def kernel_times() -> list:

@@ -5,10 +5,11 @@
 //   sbwt search -o <out> -i <index> -q <query> [-z]        (sbwt_search.cpp:151-157)
 //   sbwt matching-statistics -i <index> -q <query> -o <out> [-z] [--intervals]
 //               k-bounded matching statistics: one line per read, one token per base ("d", or "d,first,second")
-//   sbwt build-colors -i <index> -r <refs.txt> -o <colours> [--both-strands] [--wide | --compress]
+//   sbwt build-colors -i <index> -r <refs.txt> -o <colours> [--both-strands] [--wide | --compress [--stream]]
 //               one colour per listed reference file, set on the columns of the index's k-mers that the file holds
 //               (--wide: up to 4096 files, a colour file of several words per column; --compress: up to 4096 files, a
-//               colour-set file of one id per column and the distinct colour sets)
+//               colour-set file of one id per column and the distinct colour sets; --compress --stream: the same file, built
+//               one reference at a time without the wide matrix on the device)
 //   sbwt compress-colors -i <index> -c <colours> -o <colour sets>
 //               the colour-set file of a colour file written with or without --wide
 //   sbwt pseudoalign -i <index> -c <colours> -q <query> -o <out> [-z] [--threshold 0.7] [--all-kmers] [--both-strands]
@@ -925,6 +926,10 @@ struct ColorSetsHandle {
     sbwtgpu_colorsets *h = nullptr;
     ~ColorSetsHandle() { sbwtgpu_colorsets_destroy(h); }
 };
+struct ColorSetsBuilderHandle {
+    sbwtgpu_colorsets_builder *h = nullptr;
+    ~ColorSetsBuilderHandle() { sbwtgpu_colorsets_builder_destroy(h); }
+};
 
 // the first 8 bytes of a colour file say which calls it goes through
 bool file_has_magic(const string &file, const char *magic) {
@@ -934,21 +939,30 @@ bool file_has_magic(const string &file, const char *magic) {
     return in.gcount() == 8 && memcmp(got, magic, 8) == 0;
 }
 
-// compresses a colours object (sbwtgpu_colorsets_compress: the canonical form) and writes it as an "SBWTCOL3" file
-void compress_and_write(const sbwtgpu_colors *col, const string &outfile) {
-    ColorSetsHandle sets;
-    colors_check(sbwtgpu_colorsets_compress(col, &sets.h));
+// writes a colour-set object as an "SBWTCOL3" file; count_color >= 0: *count_out = the columns whose set holds that colour
+void write_colorsets(const sbwtgpu_colorsets *sets, const string &outfile, int count_color = -1, int64_t *count_out = nullptr) {
     int64_t n_columns = 0, ck = 0, n_sets = 0, n_colored = 0, bytes = 0;
     int32_t n_colors = 0, words = 0;
-    colors_check(sbwtgpu_colorsets_info(sets.h, &n_columns, &ck, &n_colors, &words, &n_sets, &n_colored, &bytes));
+    colors_check(sbwtgpu_colorsets_info(sets, &n_columns, &ck, &n_colors, &words, &n_sets, &n_colored, &bytes));
     vector<uint32_t> ids((size_t)n_columns);
     vector<uint64_t> table((size_t)(n_sets * words));
-    colors_check(sbwtgpu_colorsets_copy(sets.h, ids.data(), table.data()));
+    colors_check(sbwtgpu_colorsets_copy(sets, ids.data(), table.data()));
+    if (count_color >= 0 && count_out) {
+        *count_out = 0;
+        for (uint32_t id : ids) *count_out += (int64_t)((table[(size_t)id * words + (count_color >> 6)] >> (count_color & 63)) & 1u);
+    }
     if (sbwthost_colorsets_write(outfile.c_str(), ids.data(), table.data(), n_columns, n_colors, ck, n_sets) != 0)
         throw std::runtime_error(sbwthost_last_error());
     write_log("Wrote " + std::to_string(n_sets) + " colour sets of " + std::to_string(n_colors) + " colours over " +
                   std::to_string(n_colored) + " coloured columns (" + std::to_string(bytes) + " bytes on the device) to " + outfile,
               LogLevel::MAJOR);
+}
+
+// compresses a colours object (sbwtgpu_colorsets_compress: the canonical form) and writes it as an "SBWTCOL3" file
+void compress_and_write(const sbwtgpu_colors *col, const string &outfile) {
+    ColorSetsHandle sets;
+    colors_check(sbwtgpu_colorsets_compress(col, &sets.h));
+    write_colorsets(sets.h, outfile);
 }
 
 void load_plain_matrix(const string &indexfile, plain_matrix_sbwt_t &index) {
@@ -971,6 +985,7 @@ int build_colors_main(int argc, char **argv) {
         {"both-strands", 0, false, "Also colour the reverse complement of every k-mer (for indexes built with reverse complements).", ""},
         {"wide", 0, false, "Up to 4096 lines in the list; writes a wide colour file (several 64-bit words per column).", ""},
         {"compress", 0, false, "Up to 4096 lines in the list; writes a colour-set file (one id per column and the distinct colour sets).", ""},
+        {"stream", 0, false, "With --compress: merge one reference at a time into the colour sets, without the wide matrix on the device. The same file.", ""},
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
@@ -985,6 +1000,9 @@ int build_colors_main(int argc, char **argv) {
     check_readable(refsfile);
     const vector<string> refs = readlines(refsfile);
     const bool compress = opts.count("compress");
+    const bool stream = opts.count("stream");
+    if (stream && !compress)
+        throw std::runtime_error("Error: --stream builds a colour-set file and needs --compress (a colour file of rows is the matrix itself)");
     const bool wide = opts.count("wide") || compress;
     if (wide && (refs.empty() || refs.size() > SBWTGPU_MAX_COLORS))
         throw std::runtime_error("Error: " + refsfile + " lists " + std::to_string(refs.size()) + " files; a wide colour file holds 1 to " +
@@ -1001,9 +1019,12 @@ int build_colors_main(int argc, char **argv) {
     plain_matrix_sbwt_t index;
     load_plain_matrix(indexfile, index);
     ColorsHandle col;
-    if (wide) colors_check(sbwtgpu_colors_create_wide(index.device_handle(), (int)refs.size(), nullptr, &col.h));
+    ColorSetsBuilderHandle builder;
+    if (stream) colors_check(sbwtgpu_colorsets_builder_create(index.device_handle(), (int)refs.size(), &builder.h));
+    else if (wide) colors_check(sbwtgpu_colors_create_wide(index.device_handle(), (int)refs.size(), nullptr, &col.h));
     else colors_check(sbwtgpu_colors_create(index.device_handle(), (int)refs.size(), nullptr, &col.h));
     vector<int64_t> windows(refs.size(), 0), hit_windows(refs.size(), 0);
+    int open_color = -1;            // --stream: the colour that only finish closes
     for (size_t c = 0; c < refs.size(); c++) {
         seq_io::Reader reader(refs[c]);
         bool more = true;
@@ -1016,7 +1037,12 @@ int build_colors_main(int argc, char **argv) {
             const int64_t n_reads = (int64_t)read_off.size() - 1;
             if (n_reads <= 0) continue;
             int64_t w = 0, h = 0;
-            colors_check(sbwtgpu_colors_add_batch(col.h, (int)c, bases.data(), read_off.data(), n_reads, strands, &w, &h));
+            if (stream) {
+                colors_check(sbwtgpu_colorsets_builder_add_batch(builder.h, (int)c, bases.data(), read_off.data(), n_reads, strands, &w, &h));
+                open_color = (int)c;
+            } else {
+                colors_check(sbwtgpu_colors_add_batch(col.h, (int)c, bases.data(), read_off.data(), n_reads, strands, &w, &h));
+            }
             windows[c] += w;
             hit_windows[c] += h;
         }
@@ -1024,7 +1050,16 @@ int build_colors_main(int argc, char **argv) {
     int64_t n_columns = 0, ck = 0, n_colored = 0;
     int32_t n_colors = 0;
     vector<int64_t> per_color(refs.size(), 0);
-    if (wide) {
+    ColorSetsHandle streamed;
+    if (stream) {
+        // per_color of the closed colours; the last colour with sequences is still open, finish closes it, and the builder
+        // answers nothing afterwards: its columns are counted in the object that is written
+        colors_check(sbwtgpu_colorsets_builder_info(builder.h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, per_color.data(), nullptr));
+        colors_check(sbwtgpu_colorsets_builder_finish(builder.h, &streamed.h));
+        int64_t last = 0;
+        write_colorsets(streamed.h, outfile, open_color, &last);
+        if (open_color >= 0) per_color[(size_t)open_color] = last;
+    } else if (wide) {
         colors_check(sbwtgpu_colors_info_wide(col.h, &n_columns, &ck, &n_colors, &n_colored, per_color.data()));
     } else {
         sbwtgpu_colors_info_t info;
@@ -1035,6 +1070,7 @@ int build_colors_main(int argc, char **argv) {
     for (size_t c = 0; c < refs.size(); c++)
         std::cout << "colour " << c << ": " << windows[c] << " windows, " << hit_windows[c] << " hit windows, " << per_color[c]
                   << " coloured columns" << std::endl;
+    if (stream) return 0;
     if (compress) {
         compress_and_write(col.h, outfile);
         return 0;

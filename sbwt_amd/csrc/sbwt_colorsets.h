@@ -34,3 +34,37 @@ void sbwt_launch_pa_reduce_sets(const int *d_res, const int *d_res2, const long 
                                 const unsigned *d_ids, const unsigned long long *d_table, long long n_nodes, long long n_sets,
                                 int words, int n_colors, int threshold_ppm, int denominator, SbwtReadFound *d_out,
                                 unsigned long long *d_colors, int *d_counts, hipStream_t stream);
+
+// ---- the builder: colour sets made one colour at a time ----
+// What a builder holds on the device: ids (n uint32, all 0 at first), a table of `cap` rows of `words` words of which n_sets
+// are in use (row 0 zero), cnt (cap uint32: the columns that carry each id; cnt[0] = n at first) and the mark bitmap (one bit
+// per column in 64-bit words).  The capacity starts at SBWT_CSB_FIRST_CAPACITY rows and doubles.
+#define SBWT_CSB_FIRST_CAPACITY 64
+struct SbwtCsbState {
+    long long n = 0;
+    int words = 1;
+    long long cap = 0, n_sets = 1, n_colored = 0;
+    unsigned *d_ids = nullptr, *d_cnt = nullptr;
+    unsigned long long *d_table = nullptr, *d_marks = nullptr;
+};
+
+// allocates and zeroes the state; on an error nothing is left allocated.  Synchronises `stream`.
+hipError_t sbwt_csb_init(SbwtCsbState *b, long long n, int words, hipStream_t stream);
+void sbwt_csb_free(SbwtCsbState *b);
+// 4 n + 8 ceil(n / 64) + cap (8 words + 4); 0 once finish has taken the state apart
+long long sbwt_csb_device_bytes(const SbwtCsbState *b);
+
+// sbwt_launch_col_mark with a bit per column in the place of a row: a hit on column j sets bit j & 63 of d_marks[j >> 6]
+void sbwt_launch_csb_mark(const int *d_res, const int *d_other, const long long *d_out_off, long long n_reads, long long max_results,
+                          unsigned long long *d_marks, long long n_nodes, int count, SbwtPaHeader *hdr, hipStream_t stream);
+
+// Closes `color` (in no row of the table yet): every marked column's set becomes its old set + the colour, the bitmap is
+// cleared, n_sets and n_colored follow, *n_marked = the marked columns.  Scratch, freed before it returns: 4 bytes per set and
+// 32 bytes.  The table grows when the sets that split need it; an error (hipErrorOutOfMemory from there, for one) leaves the
+// state unusable for anything but sbwt_csb_free.  Synchronises `stream`.
+hipError_t sbwt_csb_close(SbwtCsbState *b, int color, long long *n_marked, hipStream_t stream);
+
+// The canonical colour-set object of the state (no colour open): *d_ids is the state's id array renumbered, *d_table a new
+// table of *n_sets rows; both belong to the caller and the state is freed.  Scratch: 4 bytes per set, 1 + 4 bytes per column
+// and rocPRIM's temporary storage.  On an error the state keeps what it had.  Synchronises `stream`.
+hipError_t sbwt_csb_finish(SbwtCsbState *b, unsigned **d_ids, unsigned long long **d_table, long long *n_sets, hipStream_t stream);

@@ -403,3 +403,381 @@ void sbwt_launch_pa_reduce_sets(const int *d_res, const int *d_res2, const long 
                            (const u64 *)d_table, (i64)n_nodes, (unsigned)n_sets, words, n_colors, threshold_ppm, denominator, (int2 *)d_out,
                            (u64 *)d_colors, d_counts);
 }
+
+// ---------------------------------------------------------------------------------------------
+// the builder: colour sets made one colour at a time, without the wide matrix
+// ---------------------------------------------------------------------------------------------
+// State (SbwtCsbState): ids[n], table[cap x words] with row 0 zero, cnt[cap] = the columns that carry each id, and a mark
+// bitmap of one bit per column, 64 columns a word.  A colour is marked into the bitmap by any number of searches and then
+// CLOSED: every marked column's set becomes its old set + the colour.  A closed colour is in no row of the table, so
+//   k_csb_count   bitmap -> hit[old id] = the marked columns that carry it.  A wave takes a bitmap word, lane l its column
+//                 64 w + l; ids are gathered for set bits only and the distinct ids of the word are peeled as k_pa_reduce_sets
+//                 peels keys (readlane, ballot, popcount): one add per distinct id and word, into the block's LDS counters
+//                 for ids below CSB_LDS_IDS -- a strain's millions of columns share a handful of ids, which would otherwise
+//                 all meet at a few addresses in L2 -- and into `hit` directly above that.
+//   k_csb_plan    a lane per old id: hit == cnt and id != 0 -> every column of the set moves: the colour's bit is set in the
+//                 row in place and hit becomes 0 ("stays"); any other hit != 0 -> the set splits, counted in ctr[1].
+//                 The host reads ctr and grows table and cnt when old sets + splits pass the capacity.
+//   k_csb_assign  a lane per old id that splits: a new id from an atomic counter (any order: finish fixes the numbering),
+//                 cnt[new] = hit, cnt[old] -= hit, hit[old] = the new id -- the array now is the remap, 0 = stays.
+//   k_csb_rows    grid-stride over old sets x words: table[new] = table[old] | the colour's bit
+//   k_csb_move    bitmap -> ids: marked columns of split sets take remap[id]; the word is cleared
+// The table's rows stay pairwise distinct and every row but 0 stays in use: new rows hold the colour and surviving old rows
+// do not, distinct old rows give distinct new ones, and a row that would become unused is the one changed in place.
+//   finish:  k_csb_first (atomicMin of the columns that carry each id, the atomic skipped when it would not lower it; ids below
+//            CSB_LDS_IDS in the block's LDS first),
+//            k_csb_flag, rocPRIM's exclusive scan over the n flags, k_csb_renumber, k_csb_permute -- compress's flag / scan /
+//            assign passes over again, so the result is the canonical form.
+#define CSB_LDS_IDS 1024
+
+// grid for a loop in which a wave takes one bitmap word per round
+static inline unsigned csb_word_grid(i64 n_words) {
+    const i64 g = (n_words + 3) / 4;
+    return (unsigned)(g < 1 ? 1 : g > 2048 ? 2048 : g);
+}
+
+// k_col_mark with a bit per column for a row of words: the same window count
+__global__ void __launch_bounds__(256) k_csb_mark(const int *__restrict__ res, const int *__restrict__ other,
+                                                  const i64 *__restrict__ out_off, i64 n_reads, u64 *marks, i64 n_nodes, int count,
+                                                  SbwtPaHeader *__restrict__ hdr) {
+    const i64 W = out_off[n_reads];
+    u64 mine = 0;                                          // windows with a hit, of this lane's wave (kept by its lane 0)
+    for (i64 i0 = (i64)blockIdx.x * 256 + (threadIdx.x & ~63u); i0 < W; i0 += (i64)gridDim.x * 256) {
+        const i64 i = i0 + (threadIdx.x & 63);
+        bool hit = false;
+        if (i < W) {
+            const i64 v = res[i];
+            if (v >= 0 && v < n_nodes) {
+                hit = true;
+                const u64 bit = 1ull << (v & 63);
+                u64 *word = marks + (v >> 6);
+                if (!(*word & bit)) atomicOr(word, bit);
+            }
+            if (count && !hit && other) hit = other[W - 1 - i] >= 0;
+        }
+        if (count) mine += (u64)__popcll(__ballot(hit));
+    }
+    if (count && mine && (threadIdx.x & 63) == 0) atomicAdd(&hdr->n_hit, mine);
+}
+
+// ctr[0] += the marked columns
+__global__ void __launch_bounds__(256) k_csb_count(const u64 *__restrict__ marks, i64 n_words, i64 n, const unsigned *__restrict__ ids,
+                                                   unsigned n_sets, unsigned *__restrict__ hit, u64 *__restrict__ ctr) {
+    __shared__ unsigned lds_hit[CSB_LDS_IDS];
+    const int lane = threadIdx.x & 63;
+    for (int i = threadIdx.x; i < CSB_LDS_IDS; i += 256) lds_hit[i] = 0;
+    __syncthreads();
+    u64 mine = 0;
+    for (i64 w = (i64)blockIdx.x * 4 + (threadIdx.x >> 6); w < n_words; w += (i64)gridDim.x * 4) {
+        const u64 bits = marks[w];                         // (the same address, and so the same value, in every lane)
+        if (!bits) continue;
+        const i64 j = w * 64 + lane;
+        const bool on = ((bits >> lane) & 1ull) && j < n;
+        unsigned id = on ? ids[j] : 0;
+        if (id >= n_sets) id = 0;                          // (never: ids stay below n_sets)
+        u64 live = __ballot(on);
+        mine += (u64)__popcll(live);
+        while (live) {                                     // one trip per distinct id of the word
+            const int src = __ffsll((i64)live) - 1;
+            const unsigned k0 = (unsigned)__builtin_amdgcn_readlane((int)id, src);
+            const u64 eq = __ballot(on && id == k0);
+            live &= ~eq;
+            if (lane == 0) {
+                if (k0 < CSB_LDS_IDS) atomicAdd(lds_hit + k0, (unsigned)__popcll(eq));
+                else atomicAdd(hit + k0, (unsigned)__popcll(eq));
+            }
+        }
+    }
+    if (mine && lane == 0) atomicAdd(ctr, mine);
+    __syncthreads();
+    for (unsigned i = threadIdx.x; i < CSB_LDS_IDS && i < n_sets; i += 256) {
+        const unsigned v = lds_hit[i];
+        if (v) atomicAdd(hit + i, v);
+    }
+}
+
+// ctr[1] += the sets that split; ctr[2] = hit[0], the columns that were not coloured and now are
+__global__ void __launch_bounds__(256) k_csb_plan(unsigned *__restrict__ hit, const unsigned *__restrict__ cnt, unsigned n_sets,
+                                                  u64 *__restrict__ table, int words, int color, u64 *__restrict__ ctr) {
+    u64 mine = 0;
+    for (unsigned r0 = blockIdx.x * 256 + (threadIdx.x & ~63u); r0 < n_sets; r0 += gridDim.x * 256) {
+        const unsigned r = r0 + (threadIdx.x & 63);
+        bool split = false;
+        if (r < n_sets) {
+            const unsigned h = hit[r];
+            if (r == 0) ctr[2] = h;
+            if (h != 0 && r != 0 && h == cnt[r]) {
+                table[(i64)r * words + (color >> 6)] |= 1ull << (color & 63);
+                hit[r] = 0;
+            } else {
+                split = h != 0;
+            }
+        }
+        mine += (u64)__popcll(__ballot(split));
+    }
+    if (mine && (threadIdx.x & 63) == 0) atomicAdd(ctr + 1, mine);
+}
+
+// ctr[3]: the new ids handed out so far
+__global__ void __launch_bounds__(256) k_csb_assign(unsigned *__restrict__ hit, unsigned *__restrict__ cnt, unsigned n_sets,
+                                                    u64 *__restrict__ ctr) {
+    for (unsigned r = blockIdx.x * 256 + threadIdx.x; r < n_sets; r += gridDim.x * 256) {
+        const unsigned h = hit[r];
+        if (h == 0) continue;
+        const unsigned fresh = n_sets + (unsigned)atomicAdd(ctr + 3, 1ull);
+        cnt[fresh] = h;
+        cnt[r] -= h;
+        hit[r] = fresh;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_csb_rows(const unsigned *__restrict__ remap, unsigned n_sets, u64 *table, int words, int color) {
+    const i64 total = (i64)n_sets * words;
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < total; i += (i64)gridDim.x * 256) {
+        const i64 r = i / words;
+        const int w = (int)(i - r * words);
+        const unsigned fresh = remap[r];
+        if (fresh) table[(i64)fresh * words + w] = table[i] | (w == (color >> 6) ? 1ull << (color & 63) : 0ull);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_csb_move(u64 *__restrict__ marks, i64 n_words, i64 n, unsigned *__restrict__ ids,
+                                                  const unsigned *__restrict__ remap, unsigned n_sets) {
+    const int lane = threadIdx.x & 63;
+    for (i64 w = (i64)blockIdx.x * 4 + (threadIdx.x >> 6); w < n_words; w += (i64)gridDim.x * 4) {
+        const u64 bits = marks[w];
+        if (!bits) continue;                               // (the same in every lane)
+        const i64 j = w * 64 + lane;
+        if (((bits >> lane) & 1ull) && j < n) {
+            const unsigned id = ids[j];
+            const unsigned fresh = id < n_sets ? remap[id] : 0;
+            if (fresh) ids[j] = fresh;
+        }
+        if (lane == 0) marks[w] = 0;
+    }
+}
+
+// first[id] = the smallest column that carries id (first[] starts as CS_EMPTY).  Columns come to a block in ascending order, so
+// a minimum is loaded first and the atomic skipped when it would not lower it: after a block's first round nearly all skip.
+// Ids below CSB_LDS_IDS meet in the block's LDS and reach `first` once per block and id -- the few sets that millions of
+// columns share would otherwise send every wave of the first round to the same few addresses in L2.
+__global__ void __launch_bounds__(256) k_csb_first(const unsigned *__restrict__ ids, i64 n, unsigned n_sets, unsigned *first) {
+    __shared__ unsigned lds_min[CSB_LDS_IDS];
+    for (int i = threadIdx.x; i < CSB_LDS_IDS; i += 256) lds_min[i] = CS_EMPTY;
+    __syncthreads();
+    for (i64 j = (i64)blockIdx.x * 256 + threadIdx.x; j < n; j += (i64)gridDim.x * 256) {
+        const unsigned id = ids[j];
+        if (id == 0 || id >= n_sets) continue;
+        if (id < CSB_LDS_IDS) {
+            if ((unsigned)j < lds_min[id]) atomicMin(lds_min + id, (unsigned)j);
+        } else if ((unsigned)j < first[id]) {
+            atomicMin(first + id, (unsigned)j);
+        }
+    }
+    __syncthreads();
+    for (unsigned i = threadIdx.x; i < CSB_LDS_IDS && i < n_sets; i += 256) {
+        const unsigned v = lds_min[i];
+        if (v != CS_EMPTY && v < first[i]) atomicMin(first + i, v);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_csb_flag(const unsigned *__restrict__ first, unsigned n_sets, i64 n, unsigned char *__restrict__ flags) {
+    for (unsigned r = 1 + blockIdx.x * 256 + threadIdx.x; r < n_sets; r += gridDim.x * 256) {
+        const unsigned f = first[r];
+        if ((i64)f < n) flags[f] = 1;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_csb_renumber(unsigned *__restrict__ ids, i64 n, unsigned n_sets, const unsigned *__restrict__ first,
+                                                      const unsigned *__restrict__ rank) {
+    for (i64 j = (i64)blockIdx.x * 256 + threadIdx.x; j < n; j += (i64)gridDim.x * 256) {
+        const unsigned id = ids[j];
+        if (id == 0) continue;
+        const unsigned f = id < n_sets ? first[id] : CS_EMPTY;
+        ids[j] = (i64)f < n ? 1u + rank[f] : 0u;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_csb_permute(const u64 *__restrict__ table, unsigned n_sets, int words, i64 n,
+                                                     const unsigned *__restrict__ first, const unsigned *__restrict__ rank,
+                                                     u64 *__restrict__ out) {
+    const i64 total = (i64)n_sets * words;
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < total; i += (i64)gridDim.x * 256) {
+        const i64 r = i / words;
+        if (r == 0) { out[i] = 0; continue; }
+        const unsigned f = first[r];
+        if ((i64)f < n) out[(i64)(1u + rank[f]) * words + (i - r * words)] = table[i];
+    }
+}
+
+void sbwt_launch_csb_mark(const int *d_res, const int *d_other, const long long *d_out_off, long long n_reads, long long max_results,
+                          unsigned long long *d_marks, long long n_nodes, int count, SbwtPaHeader *hdr, hipStream_t stream) {
+    hipLaunchKernelGGL(k_csb_mark, dim3(cs_stride_grid(max_results)), dim3(256), 0, stream, d_res, d_other, d_out_off, (i64)n_reads,
+                       (u64 *)d_marks, (i64)n_nodes, count, hdr);
+}
+
+static inline i64 csb_mark_words(i64 n) { return (n + 63) / 64; }
+
+long long sbwt_csb_device_bytes(const SbwtCsbState *b) {
+    if (!b->d_ids) return 0;
+    return b->n * 4 + csb_mark_words(b->n) * 8 + b->cap * ((i64)b->words * 8 + 4);
+}
+
+void sbwt_csb_free(SbwtCsbState *b) {
+    (void)hipFree(b->d_ids);
+    (void)hipFree(b->d_table);
+    (void)hipFree(b->d_cnt);
+    (void)hipFree(b->d_marks);
+    b->d_ids = b->d_cnt = nullptr;
+    b->d_table = b->d_marks = nullptr;
+    b->cap = 0;
+}
+
+hipError_t sbwt_csb_init(SbwtCsbState *b, long long n, int words, hipStream_t stream) {
+    b->n = n;
+    b->words = words;
+    b->cap = SBWT_CSB_FIRST_CAPACITY;
+    b->n_sets = 1;
+    b->n_colored = 0;
+    b->d_ids = b->d_cnt = nullptr;
+    b->d_table = b->d_marks = nullptr;
+    const size_t mark_bytes = (size_t)csb_mark_words(n) * 8, table_bytes = (size_t)b->cap * (size_t)words * 8;
+    const unsigned all = (unsigned)n;
+    hipError_t e = hipMalloc((void **)&b->d_ids, (size_t)n * 4 + 16);
+    if (e == hipSuccess) e = hipMalloc((void **)&b->d_marks, mark_bytes + 16);
+    if (e == hipSuccess) e = hipMalloc((void **)&b->d_table, table_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&b->d_cnt, (size_t)b->cap * 4);
+    if (e == hipSuccess) e = hipMemsetAsync(b->d_ids, 0, (size_t)n * 4 + 16, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(b->d_marks, 0, mark_bytes + 16, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(b->d_table, 0, table_bytes, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(b->d_cnt, 0, (size_t)b->cap * 4, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b->d_cnt, &all, 4, hipMemcpyHostToDevice, stream);
+    const hipError_t e2 = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) sbwt_csb_free(b);
+    return e;
+}
+
+// table and cnt of at least `need` rows: the capacity doubles, the rows in use are copied on the device
+static hipError_t csb_grow(SbwtCsbState *b, i64 need, hipStream_t stream) {
+    i64 cap = b->cap;
+    while (cap < need) cap *= 2;
+    if (cap == b->cap) return hipSuccess;
+    u64 *table = nullptr;
+    unsigned *cnt = nullptr;
+    const size_t row = (size_t)b->words * 8;
+    hipError_t e = hipMalloc((void **)&table, (size_t)cap * row);
+    if (e == hipSuccess) e = hipMalloc((void **)&cnt, (size_t)cap * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(table, b->d_table, (size_t)b->n_sets * row, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(cnt, b->d_cnt, (size_t)b->n_sets * 4, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(cnt + b->n_sets, 0, (size_t)(cap - b->n_sets) * 4, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) {
+        (void)hipFree(table);
+        (void)hipFree(cnt);
+        return e;
+    }
+    (void)hipFree(b->d_table);
+    (void)hipFree(b->d_cnt);
+    b->d_table = (unsigned long long *)table;
+    b->d_cnt = cnt;
+    b->cap = cap;
+    return hipSuccess;
+}
+
+hipError_t sbwt_csb_close(SbwtCsbState *b, int color, long long *n_marked, hipStream_t stream) {
+    const i64 n_words = csb_mark_words(b->n);
+    const unsigned old = (unsigned)b->n_sets;
+    const unsigned gw = csb_word_grid(n_words), gs = cs_stride_grid((i64)old);
+    unsigned *hit = nullptr;                                // hit, then remap: one uint32 per old set; the four counters behind
+    u64 h_ctr[4] = {0, 0, 0, 0};
+    *n_marked = 0;
+    const size_t hit_bytes = ((size_t)old * 4 + 15) & ~(size_t)15;
+    hipError_t e = hipMalloc((void **)&hit, hit_bytes + 32);
+    u64 *ctr = reinterpret_cast<u64 *>(reinterpret_cast<char *>(hit) + hit_bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(hit, 0, hit_bytes + 32, stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_csb_count, dim3(gw), dim3(256), 0, stream, (const u64 *)b->d_marks, n_words, (i64)b->n,
+                           (const unsigned *)b->d_ids, old, hit, ctr);
+        hipLaunchKernelGGL(k_csb_plan, dim3(gs), dim3(256), 0, stream, hit, (const unsigned *)b->d_cnt, old, (u64 *)b->d_table, b->words,
+                           color, ctr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h_ctr, ctr, 32, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    const i64 fresh = (i64)h_ctr[1];
+    if (e == hipSuccess && fresh > 0 && (i64)old + fresh > (i64)0xFFFFFFFFll) e = hipErrorOutOfMemory;          // (ids are uint32)
+    if (e == hipSuccess && fresh > 0) e = csb_grow(b, (i64)old + fresh, stream);
+    if (e == hipSuccess && h_ctr[0] != 0) {
+        if (fresh > 0) {
+            hipLaunchKernelGGL(k_csb_assign, dim3(gs), dim3(256), 0, stream, hit, b->d_cnt, old, ctr);
+            hipLaunchKernelGGL(k_csb_rows, dim3(cs_stride_grid((i64)old * b->words)), dim3(256), 0, stream, (const unsigned *)hit, old,
+                               (u64 *)b->d_table, b->words, color);
+        }
+        hipLaunchKernelGGL(k_csb_move, dim3(gw), dim3(256), 0, stream, (u64 *)b->d_marks, n_words, (i64)b->n, b->d_ids,
+                           (const unsigned *)hit, old);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = e2;
+    (void)hipFree(hit);
+    if (e != hipSuccess) return e;
+    b->n_sets = (i64)old + fresh;
+    b->n_colored += (i64)h_ctr[2];
+    *n_marked = (long long)h_ctr[0];
+    return hipSuccess;
+}
+
+hipError_t sbwt_csb_finish(SbwtCsbState *b, unsigned **d_ids, unsigned long long **d_table, long long *n_sets, hipStream_t stream) {
+    const i64 n = b->n;
+    const unsigned sets = (unsigned)b->n_sets;
+    unsigned *first = nullptr, *rank = nullptr;
+    unsigned char *flags = nullptr;
+    void *tmp = nullptr;
+    u64 *table = nullptr;
+    size_t tmp_bytes = 0;
+    unsigned total = 0;
+    *d_ids = nullptr;
+    *d_table = nullptr;
+    *n_sets = 0;
+    const unsigned g = cs_stride_grid(n), gs = cs_stride_grid((i64)sets);
+    hipError_t e = hipMalloc((void **)&first, (size_t)sets * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&flags, (size_t)n + 1);
+    if (e == hipSuccess) e = hipMalloc((void **)&rank, ((size_t)n + 1) * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&table, (size_t)sets * (size_t)b->words * 8);
+    const auto flags_in = rocprim::make_transform_iterator((const unsigned char *)flags, CsByteToU32());
+    if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, tmp_bytes, flags_in, rank, 0u, (size_t)n + 1, rocprim::plus<unsigned>(), stream);
+    if (e == hipSuccess) e = hipMalloc(&tmp, tmp_bytes + 16);
+    if (e == hipSuccess) e = hipMemsetAsync(first, 0xFF, (size_t)sets * 4, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, (size_t)n + 1, stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_csb_first, dim3(g > 2048 ? 2048 : g), dim3(256), 0, stream, (const unsigned *)b->d_ids, n, sets, first);
+        hipLaunchKernelGGL(k_csb_flag, dim3(gs), dim3(256), 0, stream, (const unsigned *)first, sets, n, flags);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp, tmp_bytes, flags_in, rank, 0u, (size_t)n + 1, rocprim::plus<unsigned>(), stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, rank + n, 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_csb_renumber, dim3(g), dim3(256), 0, stream, b->d_ids, n, sets, (const unsigned *)first, (const unsigned *)rank);
+        hipLaunchKernelGGL(k_csb_permute, dim3(cs_stride_grid((i64)sets * b->words)), dim3(256), 0, stream, (const u64 *)b->d_table, sets,
+                           b->words, n, (const unsigned *)first, (const unsigned *)rank, table);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = e2;
+    if (e == hipSuccess && total + 1u != sets) e = hipErrorAssert;          // (every row but 0 is in use: never)
+    (void)hipFree(tmp);
+    (void)hipFree(rank);
+    (void)hipFree(flags);
+    (void)hipFree(first);
+    if (e != hipSuccess) {
+        (void)hipFree(table);
+        return e;
+    }
+    *d_ids = b->d_ids;
+    *d_table = (unsigned long long *)table;
+    *n_sets = (long long)sets;
+    b->d_ids = nullptr;
+    sbwt_csb_free(b);
+    return hipSuccess;
+}

@@ -2808,6 +2808,18 @@ struct sbwtgpu_colorsets {
     unsigned long long *d_table = nullptr;
 };
 
+// a colour-set builder (sbwt_colorsets.hip, "the builder"): `base` binds it to its index; a colour is new, open or closed
+struct sbwtgpu_colorsets_builder {
+    sbwtgpu_colors base;
+    SbwtCsbState st;
+    Stream stream;                      // of the closes and of finish, for the builder's life: a stream costs milliseconds to make
+    std::vector<unsigned char> state;   // per colour: CSB_NEW, CSB_OPEN, CSB_CLOSED
+    std::vector<int64_t> per_color;     // the columns marked when the colour was closed
+    int open = -1;                      // the open colour, or -1
+    bool finished = false, broken = false;
+};
+enum { CSB_NEW = 0, CSB_OPEN = 1, CSB_CLOSED = 2 };
+
 static int colors_check_index(const sbwtgpu_index *idx) {
     if (idx->h.n_nodes >= ((int64_t)1 << 31))
         return fail(SBWTGPU_ERR_INVALID_ARG, "colours: the index has %lld columns, the colour layer reads int32 search results (fewer than 2^31 columns)",
@@ -3064,10 +3076,12 @@ int sbwtgpu_pseudoalign_wide_dev(const sbwtgpu_colors *c, const char *d_bases, i
 // flight on the parked slots of the search pipeline.  Bases and offsets go down; records, and counts if asked for, come back.
 // wide_colors != NULL: the wide query -- `out` holds 8-byte records (sbwtgpu_read_found) and wide_colors the reads' colour
 // words, 8 + 8 words bytes per read instead of 16; a chunk then also ends where its results would outgrow what 2^24 reads of
-// 64 colours with counts bring back.  sets != NULL: the wide query over a colour-set object, whose `base` is c.
+// 64 colours with counts bring back.  sets != NULL: the wide query over a colour-set object, whose `base` is c.  marks != NULL:
+// colouring for a colour-set builder, whose `base` is c -- a hit sets its column's bit in the builder's mark bitmap.
 static int colors_host_batch(const sbwtgpu_colors *c, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
                              int color, int threshold_ppm, int denominator, void *out, uint64_t *wide_colors, int32_t *counts,
-                             int64_t *n_windows, int64_t *n_hit, const sbwtgpu_colorsets *sets = nullptr) {
+                             int64_t *n_windows, int64_t *n_hit, const sbwtgpu_colorsets *sets = nullptr,
+                             unsigned long long *marks = nullptr) {
     const sbwtgpu_index *idx = c->idx;
     if (n_windows) *n_windows = 0;
     if (n_hit) *n_hit = 0;
@@ -3137,6 +3151,12 @@ static int colors_host_batch(const sbwtgpu_colors *c, const char *bases, const i
             r2 = sbwtgpu_pseudoalign_dev(c, P.d_mem, nb, d_roff, nr, strands, threshold_ppm, denominator,
                                          (sbwtgpu_pseudoalignment *)(P.d_mem + o_rec), counts ? (int32_t *)(P.d_mem + o_cnt) : nullptr,
                                          P.d_mem + o_ws, ws_bytes, P.st);
+        } else if (marks) {
+            r2 = colors_dev_common(c, P.d_mem, nb, d_roff, nr, strands, P.d_mem + o_ws, ws_bytes, P.st,
+                                   [&](const int *res, const int *res2, const long long *ooff, SbwtPaHeader *hdr, hipStream_t st) {
+                                       sbwt_launch_csb_mark(res, res2, ooff, nr, nb, marks, c->n_nodes, 1, hdr, st);
+                                       if (res2) sbwt_launch_csb_mark(res2, nullptr, ooff, nr, nb, marks, c->n_nodes, 0, hdr, st);
+                                   });
         } else {
             r2 = colors_dev_common(c, P.d_mem, nb, d_roff, nr, strands, P.d_mem + o_ws, ws_bytes, P.st,
                                    [&](const int *res, const int *res2, const long long *ooff, SbwtPaHeader *hdr, hipStream_t st) {
@@ -3407,6 +3427,138 @@ int sbwtgpu_pseudoalign_sets_batch(const sbwtgpu_colorsets *s, const char *bases
     if (n_reads > 0 && (!out || !colors_out)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
     return colors_host_batch(&s->base, bases, read_off, n_reads, strands, 0, threshold_ppm, denominator, out, colors_out, counts_or_null,
                              nullptr, nullptr, s);
+}
+
+// ---- the colour-set builder (sbwt_colorsets.hip, "the builder") -----------------------------------------
+static int builder_check(const sbwtgpu_colorsets_builder *b) {
+    if (!b) return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set builder is NULL");
+    if (b->finished) return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set builder: finish has consumed it, only destroy is left");
+    if (b->broken) return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set builder is broken by an earlier error, only destroy is left");
+    return colors_check(&b->base);
+}
+
+static int builder_failed(sbwtgpu_colorsets_builder *b, hipError_t e) {
+    (void)hipGetLastError();
+    b->broken = true;
+    return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "colour-set builder: %s", hipGetErrorString(e));
+}
+
+// merges the open colour's marks into (ids, table); nothing open: nothing to do
+static int builder_close_open(sbwtgpu_colorsets_builder *b) {
+    if (b->open < 0) return SBWTGPU_OK;
+    long long marked = 0;
+    const hipError_t e = sbwt_csb_close(&b->st, b->open, &marked, b->stream.s);
+    if (e != hipSuccess) return builder_failed(b, e);
+    b->per_color[(size_t)b->open] = marked;
+    b->state[(size_t)b->open] = CSB_CLOSED;
+    b->open = -1;
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_colorsets_builder_create(const sbwtgpu_index *idx, int n_colors, sbwtgpu_colorsets_builder **out) {
+    if (!idx || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    const int rc = colors_check_index(idx);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_colors < 1 || n_colors > SBWTGPU_MAX_COLORS)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "n_colors must be in 1 .. %d, not %d", SBWTGPU_MAX_COLORS, n_colors);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", idx->device);
+    sbwtgpu_colorsets_builder *b = new (std::nothrow) sbwtgpu_colorsets_builder();
+    if (!b) return fail(SBWTGPU_ERR_OOM, "out of host memory");
+    try {
+        b->state.assign((size_t)n_colors, CSB_NEW);
+        b->per_color.assign((size_t)n_colors, 0);
+    } catch (const std::bad_alloc &) {
+        delete b;
+        return fail(SBWTGPU_ERR_OOM, "out of host memory");
+    }
+    b->base.idx = idx;
+    b->base.device = idx->device;
+    b->base.n_nodes = idx->h.n_nodes;
+    b->base.k = idx->h.k;
+    b->base.n_colors = n_colors;
+    b->base.words = (n_colors + 63) / 64;
+    hipError_t e = hipStreamCreateWithFlags(&b->stream.s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = sbwt_csb_init(&b->st, b->base.n_nodes, b->base.words, b->stream.s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        delete b;
+        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "colour-set builder: %s", hipGetErrorString(e));
+    }
+    *out = b;
+    return SBWTGPU_OK;
+}
+
+void sbwtgpu_colorsets_builder_destroy(sbwtgpu_colorsets_builder *b) {
+    if (!b) return;
+    DeviceGuard guard(b->base.device);
+    sbwt_csb_free(&b->st);
+    delete b;
+}
+
+int sbwtgpu_colorsets_builder_add_batch(sbwtgpu_colorsets_builder *b, int color, const char *bases, const int64_t *read_off,
+                                        int64_t n_reads, int strands, int64_t *n_windows, int64_t *n_hit_windows) {
+    int rc = builder_check(b);
+    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc != SBWTGPU_OK) return rc;
+    if (color < 0 || color >= b->base.n_colors)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "color %d is out of range: the colour-set builder has %d colours", color, b->base.n_colors);
+    if (b->state[(size_t)color] == CSB_CLOSED)
+        return fail(SBWTGPU_ERR_INVALID_ARG,
+                    "colour %d is closed: the sequences of one colour must come in consecutive calls (another colour was added after it)", color);
+    // (what colors_host_batch would refuse is refused here, before the call closes a colour)
+    if (n_reads > 0 && (!read_off || (read_off[n_reads] > read_off[0] && !bases))) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    for (int64_t r = 0; r < n_reads; r++)
+        if ((rc = check_read_length(read_off, r)) != SBWTGPU_OK) return rc;
+    DeviceGuard guard(b->base.device);
+    if (b->open != color) {
+        if ((rc = builder_close_open(b)) != SBWTGPU_OK) return rc;
+        b->open = color;
+        b->state[(size_t)color] = CSB_OPEN;
+    }
+    rc = colors_host_batch(&b->base, bases, read_off, n_reads, strands, color, 0, 0, nullptr, nullptr, nullptr, n_windows, n_hit_windows,
+                           nullptr, b->st.d_marks);
+    if (rc == SBWTGPU_ERR_OOM || rc == SBWTGPU_ERR_HIP) b->broken = true;          // (some of the batch may be marked, some not)
+    return rc;
+}
+
+int sbwtgpu_colorsets_builder_info(const sbwtgpu_colorsets_builder *b, int64_t *n_columns, int64_t *k, int32_t *n_colors, int32_t *words,
+                                   int64_t *n_sets, int64_t *n_colored_columns, int64_t *per_color, int64_t *device_bytes) {
+    const int rc = builder_check(b);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_columns) *n_columns = b->base.n_nodes;
+    if (k) *k = b->base.k;
+    if (n_colors) *n_colors = b->base.n_colors;
+    if (words) *words = b->base.words;
+    if (n_sets) *n_sets = b->st.n_sets;
+    if (n_colored_columns) *n_colored_columns = b->st.n_colored;
+    if (per_color) std::copy(b->per_color.begin(), b->per_color.end(), per_color);
+    if (device_bytes) *device_bytes = sbwt_csb_device_bytes(&b->st);
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_colorsets_builder_finish(sbwtgpu_colorsets_builder *b, sbwtgpu_colorsets **out) {
+    if (!out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    int rc = builder_check(b);
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(b->base.device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", b->base.device);
+    if ((rc = builder_close_open(b)) != SBWTGPU_OK) return rc;
+    sbwtgpu_colorsets *s = colorsets_new(b->base.idx, b->base.n_colors);
+    if (!s) return fail(SBWTGPU_ERR_OOM, "out of host memory");
+    long long n_sets = 0;
+    s->n_colored = b->st.n_colored;
+    const hipError_t e = sbwt_csb_finish(&b->st, &s->d_ids, &s->d_table, &n_sets, b->stream.s);
+    s->n_sets = n_sets;
+    if (e != hipSuccess) {
+        sbwtgpu_colorsets_destroy(s);
+        return builder_failed(b, e);
+    }
+    b->finished = true;
+    *out = s;
+    return SBWTGPU_OK;
 }
 
 // ---- set operations (sbwt_setops.hip) ---------------------------------------------------------------
