@@ -720,6 +720,39 @@ int  sbwtgpu_colorsets_builder_info(const sbwtgpu_colorsets_builder *b, int64_t 
 int  sbwtgpu_colorsets_builder_finish(sbwtgpu_colorsets_builder *b, sbwtgpu_colorsets **out);
 void sbwtgpu_colorsets_builder_destroy(sbwtgpu_colorsets_builder *b);
 
+/* ---- colour sets carried onto another index: the coloured merge ----
+ * sbwtgpu_index_setop combines two indexes when their sequences are gone; this call carries their colours along, without the
+ * sequences and without a wide matrix.
+ * Inputs: u is a target index; sa is a colour-set object of an index a; sb, which is optional, one of an index b;
+ * color_offset_b is an integer.  For a k-mer x, S_a(x) is the colour set sa means for x's column in a, and the empty set when
+ * x is not a k-mer of a.  S_b is defined likewise.
+ * The result is a colour-set object OF u:
+ *   - Every real column j of u, with k-mer x, has the set S_a(x) + { c + color_offset_b : c in S_b(x) }.
+ *   - Dummy columns have id 0.
+ *   - n_colors_out = max(n_colors_a, color_offset_b + n_colors_b).  It is n_colors_a when sb is NULL.
+ *   - W_out = ceil(n_colors_out / 64).
+ *   - The object is in the canonical form above: distinct non-zero rows numbered by the smallest column of u that carries
+ *     them, row 0 empty, no row unused or duplicated.
+ * u may be any index with the same k: the union (the coloured merge), the intersection or a difference (colours restricted
+ * to the surviving k-mers), a itself (re-canonicalises an uploaded object), an unrelated index (everything is empty and
+ * n_sets = 1).  color_offset_b = n_colors_a concatenates the two colour spaces; color_offset_b = 0 says colour c is the same
+ * reference on both sides, and rows are OR-ed.  The inputs may be non-canonical uploaded objects, and with overlapping colour
+ * spaces two different pairs (id_a, id_b) can give the same row: the result is canonical in both cases.
+ * info (may be NULL): n_real_u = the real columns of u; n_from_a / n_from_b / n_from_both = those whose k-mer is in a / b /
+ * both; n_pairs = the distinct pairs (id_a, id_b) other than (0, 0); n_sets of the result; pass_ms on the host clock: keys,
+ * locate and gather, pairs and rows, canonical numbering.
+ * Refusals (SBWTGPU_ERR_INVALID_ARG with a message that names the cause): NULL u, sa or out; different k among u, a, b; k
+ * outside 2 .. 64 (the set operations' range); a rank-only index among the three; u of 2^31 columns or more; different
+ * devices; color_offset_b < 0; color_offset_b != 0 when sb is NULL; n_colors_out > SBWTGPU_MAX_COLORS.
+ * sa and sb may be the same object, and u may be a or b.  SBWTGPU_ERR_OOM leaves everything usable.  Scratch, all released
+ * before the call returns: the set operations' 37 / 69 bytes per column of one index at a time, 12 / 20 bytes per k-mer of
+ * the three indexes for keys and columns, then 25 bytes per k-mer of u and 25 + 8 W_out per distinct pair.
+ * Thread-safe on immutable handles: the call owns its stream.  The returned object is bound to u, as every colour-set object
+ * is bound to its index; u must outlive it. */
+typedef struct { int64_t n_real_u, n_from_a, n_from_b, n_from_both, n_pairs, n_sets; double pass_ms[4]; } sbwtgpu_colorsets_merge_info;
+int  sbwtgpu_colorsets_merge(const sbwtgpu_index *u, const sbwtgpu_colorsets *sa, const sbwtgpu_colorsets *sb /* may be NULL */,
+                             int color_offset_b, sbwtgpu_colorsets **out, sbwtgpu_colorsets_merge_info *info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_pseudoalign_sets_dev",
     "sbwtgpu_colorsets_builder_create", "sbwtgpu_colorsets_builder_add_batch", "sbwtgpu_colorsets_builder_info",
     "sbwtgpu_colorsets_builder_finish", "sbwtgpu_colorsets_builder_destroy",
+    "sbwtgpu_colorsets_merge",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -130,6 +131,16 @@ class SetopInfoC(C.Structure):
     def as_dict(self) -> dict:
         d = {f: int(getattr(self, f)) for f in ("n_a", "n_b", "n_both", "n_either", "n_result", "n_nopred")}
         d["pass_ms"] = dict(zip(("keys_a", "keys_b", "merge_select", "tail_columns"), (float(x) for x in self.pass_ms)))
+        return d
+
+
+class ColorsetsMergeInfoC(C.Structure):
+    _fields_ = [("n_real_u", C.c_int64), ("n_from_a", C.c_int64), ("n_from_b", C.c_int64), ("n_from_both", C.c_int64),
+                ("n_pairs", C.c_int64), ("n_sets", C.c_int64), ("pass_ms", C.c_double * 4)]
+
+    def as_dict(self) -> dict:
+        d = {f: int(getattr(self, f)) for f in ("n_real_u", "n_from_a", "n_from_b", "n_from_both", "n_pairs", "n_sets")}
+        d["pass_ms"] = dict(zip(("keys", "locate_gather", "pairs_rows", "canonical"), (float(x) for x in self.pass_ms)))
         return d
 
 
@@ -269,6 +280,7 @@ def lib() -> C.CDLL:
         L.sbwtgpu_colorsets_builder_finish.argtypes = [vp, C.POINTER(vp)]
         L.sbwtgpu_colorsets_builder_destroy.argtypes = [vp]
         L.sbwtgpu_colorsets_builder_destroy.restype = None
+        L.sbwtgpu_colorsets_merge.argtypes = [vp, vp, vp, ci, C.POINTER(vp), C.POINTER(ColorsetsMergeInfoC)]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -957,6 +969,21 @@ class ColorSets:
         h = C.c_void_p()
         _check(lib().sbwtgpu_colorsets_create(index.handle, n_colors, ids.ctypes.data, table.shape[0], table.ctypes.data, C.byref(h)))
         return cls(h, index)
+
+    @classmethod
+    def merge(cls, u: Index, sa: "ColorSets", sb: Optional["ColorSets"] = None, color_offset: Optional[int] = None) -> "ColorSets":
+        """sbwtgpu_colorsets_merge: the canonical colour-set object of index u whose column of k-mer x carries what sa says
+        about x in its index, plus what sb says about it in its own with color_offset added to every colour (default: sa's
+        n_colors, the two colour spaces one after the other; 0 without sb).  The counts and pass times of the call are the
+        result's merge_info."""
+        if color_offset is None:
+            color_offset = sa.n_colors if sb is not None else 0
+        h, info = C.c_void_p(), ColorsetsMergeInfoC()
+        _check(lib().sbwtgpu_colorsets_merge(u.handle, sa.handle, sb.handle if sb is not None else None, color_offset, C.byref(h),
+                                             C.byref(info)))
+        out = cls(h, u)
+        out.merge_info = info.as_dict()
+        return out
 
     def __enter__(self):
         return self

@@ -12,6 +12,10 @@
 //               one reference at a time without the wide matrix on the device)
 //   sbwt compress-colors -i <index> -c <colours> -o <colour sets>
 //               the colour-set file of a colour file written with or without --wide
+//   sbwt merge-colors -u <index U> -a <index A> --colors-a <colours of A> [-b <index B> --colors-b <colours of B>]
+//               [--color-offset <n>] -o <colour sets of U>
+//               the colour sets of A (and B, its colours moved up by the offset) carried onto U's k-mers: run set-op first,
+//               then merge-colors on its output
 //   sbwt pseudoalign -i <index> -c <colours> -q <query> -o <out> [-z] [--threshold 0.7] [--all-kmers] [--both-strands]
 //               one line per read: its number, then the colours that hold it
 //   sbwt build  -i <in> -o <index> -k <k> [-p <precalc>] [--add-reverse-complements]
@@ -1126,6 +1130,88 @@ int compress_colors_main(int argc, char **argv) {
     return 0;
 }
 
+// the colour-set object of a colour file of `index`: an "SBWTCOL3" file goes in directly, an "SBWTCOL1" or "SBWTCOL2" file is
+// compressed on the device first (sbwtgpu_colorsets_compress, as compress-colors does); a file of another index is refused
+void load_colorsets(const string &colorsfile, const string &indexfile, const plain_matrix_sbwt_t &index, ColorSetsHandle &out) {
+    const bool sets = file_has_magic(colorsfile, "SBWTCOL3");
+    int64_t n_columns = 0, n_colors = 0, ck = 0, words = 1, n_sets = 0;
+    if ((sets ? sbwthost_colorsets_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, &n_sets, nullptr, 0, nullptr, 0)
+              : sbwthost_colors_read_wide(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, nullptr, 0)) != 0)
+        throw std::runtime_error(sbwthost_last_error());
+    if (n_columns != index.number_of_subsets() || ck != index.get_k())
+        throw std::runtime_error("Error: " + colorsfile + " colours an index of " + std::to_string(n_columns) + " columns at k = " +
+                                 std::to_string(ck) + ", " + indexfile + " has " + std::to_string(index.number_of_subsets()) +
+                                 " columns at k = " + std::to_string(index.get_k()));
+    if (sets) {
+        vector<uint32_t> ids((size_t)n_columns);
+        vector<uint64_t> table((size_t)(n_sets * words));
+        if (sbwthost_colorsets_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, &n_sets, ids.data(), n_columns, table.data(),
+                                    n_sets * words) != 0)
+            throw std::runtime_error(sbwthost_last_error());
+        colors_check(sbwtgpu_colorsets_create(index.device_handle(), (int)n_colors, ids.data(), n_sets, table.data(), &out.h));
+        return;
+    }
+    ColorsHandle col;
+    vector<uint64_t> rows((size_t)(n_columns * words));
+    if (sbwthost_colors_read_wide(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, rows.data(), n_columns * words) != 0)
+        throw std::runtime_error(sbwthost_last_error());
+    colors_check(sbwtgpu_colors_create_wide(index.device_handle(), (int)n_colors, rows.data(), &col.h));
+    colors_check(sbwtgpu_colorsets_compress(col.h, &out.h));
+}
+
+// sbwt merge-colors: the colour sets of one or two coloured indexes carried onto index U (the output of `sbwt set-op`, for
+// one), without any sequence file: the "SBWTCOL3" file that build-colors --compress writes for U and the same colouring
+int merge_colors_main(int argc, char **argv) {
+    set_log_level(LogLevel::MINOR);
+    Options opts({
+        {"index-u", 'u', true, "Target index input file (the output of set-op, or any index with the same k).", ""},
+        {"index-a", 'a', true, "First coloured index input file.", ""},
+        {"colors-a", 0, true, "Colour file or colour-set file of the first index.", ""},
+        {"index-b", 'b', true, "Second coloured index input file (optional; needs --colors-b).", ""},
+        {"colors-b", 0, true, "Colour file or colour-set file of the second index.", ""},
+        {"color-offset", 0, true, "Added to every colour of the second index (default: the number of colours of the first; 0 shares the colour space).", ""},
+        {"out-file", 'o', true, "Output colour-set file of the target index.", ""},
+        {"gpu", 0, true, "HIP device to run on.", "0"},
+        {"help", 'h', false, "Print usage", ""},
+    });
+    opts.parse(argc, argv);
+    if (argc == 1 || opts.count("help")) {
+        std::cerr << opts.help(argv[0], "Carry the colour sets of one or two indexes onto another index (merge-colors), without the sequences.") << std::endl;
+        exit(1);
+    }
+    const string file_u = opts.get("index-u"), file_a = opts.get("index-a"), colors_a = opts.get("colors-a"), outfile = opts.get("out-file");
+    const bool two = opts.count("index-b") || opts.count("colors-b");
+    if (two && !(opts.count("index-b") && opts.count("colors-b")))
+        throw std::runtime_error("Error: --index-b and --colors-b come together");
+    if (!two && opts.count("color-offset") && atoll(opts.get("color-offset").c_str()) != 0)
+        throw std::runtime_error("Error: --color-offset needs a second index (--index-b and --colors-b)");
+    const string file_b = two ? opts.get("index-b") : string(), colors_b = two ? opts.get("colors-b") : string();
+    for (const string &f : {file_u, file_a, colors_a}) check_readable(f);
+    if (two) {
+        check_readable(file_b);
+        check_readable(colors_b);
+    }
+    check_writable(outfile);
+    set_default_device(atoi(opts.get("gpu").c_str()));
+    plain_matrix_sbwt_t U, A, B;
+    load_plain_matrix(file_u, U);
+    load_plain_matrix(file_a, A);
+    if (two) load_plain_matrix(file_b, B);
+    ColorSetsHandle sa, sb, merged;
+    load_colorsets(colors_a, file_a, A, sa);
+    if (two) load_colorsets(colors_b, file_b, B, sb);
+    int32_t n_colors_a = 0;
+    colors_check(sbwtgpu_colorsets_info(sa.h, nullptr, nullptr, &n_colors_a, nullptr, nullptr, nullptr, nullptr));
+    const long long offset = opts.count("color-offset") ? atoll(opts.get("color-offset").c_str()) : (two ? n_colors_a : 0);
+    if (offset < -2147483647ll || offset > 2147483647ll) throw std::runtime_error("Error: --color-offset " + opts.get("color-offset") + " is out of range");
+    sbwtgpu_colorsets_merge_info info;
+    colors_check(sbwtgpu_colorsets_merge(U.device_handle(), sa.h, sb.h, (int)offset, &merged.h, &info));
+    write_colorsets(merged.h, outfile);
+    std::cout << "merge-colors: " << info.n_real_u << " k-mers in u, " << info.n_from_a << " from a, " << info.n_from_b << " from b, "
+              << info.n_from_both << " from both, " << info.n_pairs << " pairs, " << info.n_sets << " colour sets" << std::endl;
+    return 0;
+}
+
 // sbwt pseudoalign: one line per read in input order -- the read's 0-based number, then the ids of its colours, ascending,
 // separated by single spaces
 int pseudoalign_main(int argc, char **argv) {
@@ -1252,7 +1338,7 @@ int pseudoalign_main(int argc, char **argv) {
     return 0;
 }
 
-const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "set-op", "read-hits", "build-colors", "compress-colors", "pseudoalign"};
+const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "set-op", "read-hits", "build-colors", "compress-colors", "merge-colors", "pseudoalign"};
 
 void print_help(char **argv) {
     std::cerr << "Available commands: " << std::endl;
@@ -1287,6 +1373,7 @@ int main(int argc, char **argv) {   // sbwt.cpp:19-57
         else if (command == "read-hits") return read_hits_main(argc, argv);
         else if (command == "build-colors") return build_colors_main(argc, argv);
         else if (command == "compress-colors") return compress_colors_main(argc, argv);
+        else if (command == "merge-colors") return merge_colors_main(argc, argv);
         else if (command == "pseudoalign") return pseudoalign_main(argc, argv);
         else throw std::runtime_error("Invalid command: " + command);
     } catch (const std::runtime_error &e) {

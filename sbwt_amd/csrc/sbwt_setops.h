@@ -10,8 +10,9 @@ long long sbwt_setops_scratch_bytes(long long n_nodes, int k);
 // The keys of the real columns of an index, in column order = ascending key order, no duplicates: the builder's format
 // (sbwt_build.hip: char i of the k-mer at bits 2i; 8 bytes each for k <= 32, 16 for 32 < k <= 64).  *d_keys is a device
 // allocation of its own that the caller frees (never null on success).  Synchronises `stream`.  On failure nothing is left
-// allocated.
-hipError_t sbwt_setops_keys(const SbwtIndexView &ix, void **d_keys, long long *n_keys, hipStream_t stream);
+// allocated.  With d_cols: *d_cols is a second allocation of the caller's, the column of every key (4 bytes each).
+hipError_t sbwt_setops_keys(const SbwtIndexView &ix, void **d_keys, long long *n_keys, hipStream_t stream,
+                            unsigned **d_cols = nullptr);
 
 struct SbwtSetopCounts {
     long long n_a = 0, n_b = 0, n_both = 0, n_either = 0, n_result = 0;

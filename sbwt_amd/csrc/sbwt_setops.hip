@@ -16,7 +16,8 @@
 //      dummy's window holds bits that mean nothing.  A real column's k-1 predecessors never are the root (that is what real
 //      means), every window of length <= k that a real column combines lies within them, so its key never contains such bits.
 //      Only the real columns' keys leave this file.
-//   4  real flags -> exclusive scan (sbwt_scan.h) -> the keys compacted in column order = ascending key order
+//   4  real flags -> exclusive scan (sbwt_scan.h) -> the keys compacted in column order = ascending key order; on request
+//      the column of every key beside it (sbwt_colormerge.hip gathers per-column data through it)
 //
 // Merge and select (sbwt_setops_merge): rocprim::merge by key with the origin (0 = a, 1 = b) as the value -- no sort of any
 // kind.  Each list is duplicate-free, so a run of equal keys in the merged order has length 1 or 2; the first element of a run
@@ -68,9 +69,12 @@ __global__ void __launch_bounds__(256) k_so_real(i64 n, const unsigned char *__r
 }
 template <typename KT>
 __global__ void __launch_bounds__(256) k_so_gather(i64 n, const SoState<KT> *__restrict__ st, const unsigned char *__restrict__ lev,
-                                                   const i64 *__restrict__ pos, KT *__restrict__ keys) {
+                                                   const i64 *__restrict__ pos, KT *__restrict__ keys, unsigned *__restrict__ cols) {
     const i64 v = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (v < n && lev[v] == 0) keys[pos[v]] = st[v].w;
+    if (v < n && lev[v] == 0) {
+        keys[pos[v]] = st[v].w;
+        if (cols) cols[pos[v]] = (unsigned)v;
+    }
 }
 
 // ---- merge and select ----
@@ -138,7 +142,7 @@ static void so_scan(const i64 *in, i64 n, i64 *bsum, i64 *out, hipStream_t strea
     } while (0)
 
 template <typename KT>
-static hipError_t setops_keys_t(const SbwtIndexView &ix, void **d_keys, long long *n_keys, hipStream_t stream) {
+static hipError_t setops_keys_t(const SbwtIndexView &ix, void **d_keys, long long *n_keys, hipStream_t stream, unsigned **d_cols) {
     const bool mega = ix.n_mega > 1 || ix.force_mega;
     const i64 n = ix.n_nodes;
     const int k = ix.k;
@@ -147,6 +151,7 @@ static hipError_t setops_keys_t(const SbwtIndexView &ix, void **d_keys, long lon
     hipError_t e = hipSuccess;
     char *base = nullptr;
     KT *keys = nullptr;
+    unsigned *cols = nullptr;
     unsigned *pred = nullptr;
     unsigned char *lev = nullptr;
     SoState<KT> *st[2] = {nullptr, nullptr};
@@ -155,6 +160,7 @@ static hipError_t setops_keys_t(const SbwtIndexView &ix, void **d_keys, long lon
     int cur = 0, m = 1, top = 0;
     *d_keys = nullptr;
     *n_keys = 0;
+    if (d_cols) *d_cols = nullptr;
     SO_TRY(hipMalloc((void **)&base, (size_t)L.bytes));
     pred = reinterpret_cast<unsigned *>(base + L.pred);
     lev = reinterpret_cast<unsigned char *>(base + L.lev);
@@ -188,13 +194,16 @@ static hipError_t setops_keys_t(const SbwtIndexView &ix, void **d_keys, long lon
     SO_TRY(hipMemcpyAsync(&nk, pos + n, 8, hipMemcpyDeviceToHost, stream));
     SO_TRY(hipStreamSynchronize(stream));
     SO_TRY(hipMalloc((void **)&keys, (size_t)(nk ? nk : 1) * sizeof(KT)));
+    if (d_cols) SO_TRY(hipMalloc((void **)&cols, (size_t)(nk ? nk : 1) * 4));
     hipLaunchKernelGGL(k_so_gather<KT>, dim3(g), dim3(256), 0, stream, n, (const SoState<KT> *)st[cur], (const unsigned char *)lev,
-                       (const i64 *)pos, keys);
+                       (const i64 *)pos, keys, cols);
     SO_TRY(hipGetLastError());
     SO_TRY(hipStreamSynchronize(stream));
     *d_keys = keys;
     *n_keys = nk;
+    if (d_cols) *d_cols = cols;
     keys = nullptr;
+    cols = nullptr;
 done:
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(stream);
@@ -202,10 +211,11 @@ done:
     }
     (void)hipFree(base);
     (void)hipFree(keys);
+    (void)hipFree(cols);
     return e;
 }
-hipError_t sbwt_setops_keys(const SbwtIndexView &ix, void **d_keys, long long *n_keys, hipStream_t stream) {
-    return ix.k <= 32 ? setops_keys_t<u64>(ix, d_keys, n_keys, stream) : setops_keys_t<u128>(ix, d_keys, n_keys, stream);
+hipError_t sbwt_setops_keys(const SbwtIndexView &ix, void **d_keys, long long *n_keys, hipStream_t stream, unsigned **d_cols) {
+    return ix.k <= 32 ? setops_keys_t<u64>(ix, d_keys, n_keys, stream, d_cols) : setops_keys_t<u128>(ix, d_keys, n_keys, stream, d_cols);
 }
 
 template <typename KT>

@@ -25,6 +25,7 @@
 #include "sbwt_readhits.h"
 #include "sbwt_colors.h"
 #include "sbwt_colorsets.h"
+#include "sbwt_colormerge.h"
 
 namespace {
 
@@ -3695,6 +3696,61 @@ int sbwtgpu_index_kmer_keys(const sbwtgpu_index *idx, void *out_keys, int64_t ca
         return fail(SBWTGPU_ERR_INVALID_ARG, "k-mer keys: %lld keys of %d bytes need %lld bytes, cap_bytes is %lld", n, kb, n * kb,
                     (long long)cap_bytes);
     if (n > 0) HIP_TRY(hipMemcpy(out_keys, keys.p, (size_t)(n * kb), hipMemcpyDeviceToHost));
+    return SBWTGPU_OK;
+}
+
+// ---- colour sets carried onto another index (sbwt_colormerge.hip) ---------------------------------------
+int sbwtgpu_colorsets_merge(const sbwtgpu_index *u, const sbwtgpu_colorsets *sa, const sbwtgpu_colorsets *sb, int color_offset_b,
+                            sbwtgpu_colorsets **out, sbwtgpu_colorsets_merge_info *info) {
+    if (info) memset(info, 0, sizeof(*info));
+    if (out) *out = nullptr;
+    if (!u || !sa || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set merge: NULL argument (u, sa and out are needed)");
+    int rc = colorsets_check(sa);
+    if (rc == SBWTGPU_OK && sb) rc = colorsets_check(sb);
+    if (rc != SBWTGPU_OK) return rc;
+    const sbwtgpu_index *a = sa->base.idx, *b = sb ? sb->base.idx : nullptr;
+    if (u->h.n_nodes >= ((int64_t)1 << 31))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set merge: u has %lld columns, a colour-set object needs fewer than 2^31 columns",
+                    (long long)u->h.n_nodes);
+    if (u->h.k != a->h.k || (b && b->h.k != a->h.k))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set merge: the indexes differ in k (u %lld, a %lld, b %lld)", (long long)u->h.k,
+                    (long long)a->h.k, (long long)(b ? b->h.k : a->h.k));
+    if ((rc = setop_check_index(u, "colour-set merge, u")) != SBWTGPU_OK) return rc;
+    if (a != u && (rc = setop_check_index(a, "colour-set merge, a")) != SBWTGPU_OK) return rc;
+    if (b && b != u && b != a && (rc = setop_check_index(b, "colour-set merge, b")) != SBWTGPU_OK) return rc;
+    if (u->device != a->device || (b && b->device != a->device))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set merge: the indexes are on different devices (u %d, a %d, b %d)", u->device,
+                    a->device, b ? b->device : a->device);
+    if (color_offset_b < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set merge: color_offset_b must not be negative, not %d", color_offset_b);
+    if (!sb && color_offset_b != 0)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set merge: color_offset_b = %d without sb (it must be 0 then)", color_offset_b);
+    const int64_t n_colors_out = std::max<int64_t>(sa->base.n_colors, sb ? (int64_t)color_offset_b + sb->base.n_colors : 0);
+    if (n_colors_out > SBWTGPU_MAX_COLORS)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set merge: color_offset_b %d + %d colours of b = %lld colours, more than %d",
+                    color_offset_b, sb ? sb->base.n_colors : 0, (long long)n_colors_out, SBWTGPU_MAX_COLORS);
+    DeviceGuard guard(u->device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", u->device);
+    sbwtgpu_colorsets *s = colorsets_new(u, (int)n_colors_out);
+    if (!s) return fail(SBWTGPU_ERR_OOM, "out of host memory");
+    SbwtCmSide A{a->view()}, B{a->view()};
+    A.d_ids = sa->d_ids; A.d_table = sa->d_table; A.n_sets = sa->n_sets; A.words = sa->base.words;
+    if (sb) { B.ix = b->view(); B.d_ids = sb->d_ids; B.d_table = sb->d_table; B.n_sets = sb->n_sets; B.words = sb->base.words; }
+    SbwtCmInfo ci;
+    Stream st;
+    long long n_sets = 0;
+    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
+    if (e == hipSuccess)
+        e = sbwt_colormerge(u->view(), A, sb ? &B : nullptr, u == a ? 1 : (b && u == b) ? 2 : 0, b == a, color_offset_b, s->base.words,
+                            &s->d_ids, &s->d_table, &n_sets, &ci, st.s);
+    s->n_sets = n_sets;
+    if (e == hipSuccess) e = colorsets_count(s, st.s);
+    if (e != hipSuccess) return colorsets_hip_failed(s, e);
+    if (info) {
+        info->n_real_u = ci.n_real_u; info->n_from_a = ci.n_from_a; info->n_from_b = ci.n_from_b; info->n_from_both = ci.n_from_both;
+        info->n_pairs = ci.n_pairs; info->n_sets = ci.n_sets;
+        for (int i = 0; i < 4; i++) info->pass_ms[i] = ci.pass_ms[i];
+    }
+    *out = s;
     return SBWTGPU_OK;
 }
 
