@@ -403,6 +403,7 @@ int  sbwtgpu_ms_workspace_stats(const void *d_workspace, void *stream, int64_t s
  * SBWTGPU_ERR_OOM leaves the index usable.  Rank-only indexes: SBWTGPU_ERR_INVALID_ARG.  An index with no real column
  * gives 0 unitigs.  Thread-safe on an immutable handle like the query calls (a call owns its stream and its scratch). */
 typedef struct sbwtgpu_unitigs sbwtgpu_unitigs;
+typedef struct sbwtgpu_colorsets sbwtgpu_colorsets;     /* (described with the colour sets, below) */
 int  sbwtgpu_unitigs_create(const sbwtgpu_index *idx, sbwtgpu_unitigs **out);      /* device-resident result */
 /* n_kmers = the sum of (length of unitig i) - k + 1 = the index's n_kmers */
 int  sbwtgpu_unitigs_info(const sbwtgpu_unitigs *u, int64_t *n_unitigs, int64_t *total_bases, int64_t *n_kmers);
@@ -417,6 +418,43 @@ int  sbwtgpu_unitigs_copy(const sbwtgpu_unitigs *u, char *bases, int64_t *off, i
  * pointer-jumping rounds */
 int  sbwtgpu_unitigs_stats(const sbwtgpu_unitigs *u, double pass_ms[6], int64_t *jump_rounds);
 void sbwtgpu_unitigs_destroy(sbwtgpu_unitigs *u);
+
+/* ---- coloured unitigs: unitigs cut where the colour set changes ----
+ * The maximal paths on which every k-mer carries the same colour set, each with the id of that set: what a coloured index
+ * exports (a FASTA file and a table of sets).  The input is a colour-set object s of an index (declared further down); the
+ * terms real column, out-neighbours, in-neighbours, spelling, order and strands are those of sbwtgpu_unitigs_create.
+ *
+ *   S(v)            for a real column v the set s means for it: the row table[ids[v]].  Two columns have the same set when
+ *                   their rows are equal word for word; equal ids are sufficient but not necessary (an uploaded object may
+ *                   hold duplicate rows).
+ *   internal edge   v -> w with outdeg(v) = 1, indeg(w) = 1 and S(v) = S(w).
+ *   colour break    v -> w with outdeg(v) = 1, indeg(w) = 1 and S(v) != S(w).  n_color_breaks counts them.
+ *   coloured unitig a maximal sequence of distinct real columns joined by (coloured) internal edges.
+ *   start           v is a start unless it has exactly one in-neighbour u, outdeg(u) = 1 and S(u) = S(v).
+ *   pure cycle      a component of coloured internal edges with no start, so all of its columns carry one set.  It starts at
+ *                   its smallest column and is not closed again.
+ *   cycle with a break  a cycle of plain internal edges with at least one colour break is not a pure cycle: its pieces start
+ *                   at the targets of the breaks, and a piece may run across the place where the plain unitig was cut.
+ *   empty set       real columns with the empty set (id 0) form coloured unitigs like any other set.  Nothing is dropped:
+ *                   the sum of (length - k + 1) over the result is n_kmers.
+ *   set id          of unitig i: ids[first_col[i]].  For an object in canonical form it is the id of the set; for one with
+ *                   duplicate rows, the id its first column happens to carry.
+ *   order           ascending column of the first k-mer.
+ *   determinism     the output is a function of the index, the matrix the object means and, for set_id only, its ids:
+ *                   byte-identical between runs, image levels, layouts and devices.
+ *   no breaks       if every real column carries the same set, bases, offsets and first columns equal those of
+ *                   sbwtgpu_unitigs_create byte for byte.
+ *
+ * The object knows its index (as in sbwtgpu_pseudoalign_sets_*); the index must outlive the call, the result does not
+ * reference the colour-set object afterwards.  sbwtgpu_unitigs_info, _dev, _copy, _stats and _destroy serve the handle as they
+ * serve a plain one (the set-id gather is booked under pass [4]); the three calls below on a handle of sbwtgpu_unitigs_create:
+ * SBWTGPU_ERR_INVALID_ARG.  Refused with SBWTGPU_ERR_INVALID_ARG: NULL arguments and what sbwtgpu_unitigs_create refuses for
+ * the object's index.  Scratch stays 38 bytes per column (ids and table are read in place), the result grows by 4 bytes per
+ * unitig.  SBWTGPU_ERR_OOM leaves index and object usable.  Thread-safe on immutable handles. */
+int  sbwtgpu_unitigs_create_colored(const sbwtgpu_colorsets *s, sbwtgpu_unitigs **out);
+int  sbwtgpu_unitigs_set_ids_dev (const sbwtgpu_unitigs *u, const uint32_t **d_set_id /* n_unitigs */);
+int  sbwtgpu_unitigs_set_ids_copy(const sbwtgpu_unitigs *u, uint32_t *set_id);
+int  sbwtgpu_unitigs_color_info  (const sbwtgpu_unitigs *u, int64_t *n_color_breaks, int64_t *n_sets, int32_t *n_colors);
 
 /* ---- set operations on two indexes: union, intersection, difference, symmetric difference ----
  * The columns of an index are its k-mers in sorted order, so two indexes combine without their input sequences and without
@@ -650,8 +688,8 @@ int  sbwtgpu_pseudoalign_wide_dev(const sbwtgpu_colors *c, const char *d_bases, 
  * Refusals (SBWTGPU_ERR_INVALID_ARG with a message that names the cause): those of the colour calls above (rank-only indexes,
  * 2^31 columns or more, ranges, an object of another index, NULL pointers) and, for create, every broken invariant but the
  * dummy columns' ids, which it sets to 0.  SBWTGPU_ERR_OOM leaves index and inputs usable.
- * Concurrency: the queries (pseudoalign_sets_batch / _dev, expand, info, copy) are thread-safe on one object. */
-typedef struct sbwtgpu_colorsets sbwtgpu_colorsets;
+ * Concurrency: the queries (pseudoalign_sets_batch / _dev, expand, info, copy) are thread-safe on one object.
+ * (The type is declared with the unitigs above, whose coloured call takes one.) */
 
 /* any colours object, W = 1 included */
 int  sbwtgpu_colorsets_compress(const sbwtgpu_colors *c, sbwtgpu_colorsets **out);

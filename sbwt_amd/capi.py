@@ -46,7 +46,8 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_index_build_lcs", "sbwtgpu_index_get_lcs", "sbwtgpu_matching_statistics_batch", "sbwtgpu_ms_workspace_bytes",
     "sbwtgpu_matching_statistics_dev", "sbwtgpu_ms_workspace_stats",
     "sbwtgpu_unitigs_create", "sbwtgpu_unitigs_info", "sbwtgpu_unitigs_dev", "sbwtgpu_unitigs_copy", "sbwtgpu_unitigs_stats",
-    "sbwtgpu_unitigs_destroy",
+    "sbwtgpu_unitigs_destroy", "sbwtgpu_unitigs_create_colored", "sbwtgpu_unitigs_set_ids_dev", "sbwtgpu_unitigs_set_ids_copy",
+    "sbwtgpu_unitigs_color_info",
     "sbwtgpu_index_setop", "sbwtgpu_index_setop_counts", "sbwtgpu_index_kmer_keys",
     "sbwtgpu_read_hits_batch", "sbwtgpu_read_hits_workspace_bytes", "sbwtgpu_read_hits_dev",
     "sbwtgpu_colors_create", "sbwtgpu_colors_destroy", "sbwtgpu_colors_add_batch", "sbwtgpu_colors_info", "sbwtgpu_colors_copy",
@@ -239,6 +240,10 @@ def lib() -> C.CDLL:
         L.sbwtgpu_unitigs_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i64)]
         L.sbwtgpu_unitigs_destroy.argtypes = [vp]
         L.sbwtgpu_unitigs_destroy.restype = None
+        L.sbwtgpu_unitigs_create_colored.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_unitigs_set_ids_dev.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_unitigs_set_ids_copy.argtypes = [vp, vp]
+        L.sbwtgpu_unitigs_color_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_int32)]
         L.sbwtgpu_index_setop.argtypes = [vp, vp, ci, ci, C.POINTER(PlainMatrixBitsC), C.POINTER(SetopInfoC)]
         L.sbwtgpu_index_setop_counts.argtypes = [vp, vp, C.POINTER(SetopInfoC)]
         L.sbwtgpu_index_kmer_keys.argtypes = [vp, vp, i64, C.POINTER(i64), C.POINTER(ci)]
@@ -753,6 +758,25 @@ class Unitigs:
         return {"pass_ms": dict(zip(names, (float(x) for x in ms))), "jump_rounds": int(r.value)}
 
 
+    # ---- a coloured handle only (ColorSets.unitigs_dev) ----
+    def set_ids_dev(self) -> int:
+        """d_set_id (n_unitigs uint32) as an integer; valid until close()."""
+        p = C.c_void_p()
+        _check(lib().sbwtgpu_unitigs_set_ids_dev(self._h, C.byref(p)))
+        return p.value or 0
+
+    def set_ids(self) -> np.ndarray:
+        """uint32[n_unitigs]: the colour-set id of every unitig (the id of its first column)."""
+        set_id = np.empty(self.n_unitigs, dtype=np.uint32)
+        _check(lib().sbwtgpu_unitigs_set_ids_copy(self._h, set_id.ctypes.data))
+        return set_id
+
+    def color_info(self) -> dict:
+        nb, ns, nc = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        _check(lib().sbwtgpu_unitigs_color_info(self._h, C.byref(nb), C.byref(ns), C.byref(nc)))
+        return {"n_color_breaks": int(nb.value), "n_sets": int(ns.value), "n_colors": int(nc.value)}
+
+
 class Colors:
     """Owns an sbwtgpu_colors handle: the colour matrix of an index (one uint64 row per column, bit c = reference c holds the
     column's k-mer) and pseudoalignment over it.  The index must stay alive as long as the object (it is kept referenced)."""
@@ -1027,6 +1051,17 @@ class ColorSets:
         a, b = C.c_void_p(), C.c_void_p()
         _check(lib().sbwtgpu_colorsets_dev(self._h, C.byref(a), C.byref(b)))
         return a.value or 0, b.value or 0
+
+    def unitigs_dev(self) -> "Unitigs":
+        """sbwtgpu_unitigs_create_colored: the unitigs of the index cut where the colour set changes, device-resident."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_unitigs_create_colored(self._h, C.byref(h)))
+        return Unitigs(h)
+
+    def unitigs(self):
+        """(bases, off, first_col, set_id): Index.unitigs() of the coloured unitigs, and uint32[n] the set id of each."""
+        with self.unitigs_dev() as u:
+            return u.copy() + (u.set_ids(),)
 
     def expand(self) -> "WideColors":
         """sbwtgpu_colorsets_expand: the wide colours object this one means."""

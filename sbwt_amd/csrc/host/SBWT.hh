@@ -479,6 +479,35 @@ public:
         detail::gpu_check(rc);
         return r;
     }
+    // the coloured unitigs of the index under a colour-set object of it (include/sbwtgpu.h): unitigs cut where the colour
+    // set changes; set_id[i] = the object's id of unitig i's first column.  The object is one of THIS index.
+    struct ColoredUnitigs {
+        std::vector<char> bases;
+        std::vector<int64_t> off, first_col;
+        std::vector<uint32_t> set_id;
+        int64_t n_color_breaks = 0, n_sets = 0;
+        int32_t n_colors = 0;
+    };
+    ColoredUnitigs colored_unitigs(const sbwtgpu_colorsets *sets) const {
+        need_device();
+        sbwtgpu_unitigs *u = nullptr;
+        detail::gpu_check(sbwtgpu_unitigs_create_colored(sets, &u));
+        ColoredUnitigs r;
+        int64_t n = 0, total = 0;
+        int rc = sbwtgpu_unitigs_info(u, &n, &total, nullptr);
+        if (rc == SBWTGPU_OK) {
+            r.bases.resize((size_t)total);
+            r.off.resize((size_t)n + 1);
+            r.first_col.resize((size_t)n);
+            r.set_id.resize((size_t)n);
+            rc = sbwtgpu_unitigs_copy(u, r.bases.data(), r.off.data(), r.first_col.data());
+        }
+        if (rc == SBWTGPU_OK) rc = sbwtgpu_unitigs_set_ids_copy(u, r.set_id.data());
+        if (rc == SBWTGPU_OK) rc = sbwtgpu_unitigs_color_info(u, &r.n_color_breaks, &r.n_sets, &r.n_colors);
+        sbwtgpu_unitigs_destroy(u);
+        detail::gpu_check(rc);
+        return r;
+    }
     // Set operations on the k-mer sets of two indexes (include/sbwtgpu.h: SBWTGPU_SETOP_UNION, _INTERSECTION, _DIFFERENCE = a
     // minus b, _SYMMETRIC_DIFFERENCE): the columns of the result, bit for bit what the builder gives for the result's k-mers.
     // Both indexes on one device, the same k, 2 <= k <= 64.  `info` (optional) receives the counts and pass times.

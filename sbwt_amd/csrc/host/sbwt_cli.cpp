@@ -777,13 +777,18 @@ int read_hits_main(int argc, char **argv) {
 }
 
 // sbwt dump-unitigs: the index turned back into sequence -- FASTA, one record per unitig in the order of the API (ascending
-// first column), the header the unitig's number
+// first column), the header the unitig's number.  With --colors the unitigs are cut where the colour set changes and the
+// header is "number set-id" (dump_unitigs_colored, below the colour helpers); --sets-out writes the table of the sets.
+int dump_unitigs_colored(const plain_matrix_sbwt_t &index, const string &indexfile, const string &colorsfile, const string &outfile,
+                         const string &setsfile, bool gzip);
 int dump_unitigs_main(int argc, char **argv) {
     set_log_level(LogLevel::MINOR);
     Options opts({
         {"out-file", 'o', true, "Output FASTA filename.", ""},
         {"index-file", 'i', true, "Index input file.", ""},
         {"gzip-output", 'z', false, "Writes output in gzipped form.", ""},
+        {"colors", 0, true, "Colour file or colour-set file of the index: cut the unitigs where the colour set changes; headers become `>number set-id`.", ""},
+        {"sets-out", 0, true, "With --colors: write one line per set id -- the id, then its colours, ascending.", ""},
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"help", 'h', false, "Print usage", ""},
     });
@@ -793,8 +798,13 @@ int dump_unitigs_main(int argc, char **argv) {
         exit(1);
     }
     const string indexfile = opts.get("index-file"), outfile = opts.get("out-file");
+    const bool colored = opts.count("colors");
+    if (opts.count("sets-out") && !colored) throw std::runtime_error("Error: --sets-out needs --colors");
+    const string colorsfile = colored ? opts.get("colors") : string(), setsfile = opts.count("sets-out") ? opts.get("sets-out") : string();
     check_readable(indexfile);
+    if (colored) check_readable(colorsfile);
     check_writable(outfile);
+    if (!setsfile.empty()) check_writable(setsfile);
     set_default_device(atoi(opts.get("gpu").c_str()));
     std::ifstream in(indexfile, std::ios::binary);
     if (!in.good()) throw std::runtime_error("Error opening file: " + indexfile);
@@ -803,6 +813,7 @@ int dump_unitigs_main(int argc, char **argv) {
         throw std::runtime_error("Error: only the plain-matrix variant is supported by the GPU path (got " + variant + ")");
     plain_matrix_sbwt_t index;
     index.load(in);
+    if (colored) return dump_unitigs_colored(index, indexfile, colorsfile, outfile, setsfile, opts.count("gzip-output"));
     const plain_matrix_sbwt_t::Unitigs u = index.unitigs();
     const int64_t n = (int64_t)u.first_col.size();
     string text;
@@ -1157,6 +1168,53 @@ void load_colorsets(const string &colorsfile, const string &indexfile, const pla
         throw std::runtime_error(sbwthost_last_error());
     colors_check(sbwtgpu_colors_create_wide(index.device_handle(), (int)n_colors, rows.data(), &col.h));
     colors_check(sbwtgpu_colorsets_compress(col.h, &out.h));
+}
+
+// dump-unitigs --colors: coloured unitigs as FASTA, the header "number set-id" (a parser that takes the id up to the first
+// blank still sees the number); --sets-out: line i = "i c1 c2 ..." for set id i = 0 .. n_sets - 1, the line of set 0 is "0"
+int dump_unitigs_colored(const plain_matrix_sbwt_t &index, const string &indexfile, const string &colorsfile, const string &outfile,
+                         const string &setsfile, bool gzip) {
+    ColorSetsHandle sets;
+    load_colorsets(colorsfile, indexfile, index, sets);
+    const plain_matrix_sbwt_t::ColoredUnitigs u = index.colored_unitigs(sets.h);
+    const int64_t n = (int64_t)u.first_col.size();
+    string text;
+    text.reserve(u.bases.size() + (size_t)n * 20);
+    for (int64_t i = 0; i < n; i++) {
+        text.push_back('>');
+        append_int(i, text);
+        text.push_back(' ');
+        append_int((int64_t)u.set_id[(size_t)i], text);
+        text.push_back('\n');
+        text.append(u.bases.data() + u.off[(size_t)i], (size_t)(u.off[(size_t)i + 1] - u.off[(size_t)i]));
+        text.push_back('\n');
+    }
+    if (sbwthost_write_file(outfile.c_str(), text.data(), (int64_t)text.size(), gzip ? 1 : 0, 0) != 0)
+        throw std::runtime_error(string("Error writing ") + outfile + ": " + sbwthost_last_error());
+    if (!setsfile.empty()) {
+        int32_t words = 0;
+        int64_t n_columns = 0, n_sets = 0;
+        colors_check(sbwtgpu_colorsets_info(sets.h, &n_columns, nullptr, nullptr, &words, &n_sets, nullptr, nullptr));
+        vector<uint32_t> ids((size_t)n_columns);
+        vector<uint64_t> table((size_t)(n_sets * words));
+        colors_check(sbwtgpu_colorsets_copy(sets.h, ids.data(), table.data()));
+        string lines;
+        for (int64_t i = 0; i < n_sets; i++) {
+            append_int(i, lines);
+            for (int w = 0; w < words; w++)
+                for (uint64_t bits = table[(size_t)(i * words + w)]; bits; bits &= bits - 1) {
+                    lines.push_back(' ');
+                    append_int((int64_t)w * 64 + __builtin_ctzll(bits), lines);
+                }
+            lines.push_back('\n');
+        }
+        if (sbwthost_write_file(setsfile.c_str(), lines.data(), (int64_t)lines.size(), 0, 0) != 0)
+            throw std::runtime_error(string("Error writing ") + setsfile + ": " + sbwthost_last_error());
+    }
+    write_log("Wrote " + std::to_string(n) + " coloured unitigs, " + std::to_string(u.bases.size()) + " bases, " +
+                  std::to_string(u.n_color_breaks) + " colour breaks, " + std::to_string(u.n_sets) + " colour sets",
+              LogLevel::MAJOR);
+    return 0;
 }
 
 // sbwt merge-colors: the colour sets of one or two coloured indexes carried onto index U (the output of `sbwt set-op`, for

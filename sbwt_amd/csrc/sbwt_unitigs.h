@@ -17,6 +17,8 @@ struct SbwtUnitigRun {
     char *d_bases = nullptr;                // total_bases bytes
     long long *d_off = nullptr;             // n_unitigs + 1
     long long *d_first_col = nullptr;       // n_unitigs
+    unsigned *d_set_id = nullptr;           // n_unitigs: ids[first column], a coloured run only
+    long long n_color_breaks = 0;           // single edges between two sets (a coloured run only)
     long long n_unitigs = 0, total_bases = 0;
     int jump_rounds = 0;                    // launches of the pointer-jumping kernel
     float ms[SBWT_UT_N_PASSES] = {0, 0, 0, 0, 0, 0};
@@ -28,4 +30,8 @@ long long sbwt_unitigs_scratch_bytes(long long n_nodes);
 // has_marks: the blocks carry suffix-group marks (given or derived); otherwise they are derived into the scratch.
 // Synchronises `stream` between passes (it reads two counts and a flag per jump round back).  hipSuccess, or the error of
 // the call that failed (hipErrorOutOfMemory: a result could not be allocated); on failure nothing is left allocated.
-hipError_t sbwt_unitigs_run(const SbwtIndexView &ix, int has_marks, void *d_scratch, SbwtUnitigRun *run, hipStream_t stream);
+// A colour view (d_ids: n_nodes ids, d_table: rows of `words` words, both read in place) selects the coloured run of DESIGN.md
+// section 18: unitigs end where the colour set changes, run->d_set_id and run->n_color_breaks are filled.  d_ids == nullptr
+// is the plain run.
+hipError_t sbwt_unitigs_run(const SbwtIndexView &ix, int has_marks, void *d_scratch, SbwtUnitigRun *run, hipStream_t stream,
+                            const unsigned *d_ids = nullptr, const unsigned long long *d_table = nullptr, int words = 0);

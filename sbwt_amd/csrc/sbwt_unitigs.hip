@@ -20,7 +20,10 @@
 //      scan -> 64-bit offsets into the bases
 //   6  every real column stores its last character at off[id(head)] + k - 1 + rank; every start walks k-1 predecessors for the
 //      first k-1 characters of its label
-// No lane loops over a unitig: the longest loop of a lane is k steps.  Columns are 32-bit unsigned as in the image.
+// A coloured run (d_ids given) cuts where the colour set changes: passes 3 and 5 take an edge for
+// internal only if both ends carry the same set, pass 5 gathers the set id of every unitig.  Passes 1, 2, 4 and 6 are the same.
+// No lane loops over a unitig: the longest loop of a lane is k steps (or the words of a row across a candidate break).
+// Columns are 32-bit unsigned as in the image.
 //
 // Pass 6 scatters single bytes instead of filling an order[] array first and streaming it out: a scattered store moves a whole
 // sector whether it carries one byte or four, so the array would add a 4-byte write and a 4-byte read per column on top of the
@@ -82,16 +85,42 @@ __device__ __forceinline__ bool ut_single_out(const SbwtIndexView &ix, const uns
     for (int c = 0; c < 4; c++) deg += (int)((quad_bits(blk[c]) >> (p & 63)) & 1ull);
     return deg == 1;
 }
+// the colour view of a coloured run (section 18): the ids and the table of a colour-set object, read in place
+struct UtColors {
+    const unsigned *__restrict__ ids;      // n_nodes
+    const u64 *__restrict__ table;         // n_sets x words
+    int words;
+};
+// do columns a and b carry the same set?  Equal ids do; otherwise the two rows decide, word for word (an uploaded object may
+// hold one row twice).  Called across single edges only, so the rows are read where a break is possible, not per column.
+__device__ __forceinline__ bool ut_same_set(const UtColors &cs, i64 a, i64 b) {
+    const unsigned ia = cs.ids[a], ib = cs.ids[b];
+    if (ia == ib) return true;
+    const u64 *ra = cs.table + (i64)ia * cs.words, *rb = cs.table + (i64)ib * cs.words;
+    for (int w = 0; w < cs.words; w++)
+        if (ra[w] != rb[w]) return false;
+    return true;
+}
+// COLORED: an edge is internal only if both ends carry the same set; the others of the single edges are the colour breaks,
+// counted per wave into *n_breaks
+template <bool COLORED>
 __global__ void __launch_bounds__(256) k_ut_link(SbwtIndexView ix, const unsigned *__restrict__ pred, const unsigned char *__restrict__ lev,
-                                                 const u64 *__restrict__ marks, uint4 *__restrict__ st, int *__restrict__ open) {
+                                                 const u64 *__restrict__ marks, uint4 *__restrict__ st, int *__restrict__ open,
+                                                 UtColors cs, unsigned long long *__restrict__ n_breaks) {
     const i64 v = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (v >= ix.n_nodes) return;
+    if (v >= ix.n_nodes) return;                             // (whole waves, or the upper lanes of the last one)
     uint4 s;
+    bool brk = false;
     if (lev[v] != 0) {
         s = make_uint4(UT_NONE, 0u, UT_NONE, UT_DUMMY);
     } else {
         const i64 p = (i64)pred[v];
-        if (ut_single_out(ix, lev, marks, p)) {
+        bool internal = ut_single_out(ix, lev, marks, p);
+        if constexpr (COLORED) {
+            brk = internal && !ut_same_set(cs, p, v);
+            internal = internal && !brk;
+        }
+        if (internal) {
             s = make_uint4((unsigned)p, 0u, (unsigned)v, UT_OPEN);
             *open = 1;
         } else {
@@ -99,6 +128,10 @@ __global__ void __launch_bounds__(256) k_ut_link(SbwtIndexView ix, const unsigne
         }
     }
     st[v] = s;
+    if constexpr (COLORED) {
+        const u64 b = __ballot(brk);
+        if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_breaks, (unsigned long long)__popcll(b));   // (lane 0 outlives the return above)
+    }
 }
 
 // ---- pass 4 ----
@@ -134,11 +167,12 @@ __global__ void __launch_bounds__(256) k_ut_starts(i64 n, const uint4 *__restric
     const uint4 s = st[v];
     flag[v] = (s.w == UT_RANKED && s.y == 0u) ? 1 : 0;
 }
-// the start of a unitig notes its column, the tail (no internal edge out, or one back to the head: a cut cycle) its length
-template <bool MEGA>
+// the start of a unitig notes its column, the tail (no internal edge out, or one back to the head: a cut cycle) its length.
+// COLORED: a single edge into another set is no internal edge either.
+template <bool MEGA, bool COLORED>
 __global__ void __launch_bounds__(256) k_ut_lengths(SbwtIndexView ix, const unsigned char *__restrict__ lev, const u64 *__restrict__ marks,
                                                     const uint4 *__restrict__ st, const i64 *__restrict__ uid,
-                                                    i64 *__restrict__ first_col, i64 *__restrict__ len) {
+                                                    i64 *__restrict__ first_col, i64 *__restrict__ len, UtColors cs) {
     const i64 v = (i64)blockIdx.x * 256 + threadIdx.x;
     if (v >= ix.n_nodes) return;
     const uint4 s = st[v];
@@ -154,8 +188,20 @@ __global__ void __launch_bounds__(256) k_ut_lengths(SbwtIndexView ix, const unsi
             if ((quad_bits(q) >> (v & 63)) & 1ull) w = (i64)quad_rank<MEGA>(ix, q, v, c);
         }
         tail = w == (i64)s.x;
+        if constexpr (COLORED) {
+            if (!tail && w >= 0 && w < ix.n_nodes) tail = !ut_same_set(cs, v, w);
+        }
     }
     if (tail) len[uid[s.x]] = (i64)s.y + 1 + (ix.k - 1);
+}
+
+// the set id of a coloured unitig is the id of its first column
+__global__ void __launch_bounds__(256) k_ut_setids(const unsigned *__restrict__ ids, i64 n_nodes, const i64 *__restrict__ first_col,
+                                                   i64 n_unitigs, unsigned *__restrict__ set_id) {
+    const i64 u = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (u >= n_unitigs) return;
+    const i64 v = first_col[u];
+    set_id[u] = (v >= 0 && v < n_nodes) ? ids[v] : 0u;
 }
 
 // ---- pass 6 ----
@@ -214,7 +260,8 @@ static void ut_scan(const i64 *in, i64 n, i64 *bsum, i64 *out, hipStream_t strea
         if (e != hipSuccess) goto done;   \
     } while (0)
 
-hipError_t sbwt_unitigs_run(const SbwtIndexView &ix, int has_marks, void *d_scratch, SbwtUnitigRun *run, hipStream_t stream) {
+hipError_t sbwt_unitigs_run(const SbwtIndexView &ix, int has_marks, void *d_scratch, SbwtUnitigRun *run, hipStream_t stream,
+                            const unsigned *d_ids, const unsigned long long *d_table, int words) {
     const bool mega = ix.n_mega > 1 || ix.force_mega;
     const i64 n = ix.n_nodes;
     const UtLayout L(n);
@@ -225,6 +272,10 @@ hipError_t sbwt_unitigs_run(const SbwtIndexView &ix, int has_marks, void *d_scra
     uint4 *st[2] = {reinterpret_cast<uint4 *>(base + L.st0), reinterpret_cast<uint4 *>(base + L.st1)};
     i64 *bsum = reinterpret_cast<i64 *>(base + L.bsum);
     int *open = reinterpret_cast<int *>(base + L.ctl);
+    unsigned long long *n_breaks = reinterpret_cast<unsigned long long *>(base + L.ctl + 8);   // (the memset of `open` zeroes it)
+    const bool colored = d_ids != nullptr;
+    const UtColors cs = {d_ids, reinterpret_cast<const u64 *>(d_table), words};
+    unsigned long long h_breaks = 0;
     const unsigned g = grid_for(n);
     hipEvent_t ev[SBWT_UT_N_PASSES + 1] = {};
     hipError_t e = hipSuccess;
@@ -249,12 +300,15 @@ hipError_t sbwt_unitigs_run(const SbwtIndexView &ix, int has_marks, void *d_scra
     }
 
     UT_TRY(hipEventRecord(ev[SBWT_UT_PASS_LINK], stream));
-    hipLaunchKernelGGL(k_ut_link, dim3(g), dim3(256), 0, stream, ix, (const unsigned *)pred, (const unsigned char *)lev,
-                       (const u64 *)marks, st[0], open);
+    if (colored) hipLaunchKernelGGL(k_ut_link<true>, dim3(g), dim3(256), 0, stream, ix, (const unsigned *)pred, (const unsigned char *)lev,
+                                    (const u64 *)marks, st[0], open, cs, n_breaks);
+    else hipLaunchKernelGGL(k_ut_link<false>, dim3(g), dim3(256), 0, stream, ix, (const unsigned *)pred, (const unsigned char *)lev,
+                            (const u64 *)marks, st[0], open, cs, n_breaks);
 
     UT_TRY(hipEventRecord(ev[SBWT_UT_PASS_RANK], stream));
     while (((i64)1 << max_rounds) < n) max_rounds++;
     UT_TRY(hipMemcpyAsync(&h_open, open, sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (colored) UT_TRY(hipMemcpyAsync(&h_breaks, n_breaks, 8, hipMemcpyDeviceToHost, stream));
     UT_TRY(hipStreamSynchronize(stream));
     for (int r = 0; h_open && r < max_rounds; r++) {
         UT_TRY(hipMemsetAsync(open, 0, sizeof(int), stream));
@@ -276,10 +330,21 @@ hipError_t sbwt_unitigs_run(const SbwtIndexView &ix, int has_marks, void *d_scra
     UT_TRY(hipStreamSynchronize(stream));
     UT_TRY(hipMalloc((void **)&run->d_off, (size_t)(n_unitigs + 1) * 8));
     UT_TRY(hipMalloc((void **)&run->d_first_col, (size_t)(n_unitigs ? n_unitigs : 1) * 8));
-    if (mega) hipLaunchKernelGGL(k_ut_lengths<true>, dim3(g), dim3(256), 0, stream, ix, (const unsigned char *)lev, (const u64 *)marks,
-                                 (const uint4 *)st[cur], (const i64 *)uid, run->d_first_col, flag);
-    else hipLaunchKernelGGL(k_ut_lengths<false>, dim3(g), dim3(256), 0, stream, ix, (const unsigned char *)lev, (const u64 *)marks,
-                            (const uint4 *)st[cur], (const i64 *)uid, run->d_first_col, flag);
+    if (colored) UT_TRY(hipMalloc((void **)&run->d_set_id, (size_t)(n_unitigs ? n_unitigs : 1) * 4));
+#define UT_LENGTHS(M, C)                                                                                                             \
+    hipLaunchKernelGGL((k_ut_lengths<M, C>), dim3(g), dim3(256), 0, stream, ix, (const unsigned char *)lev, (const u64 *)marks,      \
+                       (const uint4 *)st[cur], (const i64 *)uid, run->d_first_col, flag, cs)
+    if (colored) {
+        if (mega) UT_LENGTHS(true, true);
+        else UT_LENGTHS(false, true);
+        if (n_unitigs > 0)
+            hipLaunchKernelGGL(k_ut_setids, dim3(grid_for(n_unitigs)), dim3(256), 0, stream, d_ids, n, (const i64 *)run->d_first_col,
+                               n_unitigs, run->d_set_id);
+    } else {
+        if (mega) UT_LENGTHS(true, false);
+        else UT_LENGTHS(false, false);
+    }
+#undef UT_LENGTHS
     ut_scan(flag, n_unitigs, bsum, run->d_off, stream);
     UT_TRY(hipMemcpyAsync(&total, run->d_off + n_unitigs, 8, hipMemcpyDeviceToHost, stream));
     UT_TRY(hipStreamSynchronize(stream));
@@ -298,6 +363,7 @@ hipError_t sbwt_unitigs_run(const SbwtIndexView &ix, int has_marks, void *d_scra
     for (int i = 0; i < SBWT_UT_N_PASSES; i++) UT_TRY(hipEventElapsedTime(&run->ms[i], ev[i], ev[i + 1]));
     run->n_unitigs = n_unitigs;
     run->total_bases = total;
+    run->n_color_breaks = (long long)h_breaks;
 done:
     for (int i = 0; i <= SBWT_UT_N_PASSES; i++)
         if (ev[i]) (void)hipEventDestroy(ev[i]);
@@ -307,6 +373,7 @@ done:
         if (run->d_bases) (void)hipFree(run->d_bases);
         if (run->d_off) (void)hipFree(run->d_off);
         if (run->d_first_col) (void)hipFree(run->d_first_col);
+        if (run->d_set_id) (void)hipFree(run->d_set_id);
         *run = SbwtUnitigRun();
     }
     return e;

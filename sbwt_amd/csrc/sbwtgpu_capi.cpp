@@ -2561,11 +2561,15 @@ struct sbwtgpu_unitigs {
     int device = 0;
     int64_t k = 0;
     SbwtUnitigRun run;
+    // a coloured handle (sbwtgpu_unitigs_create_colored): what its colour-set object said of itself
+    bool colored = false;
+    int64_t n_sets = 0;
+    int n_colors = 0;
 };
 
-int sbwtgpu_unitigs_create(const sbwtgpu_index *idx, sbwtgpu_unitigs **out) {
-    if (!idx || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *out = nullptr;
+// the plain call, or with a colour view (ids, table, words) the coloured one
+static int unitigs_create_common(const sbwtgpu_index *idx, const unsigned *d_ids, const unsigned long long *d_table, int words,
+                                 int64_t n_sets, int n_colors, sbwtgpu_unitigs **out) {
     if (idx->h.rank_only) return fail(SBWTGPU_ERR_INVALID_ARG, "%s", RANK_ONLY_MSG);
     if (idx->h.k < 2) return fail(SBWTGPU_ERR_INVALID_ARG, "unitigs need k >= 2");
     if (idx->h.n_nodes >= ((int64_t)1 << 32) - ((int64_t)1 << 24))
@@ -2575,11 +2579,15 @@ int sbwtgpu_unitigs_create(const sbwtgpu_index *idx, sbwtgpu_unitigs **out) {
     if (!u) return fail(SBWTGPU_ERR_OOM, "out of host memory");
     u->device = idx->device;
     u->k = idx->h.k;
+    u->colored = d_ids != nullptr;
+    u->n_sets = n_sets;
+    u->n_colors = n_colors;
     DevBuf scratch;
     Stream st;
     hipError_t e = scratch.alloc((size_t)sbwt_unitigs_scratch_bytes(idx->h.n_nodes));
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = sbwt_unitigs_run(idx->view(), idx->h.has_ssup || idx->h.ssup_derived, scratch.p, &u->run, st.s);
+    if (e == hipSuccess)
+        e = sbwt_unitigs_run(idx->view(), idx->h.has_ssup || idx->h.ssup_derived, scratch.p, &u->run, st.s, d_ids, d_table, words);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         delete u;
@@ -2595,12 +2603,19 @@ int sbwtgpu_unitigs_create(const sbwtgpu_index *idx, sbwtgpu_unitigs **out) {
     return SBWTGPU_OK;
 }
 
+int sbwtgpu_unitigs_create(const sbwtgpu_index *idx, sbwtgpu_unitigs **out) {
+    if (!idx || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    return unitigs_create_common(idx, nullptr, nullptr, 0, 0, 0, out);
+}
+
 void sbwtgpu_unitigs_destroy(sbwtgpu_unitigs *u) {
     if (!u) return;
     DeviceGuard guard(u->device);
     if (u->run.d_bases) (void)hipFree(u->run.d_bases);
     if (u->run.d_off) (void)hipFree(u->run.d_off);
     if (u->run.d_first_col) (void)hipFree(u->run.d_first_col);
+    if (u->run.d_set_id) (void)hipFree(u->run.d_set_id);
     delete u;
 }
 
@@ -2635,6 +2650,39 @@ int sbwtgpu_unitigs_stats(const sbwtgpu_unitigs *u, double pass_ms[6], int64_t *
     if (pass_ms)
         for (int i = 0; i < SBWT_UT_N_PASSES; i++) pass_ms[i] = (double)u->run.ms[i];
     if (jump_rounds) *jump_rounds = u->run.jump_rounds;
+    return SBWTGPU_OK;
+}
+
+static int unitigs_check_colored(const sbwtgpu_unitigs *u) {
+    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    if (!u->colored)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "unitigs: a handle of sbwtgpu_unitigs_create carries no colours (sbwtgpu_unitigs_create_colored does)");
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_unitigs_set_ids_dev(const sbwtgpu_unitigs *u, const uint32_t **d_set_id) {
+    const int rc = unitigs_check_colored(u);
+    if (rc != SBWTGPU_OK) return rc;
+    if (!d_set_id) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *d_set_id = reinterpret_cast<const uint32_t *>(u->run.d_set_id);
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_unitigs_set_ids_copy(const sbwtgpu_unitigs *u, uint32_t *set_id) {
+    const int rc = unitigs_check_colored(u);
+    if (rc != SBWTGPU_OK) return rc;
+    if (!set_id && u->run.n_unitigs > 0) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    DeviceGuard guard(u->device);
+    if (u->run.n_unitigs > 0) HIP_TRY(hipMemcpy(set_id, u->run.d_set_id, (size_t)u->run.n_unitigs * 4, hipMemcpyDeviceToHost));
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_unitigs_color_info(const sbwtgpu_unitigs *u, int64_t *n_color_breaks, int64_t *n_sets, int32_t *n_colors) {
+    const int rc = unitigs_check_colored(u);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_color_breaks) *n_color_breaks = u->run.n_color_breaks;
+    if (n_sets) *n_sets = u->n_sets;
+    if (n_colors) *n_colors = u->n_colors;
     return SBWTGPU_OK;
 }
 
@@ -3399,6 +3447,15 @@ int sbwtgpu_colorsets_dev(const sbwtgpu_colorsets *s, const uint32_t **d_ids, co
     if (d_ids) *d_ids = reinterpret_cast<const uint32_t *>(s->d_ids);
     if (d_table) *d_table = reinterpret_cast<const uint64_t *>(s->d_table);
     return SBWTGPU_OK;
+}
+
+// coloured unitigs (sbwt_unitigs.hip with a colour view): the object's ids and table are read in place during the call only
+int sbwtgpu_unitigs_create_colored(const sbwtgpu_colorsets *s, sbwtgpu_unitigs **out) {
+    if (!s || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    const int rc = colorsets_check(s);
+    if (rc != SBWTGPU_OK) return rc;
+    return unitigs_create_common(s->base.idx, s->d_ids, s->d_table, s->base.words, s->n_sets, s->base.n_colors, out);
 }
 
 int sbwtgpu_pseudoalign_sets_dev(const sbwtgpu_colorsets *s, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
