@@ -791,6 +791,44 @@ typedef struct { int64_t n_real_u, n_from_a, n_from_b, n_from_both, n_pairs, n_s
 int  sbwtgpu_colorsets_merge(const sbwtgpu_index *u, const sbwtgpu_colorsets *sa, const sbwtgpu_colorsets *sb /* may be NULL */,
                              int color_offset_b, sbwtgpu_colorsets **out, sbwtgpu_colorsets_merge_info *info /* may be NULL */);
 
+/* ---- shared k-mers: how many k-mers each pair of references shares ----
+ * A colour-set object s of an index of n columns has C = n_colors, W = ceil(C / 64), n_sets, ids and table.
+ *   - Set sizes: size[t] = #{ j : ids[j] = t } for 0 <= t < n_sets.  Dummy columns carry id 0, so size[0] counts them
+ *     together with the uncoloured real columns; the sizes sum to n.
+ *   - Weights: w[t] = size[t] by default, or a caller-supplied int64 with 0 <= w[t] <= 2^31 - 1.  w[0] is ignored (it is
+ *     not even checked): row 0 is the empty set.
+ *   - The shared matrix: G[a][b] = the sum of w[t] over the sets t >= 1 whose table row has bits a and b both set, for
+ *     0 <= a, b < C.  int64, C x C, row-major, exact: there is no floating point anywhere.
+ * With the default weights G[a][b] is the number of index k-mers that references a and b both hold, G[a][a] the number of
+ * k-mers of reference a, and G is symmetric (it is with any weights).  Every k-mer distance (Jaccard, containment, ...) is
+ * host arithmetic on G.  The result depends on what the object means only: an uploaded object with duplicate rows, unused
+ * rows or another numbering gives the G of its canonical form (an unused row has size 0).  Two calls give identical bytes.
+ * Objects of fewer than "gram_mfma_min_sets" sets (sbwtgpu_set_tuning; default 512, 0 = always, a huge value = never) take
+ * a plain kernel, larger ones the matrix cores (v_mfma_i32_16x16x64_i8 over 7-bit limbs of the weights, 32-bit sums added
+ * into the 64-bit matrix every "gram_flush_sets" sets at the latest: default 65536, rounded down to a multiple of 64 and
+ * at least 64; a value v with 127 v >= 2^31, or below 1, is refused).  Results never depend on either key.
+ * sbwtgpu_shared_info: n_sets_used = the sets t >= 1 with w[t] > 0; used_mfma = 1 for the matrix-core route; n_limbs = the
+ * 7-bit limbs of the largest weight (0 .. 5); pass_ms on the host clock: sizes, transpose and compaction (weights, sort,
+ * limbs, bit planes), product, mirror with copy.
+ * The _dev form takes device pointers (d_weights_or_null: n_sets int64; d_matrix: C x C int64, every entry is written;
+ * the workspace of sbwtgpu_colorsets_shared_workspace_bytes(s) bytes, 256-byte aligned), is asynchronous on `stream` and
+ * never synchronises.  It cannot report an out-of-range weight through its return value: the first 64-bit word of the
+ * workspace is a status word, all ones when every weight was in range, otherwise the smallest offending set -- such a
+ * weight was taken as 0, and the matrix is not to be used.  Read it after the stream has finished.
+ * Refusals (SBWTGPU_ERR_INVALID_ARG with a message that names the cause): NULL s or output; a weight that is negative or
+ * above 2^31 - 1 (checked on the device; the message names the smallest offending set); a workspace that is too small.
+ * Scratch of the host form, released before it returns: the matrix (8 C^2 bytes), the weights when given (8 n_sets), and
+ * the workspace: with S = n_sets and P = C, both rounded up to 64, 21 S + S P / 8 + 8 P^2 bytes and the radix sort's
+ * storage on the matrix-core route, 4 S on the plain route.  SBWTGPU_ERR_OOM leaves index and object usable.
+ * Thread-safe on one object: a call owns its stream and its scratch. */
+int     sbwtgpu_colorsets_set_sizes(const sbwtgpu_colorsets *s, int64_t *sizes_out /* n_sets */);
+typedef struct { int64_t n_sets_used; int32_t n_colors, words, used_mfma, n_limbs; double pass_ms[4]; } sbwtgpu_shared_info;
+int     sbwtgpu_colorsets_shared_kmers(const sbwtgpu_colorsets *s, const int64_t *weights_or_null /* n_sets */,
+                                       int64_t *matrix_out /* n_colors x n_colors */, sbwtgpu_shared_info *info_or_null);
+int64_t sbwtgpu_colorsets_shared_workspace_bytes(const sbwtgpu_colorsets *s);
+int     sbwtgpu_colorsets_shared_kmers_dev(const sbwtgpu_colorsets *s, const int64_t *d_weights_or_null, int64_t *d_matrix,
+                                           void *d_workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,8 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_colorsets_builder_create", "sbwtgpu_colorsets_builder_add_batch", "sbwtgpu_colorsets_builder_info",
     "sbwtgpu_colorsets_builder_finish", "sbwtgpu_colorsets_builder_destroy",
     "sbwtgpu_colorsets_merge",
+    "sbwtgpu_colorsets_set_sizes", "sbwtgpu_colorsets_shared_kmers", "sbwtgpu_colorsets_shared_workspace_bytes",
+    "sbwtgpu_colorsets_shared_kmers_dev",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -142,6 +144,17 @@ class ColorsetsMergeInfoC(C.Structure):
     def as_dict(self) -> dict:
         d = {f: int(getattr(self, f)) for f in ("n_real_u", "n_from_a", "n_from_b", "n_from_both", "n_pairs", "n_sets")}
         d["pass_ms"] = dict(zip(("keys", "locate_gather", "pairs_rows", "canonical"), (float(x) for x in self.pass_ms)))
+        return d
+
+
+class SharedInfoC(C.Structure):
+    """sbwtgpu_shared_info: what one shared-k-mers call did."""
+    _fields_ = [("n_sets_used", C.c_int64), ("n_colors", C.c_int32), ("words", C.c_int32), ("used_mfma", C.c_int32),
+                ("n_limbs", C.c_int32), ("pass_ms", C.c_double * 4)]
+
+    def as_dict(self) -> dict:
+        d = {f: int(getattr(self, f)) for f in ("n_sets_used", "n_colors", "words", "used_mfma", "n_limbs")}
+        d["pass_ms"] = dict(zip(("sizes", "transpose_compact", "product", "mirror_copy"), (float(x) for x in self.pass_ms)))
         return d
 
 
@@ -286,6 +299,11 @@ def lib() -> C.CDLL:
         L.sbwtgpu_colorsets_builder_destroy.argtypes = [vp]
         L.sbwtgpu_colorsets_builder_destroy.restype = None
         L.sbwtgpu_colorsets_merge.argtypes = [vp, vp, vp, ci, C.POINTER(vp), C.POINTER(ColorsetsMergeInfoC)]
+        L.sbwtgpu_colorsets_set_sizes.argtypes = [vp, vp]
+        L.sbwtgpu_colorsets_shared_kmers.argtypes = [vp, vp, vp, C.POINTER(SharedInfoC)]
+        L.sbwtgpu_colorsets_shared_workspace_bytes.argtypes = [vp]
+        L.sbwtgpu_colorsets_shared_workspace_bytes.restype = i64
+        L.sbwtgpu_colorsets_shared_kmers_dev.argtypes = [vp, vp, vp, vp, i64, vp]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -1068,6 +1086,37 @@ class ColorSets:
         h = C.c_void_p()
         _check(lib().sbwtgpu_colorsets_expand(self._h, C.byref(h)))
         return WideColors(h, self.index, self.n_colors)
+
+    def set_sizes(self) -> np.ndarray:
+        """sbwtgpu_colorsets_set_sizes: int64[n_sets], the columns that carry each set (entry 0: dummy and uncoloured columns)."""
+        out = np.full(self.n_sets, -12345, dtype=np.int64)
+        _check(lib().sbwtgpu_colorsets_set_sizes(self._h, out.ctypes.data))
+        return out
+
+    def shared_kmers(self, weights=None) -> np.ndarray:
+        """sbwtgpu_colorsets_shared_kmers: int64[n_colors, n_colors], G[a][b] = the sum over the sets that hold colours a and
+        b of the set's weight -- by default its size, so that G[a][b] is the number of index k-mers references a and b share;
+        or weights, n_sets integers in 0 .. 2^31 - 1 (entry 0 is ignored).  The call's info is left in self.shared_info."""
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.int64)
+            if w.shape != (self.n_sets,):
+                raise SbwtGpuError(ERR_INVALID_ARG, "weights of shape %s, the object has %d sets" % (w.shape, self.n_sets))
+        out = np.full((self.n_colors, self.n_colors), -12345, dtype=np.int64)
+        info = SharedInfoC()
+        _check(lib().sbwtgpu_colorsets_shared_kmers(self._h, w.ctypes.data if w is not None else None, out.ctypes.data, C.byref(info)))
+        self.shared_info = info.as_dict()
+        return out
+
+    def shared_workspace_bytes(self) -> int:
+        """sbwtgpu_colorsets_shared_workspace_bytes: the workspace shared_kmers_dev needs for this object."""
+        return int(lib().sbwtgpu_colorsets_shared_workspace_bytes(self._h))
+
+    def shared_kmers_dev(self, d_weights: int, d_matrix: int, d_ws: int, ws_bytes: int, stream: int = 0) -> None:
+        """sbwtgpu_colorsets_shared_kmers_dev (raw device pointers; d_weights 0 = the set sizes): asynchronous on stream.  The
+        first int64 of the workspace is -1 afterwards unless a weight was out of range (then: the smallest such set)."""
+        _check(lib().sbwtgpu_colorsets_shared_kmers_dev(self._h, d_weights or None, d_matrix or None, d_ws or None, ws_bytes,
+                                                        stream or None))
 
     def pseudoalign(self, bases, read_off, both_strands: bool = False, threshold_ppm: int = 1_000_000, denominator: int = 0,
                     counts: bool = False):

@@ -11,6 +11,7 @@
 //               colour-set file of one id per column and the distinct colour sets; --compress --stream: the same file, built
 //               one reference at a time without the wide matrix on the device)
 //   sbwt compress-colors -i <index> -c <colours> -o <colour sets>
+//   sbwt color-matrix -i <index> -c <colours> -o <shared.tsv> [--jaccard-ppm]
 //               the colour-set file of a colour file written with or without --wide
 //   sbwt merge-colors -u <index U> -a <index A> --colors-a <colours of A> [-b <index B> --colors-b <colours of B>]
 //               [--color-offset <n>] -o <colour sets of U>
@@ -1170,6 +1171,61 @@ void load_colorsets(const string &colorsfile, const string &indexfile, const pla
     colors_check(sbwtgpu_colorsets_compress(col.h, &out.h));
 }
 
+// floor(shared * 10^6 / (ka + kb - shared)) in 128-bit integers, 0 where the denominator is 0: no floats, so the text is stable
+int64_t jaccard_ppm(int64_t shared, int64_t ka, int64_t kb) {
+    const __int128 den = (__int128)ka + (__int128)kb - (__int128)shared;
+    if (den <= 0) return 0;
+    return (int64_t)((__int128)shared * 1000000 / den);
+}
+
+// sbwt color-matrix: the k-mers each pair of references shares (sbwtgpu_colorsets_shared_kmers), C lines of C tab-separated
+// integers; --jaccard-ppm: the Jaccard index of each pair in parts per million instead
+int color_matrix_main(int argc, char **argv) {
+    set_log_level(LogLevel::MINOR);
+    Options opts({
+        {"index-file", 'i', true, "Index input file.", ""},
+        {"colors-file", 'c', true, "Colour file of the index (sbwt build-colors with or without --wide or --compress, compress-colors, merge-colors).", ""},
+        {"out-file", 'o', true, "Output file: line a holds the shared k-mer counts of reference a with every reference, tab-separated.", ""},
+        {"jaccard-ppm", 0, false, "Write floor(10^6 * shared / (k-mers of a + k-mers of b - shared)) instead of the counts (0 where both have none).", ""},
+        {"gpu", 0, true, "HIP device to run on.", "0"},
+        {"help", 'h', false, "Print usage", ""},
+    });
+    opts.parse(argc, argv);
+    if (argc == 1 || opts.count("help")) {
+        std::cerr << opts.help(argv[0], "Count the k-mers that each pair of references shares.") << std::endl;
+        exit(1);
+    }
+    const string indexfile = opts.get("index-file"), colorsfile = opts.get("colors-file"), outfile = opts.get("out-file");
+    const bool jaccard = opts.count("jaccard-ppm") > 0;
+    check_readable(indexfile);
+    check_readable(colorsfile);
+    check_writable(outfile);
+    set_default_device(atoi(opts.get("gpu").c_str()));
+    plain_matrix_sbwt_t index;
+    load_plain_matrix(indexfile, index);
+    ColorSetsHandle sets;
+    load_colorsets(colorsfile, indexfile, index, sets);
+    int32_t n_colors = 0;
+    colors_check(sbwtgpu_colorsets_info(sets.h, nullptr, nullptr, &n_colors, nullptr, nullptr, nullptr, nullptr));
+    const size_t C = (size_t)n_colors;
+    vector<int64_t> G(C * C);
+    sbwtgpu_shared_info info;
+    colors_check(sbwtgpu_colorsets_shared_kmers(sets.h, nullptr, G.data(), &info));
+    string text;
+    text.reserve(C * C * 8);
+    for (size_t a = 0; a < C; a++)
+        for (size_t b = 0; b < C; b++) {
+            append_int(jaccard ? jaccard_ppm(G[a * C + b], G[a * C + a], G[b * C + b]) : G[a * C + b], text);
+            text.push_back(b + 1 == C ? '\n' : '\t');
+        }
+    if (sbwthost_write_file(outfile.c_str(), text.data(), (int64_t)text.size(), 0, 0) != 0)
+        throw std::runtime_error(string("Error writing ") + outfile + ": " + sbwthost_last_error());
+    write_log("Wrote the shared k-mers of " + std::to_string(n_colors) + " references from " + std::to_string(info.n_sets_used) +
+                  " colour sets (" + (info.used_mfma ? "matrix cores" : "plain kernel") + ")",
+              LogLevel::MAJOR);
+    return 0;
+}
+
 // dump-unitigs --colors: coloured unitigs as FASTA, the header "number set-id" (a parser that takes the id up to the first
 // blank still sees the number); --sets-out: line i = "i c1 c2 ..." for set id i = 0 .. n_sets - 1, the line of set 0 is "0"
 int dump_unitigs_colored(const plain_matrix_sbwt_t &index, const string &indexfile, const string &colorsfile, const string &outfile,
@@ -1396,7 +1452,7 @@ int pseudoalign_main(int argc, char **argv) {
     return 0;
 }
 
-const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "set-op", "read-hits", "build-colors", "compress-colors", "merge-colors", "pseudoalign"};
+const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "set-op", "read-hits", "build-colors", "compress-colors", "merge-colors", "color-matrix", "pseudoalign"};
 
 void print_help(char **argv) {
     std::cerr << "Available commands: " << std::endl;
@@ -1432,6 +1488,7 @@ int main(int argc, char **argv) {   // sbwt.cpp:19-57
         else if (command == "build-colors") return build_colors_main(argc, argv);
         else if (command == "compress-colors") return compress_colors_main(argc, argv);
         else if (command == "merge-colors") return merge_colors_main(argc, argv);
+        else if (command == "color-matrix") return color_matrix_main(argc, argv);
         else if (command == "pseudoalign") return pseudoalign_main(argc, argv);
         else throw std::runtime_error("Invalid command: " + command);
     } catch (const std::runtime_error &e) {

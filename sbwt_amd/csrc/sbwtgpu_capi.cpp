@@ -26,6 +26,7 @@
 #include "sbwt_colors.h"
 #include "sbwt_colorsets.h"
 #include "sbwt_colormerge.h"
+#include "sbwt_colormatrix.h"
 
 namespace {
 
@@ -185,6 +186,10 @@ static int g_rh_wave_min = SBWT_RH_WAVE_MIN;
 static int64_t g_rh_chunk_bases = 0;
 static int g_rh_wide = 0;
 static int64_t g_pa_chunk_bases = 0;      // "pseudoalign_chunk_bases": 0 = the default of 64 Mi
+// shared k-mers (sbwt_colormatrix.hip): objects of this many sets or more go to the matrix cores, smaller ones to the plain
+// kernel; the sets a wave adds up in 32 bits before it adds into the 64-bit matrix.  Neither shows in a result.
+static int64_t g_gram_mfma_min_sets = SBWT_GM_MIN_SETS_DEFAULT;
+static int64_t g_gram_flush_sets = SBWT_GM_FLUSH_DEFAULT;
 // depth of the sparse (hashed) prefix table built at index creation (capped at k and at 31 = one 62-bit key)
 static int g_sparse_depth = env_int("SBWTGPU_SPARSE_PRECALC", 31);
 
@@ -291,6 +296,14 @@ int sbwtgpu_set_tuning(const char *key, int64_t value) {
     if (!strcmp(key, "read_hits_chunk_bases")) { g_rh_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "read_hits_wide")) { g_rh_wide = (int)value; return SBWTGPU_OK; }
     if (!strcmp(key, "pseudoalign_chunk_bases")) { g_pa_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
+    if (!strcmp(key, "gram_mfma_min_sets")) { g_gram_mfma_min_sets = value < 0 ? 0 : value; return SBWTGPU_OK; }
+    if (!strcmp(key, "gram_flush_sets")) {
+        if (value < 1 || value > SBWT_GM_FLUSH_MAX)
+            return fail(SBWTGPU_ERR_INVALID_ARG, "gram_flush_sets must be in 1 .. %lld, not %lld: a wave adds up products of at most 127 "
+                        "per set in 32 bits, and 127 * gram_flush_sets must stay below 2^31", (long long)SBWT_GM_FLUSH_MAX, (long long)value);
+        g_gram_flush_sets = value;
+        return SBWTGPU_OK;
+    }
     if (!strcmp(key, "sparse_depth")) {      // takes effect for indexes created afterwards
         if (value < 0 || value > 31) return fail(SBWTGPU_ERR_INVALID_ARG, "sparse_depth must be in [0,31]");
         g_sparse_depth = (int)value;
@@ -3808,6 +3821,108 @@ int sbwtgpu_colorsets_merge(const sbwtgpu_index *u, const sbwtgpu_colorsets *sa,
         for (int i = 0; i < 4; i++) info->pass_ms[i] = ci.pass_ms[i];
     }
     *out = s;
+    return SBWTGPU_OK;
+}
+
+// ---- shared k-mers: the colours' weighted Gram matrix (sbwt_colormatrix.hip) -----------------------------
+int sbwtgpu_colorsets_set_sizes(const sbwtgpu_colorsets *s, int64_t *sizes_out) {
+    if (!s || !sizes_out) return fail(SBWTGPU_ERR_INVALID_ARG, "set sizes: NULL argument (s and sizes_out are needed)");
+    const int rc = colorsets_check(s);
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(s->base.device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", s->base.device);
+    Stream st;
+    DevBuf d;
+    std::vector<uint32_t> h;
+    try { h.resize((size_t)s->n_sets); } catch (const std::bad_alloc &) { return fail(SBWTGPU_ERR_OOM, "out of host memory"); }
+    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    HIP_TRY(d.alloc((size_t)s->n_sets * 4));
+    sbwt_launch_gm_sizes(s->d_ids, s->base.n_nodes, s->n_sets, static_cast<unsigned *>(d.p), st.s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h.data(), d.p, (size_t)s->n_sets * 4, hipMemcpyDeviceToHost, st.s));
+    HIP_TRY(hipStreamSynchronize(st.s));
+    for (int64_t t = 0; t < s->n_sets; t++) sizes_out[t] = (int64_t)h[(size_t)t];
+    return SBWTGPU_OK;
+}
+
+int64_t sbwtgpu_colorsets_shared_workspace_bytes(const sbwtgpu_colorsets *s) {
+    if (!s) return 0;
+    DeviceGuard guard(s->base.device);
+    return sbwt_gm_workspace_bytes(s->n_sets, s->base.n_colors);
+}
+
+int sbwtgpu_colorsets_shared_kmers_dev(const sbwtgpu_colorsets *s, const int64_t *d_weights_or_null, int64_t *d_matrix, void *d_workspace,
+                                       int64_t workspace_bytes, void *stream) {
+    if (!s || !d_matrix || !d_workspace)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "shared k-mers: NULL argument (s, d_matrix and d_workspace are needed)");
+    const int rc = colorsets_check(s);
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(s->base.device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", s->base.device);
+    const int64_t need = sbwt_gm_workspace_bytes(s->n_sets, s->base.n_colors);
+    if (need < 0) return fail(SBWTGPU_ERR_HIP, "shared k-mers: the sort's storage size could not be asked");
+    if (workspace_bytes < need)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "shared k-mers: the workspace has %lld bytes, %lld sets of %d colours need %lld "
+                    "(sbwtgpu_colorsets_shared_workspace_bytes)", (long long)workspace_bytes, (long long)s->n_sets, s->base.n_colors,
+                    (long long)need);
+    const hipError_t e = sbwt_gm_enqueue(s->d_ids, s->base.n_nodes, s->d_table, s->n_sets, s->base.n_colors,
+                                         reinterpret_cast<const long long *>(d_weights_or_null), reinterpret_cast<long long *>(d_matrix),
+                                         d_workspace, workspace_bytes, s->n_sets >= g_gram_mfma_min_sets, g_gram_flush_sets, nullptr,
+                                         static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "shared k-mers: %s", hipGetErrorString(e));
+    }
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_colorsets_shared_kmers(const sbwtgpu_colorsets *s, const int64_t *weights_or_null, int64_t *matrix_out,
+                                   sbwtgpu_shared_info *info) {
+    if (info) memset(info, 0, sizeof(*info));
+    if (!s || !matrix_out) return fail(SBWTGPU_ERR_INVALID_ARG, "shared k-mers: NULL argument (s and matrix_out are needed)");
+    const int rc = colorsets_check(s);
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(s->base.device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", s->base.device);
+    const int C = s->base.n_colors;
+    const bool use_mfma = s->n_sets >= g_gram_mfma_min_sets;
+    const int64_t ws_bytes = sbwt_gm_workspace_bytes(s->n_sets, C);
+    if (ws_bytes < 0) return fail(SBWTGPU_ERR_HIP, "shared k-mers: the sort's storage size could not be asked");
+    const size_t m_bytes = (size_t)C * (size_t)C * 8;
+    Stream st;
+    DevBuf ws, w, m;
+    SbwtGmHeader hdr;
+    double ms[4] = {0, 0, 0, 0};
+    // (the plain route touches the header and the weights only: its workspace need not hold the planes)
+    const int64_t ws_alloc = use_mfma ? ws_bytes : sbwt_gm_plain_workspace_bytes(s->n_sets);
+    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = ws.alloc((size_t)ws_alloc);
+    if (e == hipSuccess) e = m.alloc(m_bytes);
+    if (e == hipSuccess && weights_or_null) e = w.alloc((size_t)s->n_sets * 8);
+    if (e == hipSuccess && weights_or_null) e = hipMemcpyAsync(w.p, weights_or_null, (size_t)s->n_sets * 8, hipMemcpyHostToDevice, st.s);
+    if (e == hipSuccess)
+        e = sbwt_gm_enqueue(s->d_ids, s->base.n_nodes, s->d_table, s->n_sets, C, static_cast<const long long *>(w.p),
+                            static_cast<long long *>(m.p), ws.p, ws_alloc, use_mfma, g_gram_flush_sets, ms, st.s);
+    const auto t0 = std::chrono::steady_clock::now();
+    if (e == hipSuccess) e = hipMemcpyAsync(&hdr, ws.p, sizeof(hdr), hipMemcpyDeviceToHost, st.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(st.s);
+    if (e == hipSuccess && hdr.status == ~0ull) e = hipMemcpy(matrix_out, m.p, m_bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "shared k-mers: %s", hipGetErrorString(e));
+    }
+    if (hdr.status != ~0ull)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "shared k-mers: the weight of set %llu is %lld, weights must be in 0 .. 2^31 - 1",
+                    hdr.status, (long long)weights_or_null[hdr.status]);
+    ms[3] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) {
+        info->n_sets_used = (int64_t)hdr.n_used;
+        info->n_colors = C;
+        info->words = s->base.words;
+        info->used_mfma = use_mfma ? 1 : 0;
+        for (uint64_t x = hdr.max_w; x; x >>= 7) info->n_limbs++;
+        for (int i = 0; i < 4; i++) info->pass_ms[i] = ms[i];
+    }
     return SBWTGPU_OK;
 }
 
