@@ -829,6 +829,56 @@ int64_t sbwtgpu_colorsets_shared_workspace_bytes(const sbwtgpu_colorsets *s);
 int     sbwtgpu_colorsets_shared_kmers_dev(const sbwtgpu_colorsets *s, const int64_t *d_weights_or_null, int64_t *d_matrix,
                                            void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- colour select: the k-mers whose colour set satisfies a predicate, as an index ----
+ * The core k-mers of a clade, the k-mers unique to one strain, the accessory k-mers, the k-mers held by at least p of n
+ * references: each is a sub-index of a coloured index.  sbwtgpu_index_setop cannot give them, for it needs one index per
+ * reference, and the colours exist so that those indexes need not.
+ * Inputs: a colour-set object s of an index, with C = n_colors and W = ceil(C / 64) words per row, and a predicate
+ * P = (include, exclude, min_in, max_in).  include and exclude are W-word masks, bit c at bit c & 63 of word c >> 6 as
+ * everywhere else; exclude_or_null = NULL means all zero.
+ *   - A row MATCHES exactly when (row & exclude) == 0 and min_in <= popcount(row & include) <= max_in.  Integer arithmetic,
+ *     no floating point.
+ *   - A real column j is SELECTED exactly when table[ids[j]] matches.  Row 0, the empty set, is judged like any other row:
+ *     min_in = 0 therefore selects uncoloured real columns.  Dummy columns are never selected: they have no key.
+ *   - The verdict depends on what the object MEANS: an uploaded object with duplicate or unused rows selects the same k-mers
+ *     as its canonical form.
+ *   - The RESULT is bit for bit what sbwtgpu_build_plain_matrix returns for the selected k-mers given as sequences of length
+ *     k with add_revcomp = 0 -- rows, marks, n_nodes and n_kmers (the contract of sbwtgpu_index_setop).  An empty selection
+ *     gives the root column alone.  Two calls give identical bytes.
+ * The common cases:   core of a group g       include g,   exclude none,                   min_in |g|, max_in >= |g|
+ *                     unique to g             include g,   exclude the complement within C, min_in 1,   max_in any
+ *                     accessory               include all, exclude none,                   min_in 1,   max_in C - 1
+ *                     soft core (p of g)      include g,   exclude none,                   min_in p,   max_in any
+ * Example, k = 3, colour 0 = AACCG, colour 1 = CCGGTT: AAC and ACC carry {0}, CCG carries {0, 1}, CGG, GGT and GTT carry {1}.
+ * include {0, 1}, min 2 gives {CCG}; include {0}, exclude {1}, min 1 gives {AAC, ACC}; include {0, 1}, min 1, max 1 gives
+ * {AAC, ACC, CGG, GGT, GTT}; include {0, 1}, min 0, max 0 gives {} as nothing is uncoloured.
+ * sbwtgpu_colorsets_match_sets gives the verdict per table row, match_out[t] = 1 or 0 for t < n_sets (a coloured-unitig
+ * FASTA is filtered by header with it).  sbwtgpu_colorsets_select_counts gives the counts without building;
+ * sbwtgpu_colorsets_select builds.
+ * sbwtgpu_color_select_info: n_real = the real columns of the index; n_selected; n_sets_matched = the distinct rows that
+ * match and that at least one real column carries (rows by content: the number for the canonical form); n_nopred = the
+ * selected k-mers without a predecessor among them (select only; 0 from select_counts); pass_ms on the host clock: keys;
+ * verdicts, flags and select; builder tail and columns (0 from select_counts).
+ * Colours of the result need no call of their own: make an index v from the bits and call
+ * sbwtgpu_colorsets_merge(v, s, NULL, 0, ...).
+ * Refusals (SBWTGPU_ERR_INVALID_ARG with a message that names the cause): NULL s, p, include or output; a bit at or above
+ * n_colors in either mask; min_in < 0 or max_in < min_in (a min_in above popcount(include) is legal and selects nothing);
+ * an object used with another index; and, for the two select calls, what the set operations refuse: k outside 2 .. 64, a
+ * rank-only index, the column limit.
+ * The builder's dummy limit applies unchanged: n_nopred x k > 2^26 is SBWTGPU_ERR_OOM with the counts still in info.
+ * Selections are fragmented sets and reach this limit sooner than genomes do: dump the unitigs and use the host builder.
+ * Scratch, all released before the call returns: the set operations' 37 / 69 bytes per column (k <= 32 / k <= 64) while
+ * the keys are extracted, 12 / 20 bytes per k-mer for keys and columns, 6 bytes per set, 1 byte per k-mer for the flags,
+ * 8 / 16 bytes per selected k-mer, then the builder tail's.  When more than one non-empty row matches, also 4 + 8 W bytes
+ * per such row and about 17 more while they are compared by content.  SBWTGPU_ERR_OOM leaves index and object usable.
+ * Thread-safe on immutable handles: every call owns its stream and its scratch. */
+typedef struct { const uint64_t *include; const uint64_t *exclude_or_null; int32_t min_in, max_in; } sbwtgpu_color_predicate;
+typedef struct { int64_t n_real, n_selected, n_sets_matched, n_nopred; double pass_ms[3]; } sbwtgpu_color_select_info;
+int  sbwtgpu_colorsets_match_sets(const sbwtgpu_colorsets *s, const sbwtgpu_color_predicate *p, uint8_t *match_out /* n_sets */);
+int  sbwtgpu_colorsets_select_counts(const sbwtgpu_colorsets *s, const sbwtgpu_color_predicate *p, sbwtgpu_color_select_info *info);
+int  sbwtgpu_colorsets_select(const sbwtgpu_colorsets *s, const sbwtgpu_color_predicate *p, int build_streaming_support,
+                              sbwtgpu_plain_matrix_bits *out, sbwtgpu_color_select_info *info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_colorsets_merge",
     "sbwtgpu_colorsets_set_sizes", "sbwtgpu_colorsets_shared_kmers", "sbwtgpu_colorsets_shared_workspace_bytes",
     "sbwtgpu_colorsets_shared_kmers_dev",
+    "sbwtgpu_colorsets_match_sets", "sbwtgpu_colorsets_select_counts", "sbwtgpu_colorsets_select",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -155,6 +156,22 @@ class SharedInfoC(C.Structure):
     def as_dict(self) -> dict:
         d = {f: int(getattr(self, f)) for f in ("n_sets_used", "n_colors", "words", "used_mfma", "n_limbs")}
         d["pass_ms"] = dict(zip(("sizes", "transpose_compact", "product", "mirror_copy"), (float(x) for x in self.pass_ms)))
+        return d
+
+
+class ColorPredicateC(C.Structure):
+    """sbwtgpu_color_predicate: W-word include and exclude masks (exclude may be NULL) and the two bounds."""
+    _fields_ = [("include", C.c_void_p), ("exclude_or_null", C.c_void_p), ("min_in", C.c_int32), ("max_in", C.c_int32)]
+
+
+class ColorSelectInfoC(C.Structure):
+    """sbwtgpu_color_select_info: what one colour-select call counted."""
+    _fields_ = [("n_real", C.c_int64), ("n_selected", C.c_int64), ("n_sets_matched", C.c_int64), ("n_nopred", C.c_int64),
+                ("pass_ms", C.c_double * 3)]
+
+    def as_dict(self) -> dict:
+        d = {f: int(getattr(self, f)) for f in ("n_real", "n_selected", "n_sets_matched", "n_nopred")}
+        d["pass_ms"] = dict(zip(("keys", "verdict_select", "tail_columns"), (float(x) for x in self.pass_ms)))
         return d
 
 
@@ -304,6 +321,9 @@ def lib() -> C.CDLL:
         L.sbwtgpu_colorsets_shared_workspace_bytes.argtypes = [vp]
         L.sbwtgpu_colorsets_shared_workspace_bytes.restype = i64
         L.sbwtgpu_colorsets_shared_kmers_dev.argtypes = [vp, vp, vp, vp, i64, vp]
+        L.sbwtgpu_colorsets_match_sets.argtypes = [vp, C.POINTER(ColorPredicateC), vp]
+        L.sbwtgpu_colorsets_select_counts.argtypes = [vp, C.POINTER(ColorPredicateC), C.POINTER(ColorSelectInfoC)]
+        L.sbwtgpu_colorsets_select.argtypes = [vp, C.POINTER(ColorPredicateC), ci, C.POINTER(PlainMatrixBitsC), C.POINTER(ColorSelectInfoC)]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -1117,6 +1137,59 @@ class ColorSets:
         first int64 of the workspace is -1 afterwards unless a weight was out of range (then: the smallest such set)."""
         _check(lib().sbwtgpu_colorsets_shared_kmers_dev(self._h, d_weights or None, d_matrix or None, d_ws or None, ws_bytes,
                                                         stream or None))
+
+    # ---- colour select: k-mers by a predicate over their colour sets (include/sbwtgpu.h) ----
+    def color_mask(self, colors) -> np.ndarray:
+        """uint64[W] with the bits of `colors`: an iterable of colour numbers, or a ready array of W uint64 words (taken as it
+        is; the library refuses bits at or above n_colors)."""
+        if isinstance(colors, np.ndarray) and colors.dtype == np.uint64:
+            if colors.shape != (self.words,):
+                raise SbwtGpuError(ERR_INVALID_ARG, "a colour mask of shape %s, %d colours need %d words"
+                                   % (colors.shape, self.n_colors, self.words))
+            return np.ascontiguousarray(colors)
+        mask = np.zeros(self.words, dtype=np.uint64)
+        for c in colors:
+            c = int(c)
+            if not 0 <= c < self.n_colors:
+                raise SbwtGpuError(ERR_INVALID_ARG, "colour %d in a mask, the object has %d colours" % (c, self.n_colors))
+            mask[c >> 6] |= np.uint64(1) << np.uint64(c & 63)
+        return mask
+
+    def _predicate(self, include, exclude, min_in, max_in):
+        inc = self.color_mask(include)
+        exc = self.color_mask(exclude) if exclude is not None else None
+        if max_in is None:
+            max_in = sum(bin(int(x)).count("1") for x in inc)
+            max_in = max(max_in, min_in)                    # (a min_in above popcount(include) is legal and selects nothing)
+        p = ColorPredicateC(inc.ctypes.data, exc.ctypes.data if exc is not None else None, int(min_in), int(max_in))
+        return p, (inc, exc)
+
+    def match_sets(self, include, exclude=None, min_in: int = 1, max_in: Optional[int] = None) -> np.ndarray:
+        """sbwtgpu_colorsets_match_sets: uint8[n_sets], 1 where the table row has no colour of `exclude` and between min_in
+        and max_in (default: all) colours of `include`."""
+        p, keep = self._predicate(include, exclude, min_in, max_in)
+        out = np.full(self.n_sets, 0xA5, dtype=np.uint8)
+        _check(lib().sbwtgpu_colorsets_match_sets(self._h, C.byref(p), out.ctypes.data))
+        return out
+
+    def select_counts(self, include, exclude=None, min_in: int = 1, max_in: Optional[int] = None) -> dict:
+        """sbwtgpu_colorsets_select_counts: n_real, n_selected and n_sets_matched of the predicate, nothing is built."""
+        p, keep = self._predicate(include, exclude, min_in, max_in)
+        info = ColorSelectInfoC()
+        _check(lib().sbwtgpu_colorsets_select_counts(self._h, C.byref(p), C.byref(info)))
+        return info.as_dict()
+
+    def select(self, include, exclude=None, min_in: int = 1, max_in: Optional[int] = None, streaming_support: bool = True):
+        """sbwtgpu_colorsets_select: (BuiltBits, info) of the index of the k-mers whose colour set matches.  A failed call
+        raises SbwtGpuError with the counts the call got to as its `info`."""
+        p, keep = self._predicate(include, exclude, min_in, max_in)
+        out, info = PlainMatrixBitsC(), ColorSelectInfoC()
+        rc = lib().sbwtgpu_colorsets_select(self._h, C.byref(p), int(streaming_support), C.byref(out), C.byref(info))
+        if rc != OK:
+            err = SbwtGpuError(rc, lib().sbwtgpu_last_error().decode(errors="replace"))
+            err.info = info.as_dict()
+            raise err
+        return _take_bits(out), info.as_dict()
 
     def pseudoalign(self, bases, read_off, both_strands: bool = False, threshold_ppm: int = 1_000_000, denominator: int = 0,
                     counts: bool = False):

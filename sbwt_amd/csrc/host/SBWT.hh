@@ -508,6 +508,23 @@ public:
         detail::gpu_check(rc);
         return r;
     }
+    // the k-mers of the index whose colour set satisfies the predicate, as the columns of their index (include/sbwtgpu.h,
+    // "colour select"): bit for bit what the builder gives for the selected k-mers.  The object is one of THIS index;
+    // 2 <= k <= 64.  `info` (optional) receives the counts and pass times.
+    PlainMatrixBits color_select(const sbwtgpu_colorsets *sets, const sbwtgpu_color_predicate &pred, bool streaming_support,
+                                 sbwtgpu_color_select_info *info = nullptr) const {
+        need_device();
+        sbwtgpu_plain_matrix_bits r;
+        detail::gpu_check(sbwtgpu_colorsets_select(sets, &pred, streaming_support ? 1 : 0, &r, info));
+        PlainMatrixBits out;
+        out.n_nodes = r.n_nodes; out.n_kmers = r.n_kmers; out.k = r.k;
+        const size_t nw = (size_t)((r.n_nodes + 63) / 64);
+        out.A.assign(r.A_bits, r.A_bits + nw); out.C.assign(r.C_bits, r.C_bits + nw);
+        out.G.assign(r.G_bits, r.G_bits + nw); out.T.assign(r.T_bits, r.T_bits + nw);
+        if (r.suffix_group_starts) out.ssup.assign(r.suffix_group_starts, r.suffix_group_starts + nw);
+        sbwtgpu_free_plain_matrix(&r);
+        return out;
+    }
     // Set operations on the k-mer sets of two indexes (include/sbwtgpu.h: SBWTGPU_SETOP_UNION, _INTERSECTION, _DIFFERENCE = a
     // minus b, _SYMMETRIC_DIFFERENCE): the columns of the result, bit for bit what the builder gives for the result's k-mers.
     // Both indexes on one device, the same k, 2 <= k <= 64.  `info` (optional) receives the counts and pass times.

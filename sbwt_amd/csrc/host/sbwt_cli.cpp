@@ -17,6 +17,11 @@
 //               [--color-offset <n>] -o <colour sets of U>
 //               the colour sets of A (and B, its colours moved up by the offset) carried onto U's k-mers: run set-op first,
 //               then merge-colors on its output
+//   sbwt color-select -i <index> -c <colours> [--include 0,3-5|all] [--exclude <list>] [--min <n>] [--max <n>]
+//               -o <sub-index> [--colors-out <colour sets of the sub-index>] [--counts-only]
+//               the k-mers whose colour set has none of the excluded colours and between min and max of the included ones,
+//               as an index: core (--include g --min |g|), unique (--include g --exclude the others), accessory
+//               (--max C-1), soft core (--include g --min p)
 //   sbwt pseudoalign -i <index> -c <colours> -q <query> -o <out> [-z] [--threshold 0.7] [--all-kmers] [--both-strands]
 //               one line per read: its number, then the colours that hold it
 //   sbwt build  -i <in> -o <index> -k <k> [-p <precalc>] [--add-reverse-complements]
@@ -1326,6 +1331,136 @@ int merge_colors_main(int argc, char **argv) {
     return 0;
 }
 
+// a colour list of color-select: "all", or numbers and ranges "a-b" (a <= b) separated by commas, every colour below n_colors;
+// the mask's words come back
+vector<uint64_t> parse_color_list(const string &text, const string &flag, int n_colors) {
+    vector<uint64_t> mask((size_t)(n_colors + 63) / 64, 0);
+    auto bad = [&](const string &why) {
+        return std::runtime_error("Error: malformed colour list for " + flag + " (" + why + "): '" + text + "'");
+    };
+    auto set_range = [&](int64_t lo, int64_t hi) {
+        for (int64_t c = lo; c <= hi; c++) mask[(size_t)(c >> 6)] |= 1ull << (c & 63);
+    };
+    if (text == "all") {
+        set_range(0, n_colors - 1);
+        return mask;
+    }
+    if (text.empty()) throw bad("it is empty");
+    size_t pos = 0;
+    while (pos <= text.size()) {
+        size_t end = text.find(',', pos);
+        if (end == string::npos) end = text.size();
+        const string item = text.substr(pos, end - pos);
+        const size_t dash = item.find('-');
+        const string a = item.substr(0, dash), b = dash == string::npos ? a : item.substr(dash + 1);
+        for (const string &num : {a, b}) {
+            if (num.empty() || num.size() > 9) throw bad("'" + item + "' is no number or range");
+            for (char ch : num)
+                if (ch < '0' || ch > '9') throw bad("'" + item + "' is no number or range");
+        }
+        const int64_t lo = atoll(a.c_str()), hi = atoll(b.c_str());
+        if (lo > hi) throw bad("the range '" + item + "' runs backwards");
+        if (hi >= n_colors) throw bad("colour " + std::to_string(hi) + " of " + std::to_string(n_colors) + " colours");
+        set_range(lo, hi);
+        pos = end + 1;
+    }
+    return mask;
+}
+// --min / --max of color-select: a decimal number of at most nine digits
+int parse_count(const string &text, const string &flag) {
+    bool ok = !text.empty() && text.size() <= 9;
+    for (char ch : text) ok = ok && ch >= '0' && ch <= '9';
+    if (!ok) throw std::runtime_error("Error: " + flag + " must be a non-negative integer, not '" + text + "'");
+    return atoi(text.c_str());
+}
+
+// sbwt color-select: the k-mers of a coloured index whose colour set satisfies a predicate, as the index `sbwt build` would
+// write for them (sbwtgpu_colorsets_select; serialised as set-op serialises its result); --colors-out: their colour sets on
+// that index (sbwtgpu_colorsets_merge of the input's object onto it), an "SBWTCOL3" file
+int color_select_main(int argc, char **argv) {
+    set_log_level(LogLevel::MAJOR);
+    Options opts({
+        {"index-file", 'i', true, "Index input file.", ""},
+        {"colors-file", 'c', true, "Colour file of the index (sbwt build-colors with or without --wide or --compress, compress-colors, merge-colors).", ""},
+        {"include", 0, true, "Colours that count: `all`, or numbers and ranges such as 0,3-5.", "all"},
+        {"exclude", 0, true, "Colours a selected k-mer must not have (the same syntax; default: none).", ""},
+        {"min", 0, true, "A selected k-mer has at least this many of the included colours.", "1"},
+        {"max", 0, true, "... and at most this many (default: the number of included colours).", ""},
+        {"out-file", 'o', true, "Output file for the resulting index.", ""},
+        {"colors-out", 0, true, "Also write the colour sets of the resulting index to this file.", ""},
+        {"no-streaming-support", 0, false, "Do not build the streaming query support bit vector.", ""},
+        {"precalc-length", 'p', true, "Precalculate SBWT intervals of strings of this length.", "8"},
+        {"counts-only", 0, false, "Write nothing: print `n_real n_selected n_sets_matched` to stdout.", ""},
+        {"gpu", 0, true, "HIP device to run on.", "0"},
+        {"help", 'h', false, "Print usage", ""},
+    });
+    opts.parse(argc, argv);
+    if (argc == 1 || opts.count("help")) {
+        std::cerr << opts.help(argv[0], "Select the k-mers of a coloured index by their colour sets (core, unique, accessory, soft core), as an index.") << std::endl;
+        exit(1);
+    }
+    const bool counts_only = opts.count("counts-only");
+    const string indexfile = opts.get("index-file"), colorsfile = opts.get("colors-file");
+    const string outfile = counts_only ? string() : opts.get("out-file");              // (--counts-only writes no file: no -o needed)
+    const string colors_out = (!counts_only && opts.count("colors-out")) ? opts.get("colors-out") : string();
+    check_readable(indexfile);
+    check_readable(colorsfile);
+    if (!counts_only) check_writable(outfile);
+    if (!colors_out.empty()) check_writable(colors_out);
+    set_default_device(atoi(opts.get("gpu").c_str()));
+    plain_matrix_sbwt_t index;
+    load_plain_matrix(indexfile, index);
+    ColorSetsHandle sets;
+    load_colorsets(colorsfile, indexfile, index, sets);
+    int32_t n_colors = 0;
+    colors_check(sbwtgpu_colorsets_info(sets.h, nullptr, nullptr, &n_colors, nullptr, nullptr, nullptr, nullptr));
+    const vector<uint64_t> include = parse_color_list(opts.get("include"), "--include", n_colors);
+    vector<uint64_t> exclude;
+    if (opts.count("exclude")) exclude = parse_color_list(opts.get("exclude"), "--exclude", n_colors);
+    int n_included = 0;
+    for (uint64_t w : include) n_included += __builtin_popcountll(w);
+    sbwtgpu_color_predicate pred;
+    pred.include = include.data();
+    pred.exclude_or_null = exclude.empty() ? nullptr : exclude.data();
+    pred.min_in = parse_count(opts.get("min"), "--min");
+    pred.max_in = opts.count("max") ? parse_count(opts.get("max"), "--max") : std::max(n_included, (int)pred.min_in);
+    auto log_counts = [](const sbwtgpu_color_select_info &c) {
+        write_log("color-select: " + std::to_string(c.n_selected) + " of " + std::to_string(c.n_real) + " k-mers selected, " +
+                      std::to_string(c.n_sets_matched) + " colour sets matched", LogLevel::MAJOR);
+    };
+    sbwtgpu_color_select_info info;
+    if (counts_only) {
+        colors_check(sbwtgpu_colorsets_select_counts(sets.h, &pred, &info));
+        log_counts(info);
+        std::cout << info.n_real << " " << info.n_selected << " " << info.n_sets_matched << std::endl;
+        return 0;
+    }
+    const int64_t k = index.get_k();
+    int64_t precalc = atoll(opts.get("precalc-length").c_str());
+    if (precalc > k) {
+        write_log("Warning: precalc length " + std::to_string(precalc) + " is longer than k = " + std::to_string(k), LogLevel::MAJOR);
+        write_log("Setting precalc length to " + std::to_string(k), LogLevel::MAJOR);
+        precalc = k;
+    }
+    PlainMatrixBits bits = index.color_select(sets.h, pred, !opts.count("no-streaming-support"), &info);
+    log_counts(info);
+    plain_matrix_sbwt_t sub(bits, 0);
+    {
+        std::ofstream out(outfile, std::ios::binary);
+        if (!out.good()) throw std::runtime_error("Error opening file: " + outfile);
+        serialize_string("plain-matrix", out);
+        sub.do_kmer_prefix_precalc(precalc);
+        sub.serialize(out);
+    }
+    write_log("Wrote the index to " + outfile, LogLevel::MAJOR);
+    if (!colors_out.empty()) {
+        ColorSetsHandle carried;
+        colors_check(sbwtgpu_colorsets_merge(sub.device_handle(), sets.h, nullptr, 0, &carried.h, nullptr));
+        write_colorsets(carried.h, colors_out);
+    }
+    return 0;
+}
+
 // sbwt pseudoalign: one line per read in input order -- the read's 0-based number, then the ids of its colours, ascending,
 // separated by single spaces
 int pseudoalign_main(int argc, char **argv) {
@@ -1452,7 +1587,7 @@ int pseudoalign_main(int argc, char **argv) {
     return 0;
 }
 
-const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "set-op", "read-hits", "build-colors", "compress-colors", "merge-colors", "color-matrix", "pseudoalign"};
+const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "set-op", "read-hits", "build-colors", "compress-colors", "merge-colors", "color-matrix", "color-select", "pseudoalign"};
 
 void print_help(char **argv) {
     std::cerr << "Available commands: " << std::endl;
@@ -1489,6 +1624,7 @@ int main(int argc, char **argv) {   // sbwt.cpp:19-57
         else if (command == "compress-colors") return compress_colors_main(argc, argv);
         else if (command == "merge-colors") return merge_colors_main(argc, argv);
         else if (command == "color-matrix") return color_matrix_main(argc, argv);
+        else if (command == "color-select") return color_select_main(argc, argv);
         else if (command == "pseudoalign") return pseudoalign_main(argc, argv);
         else throw std::runtime_error("Invalid command: " + command);
     } catch (const std::runtime_error &e) {

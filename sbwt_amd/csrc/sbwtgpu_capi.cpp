@@ -27,6 +27,7 @@
 #include "sbwt_colorsets.h"
 #include "sbwt_colormerge.h"
 #include "sbwt_colormatrix.h"
+#include "sbwt_colorselect.h"
 
 namespace {
 
@@ -3924,6 +3925,141 @@ int sbwtgpu_colorsets_shared_kmers(const sbwtgpu_colorsets *s, const int64_t *we
         for (int i = 0; i < 4; i++) info->pass_ms[i] = ms[i];
     }
     return SBWTGPU_OK;
+}
+
+// ---- colour select: k-mers by a predicate over their colour sets (sbwt_colorselect.hip) ------------------
+}  // extern "C"
+namespace {
+// the checks of all three calls; masks: include, then exclude (2 W words, what the kernels read)
+int colorselect_check(const sbwtgpu_colorsets *s, const sbwtgpu_color_predicate *p, bool needs_keys, std::vector<uint64_t> &masks) {
+    if (!s || !p || !p->include) return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: NULL argument (s, the predicate and its include mask are needed)");
+    int rc = colorsets_check(s);
+    if (rc != SBWTGPU_OK) return rc;
+    const int W = s->base.words, C = s->base.n_colors;
+    try { masks.assign((size_t)2 * W, 0); } catch (const std::bad_alloc &) { return fail(SBWTGPU_ERR_OOM, "out of host memory"); }
+    for (int w = 0; w < W; w++) {
+        masks[(size_t)w] = p->include[w];
+        masks[(size_t)W + w] = p->exclude_or_null ? p->exclude_or_null[w] : 0;
+    }
+    if (C & 63) {
+        const uint64_t high = ~0ull << (C & 63);
+        if (masks[(size_t)W - 1] & high)
+            return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: the include mask has a bit at or above n_colors = %d", C);
+        if (masks[(size_t)2 * W - 1] & high)
+            return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: the exclude mask has a bit at or above n_colors = %d", C);
+    }
+    if (p->min_in < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: min_in must not be negative, not %d", p->min_in);
+    if (p->max_in < p->min_in) return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: max_in = %d is below min_in = %d", p->max_in, p->min_in);
+    if (needs_keys) rc = setop_check_index(s->base.idx, "colour select");
+    return rc;
+}
+int colorselect_hip_fail(hipError_t e, const char *what) {
+    (void)hipGetLastError();
+    if (e == hipErrorUnknown)
+        return fail(SBWTGPU_ERR_HIP, "colour select, %s: the ids and the keys disagree about the selected columns (a broken object)", what);
+    return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "colour select, %s: %s", what, hipGetErrorString(e));
+}
+// keys of the index, verdicts, counts and -- with d_res -- the selected keys (a device allocation the caller owns)
+int colorselect_run(const sbwtgpu_colorsets *s, const sbwtgpu_color_predicate *p, const std::vector<uint64_t> &masks, hipStream_t st,
+                    void **d_res, sbwtgpu_color_select_info *info) {
+    const sbwtgpu_index *idx = s->base.idx;
+    const int key_bytes = idx->h.k <= 32 ? 8 : 16;
+    DevBuf keys, cols, dm;
+    long long nk = 0;
+    auto t0 = std::chrono::steady_clock::now();
+    hipError_t e = sbwt_setops_keys(idx->view(), &keys.p, &nk, st, reinterpret_cast<unsigned **>(&cols.p));
+    if (e != hipSuccess) return colorselect_hip_fail(e, "keys");
+    info->pass_ms[0] = ms_since(t0);
+    info->n_real = nk;
+    t0 = std::chrono::steady_clock::now();
+    e = dm.alloc(masks.size() * 8);
+    if (e == hipSuccess) e = hipMemcpyAsync(dm.p, masks.data(), masks.size() * 8, hipMemcpyHostToDevice, st);
+    SbwtCselCounts c;
+    if (e == hipSuccess)
+        e = sbwt_colorselect(s->d_ids, s->base.n_nodes, s->d_table, s->n_sets, s->base.words, static_cast<const unsigned long long *>(dm.p),
+                             p->min_in, p->max_in, keys.p, static_cast<const unsigned *>(cols.p), nk, key_bytes, d_res, &c, st);
+    if (e != hipSuccess) return colorselect_hip_fail(e, "verdicts and select");
+    info->pass_ms[1] = ms_since(t0);
+    info->n_selected = c.n_selected;
+    info->n_sets_matched = c.n_sets_matched;
+    return SBWTGPU_OK;
+}
+}  // namespace
+extern "C" {
+
+int sbwtgpu_colorsets_match_sets(const sbwtgpu_colorsets *s, const sbwtgpu_color_predicate *p, uint8_t *match_out) {
+    if (!match_out) return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: match_out is NULL");
+    std::vector<uint64_t> masks;
+    const int rc = colorselect_check(s, p, false, masks);
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(s->base.device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", s->base.device);
+    Stream st;
+    DevBuf dm, dv;
+    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    HIP_TRY(dm.alloc(masks.size() * 8));
+    HIP_TRY(dv.alloc((size_t)s->n_sets));
+    HIP_TRY(hipMemcpyAsync(dm.p, masks.data(), masks.size() * 8, hipMemcpyHostToDevice, st.s));
+    sbwt_launch_csel_verdict(s->d_table, s->n_sets, s->base.words, static_cast<const unsigned long long *>(dm.p), p->min_in, p->max_in,
+                             static_cast<unsigned char *>(dv.p), st.s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(match_out, dv.p, (size_t)s->n_sets, hipMemcpyDeviceToHost, st.s));
+    HIP_TRY(hipStreamSynchronize(st.s));
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_colorsets_select_counts(const sbwtgpu_colorsets *s, const sbwtgpu_color_predicate *p, sbwtgpu_color_select_info *info) {
+    if (!info) return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: info is NULL");
+    memset(info, 0, sizeof(*info));
+    std::vector<uint64_t> masks;
+    const int rc = colorselect_check(s, p, true, masks);
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(s->base.device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", s->base.device);
+    Stream st;
+    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    return colorselect_run(s, p, masks, st.s, nullptr, info);
+}
+
+int sbwtgpu_colorsets_select(const sbwtgpu_colorsets *s, const sbwtgpu_color_predicate *p, int build_streaming_support,
+                             sbwtgpu_plain_matrix_bits *out, sbwtgpu_color_select_info *info) {
+    sbwtgpu_color_select_info local;
+    if (!info) info = &local;
+    memset(info, 0, sizeof(*info));
+    if (!out) return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: out is NULL");
+    memset(out, 0, sizeof(*out));
+    std::vector<uint64_t> masks;
+    int rc = colorselect_check(s, p, true, masks);
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(s->base.device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", s->base.device);
+    Stream st;
+    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    const int64_t k = s->base.k;
+    void *d_res = nullptr;
+    rc = colorselect_run(s, p, masks, st.s, &d_res, info);
+    if (rc != SBWTGPU_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    SbwtBuildState S;
+    try {
+        const int ra = sbwt_build_from_keys(d_res, info->n_selected, (int)k, &S, st.s);     // (S owns d_res now)
+        if (ra != 0) { sbwt_build_release(&S); return fail(ra == -8 ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "colour select: builder tail"); }
+        info->n_nopred = S.n_nopred;
+        if ((long long)S.n_nopred * (long long)k > (1ll << 26)) {
+            sbwt_build_release(&S);
+            return fail(SBWTGPU_ERR_OOM, "colour select: the result has %lld predecessor-less k-mers x k = %lld dummy records (limit 2^26; "
+                        "the dummies are expanded on the host).  Selections are fragmented sets and reach this limit sooner than "
+                        "genomes do: dump the unitigs and use the host builder",
+                        (long long)S.n_nopred, (long long)S.n_nopred * (long long)k);
+        }
+        rc = (k <= 32) ? build_columns_t<unsigned long long>(S, k, build_streaming_support, out)
+                       : build_columns_t<unsigned __int128>(S, k, build_streaming_support, out);
+    } catch (const std::bad_alloc &) {
+        sbwt_build_release(&S);
+        rc = fail(SBWTGPU_ERR_OOM, "out of host memory");
+    }
+    info->pass_ms[2] = ms_since(t0);
+    return rc;
 }
 
 }  // extern "C"
