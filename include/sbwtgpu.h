@@ -456,6 +456,55 @@ int  sbwtgpu_unitigs_set_ids_dev (const sbwtgpu_unitigs *u, const uint32_t **d_s
 int  sbwtgpu_unitigs_set_ids_copy(const sbwtgpu_unitigs *u, uint32_t *set_id);
 int  sbwtgpu_unitigs_color_info  (const sbwtgpu_unitigs *u, int64_t *n_color_breaks, int64_t *n_sets, int32_t *n_colors);
 
+/* ---- the unitig graph: links between unitigs, the coordinate of every k-mer ----
+ * The unitigs above are the segments of the compacted de Bruijn graph; this adds its edges and, for every indexed k-mer, where
+ * on the segments it lies.  The terms real column, out-neighbours, unitig, start, pure cycle and order (and for a coloured
+ * run internal edge and colour break) are those of the two sections above.
+ *
+ *   link            let t_i be the last column of unitig i.  For every out-neighbour w of t_i there is one link i -> j, where j
+ *                   is the unitig whose first column is w.  Such a j always exists: the edge t_i -> w is not internal, so w is
+ *                   a start, and for a cut cycle w is the head, a first column as well.  So a cut pure cycle (A^k included)
+ *                   has the self-link i -> i, a colour break is a link, and the columns of one suffix group, each the tail of
+ *                   a unitig of its own, have the same targets.
+ *   layout          CSR: link_off[n_unitigs + 1] (int64), link_to[n_links] (uint32); the links of unitig i are
+ *                   link_to[link_off[i] .. link_off[i+1]).
+ *   order           by source unitig, within a source by edge character A < C < G < T, which is also ascending target column
+ *                   and ascending target unitig.  The targets of one source are distinct.
+ *   invariant       n_links = n_edges - (n_kmers - n_unitigs), n_edges the number of pairs (x, x[1:] + c) of indexed k-mers.
+ *   column map      for a real column v: col_unitig[v] is the number of its unitig and col_offset[v] the position r of its
+ *                   k-mer in the spelling, so bases[off[u] + r .. + k) is the label of v.  Both uint32[n_nodes]; a dummy
+ *                   column has 0xFFFFFFFF in both.
+ *   locate          cols[i] is an int64 search result; the answer is (col_unitig, col_offset) of that column, and 0xFFFFFFFF
+ *                   in both for a negative value, a value >= n_nodes and a dummy column.
+ *   determinism     a function of the index and, for a coloured run, of the matrix the object means: byte-identical between
+ *                   runs, image levels, layouts, and marks given or derived.
+ *
+ * sbwtgpu_unitigs_create_graph takes exactly one of idx (the plain run) and s (the coloured run) and the flags below; flags = 0
+ * gives what sbwtgpu_unitigs_create / _create_colored give, which take that path themselves and run no kernel of this
+ * section.  The links and the map are made from the ranking state of the same call before its scratch is freed (two flat
+ * launches and a scan for the links, one launch for the map); scratch stays 38 bytes per column, the result grows by
+ * 8 (n_unitigs + 1) + 4 n_links bytes for the links and 8 n_nodes for the map.  _info, _dev, _copy, _stats, _set_ids_*,
+ * _color_info and _destroy serve a graph handle unchanged.  The _dev pointers live as long as the handle;
+ * sbwtgpu_unitigs_locate_dev runs on the caller's stream and never synchronises, _locate_batch takes host memory.
+ * Refused with SBWTGPU_ERR_INVALID_ARG: both or neither of idx and s, unknown flag bits, a links call on a handle made without
+ * SBWTGPU_UNITIGS_LINKS, a map or locate call on one made without SBWTGPU_UNITIGS_COLUMN_MAP, NULL outputs, n < 0, and what
+ * the two create calls refuse.  SBWTGPU_ERR_OOM leaves index and object usable and nothing allocated.  The queries are
+ * thread-safe on an immutable handle. */
+#define SBWTGPU_UNITIGS_LINKS       1u
+#define SBWTGPU_UNITIGS_COLUMN_MAP  2u
+int  sbwtgpu_unitigs_create_graph(const sbwtgpu_index *idx, const sbwtgpu_colorsets *s, unsigned flags, sbwtgpu_unitigs **out);
+int  sbwtgpu_unitigs_links_info (const sbwtgpu_unitigs *u, int64_t *n_links);
+int  sbwtgpu_unitigs_links_dev  (const sbwtgpu_unitigs *u, const int64_t **d_link_off /* n_unitigs + 1 */,
+                                 const uint32_t **d_link_to /* n_links */);
+int  sbwtgpu_unitigs_links_copy (const sbwtgpu_unitigs *u, int64_t *link_off, uint32_t *link_to /* may be NULL if n_links = 0 */);
+int  sbwtgpu_unitigs_column_map_dev (const sbwtgpu_unitigs *u, const uint32_t **d_col_unitig, const uint32_t **d_col_offset);
+int  sbwtgpu_unitigs_column_map_copy(const sbwtgpu_unitigs *u, uint32_t *col_unitig, uint32_t *col_offset);   /* n_nodes each */
+int  sbwtgpu_unitigs_locate_dev  (const sbwtgpu_unitigs *u, const int64_t *d_cols, int64_t n, uint32_t *d_unitig,
+                                  uint32_t *d_offset, void *stream);
+int  sbwtgpu_unitigs_locate_batch(const sbwtgpu_unitigs *u, const int64_t *cols, int64_t n, uint32_t *unitig, uint32_t *offset);
+/* measurement aid (tools/unitig_links_bench.py): device-event times of the link passes and of the map pass in ms, like _stats */
+int  sbwtgpu_unitigs_graph_stats (const sbwtgpu_unitigs *u, double *links_ms, double *map_ms);
+
 /* ---- set operations on two indexes: union, intersection, difference, symmetric difference ----
  * The columns of an index are its k-mers in sorted order, so two indexes combine without their input sequences and without
  * a sort: the keys of the real columns of each (label extraction on the device), one merge under the operation's rule, and

@@ -26,6 +26,8 @@ ERR_NOT_SINGLETON = -7
 ERR_OOM = -8
 ERR_READ_TOO_LONG = -9
 ERR_STALLED = -10
+UNITIGS_LINKS = 1               # SBWTGPU_UNITIGS_* (sbwtgpu_unitigs_create_graph)
+UNITIGS_COLUMN_MAP = 2
 
 # every symbol include/sbwtgpu.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = [
@@ -47,7 +49,9 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_matching_statistics_dev", "sbwtgpu_ms_workspace_stats",
     "sbwtgpu_unitigs_create", "sbwtgpu_unitigs_info", "sbwtgpu_unitigs_dev", "sbwtgpu_unitigs_copy", "sbwtgpu_unitigs_stats",
     "sbwtgpu_unitigs_destroy", "sbwtgpu_unitigs_create_colored", "sbwtgpu_unitigs_set_ids_dev", "sbwtgpu_unitigs_set_ids_copy",
-    "sbwtgpu_unitigs_color_info",
+    "sbwtgpu_unitigs_color_info", "sbwtgpu_unitigs_create_graph", "sbwtgpu_unitigs_links_info", "sbwtgpu_unitigs_links_dev",
+    "sbwtgpu_unitigs_links_copy", "sbwtgpu_unitigs_column_map_dev", "sbwtgpu_unitigs_column_map_copy",
+    "sbwtgpu_unitigs_locate_dev", "sbwtgpu_unitigs_locate_batch", "sbwtgpu_unitigs_graph_stats",
     "sbwtgpu_index_setop", "sbwtgpu_index_setop_counts", "sbwtgpu_index_kmer_keys",
     "sbwtgpu_read_hits_batch", "sbwtgpu_read_hits_workspace_bytes", "sbwtgpu_read_hits_dev",
     "sbwtgpu_colors_create", "sbwtgpu_colors_destroy", "sbwtgpu_colors_add_batch", "sbwtgpu_colors_info", "sbwtgpu_colors_copy",
@@ -324,6 +328,16 @@ def lib() -> C.CDLL:
         L.sbwtgpu_colorsets_match_sets.argtypes = [vp, C.POINTER(ColorPredicateC), vp]
         L.sbwtgpu_colorsets_select_counts.argtypes = [vp, C.POINTER(ColorPredicateC), C.POINTER(ColorSelectInfoC)]
         L.sbwtgpu_colorsets_select.argtypes = [vp, C.POINTER(ColorPredicateC), ci, C.POINTER(PlainMatrixBitsC), C.POINTER(ColorSelectInfoC)]
+        # (the newest last: an older build stops here with every binding it has)
+        L.sbwtgpu_unitigs_create_graph.argtypes = [vp, vp, C.c_uint, C.POINTER(vp)]
+        L.sbwtgpu_unitigs_links_info.argtypes = [vp, C.POINTER(i64)]
+        L.sbwtgpu_unitigs_links_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        L.sbwtgpu_unitigs_links_copy.argtypes = [vp, vp, vp]
+        L.sbwtgpu_unitigs_column_map_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        L.sbwtgpu_unitigs_column_map_copy.argtypes = [vp, vp, vp]
+        L.sbwtgpu_unitigs_locate_dev.argtypes = [vp, vp, i64, vp, vp, vp]
+        L.sbwtgpu_unitigs_locate_batch.argtypes = [vp, vp, i64, vp, vp]
+        L.sbwtgpu_unitigs_graph_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -684,6 +698,14 @@ class Index:
         with self.unitigs_dev() as u:
             return u.copy()
 
+    def unitig_graph_dev(self, links: bool = True, column_map: bool = False) -> "Unitigs":
+        """sbwtgpu_unitigs_create_graph: the unitigs with their links (Unitigs.links) and / or the column map
+        (Unitigs.column_map, Unitigs.locate), device-resident."""
+        h = C.c_void_p()
+        flags = (UNITIGS_LINKS if links else 0) | (UNITIGS_COLUMN_MAP if column_map else 0)
+        _check(lib().sbwtgpu_unitigs_create_graph(self._h, None, flags, C.byref(h)))
+        return Unitigs(h, self.n_nodes)
+
     # ---- set operations on two indexes (include/sbwtgpu.h) ----
     def setop(self, other: "Index", op, streaming_support: bool = True):
         """sbwtgpu_index_setop: (BuiltBits, info) of self `op` other; op is a SETOP_* value or a name of SETOPS.  A failed
@@ -751,8 +773,9 @@ class Index:
 class Unitigs:
     """Owns an sbwtgpu_unitigs handle."""
 
-    def __init__(self, handle):
+    def __init__(self, handle, n_nodes: int = 0):
         self._h = handle
+        self.n_nodes = n_nodes                  # (a graph handle: the length of the column map)
         n, total, nk = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         _check(lib().sbwtgpu_unitigs_info(self._h, C.byref(n), C.byref(total), C.byref(nk)))
         self.n_unitigs, self.total_bases, self.n_kmers = n.value, total.value, nk.value
@@ -795,6 +818,58 @@ class Unitigs:
         names = ("pred_marks", "real_flags", "internal_edges", "pointer_jumping", "ids_offsets", "bases")
         return {"pass_ms": dict(zip(names, (float(x) for x in ms))), "jump_rounds": int(r.value)}
 
+
+    # ---- a graph handle only (Index.unitig_graph_dev, ColorSets.unitig_graph_dev) ----
+    def n_links(self) -> int:
+        n = C.c_int64(0)
+        _check(lib().sbwtgpu_unitigs_links_info(self._h, C.byref(n)))
+        return int(n.value)
+
+    def links_dev(self):
+        """(d_link_off, d_link_to) as integers; valid until close()."""
+        o, t = C.c_void_p(), C.c_void_p()
+        _check(lib().sbwtgpu_unitigs_links_dev(self._h, C.byref(o), C.byref(t)))
+        return o.value or 0, t.value or 0
+
+    def links(self):
+        """(link_off: int64[n_unitigs + 1], link_to: uint32[n_links]): unitig i links to link_to[link_off[i]:link_off[i + 1]],
+        in the order of the edge character."""
+        link_off = np.empty(self.n_unitigs + 1, dtype=np.int64)
+        link_to = np.empty(self.n_links(), dtype=np.uint32)
+        _check(lib().sbwtgpu_unitigs_links_copy(self._h, link_off.ctypes.data, link_to.ctypes.data if len(link_to) else None))
+        return link_off, link_to
+
+    def column_map_dev(self):
+        """(d_col_unitig, d_col_offset) as integers; valid until close()."""
+        a, b = C.c_void_p(), C.c_void_p()
+        _check(lib().sbwtgpu_unitigs_column_map_dev(self._h, C.byref(a), C.byref(b)))
+        return a.value or 0, b.value or 0
+
+    def column_map(self):
+        """(col_unitig, col_offset): uint32[n_nodes] each, the unitig of every column and the position of its k-mer on it;
+        0xFFFFFFFF in both for a dummy column."""
+        col_unitig = np.empty(self.n_nodes, dtype=np.uint32)
+        col_offset = np.empty(self.n_nodes, dtype=np.uint32)
+        _check(lib().sbwtgpu_unitigs_column_map_copy(self._h, col_unitig.ctypes.data, col_offset.ctypes.data))
+        return col_unitig, col_offset
+
+    def locate(self, cols):
+        """sbwtgpu_unitigs_locate_batch: (unitig, offset), uint32 each, of int64 search results; 0xFFFFFFFF for no column."""
+        cols = np.ascontiguousarray(cols, dtype=np.int64)
+        unitig = np.empty(len(cols), dtype=np.uint32)
+        offset = np.empty(len(cols), dtype=np.uint32)
+        _check(lib().sbwtgpu_unitigs_locate_batch(self._h, cols.ctypes.data, len(cols), unitig.ctypes.data, offset.ctypes.data))
+        return unitig, offset
+
+    def locate_dev(self, d_cols: int, n: int, d_unitig: int, d_offset: int, stream: int = 0) -> None:
+        """sbwtgpu_unitigs_locate_dev (raw device pointers)."""
+        _check(lib().sbwtgpu_unitigs_locate_dev(self._h, d_cols, n, d_unitig, d_offset, stream))
+
+    def graph_stats(self) -> dict:
+        """Device-event times (ms) of the link passes and of the map pass of the create call."""
+        a, b = C.c_double(0), C.c_double(0)
+        _check(lib().sbwtgpu_unitigs_graph_stats(self._h, C.byref(a), C.byref(b)))
+        return {"links_ms": float(a.value), "map_ms": float(b.value)}
 
     # ---- a coloured handle only (ColorSets.unitigs_dev) ----
     def set_ids_dev(self) -> int:
@@ -1095,6 +1170,13 @@ class ColorSets:
         h = C.c_void_p()
         _check(lib().sbwtgpu_unitigs_create_colored(self._h, C.byref(h)))
         return Unitigs(h)
+
+    def unitig_graph_dev(self, links: bool = True, column_map: bool = False) -> "Unitigs":
+        """sbwtgpu_unitigs_create_graph on the object: the coloured unitigs with their links and / or the column map."""
+        h = C.c_void_p()
+        flags = (UNITIGS_LINKS if links else 0) | (UNITIGS_COLUMN_MAP if column_map else 0)
+        _check(lib().sbwtgpu_unitigs_create_graph(None, self._h, flags, C.byref(h)))
+        return Unitigs(h, self.index.n_nodes)
 
     def unitigs(self):
         """(bases, off, first_col, set_id): Index.unitigs() of the coloured unitigs, and uint32[n] the set id of each."""

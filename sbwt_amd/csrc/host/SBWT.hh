@@ -461,11 +461,18 @@ public:
         detail::gpu_check(sbwtgpu_read_hits_batch(need_device(), bases, read_off, n_reads, strands, out));
     }
     // the unitigs of the index (include/sbwtgpu.h): unitig i is bases[off[i] .. off[i+1]) and starts with the label of column
-    // first_col[i]; ascending first_col
-    struct Unitigs { std::vector<char> bases; std::vector<int64_t> off, first_col; };
-    Unitigs unitigs() const {
+    // first_col[i]; ascending first_col.  links = true adds the links between the unitigs (include/sbwtgpu.h, "the unitig
+    // graph"): unitig i links to link_to[link_off[i] .. link_off[i+1]); otherwise both stay empty
+    struct Unitigs {
+        std::vector<char> bases;
+        std::vector<int64_t> off, first_col;
+        std::vector<int64_t> link_off;
+        std::vector<uint32_t> link_to;
+    };
+    Unitigs unitigs(bool links = false) const {
         sbwtgpu_unitigs *u = nullptr;
-        detail::gpu_check(sbwtgpu_unitigs_create(need_device(), &u));
+        if (links) detail::gpu_check(sbwtgpu_unitigs_create_graph(need_device(), nullptr, SBWTGPU_UNITIGS_LINKS, &u));
+        else detail::gpu_check(sbwtgpu_unitigs_create(need_device(), &u));
         Unitigs r;
         int64_t n = 0, total = 0;
         int rc = sbwtgpu_unitigs_info(u, &n, &total, nullptr);
@@ -475,6 +482,7 @@ public:
             r.first_col.resize((size_t)n);
             rc = sbwtgpu_unitigs_copy(u, r.bases.data(), r.off.data(), r.first_col.data());
         }
+        if (rc == SBWTGPU_OK && links) rc = copy_links(u, n, r.link_off, r.link_to);
         sbwtgpu_unitigs_destroy(u);
         detail::gpu_check(rc);
         return r;
@@ -487,11 +495,14 @@ public:
         std::vector<uint32_t> set_id;
         int64_t n_color_breaks = 0, n_sets = 0;
         int32_t n_colors = 0;
+        std::vector<int64_t> link_off;          // links = true only, as in Unitigs
+        std::vector<uint32_t> link_to;
     };
-    ColoredUnitigs colored_unitigs(const sbwtgpu_colorsets *sets) const {
+    ColoredUnitigs colored_unitigs(const sbwtgpu_colorsets *sets, bool links = false) const {
         need_device();
         sbwtgpu_unitigs *u = nullptr;
-        detail::gpu_check(sbwtgpu_unitigs_create_colored(sets, &u));
+        if (links) detail::gpu_check(sbwtgpu_unitigs_create_graph(nullptr, sets, SBWTGPU_UNITIGS_LINKS, &u));
+        else detail::gpu_check(sbwtgpu_unitigs_create_colored(sets, &u));
         ColoredUnitigs r;
         int64_t n = 0, total = 0;
         int rc = sbwtgpu_unitigs_info(u, &n, &total, nullptr);
@@ -504,9 +515,19 @@ public:
         }
         if (rc == SBWTGPU_OK) rc = sbwtgpu_unitigs_set_ids_copy(u, r.set_id.data());
         if (rc == SBWTGPU_OK) rc = sbwtgpu_unitigs_color_info(u, &r.n_color_breaks, &r.n_sets, &r.n_colors);
+        if (rc == SBWTGPU_OK && links) rc = copy_links(u, n, r.link_off, r.link_to);
         sbwtgpu_unitigs_destroy(u);
         detail::gpu_check(rc);
         return r;
+    }
+    // the links of a graph handle of n unitigs into host vectors
+    static int copy_links(const sbwtgpu_unitigs *u, int64_t n, std::vector<int64_t> &link_off, std::vector<uint32_t> &link_to) {
+        int64_t n_links = 0;
+        const int rc = sbwtgpu_unitigs_links_info(u, &n_links);
+        if (rc != SBWTGPU_OK) return rc;
+        link_off.resize((size_t)n + 1);
+        link_to.resize((size_t)n_links);
+        return sbwtgpu_unitigs_links_copy(u, link_off.data(), link_to.data());
     }
     // the k-mers of the index whose colour set satisfies the predicate, as the columns of their index (include/sbwtgpu.h,
     // "colour select"): bit for bit what the builder gives for the selected k-mers.  The object is one of THIS index;

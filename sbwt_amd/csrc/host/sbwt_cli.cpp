@@ -785,8 +785,41 @@ int read_hits_main(int argc, char **argv) {
 // sbwt dump-unitigs: the index turned back into sequence -- FASTA, one record per unitig in the order of the API (ascending
 // first column), the header the unitig's number.  With --colors the unitigs are cut where the colour set changes and the
 // header is "number set-id" (dump_unitigs_colored, below the colour helpers); --sets-out writes the table of the sets.
+// With --gfa the output file is GFA 1 instead: the unitigs as segments, then the links between them.
 int dump_unitigs_colored(const plain_matrix_sbwt_t &index, const string &indexfile, const string &colorsfile, const string &outfile,
-                         const string &setsfile, bool gzip);
+                         const string &setsfile, bool gzip, bool gfa);
+// GFA 1: "H VN:Z:1.0", one "S number bases [cs:i:set-id]" per unitig, then one "L i + j + (k-1)M" per link in link order
+static string gfa_text(const vector<char> &bases, const vector<int64_t> &off, const vector<int64_t> &link_off,
+                       const vector<uint32_t> &link_to, const vector<uint32_t> *set_id, int64_t k) {
+    const int64_t n = (int64_t)off.size() - 1;
+    string text;
+    text.reserve(bases.size() + (size_t)n * 24 + link_to.size() * 32 + 16);
+    text.append("H\tVN:Z:1.0\n");
+    for (int64_t i = 0; i < n; i++) {
+        text.append("S\t");
+        append_int(i, text);
+        text.push_back('\t');
+        text.append(bases.data() + off[(size_t)i], (size_t)(off[(size_t)i + 1] - off[(size_t)i]));
+        if (set_id) {
+            text.append("\tcs:i:");
+            append_int((int64_t)(*set_id)[(size_t)i], text);
+        }
+        text.push_back('\n');
+    }
+    string overlap;
+    append_int(k - 1, overlap);
+    overlap.append("M\n");
+    for (int64_t i = 0; i < n; i++)
+        for (int64_t e = link_off[(size_t)i]; e < link_off[(size_t)i + 1]; e++) {
+            text.append("L\t");
+            append_int(i, text);
+            text.append("\t+\t");
+            append_int((int64_t)link_to[(size_t)e], text);
+            text.append("\t+\t");
+            text.append(overlap);
+        }
+    return text;
+}
 int dump_unitigs_main(int argc, char **argv) {
     set_log_level(LogLevel::MINOR);
     Options opts({
@@ -795,6 +828,7 @@ int dump_unitigs_main(int argc, char **argv) {
         {"gzip-output", 'z', false, "Writes output in gzipped form.", ""},
         {"colors", 0, true, "Colour file or colour-set file of the index: cut the unitigs where the colour set changes; headers become `>number set-id`.", ""},
         {"sets-out", 0, true, "With --colors: write one line per set id -- the id, then its colours, ascending.", ""},
+        {"gfa", 0, false, "Write the output file as GFA 1: segments and the links between them (with --colors a cs:i: tag per segment).", ""},
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"help", 'h', false, "Print usage", ""},
     });
@@ -819,21 +853,28 @@ int dump_unitigs_main(int argc, char **argv) {
         throw std::runtime_error("Error: only the plain-matrix variant is supported by the GPU path (got " + variant + ")");
     plain_matrix_sbwt_t index;
     index.load(in);
-    if (colored) return dump_unitigs_colored(index, indexfile, colorsfile, outfile, setsfile, opts.count("gzip-output"));
-    const plain_matrix_sbwt_t::Unitigs u = index.unitigs();
+    const bool gfa = opts.count("gfa");
+    if (colored) return dump_unitigs_colored(index, indexfile, colorsfile, outfile, setsfile, opts.count("gzip-output"), gfa);
+    const plain_matrix_sbwt_t::Unitigs u = index.unitigs(gfa);
     const int64_t n = (int64_t)u.first_col.size();
     string text;
-    text.reserve(u.bases.size() + (size_t)n * 12);
-    for (int64_t i = 0; i < n; i++) {
-        text.push_back('>');
-        append_int(i, text);
-        text.push_back('\n');
-        text.append(u.bases.data() + u.off[(size_t)i], (size_t)(u.off[(size_t)i + 1] - u.off[(size_t)i]));
-        text.push_back('\n');
+    if (gfa) {
+        text = gfa_text(u.bases, u.off, u.link_off, u.link_to, nullptr, index.get_k());
+    } else {
+        text.reserve(u.bases.size() + (size_t)n * 12);
+        for (int64_t i = 0; i < n; i++) {
+            text.push_back('>');
+            append_int(i, text);
+            text.push_back('\n');
+            text.append(u.bases.data() + u.off[(size_t)i], (size_t)(u.off[(size_t)i + 1] - u.off[(size_t)i]));
+            text.push_back('\n');
+        }
     }
     if (sbwthost_write_file(outfile.c_str(), text.data(), (int64_t)text.size(), opts.count("gzip-output") ? 1 : 0, 0) != 0)
         throw std::runtime_error(string("Error writing ") + outfile + ": " + sbwthost_last_error());
-    write_log("Wrote " + std::to_string(n) + " unitigs, " + std::to_string(u.bases.size()) + " bases", LogLevel::MAJOR);
+    write_log("Wrote " + std::to_string(n) + " unitigs, " + std::to_string(u.bases.size()) + " bases" +
+                  (gfa ? ", " + std::to_string(u.link_to.size()) + " links" : string()),
+              LogLevel::MAJOR);
     return 0;
 }
 
@@ -1234,21 +1275,25 @@ int color_matrix_main(int argc, char **argv) {
 // dump-unitigs --colors: coloured unitigs as FASTA, the header "number set-id" (a parser that takes the id up to the first
 // blank still sees the number); --sets-out: line i = "i c1 c2 ..." for set id i = 0 .. n_sets - 1, the line of set 0 is "0"
 int dump_unitigs_colored(const plain_matrix_sbwt_t &index, const string &indexfile, const string &colorsfile, const string &outfile,
-                         const string &setsfile, bool gzip) {
+                         const string &setsfile, bool gzip, bool gfa) {
     ColorSetsHandle sets;
     load_colorsets(colorsfile, indexfile, index, sets);
-    const plain_matrix_sbwt_t::ColoredUnitigs u = index.colored_unitigs(sets.h);
+    const plain_matrix_sbwt_t::ColoredUnitigs u = index.colored_unitigs(sets.h, gfa);
     const int64_t n = (int64_t)u.first_col.size();
     string text;
-    text.reserve(u.bases.size() + (size_t)n * 20);
-    for (int64_t i = 0; i < n; i++) {
-        text.push_back('>');
-        append_int(i, text);
-        text.push_back(' ');
-        append_int((int64_t)u.set_id[(size_t)i], text);
-        text.push_back('\n');
-        text.append(u.bases.data() + u.off[(size_t)i], (size_t)(u.off[(size_t)i + 1] - u.off[(size_t)i]));
-        text.push_back('\n');
+    if (gfa) {
+        text = gfa_text(u.bases, u.off, u.link_off, u.link_to, &u.set_id, index.get_k());
+    } else {
+        text.reserve(u.bases.size() + (size_t)n * 20);
+        for (int64_t i = 0; i < n; i++) {
+            text.push_back('>');
+            append_int(i, text);
+            text.push_back(' ');
+            append_int((int64_t)u.set_id[(size_t)i], text);
+            text.push_back('\n');
+            text.append(u.bases.data() + u.off[(size_t)i], (size_t)(u.off[(size_t)i + 1] - u.off[(size_t)i]));
+            text.push_back('\n');
+        }
     }
     if (sbwthost_write_file(outfile.c_str(), text.data(), (int64_t)text.size(), gzip ? 1 : 0, 0) != 0)
         throw std::runtime_error(string("Error writing ") + outfile + ": " + sbwthost_last_error());
@@ -1273,7 +1318,8 @@ int dump_unitigs_colored(const plain_matrix_sbwt_t &index, const string &indexfi
             throw std::runtime_error(string("Error writing ") + setsfile + ": " + sbwthost_last_error());
     }
     write_log("Wrote " + std::to_string(n) + " coloured unitigs, " + std::to_string(u.bases.size()) + " bases, " +
-                  std::to_string(u.n_color_breaks) + " colour breaks, " + std::to_string(u.n_sets) + " colour sets",
+                  std::to_string(u.n_color_breaks) + " colour breaks, " + std::to_string(u.n_sets) + " colour sets" +
+                  (gfa ? ", " + std::to_string(u.link_to.size()) + " links" : string()),
               LogLevel::MAJOR);
     return 0;
 }

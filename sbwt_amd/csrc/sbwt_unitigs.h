@@ -11,6 +11,9 @@ enum { SBWT_UT_PASS_PRED = 0,   // predecessor array + suffix-group marks (copie
        SBWT_UT_PASS_OFFSETS,    // start flags -> unitig ids, lengths -> 64-bit base offsets
        SBWT_UT_PASS_BASES,      // every column's last character + every start's label
        SBWT_UT_N_PASSES };
+// what a run adds to the unitigs when asked; the values are those of SBWTGPU_UNITIGS_* in the ABI
+enum { SBWT_UT_GRAPH_LINKS = 1u,        // pass 7: the links between the unitigs, CSR
+       SBWT_UT_GRAPH_COLUMN_MAP = 2u }; // pass 8: (unitig, offset) of every column
 
 struct SbwtUnitigRun {
     // results: device allocations of their own, owned by the caller of sbwt_unitigs_run on success
@@ -22,6 +25,13 @@ struct SbwtUnitigRun {
     long long n_unitigs = 0, total_bases = 0;
     int jump_rounds = 0;                    // launches of the pointer-jumping kernel
     float ms[SBWT_UT_N_PASSES] = {0, 0, 0, 0, 0, 0};
+    // the graph (section 21), filled as far as the run was asked to; device allocations like the results above
+    long long *d_link_off = nullptr;        // n_unitigs + 1
+    unsigned *d_link_to = nullptr;          // n_links
+    long long n_links = 0;
+    unsigned *d_col_unitig = nullptr;       // n_nodes: 0xFFFFFFFF for a dummy column
+    unsigned *d_col_offset = nullptr;       // n_nodes
+    float links_ms = 0, map_ms = 0;
 };
 
 // scratch per column while sbwt_unitigs_run works (freed before it returns): 4 (pred) + 1 (dummy level) + 1/8 (marks) +
@@ -32,6 +42,11 @@ long long sbwt_unitigs_scratch_bytes(long long n_nodes);
 // the call that failed (hipErrorOutOfMemory: a result could not be allocated); on failure nothing is left allocated.
 // A colour view (d_ids: n_nodes ids, d_table: rows of `words` words, both read in place) selects the coloured run of DESIGN.md
 // section 18: unitigs end where the colour set changes, run->d_set_id and run->n_color_breaks are filled.  d_ids == nullptr
-// is the plain run.
+// is the plain run.  `graph`: SBWT_UT_GRAPH_* bits; 0 runs passes 1 to 6 and nothing else.
 hipError_t sbwt_unitigs_run(const SbwtIndexView &ix, int has_marks, void *d_scratch, SbwtUnitigRun *run, hipStream_t stream,
-                            const unsigned *d_ids = nullptr, const unsigned long long *d_table = nullptr, int words = 0);
+                            const unsigned *d_ids = nullptr, const unsigned long long *d_table = nullptr, int words = 0,
+                            unsigned graph = 0);
+// (unitig, offset) of the columns cols[0 .. n) from a column map: a gather on `stream`, which it never synchronises.  A value
+// outside [0, n_nodes) gives 0xFFFFFFFF in both, as a dummy column does.
+hipError_t sbwt_unitigs_locate(const unsigned *d_col_unitig, const unsigned *d_col_offset, long long n_nodes, const long long *d_cols,
+                               long long n, unsigned *d_unitig, unsigned *d_offset, hipStream_t stream);

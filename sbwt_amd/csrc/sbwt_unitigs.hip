@@ -22,6 +22,10 @@
 //      first k-1 characters of its label
 // A coloured run (d_ids given) cuts where the colour set changes: passes 3 and 5 take an edge for
 // internal only if both ends carry the same set, pass 5 gathers the set id of every unitig.  Passes 1, 2, 4 and 6 are the same.
+// Asked for a graph, the run goes on after pass 6, on the state the six passes leave:
+//   7  links: every tail counts the set bits of its group's first column into deg[unitig]; exclusive scan -> link_off; every
+//      tail writes the unitig ids of its out-neighbours, which are first columns, in character order
+//   8  column map: every real column stores uid[head] and its rank
 // No lane loops over a unitig: the longest loop of a lane is k steps (or the words of a row across a candidate break).
 // Columns are 32-bit unsigned as in the image.
 //
@@ -170,14 +174,8 @@ __global__ void __launch_bounds__(256) k_ut_starts(i64 n, const uint4 *__restric
 // the start of a unitig notes its column, the tail (no internal edge out, or one back to the head: a cut cycle) its length.
 // COLORED: a single edge into another set is no internal edge either.
 template <bool MEGA, bool COLORED>
-__global__ void __launch_bounds__(256) k_ut_lengths(SbwtIndexView ix, const unsigned char *__restrict__ lev, const u64 *__restrict__ marks,
-                                                    const uint4 *__restrict__ st, const i64 *__restrict__ uid,
-                                                    i64 *__restrict__ first_col, i64 *__restrict__ len, UtColors cs) {
-    const i64 v = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (v >= ix.n_nodes) return;
-    const uint4 s = st[v];
-    if (s.w != UT_RANKED) return;
-    if (s.y == 0u) first_col[uid[v]] = v;
+__device__ __forceinline__ bool ut_is_tail(const SbwtIndexView &ix, const unsigned char *__restrict__ lev, const u64 *__restrict__ marks,
+                                           const uint4 &s, i64 v, const UtColors &cs) {
     bool tail = true;
     if (ut_single_out(ix, lev, marks, v)) {
         const uint4 *blk = ix.blocks + ((v >> 6) << 2);
@@ -192,7 +190,18 @@ __global__ void __launch_bounds__(256) k_ut_lengths(SbwtIndexView ix, const unsi
             if (!tail && w >= 0 && w < ix.n_nodes) tail = !ut_same_set(cs, v, w);
         }
     }
-    if (tail) len[uid[s.x]] = (i64)s.y + 1 + (ix.k - 1);
+    return tail;
+}
+template <bool MEGA, bool COLORED>
+__global__ void __launch_bounds__(256) k_ut_lengths(SbwtIndexView ix, const unsigned char *__restrict__ lev, const u64 *__restrict__ marks,
+                                                    const uint4 *__restrict__ st, const i64 *__restrict__ uid,
+                                                    i64 *__restrict__ first_col, i64 *__restrict__ len, UtColors cs) {
+    const i64 v = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (v >= ix.n_nodes) return;
+    const uint4 s = st[v];
+    if (s.w != UT_RANKED) return;
+    if (s.y == 0u) first_col[uid[v]] = v;
+    if (ut_is_tail<MEGA, COLORED>(ix, lev, marks, s, v, cs)) len[uid[s.x]] = (i64)s.y + 1 + (ix.k - 1);
 }
 
 // the set id of a coloured unitig is the id of its first column
@@ -223,6 +232,76 @@ __global__ void __launch_bounds__(256) k_ut_labels(SbwtIndexView ix, const unsig
         v = (i64)pred[v];
         to[-j] = "ACGT"[ut_last_char(ix, v)];
     }
+}
+
+// ---- pass 7: links (section 21) ----
+// the first column of v's suffix group: a group holds at most 4 columns (one per character that can precede its suffix), so at
+// most 3 steps back, possibly into the previous word of the marks; column 0 starts a group
+__device__ __forceinline__ i64 ut_group_first(const u64 *__restrict__ marks, i64 v) {
+    i64 g = v;
+    for (int i = 0; i < 3 && g > 0 && !ut_mark(marks, g); i++) g--;
+    return g;
+}
+// the tail of every unitig counts its out-neighbours: the set bits of its group's first column
+template <bool MEGA, bool COLORED>
+__global__ void __launch_bounds__(256) k_ut_link_count(SbwtIndexView ix, const unsigned char *__restrict__ lev, const u64 *__restrict__ marks,
+                                                       const uint4 *__restrict__ st, const i64 *__restrict__ uid, i64 *__restrict__ deg,
+                                                       UtColors cs) {
+    const i64 v = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (v >= ix.n_nodes) return;
+    const uint4 s = st[v];
+    if (s.w != UT_RANKED || !ut_is_tail<MEGA, COLORED>(ix, lev, marks, s, v, cs)) return;
+    const i64 g = ut_group_first(marks, v);
+    const uint4 *blk = ix.blocks + ((g >> 6) << 2);
+    int d = 0;
+#pragma unroll
+    for (int c = 0; c < 4; c++) d += (int)((quad_bits(blk[c]) >> (g & 63)) & 1ull);
+    deg[uid[s.x]] = d;
+}
+// ... and writes their unitigs in character order: an out-neighbour of a tail is a first column, so uid[] of it is its unitig
+template <bool MEGA, bool COLORED>
+__global__ void __launch_bounds__(256) k_ut_link_fill(SbwtIndexView ix, const unsigned char *__restrict__ lev, const u64 *__restrict__ marks,
+                                                      const uint4 *__restrict__ st, const i64 *__restrict__ uid,
+                                                      const i64 *__restrict__ link_off, unsigned *__restrict__ link_to, UtColors cs) {
+    const i64 v = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (v >= ix.n_nodes) return;
+    const uint4 s = st[v];
+    if (s.w != UT_RANKED || !ut_is_tail<MEGA, COLORED>(ix, lev, marks, s, v, cs)) return;
+    const i64 g = ut_group_first(marks, v);
+    const uint4 *blk = ix.blocks + ((g >> 6) << 2);
+    const i64 u = uid[s.x];
+    i64 at = link_off[u];
+    const i64 end = link_off[u + 1];                         // (what k_ut_link_count counted from the same bits)
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const uint4 q = blk[c];
+        if (((quad_bits(q) >> (g & 63)) & 1ull) && at < end) {
+            const u64 w = quad_rank<MEGA>(ix, q, g, c);
+            link_to[at++] = w < (u64)ix.n_nodes ? (unsigned)uid[w] : UT_NONE;
+        }
+    }
+}
+
+// ---- pass 8: column map ----
+__global__ void __launch_bounds__(256) k_ut_colmap(i64 n, const uint4 *__restrict__ st, const i64 *__restrict__ uid,
+                                                   unsigned *__restrict__ col_unitig, unsigned *__restrict__ col_offset) {
+    const i64 v = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (v >= n) return;
+    const uint4 s = st[v];
+    const bool real = s.w == UT_RANKED;
+    col_unitig[v] = real ? (unsigned)uid[s.x] : UT_NONE;
+    col_offset[v] = real ? s.y : UT_NONE;
+}
+// locate: the map gathered at search results
+__global__ void __launch_bounds__(256) k_ut_locate(const unsigned *__restrict__ col_unitig, const unsigned *__restrict__ col_offset,
+                                                   i64 n_nodes, const i64 *__restrict__ cols, i64 n, unsigned *__restrict__ unitig,
+                                                   unsigned *__restrict__ offset) {
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const i64 c = cols[i];
+    const bool in = c >= 0 && c < n_nodes;
+    unitig[i] = in ? col_unitig[c] : UT_NONE;
+    offset[i] = in ? col_offset[c] : UT_NONE;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -261,7 +340,7 @@ static void ut_scan(const i64 *in, i64 n, i64 *bsum, i64 *out, hipStream_t strea
     } while (0)
 
 hipError_t sbwt_unitigs_run(const SbwtIndexView &ix, int has_marks, void *d_scratch, SbwtUnitigRun *run, hipStream_t stream,
-                            const unsigned *d_ids, const unsigned long long *d_table, int words) {
+                            const unsigned *d_ids, const unsigned long long *d_table, int words, unsigned graph) {
     const bool mega = ix.n_mega > 1 || ix.force_mega;
     const i64 n = ix.n_nodes;
     const UtLayout L(n);
@@ -282,6 +361,8 @@ hipError_t sbwt_unitigs_run(const SbwtIndexView &ix, int has_marks, void *d_scra
     int cur = 0, h_open = 0, max_rounds = 0;
     i64 n_unitigs = 0, total = 0;
     i64 *flag = nullptr, *uid = nullptr;
+    hipEvent_t evg[2] = {};
+    i64 n_links = 0;
     *run = SbwtUnitigRun();
     for (int i = 0; i <= SBWT_UT_N_PASSES; i++) UT_TRY(hipEventCreate(&ev[i]));
 
@@ -358,15 +439,65 @@ hipError_t sbwt_unitigs_run(const SbwtIndexView &ix, int has_marks, void *d_scra
                            (const i64 *)run->d_first_col, (const i64 *)run->d_off, n_unitigs, run->d_bases);
     }
     UT_TRY(hipEventRecord(ev[SBWT_UT_N_PASSES], stream));
+    if (graph) {
+        for (int i = 0; i < 2; i++) UT_TRY(hipEventCreate(&evg[i]));
+        if (graph & SBWT_UT_GRAPH_LINKS) {
+            // the degrees take the place of the lengths, which the offsets were scanned from
+            UT_TRY(hipMalloc((void **)&run->d_link_off, (size_t)(n_unitigs + 1) * 8));
+#define UT_LINK_COUNT(M, C)                                                                                                          \
+    hipLaunchKernelGGL((k_ut_link_count<M, C>), dim3(g), dim3(256), 0, stream, ix, (const unsigned char *)lev, (const u64 *)marks,   \
+                       (const uint4 *)st[cur], (const i64 *)uid, flag, cs)
+            if (colored) {
+                if (mega) UT_LINK_COUNT(true, true);
+                else UT_LINK_COUNT(false, true);
+            } else {
+                if (mega) UT_LINK_COUNT(true, false);
+                else UT_LINK_COUNT(false, false);
+            }
+#undef UT_LINK_COUNT
+            ut_scan(flag, n_unitigs, bsum, run->d_link_off, stream);
+            UT_TRY(hipMemcpyAsync(&n_links, run->d_link_off + n_unitigs, 8, hipMemcpyDeviceToHost, stream));
+            UT_TRY(hipStreamSynchronize(stream));
+            UT_TRY(hipMalloc((void **)&run->d_link_to, (size_t)(n_links ? n_links : 1) * 4));
+#define UT_LINK_FILL(M, C)                                                                                                           \
+    hipLaunchKernelGGL((k_ut_link_fill<M, C>), dim3(g), dim3(256), 0, stream, ix, (const unsigned char *)lev, (const u64 *)marks,    \
+                       (const uint4 *)st[cur], (const i64 *)uid, (const i64 *)run->d_link_off, run->d_link_to, cs)
+            if (n_links > 0) {
+                if (colored) {
+                    if (mega) UT_LINK_FILL(true, true);
+                    else UT_LINK_FILL(false, true);
+                } else {
+                    if (mega) UT_LINK_FILL(true, false);
+                    else UT_LINK_FILL(false, false);
+                }
+            }
+#undef UT_LINK_FILL
+        }
+        UT_TRY(hipEventRecord(evg[0], stream));
+        if (graph & SBWT_UT_GRAPH_COLUMN_MAP) {
+            UT_TRY(hipMalloc((void **)&run->d_col_unitig, (size_t)n * 4));
+            UT_TRY(hipMalloc((void **)&run->d_col_offset, (size_t)n * 4));
+            hipLaunchKernelGGL(k_ut_colmap, dim3(g), dim3(256), 0, stream, n, (const uint4 *)st[cur], (const i64 *)uid, run->d_col_unitig,
+                               run->d_col_offset);
+        }
+        UT_TRY(hipEventRecord(evg[1], stream));
+    }
     UT_TRY(hipGetLastError());
     UT_TRY(hipStreamSynchronize(stream));
     for (int i = 0; i < SBWT_UT_N_PASSES; i++) UT_TRY(hipEventElapsedTime(&run->ms[i], ev[i], ev[i + 1]));
+    if (graph) {
+        UT_TRY(hipEventElapsedTime(&run->links_ms, ev[SBWT_UT_N_PASSES], evg[0]));
+        UT_TRY(hipEventElapsedTime(&run->map_ms, evg[0], evg[1]));
+    }
+    run->n_links = n_links;
     run->n_unitigs = n_unitigs;
     run->total_bases = total;
     run->n_color_breaks = (long long)h_breaks;
 done:
     for (int i = 0; i <= SBWT_UT_N_PASSES; i++)
         if (ev[i]) (void)hipEventDestroy(ev[i]);
+    for (int i = 0; i < 2; i++)
+        if (evg[i]) (void)hipEventDestroy(evg[i]);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(stream);
         (void)hipGetLastError();
@@ -374,7 +505,22 @@ done:
         if (run->d_off) (void)hipFree(run->d_off);
         if (run->d_first_col) (void)hipFree(run->d_first_col);
         if (run->d_set_id) (void)hipFree(run->d_set_id);
+        if (run->d_link_off) (void)hipFree(run->d_link_off);
+        if (run->d_link_to) (void)hipFree(run->d_link_to);
+        if (run->d_col_unitig) (void)hipFree(run->d_col_unitig);
+        if (run->d_col_offset) (void)hipFree(run->d_col_offset);
         *run = SbwtUnitigRun();
     }
     return e;
+}
+
+hipError_t sbwt_unitigs_locate(const unsigned *d_col_unitig, const unsigned *d_col_offset, long long n_nodes, const long long *d_cols,
+                               long long n, unsigned *d_unitig, unsigned *d_offset, hipStream_t stream) {
+    const i64 chunk = (i64)1 << 30;                          // (one dispatch holds fewer than 2^32 work-items)
+    for (i64 at = 0; at < n; at += chunk) {
+        const i64 m = n - at < chunk ? n - at : chunk;
+        hipLaunchKernelGGL(k_ut_locate, dim3(grid_for(m)), dim3(256), 0, stream, d_col_unitig, d_col_offset, (i64)n_nodes,
+                           (const i64 *)d_cols + at, m, d_unitig + at, d_offset + at);
+    }
+    return hipGetLastError();
 }

@@ -2579,11 +2579,14 @@ struct sbwtgpu_unitigs {
     bool colored = false;
     int64_t n_sets = 0;
     int n_colors = 0;
+    // a graph handle (sbwtgpu_unitigs_create_graph): the SBWTGPU_UNITIGS_* flags it was made with, and what locate checks against
+    unsigned graph = 0;
+    int64_t n_nodes = 0;
 };
 
-// the plain call, or with a colour view (ids, table, words) the coloured one
+// the plain call, or with a colour view (ids, table, words) the coloured one; graph: SBWTGPU_UNITIGS_* flags
 static int unitigs_create_common(const sbwtgpu_index *idx, const unsigned *d_ids, const unsigned long long *d_table, int words,
-                                 int64_t n_sets, int n_colors, sbwtgpu_unitigs **out) {
+                                 int64_t n_sets, int n_colors, unsigned graph, sbwtgpu_unitigs **out) {
     if (idx->h.rank_only) return fail(SBWTGPU_ERR_INVALID_ARG, "%s", RANK_ONLY_MSG);
     if (idx->h.k < 2) return fail(SBWTGPU_ERR_INVALID_ARG, "unitigs need k >= 2");
     if (idx->h.n_nodes >= ((int64_t)1 << 32) - ((int64_t)1 << 24))
@@ -2596,12 +2599,15 @@ static int unitigs_create_common(const sbwtgpu_index *idx, const unsigned *d_ids
     u->colored = d_ids != nullptr;
     u->n_sets = n_sets;
     u->n_colors = n_colors;
+    u->graph = graph;
+    u->n_nodes = idx->h.n_nodes;
     DevBuf scratch;
     Stream st;
     hipError_t e = scratch.alloc((size_t)sbwt_unitigs_scratch_bytes(idx->h.n_nodes));
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
     if (e == hipSuccess)
-        e = sbwt_unitigs_run(idx->view(), idx->h.has_ssup || idx->h.ssup_derived, scratch.p, &u->run, st.s, d_ids, d_table, words);
+        e = sbwt_unitigs_run(idx->view(), idx->h.has_ssup || idx->h.ssup_derived, scratch.p, &u->run, st.s, d_ids, d_table, words,
+                             graph);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         delete u;
@@ -2620,7 +2626,7 @@ static int unitigs_create_common(const sbwtgpu_index *idx, const unsigned *d_ids
 int sbwtgpu_unitigs_create(const sbwtgpu_index *idx, sbwtgpu_unitigs **out) {
     if (!idx || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
     *out = nullptr;
-    return unitigs_create_common(idx, nullptr, nullptr, 0, 0, 0, out);
+    return unitigs_create_common(idx, nullptr, nullptr, 0, 0, 0, 0u, out);
 }
 
 void sbwtgpu_unitigs_destroy(sbwtgpu_unitigs *u) {
@@ -2630,6 +2636,10 @@ void sbwtgpu_unitigs_destroy(sbwtgpu_unitigs *u) {
     if (u->run.d_off) (void)hipFree(u->run.d_off);
     if (u->run.d_first_col) (void)hipFree(u->run.d_first_col);
     if (u->run.d_set_id) (void)hipFree(u->run.d_set_id);
+    if (u->run.d_link_off) (void)hipFree(u->run.d_link_off);
+    if (u->run.d_link_to) (void)hipFree(u->run.d_link_to);
+    if (u->run.d_col_unitig) (void)hipFree(u->run.d_col_unitig);
+    if (u->run.d_col_offset) (void)hipFree(u->run.d_col_offset);
     delete u;
 }
 
@@ -2697,6 +2707,99 @@ int sbwtgpu_unitigs_color_info(const sbwtgpu_unitigs *u, int64_t *n_color_breaks
     if (n_color_breaks) *n_color_breaks = u->run.n_color_breaks;
     if (n_sets) *n_sets = u->n_sets;
     if (n_colors) *n_colors = u->n_colors;
+    return SBWTGPU_OK;
+}
+
+// ---- the unitig graph: links, column map, locate (sbwtgpu_unitigs_create_graph is with the colour sets) ----
+static int unitigs_check_graph(const sbwtgpu_unitigs *u, unsigned need, const char *what) {
+    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    if (!(u->graph & need))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "unitigs: the handle was made without %s (sbwtgpu_unitigs_create_graph takes the flag)", what);
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_unitigs_links_info(const sbwtgpu_unitigs *u, int64_t *n_links) {
+    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_LINKS, "SBWTGPU_UNITIGS_LINKS");
+    if (rc != SBWTGPU_OK) return rc;
+    if (!n_links) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *n_links = u->run.n_links;
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_unitigs_links_dev(const sbwtgpu_unitigs *u, const int64_t **d_link_off, const uint32_t **d_link_to) {
+    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_LINKS, "SBWTGPU_UNITIGS_LINKS");
+    if (rc != SBWTGPU_OK) return rc;
+    if (!d_link_off || !d_link_to) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *d_link_off = reinterpret_cast<const int64_t *>(u->run.d_link_off);
+    *d_link_to = reinterpret_cast<const uint32_t *>(u->run.d_link_to);
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_unitigs_links_copy(const sbwtgpu_unitigs *u, int64_t *link_off, uint32_t *link_to) {
+    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_LINKS, "SBWTGPU_UNITIGS_LINKS");
+    if (rc != SBWTGPU_OK) return rc;
+    if (!link_off || (!link_to && u->run.n_links > 0)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    DeviceGuard guard(u->device);
+    HIP_TRY(hipMemcpy(link_off, u->run.d_link_off, (size_t)(u->run.n_unitigs + 1) * 8, hipMemcpyDeviceToHost));
+    if (u->run.n_links > 0) HIP_TRY(hipMemcpy(link_to, u->run.d_link_to, (size_t)u->run.n_links * 4, hipMemcpyDeviceToHost));
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_unitigs_column_map_dev(const sbwtgpu_unitigs *u, const uint32_t **d_col_unitig, const uint32_t **d_col_offset) {
+    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_COLUMN_MAP, "SBWTGPU_UNITIGS_COLUMN_MAP");
+    if (rc != SBWTGPU_OK) return rc;
+    if (!d_col_unitig || !d_col_offset) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *d_col_unitig = reinterpret_cast<const uint32_t *>(u->run.d_col_unitig);
+    *d_col_offset = reinterpret_cast<const uint32_t *>(u->run.d_col_offset);
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_unitigs_column_map_copy(const sbwtgpu_unitigs *u, uint32_t *col_unitig, uint32_t *col_offset) {
+    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_COLUMN_MAP, "SBWTGPU_UNITIGS_COLUMN_MAP");
+    if (rc != SBWTGPU_OK) return rc;
+    if (!col_unitig || !col_offset) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    DeviceGuard guard(u->device);
+    HIP_TRY(hipMemcpy(col_unitig, u->run.d_col_unitig, (size_t)u->n_nodes * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(col_offset, u->run.d_col_offset, (size_t)u->n_nodes * 4, hipMemcpyDeviceToHost));
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_unitigs_locate_dev(const sbwtgpu_unitigs *u, const int64_t *d_cols, int64_t n, uint32_t *d_unitig, uint32_t *d_offset,
+                               void *stream) {
+    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_COLUMN_MAP, "SBWTGPU_UNITIGS_COLUMN_MAP");
+    if (rc != SBWTGPU_OK) return rc;
+    if (n < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative n");
+    if (n == 0) return SBWTGPU_OK;
+    if (!d_cols || !d_unitig || !d_offset) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    DeviceGuard guard(u->device);
+    HIP_TRY(sbwt_unitigs_locate(u->run.d_col_unitig, u->run.d_col_offset, u->n_nodes, reinterpret_cast<const long long *>(d_cols), n,
+                                d_unitig, d_offset, static_cast<hipStream_t>(stream)));
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_unitigs_locate_batch(const sbwtgpu_unitigs *u, const int64_t *cols, int64_t n, uint32_t *unitig, uint32_t *offset) {
+    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_COLUMN_MAP, "SBWTGPU_UNITIGS_COLUMN_MAP");
+    if (rc != SBWTGPU_OK) return rc;
+    if (n < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative n");
+    if (n == 0) return SBWTGPU_OK;
+    if (!cols || !unitig || !offset) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    DeviceGuard guard(u->device);
+    // [cols] in, [unitig][offset] back
+    const size_t o_u = align256((size_t)n * 8), o_o = o_u + align256((size_t)n * 4);
+    Staging sg;
+    STG_TRY(sg.open(u->device, o_o + (size_t)n * 4));
+    STG_TRY(sg.in(0, cols, (size_t)n * 8));
+    STG_TRY(sg.upload());
+    STG_TRY(sbwtgpu_unitigs_locate_dev(u, sg.at<const int64_t>(0), n, sg.at<uint32_t>(o_u), sg.at<uint32_t>(o_o), sg.stream));
+    STG_TRY(sg.out(o_u, unitig, (size_t)n * 4));
+    STG_TRY(sg.out(o_o, offset, (size_t)n * 4));
+    return sg.finish();
+}
+
+int sbwtgpu_unitigs_graph_stats(const sbwtgpu_unitigs *u, double *links_ms, double *map_ms) {
+    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    if (links_ms) *links_ms = (double)u->run.links_ms;
+    if (map_ms) *map_ms = (double)u->run.map_ms;
     return SBWTGPU_OK;
 }
 
@@ -3469,7 +3572,22 @@ int sbwtgpu_unitigs_create_colored(const sbwtgpu_colorsets *s, sbwtgpu_unitigs *
     *out = nullptr;
     const int rc = colorsets_check(s);
     if (rc != SBWTGPU_OK) return rc;
-    return unitigs_create_common(s->base.idx, s->d_ids, s->d_table, s->base.words, s->n_sets, s->base.n_colors, out);
+    return unitigs_create_common(s->base.idx, s->d_ids, s->d_table, s->base.words, s->n_sets, s->base.n_colors, 0u, out);
+}
+
+// the unitigs as a graph (section 21): the plain run of idx or the coloured run of s, with the links and the column map asked for
+int sbwtgpu_unitigs_create_graph(const sbwtgpu_index *idx, const sbwtgpu_colorsets *s, unsigned flags, sbwtgpu_unitigs **out) {
+    if (!out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if ((idx != nullptr) == (s != nullptr))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "unitig graph: give exactly one of idx (a plain run) and s (a coloured run), %s were given",
+                    idx ? "both" : "neither");
+    if (flags & ~(unsigned)(SBWTGPU_UNITIGS_LINKS | SBWTGPU_UNITIGS_COLUMN_MAP))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "unitig graph: unknown flag bits 0x%x", flags & ~(unsigned)(SBWTGPU_UNITIGS_LINKS | SBWTGPU_UNITIGS_COLUMN_MAP));
+    if (idx) return unitigs_create_common(idx, nullptr, nullptr, 0, 0, 0, flags, out);
+    const int rc = colorsets_check(s);
+    if (rc != SBWTGPU_OK) return rc;
+    return unitigs_create_common(s->base.idx, s->d_ids, s->d_table, s->base.words, s->n_sets, s->base.n_colors, flags, out);
 }
 
 int sbwtgpu_pseudoalign_sets_dev(const sbwtgpu_colorsets *s, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
