@@ -114,6 +114,8 @@ int         sbwtgpu_device_count(int *count);
  *   "read_hits_chunk_bases" sbwtgpu_read_hits_batch cuts its batch into chunks of whole reads of at most this many bases (a
  *                        chunk always takes one read); 0 (default) = 64 Mi
  *   "read_hits_wide"     1: the read-hits calls take the int64 search route also on indexes of fewer than 2^31 columns (tests)
+ *   "walks_chunk_bases"  sbwtgpu_unitigs_walks_batch cuts its batch into chunks of whole reads of at most this many bases (a chunk
+ *                        always takes one read); 0 (default) = 64 Mi
  *   "pseudoalign_chunk_bases" sbwtgpu_pseudoalign_batch (_wide_batch, _sets_batch) and sbwtgpu_colors_add_batch cut their batch
  *                        into chunks of whole reads of at most this many bases (a chunk always takes one read); 0 (default) = 64 Mi
  *   "trans_ext", "trans_wide"   accepted and ignored (round-2 table formats)
@@ -585,6 +587,63 @@ int64_t sbwtgpu_read_hits_workspace_bytes(int64_t total_bases, int64_t n_reads, 
 int     sbwtgpu_read_hits_dev(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
                               int64_t n_reads, int strands, sbwtgpu_read_hits *d_out, void *d_workspace,
                               int64_t workspace_bytes, void *stream);
+
+/* ---- reads threaded through the unitig graph: walks and unitig coverage ----
+ * Which unitigs a read runs along, and how far: a few 16-byte records per read instead of 8 bytes per window from search +
+ * locate.  The inputs are an index, a graph handle u made from it with SBWTGPU_UNITIGS_COLUMN_MAP (plain or coloured) and a
+ * batch of reads given as sbwtgpu_read_hits_* takes them.  One strand only.
+ *
+ * Read r has L bases and m = max(0, L - k + 1) windows.  Window i hits when SBWT::search of it is >= 0 -- the rule of
+ * sbwtgpu_search_batch: any byte other than upper-case A/C/G/T in the window means no hit.  A hit has a coordinate (U_i, O_i):
+ * the column map's pair for its column (a search result is never a dummy column).
+ *   step        a maximal range of windows [i, i + n) of one read in which every window hits and U_{j+1} = U_j,
+ *               O_{j+1} = O_j + 1 for every consecutive pair.
+ *   record      { unitig = U_i, offset = O_i, read_pos = i, n_kmers = n }
+ *   layout      CSR: step_off[n_reads + 1] (int64, step_off[0] = 0); steps[step_off[r] .. step_off[r+1]) are read r's steps by
+ *               ascending read_pos.  A read with no hit, or with m = 0, has none.
+ *   what follows  the steps of a read do not overlap.  Step s+1 CONTINUES step s when read_pos[s+1] = read_pos[s] + n_kmers[s];
+ *               then offset[s] + n_kmers[s] is unitig s's k-mer count, offset[s+1] = 0, and (unitig[s], unitig[s+1]) is a link
+ *               of the handle (for a coloured handle a colour break is a link; a read going round a cut cycle repeats the
+ *               unitig through its self-link).  Otherwise at least one window between the two misses.  The sum of n_kmers over
+ *               a read is n_found of its sbwtgpu_read_hits record (strands = 1).
+ *   coverage    optional int64[n_unitigs]: entry j is the sum of n_kmers over all steps of the batch with unitig = j -- the
+ *               GFA KC value of segment j for the read set.
+ *   determinism a function of the index, the handle and the reads: byte-identical between runs, image levels, tuning, chunking,
+ *               and marks given or derived.
+ *
+ * sbwtgpu_unitigs_walks_prepare builds the handle's start bitmap (one bit per column: its offset in its unitig is 0; n_nodes / 8
+ * bytes, owned by the handle and freed by sbwtgpu_unitigs_destroy) with one streaming pass over the column map; idempotent and
+ * thread-safe.  The create calls are unchanged and launch and allocate nothing for it.
+ *
+ * _dev: asynchronous on `stream`, never synchronises, never allocates; needs a prepared handle.  The preconditions are those of
+ * sbwtgpu_read_hits_dev (d_read_off[0] need not be 0, n_reads < 2^31).  d_step_off[n_reads] always receives the true number of
+ * steps, also when it exceeds steps_cap: the caller compares (the number of windows is always enough).  Only the steps of
+ * number < steps_cap are stored, nothing at or beyond d_steps[steps_cap].  d_unitig_kmers, when given, is ADDED to (all steps
+ * count, stored or not), so a caller sums batches; steps_cap below the number of steps TOGETHER with coverage is a slow path
+ * (every step that is not stored is walked back to its start, 64 windows per load).  The workspace (16-byte aligned) holds the search workspace first -- so
+ * sbwtgpu_workspace_status reports the search's status word -- then the int32 results (4 bytes per base), three bit vectors over
+ * the windows and two rank directories (about 0.88 bytes per base) and 32 bytes per read; its size is non-decreasing in both
+ * arguments.
+ *
+ * _batch: host buffers; prepares the handle if needed; cuts the batch into chunks of whole reads (tuning "walks_chunk_bases"),
+ * so device memory is bounded.  step_off (n_reads + 1 entries, the caller's) is global over the batch; *steps_out is host
+ * memory of the library (release it with sbwtgpu_free_host), NULL with *n_steps = 0 when there are no steps.  unitig_kmers,
+ * when given, receives the totals of this call.  Thread-safe on one index and handle like the other queries.
+ *
+ * SBWTGPU_ERR_INVALID_ARG, with a message naming the cause: a handle made without SBWTGPU_UNITIGS_COLUMN_MAP; _dev on a handle
+ * that was not prepared; a handle whose n_nodes or k differ from the index's; an index of 2^31 columns or more; a rank-only
+ * index; NULL outputs; n_reads < 0; steps_cap < 0; a workspace that is too small.  A read of 2^31 bases or more:
+ * SBWTGPU_ERR_READ_TOO_LONG. */
+typedef struct { uint32_t unitig, offset; int32_t read_pos, n_kmers; } sbwtgpu_walk_step;
+int     sbwtgpu_unitigs_walks_prepare(sbwtgpu_unitigs *u);
+int64_t sbwtgpu_unitigs_walks_workspace_bytes(int64_t total_bases, int64_t n_reads);
+int     sbwtgpu_unitigs_walks_dev(const sbwtgpu_index *idx, const sbwtgpu_unitigs *u, const char *d_bases, int64_t total_bases,
+                                  const int64_t *d_read_off, int64_t n_reads, int64_t *d_step_off /* n_reads + 1 */,
+                                  sbwtgpu_walk_step *d_steps, int64_t steps_cap, int64_t *d_unitig_kmers_or_null /* n_unitigs, added to */,
+                                  void *d_workspace, int64_t workspace_bytes, void *stream);
+int     sbwtgpu_unitigs_walks_batch(const sbwtgpu_index *idx, const sbwtgpu_unitigs *u, const char *bases, const int64_t *read_off,
+                                    int64_t n_reads, int64_t *step_off /* n_reads + 1 */, sbwtgpu_walk_step **steps_out,
+                                    int64_t *n_steps, int64_t *unitig_kmers_or_null /* n_unitigs, the totals of this call */);
 
 /* ---- colours and pseudoalignment: which of the indexed references hold a k-mer or a read ----
  * One index over N references (strains of a pan-genome) and one search answer "which references hold this read", instead of

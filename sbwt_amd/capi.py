@@ -28,6 +28,8 @@ ERR_READ_TOO_LONG = -9
 ERR_STALLED = -10
 UNITIGS_LINKS = 1               # SBWTGPU_UNITIGS_* (sbwtgpu_unitigs_create_graph)
 UNITIGS_COLUMN_MAP = 2
+# sbwtgpu_walk_step: one step of a read through the unitig graph (Unitigs.walks)
+WALK_STEP = np.dtype([("unitig", np.uint32), ("offset", np.uint32), ("read_pos", np.int32), ("n_kmers", np.int32)])
 
 # every symbol include/sbwtgpu.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = [
@@ -52,6 +54,7 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_unitigs_color_info", "sbwtgpu_unitigs_create_graph", "sbwtgpu_unitigs_links_info", "sbwtgpu_unitigs_links_dev",
     "sbwtgpu_unitigs_links_copy", "sbwtgpu_unitigs_column_map_dev", "sbwtgpu_unitigs_column_map_copy",
     "sbwtgpu_unitigs_locate_dev", "sbwtgpu_unitigs_locate_batch", "sbwtgpu_unitigs_graph_stats",
+    "sbwtgpu_unitigs_walks_prepare", "sbwtgpu_unitigs_walks_workspace_bytes", "sbwtgpu_unitigs_walks_dev", "sbwtgpu_unitigs_walks_batch",
     "sbwtgpu_index_setop", "sbwtgpu_index_setop_counts", "sbwtgpu_index_kmer_keys",
     "sbwtgpu_read_hits_batch", "sbwtgpu_read_hits_workspace_bytes", "sbwtgpu_read_hits_dev",
     "sbwtgpu_colors_create", "sbwtgpu_colors_destroy", "sbwtgpu_colors_add_batch", "sbwtgpu_colors_info", "sbwtgpu_colors_copy",
@@ -338,6 +341,11 @@ def lib() -> C.CDLL:
         L.sbwtgpu_unitigs_locate_dev.argtypes = [vp, vp, i64, vp, vp, vp]
         L.sbwtgpu_unitigs_locate_batch.argtypes = [vp, vp, i64, vp, vp]
         L.sbwtgpu_unitigs_graph_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.sbwtgpu_unitigs_walks_prepare.argtypes = [vp]
+        L.sbwtgpu_unitigs_walks_workspace_bytes.argtypes = [i64, i64]
+        L.sbwtgpu_unitigs_walks_workspace_bytes.restype = i64
+        L.sbwtgpu_unitigs_walks_dev.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp]
+        L.sbwtgpu_unitigs_walks_batch.argtypes = [vp, vp, vp, vp, i64, vp, C.POINTER(vp), C.POINTER(i64), vp]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -871,6 +879,42 @@ class Unitigs:
         _check(lib().sbwtgpu_unitigs_graph_stats(self._h, C.byref(a), C.byref(b)))
         return {"links_ms": float(a.value), "map_ms": float(b.value)}
 
+    # ---- reads threaded through the graph (a handle with the column map) ----
+    def walks_prepare(self) -> None:
+        """sbwtgpu_unitigs_walks_prepare: builds the handle's start bitmap (idempotent)."""
+        _check(lib().sbwtgpu_unitigs_walks_prepare(self._h))
+
+    def walks(self, index: "Index", bases, read_off, coverage: bool = False):
+        """sbwtgpu_unitigs_walks_batch: (step_off: int64[n_reads + 1], steps: WALK_STEP[n_steps]) -- read r's steps are
+        steps[step_off[r]:step_off[r + 1]] -- and with coverage=True also int64[n_unitigs], the k-mer hits per unitig."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        n = max(len(read_off) - 1, 0)
+        step_off = np.full(n + 1, -12345, dtype=np.int64)
+        cov = np.full(self.n_unitigs, -12345, dtype=np.int64) if coverage else None
+        p, ns = C.c_void_p(), C.c_int64(0)
+        _check(lib().sbwtgpu_unitigs_walks_batch(index._h, self._h, bases.ctypes.data, read_off.ctypes.data, n, step_off.ctypes.data,
+                                                 C.byref(p), C.byref(ns), cov.ctypes.data if coverage else None))
+        try:
+            steps = np.empty(ns.value, dtype=WALK_STEP)
+            if ns.value:
+                C.memmove(steps.ctypes.data, p.value, ns.value * WALK_STEP.itemsize)
+        finally:
+            if p.value:
+                lib().sbwtgpu_free_host(p)
+        return (step_off, steps, cov) if coverage else (step_off, steps)
+
+    def walks_reads(self, index: "Index", reads: Sequence[bytes], coverage: bool = False):
+        """The same for a list of byte strings."""
+        bases, off = concat_reads(reads)
+        return self.walks(index, bases, off, coverage)
+
+    def walks_dev(self, index: "Index", d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_step_off: int, d_steps: int,
+                  steps_cap: int, d_unitig_kmers: int, d_ws: int, ws_bytes: int, stream: int = 0) -> None:
+        """sbwtgpu_unitigs_walks_dev (raw device pointers; d_unitig_kmers 0 = no coverage); needs walks_prepare()."""
+        _check(lib().sbwtgpu_unitigs_walks_dev(index._h, self._h, d_bases, total_bases, d_read_off, n_reads, d_step_off, d_steps,
+                                               steps_cap, d_unitig_kmers or None, d_ws, ws_bytes, stream))
+
     # ---- a coloured handle only (ColorSets.unitigs_dev) ----
     def set_ids_dev(self) -> int:
         """d_set_id (n_unitigs uint32) as an integer; valid until close()."""
@@ -1392,6 +1436,10 @@ def ms_workspace_bytes(total_bases: int) -> int:
 
 def read_hits_workspace_bytes(total_bases: int, n_reads: int, both_strands: bool = False) -> int:
     return int(lib().sbwtgpu_read_hits_workspace_bytes(total_bases, n_reads, 2 if both_strands else 1))
+
+
+def walks_workspace_bytes(total_bases: int, n_reads: int) -> int:
+    return int(lib().sbwtgpu_unitigs_walks_workspace_bytes(total_bases, n_reads))
 
 
 def pseudoalign_workspace_bytes(total_bases: int, n_reads: int, both_strands: bool = False) -> int:

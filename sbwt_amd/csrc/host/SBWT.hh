@@ -520,6 +520,73 @@ public:
         detail::gpu_check(rc);
         return r;
     }
+    // Reads threaded through the unitig graph (include/sbwtgpu.h, "walks"): a graph handle of the index -- plain, or coloured
+    // under a colour-set object of THIS index -- with links and column map, kept for as many batches as the caller has.
+    class UnitigGraph {
+    public:
+        UnitigGraph() = default;
+        UnitigGraph(const UnitigGraph &) = delete;
+        UnitigGraph &operator=(const UnitigGraph &) = delete;
+        UnitigGraph(UnitigGraph &&o) noexcept : h(o.h), colored(o.colored) { o.h = nullptr; }
+        ~UnitigGraph() { if (h) sbwtgpu_unitigs_destroy(h); }
+        // what unitigs(true) / colored_unitigs(sets, true) return, from this handle (set_id stays empty for a plain graph)
+        ColoredUnitigs unitigs() const {
+            ColoredUnitigs r;
+            int64_t n = 0, total = 0;
+            detail::gpu_check(sbwtgpu_unitigs_info(h, &n, &total, nullptr));
+            r.bases.resize((size_t)total);
+            r.off.resize((size_t)n + 1);
+            r.first_col.resize((size_t)n);
+            detail::gpu_check(sbwtgpu_unitigs_copy(h, r.bases.data(), r.off.data(), r.first_col.data()));
+            if (colored) {
+                r.set_id.resize((size_t)n);
+                detail::gpu_check(sbwtgpu_unitigs_set_ids_copy(h, r.set_id.data()));
+                detail::gpu_check(sbwtgpu_unitigs_color_info(h, &r.n_color_breaks, &r.n_sets, &r.n_colors));
+            }
+            detail::gpu_check(copy_links(h, n, r.link_off, r.link_to));
+            return r;
+        }
+        sbwtgpu_unitigs *h = nullptr;
+        bool colored = false;
+    };
+    UnitigGraph unitig_graph(const sbwtgpu_colorsets *sets = nullptr) const {
+        UnitigGraph g;
+        const sbwtgpu_index *idx = need_device();
+        g.colored = sets != nullptr;
+        detail::gpu_check(sbwtgpu_unitigs_create_graph(sets ? nullptr : idx, sets, SBWTGPU_UNITIGS_LINKS | SBWTGPU_UNITIGS_COLUMN_MAP, &g.h));
+        return g;
+    }
+    // read r's steps are steps[step_off[r] .. step_off[r+1]); unitig_kmers (coverage = true) has the k-mer hits per unitig
+    struct Walks {
+        std::vector<int64_t> step_off;
+        std::vector<sbwtgpu_walk_step> steps;
+        std::vector<int64_t> unitig_kmers;
+    };
+    Walks walks(const UnitigGraph &g, const char *bases, const int64_t *read_off, int64_t n_reads, bool coverage = false) const {
+        Walks w;
+        w.step_off.resize((size_t)std::max<int64_t>(n_reads, 0) + 1);
+        if (coverage) {
+            int64_t n = 0;
+            detail::gpu_check(sbwtgpu_unitigs_info(g.h, &n, nullptr, nullptr));
+            w.unitig_kmers.resize((size_t)n);
+        }
+        sbwtgpu_walk_step *steps = nullptr;
+        int64_t n_steps = 0;
+        detail::gpu_check(sbwtgpu_unitigs_walks_batch(need_device(), g.h, bases, read_off, n_reads, w.step_off.data(), &steps, &n_steps,
+                                                      coverage ? w.unitig_kmers.data() : nullptr));
+        if (n_steps > 0) w.steps.assign(steps, steps + n_steps);
+        sbwtgpu_free_host(steps);
+        return w;
+    }
+    Walks walks(const UnitigGraph &g, const std::vector<std::string> &reads, bool coverage = false) const {
+        std::string bases;
+        std::vector<int64_t> read_off{0};
+        for (const std::string &r : reads) {
+            bases += r;
+            read_off.push_back((int64_t)bases.size());
+        }
+        return walks(g, bases.data(), read_off.data(), (int64_t)reads.size(), coverage);
+    }
     // the links of a graph handle of n unitigs into host vectors
     static int copy_links(const sbwtgpu_unitigs *u, int64_t n, std::vector<int64_t> &link_off, std::vector<uint32_t> &link_to) {
         int64_t n_links = 0;

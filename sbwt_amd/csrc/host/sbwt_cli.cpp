@@ -788,9 +788,10 @@ int read_hits_main(int argc, char **argv) {
 // With --gfa the output file is GFA 1 instead: the unitigs as segments, then the links between them.
 int dump_unitigs_colored(const plain_matrix_sbwt_t &index, const string &indexfile, const string &colorsfile, const string &outfile,
                          const string &setsfile, bool gzip, bool gfa);
-// GFA 1: "H VN:Z:1.0", one "S number bases [cs:i:set-id]" per unitig, then one "L i + j + (k-1)M" per link in link order
+// GFA 1: "H VN:Z:1.0", one "S number bases [cs:i:set-id] [KC:i:k-mer hits]" per unitig, then one "L i + j + (k-1)M" per link in
+// link order
 static string gfa_text(const vector<char> &bases, const vector<int64_t> &off, const vector<int64_t> &link_off,
-                       const vector<uint32_t> &link_to, const vector<uint32_t> *set_id, int64_t k) {
+                       const vector<uint32_t> &link_to, const vector<uint32_t> *set_id, int64_t k, const vector<int64_t> *kc = nullptr) {
     const int64_t n = (int64_t)off.size() - 1;
     string text;
     text.reserve(bases.size() + (size_t)n * 24 + link_to.size() * 32 + 16);
@@ -803,6 +804,10 @@ static string gfa_text(const vector<char> &bases, const vector<int64_t> &off, co
         if (set_id) {
             text.append("\tcs:i:");
             append_int((int64_t)(*set_id)[(size_t)i], text);
+        }
+        if (kc) {
+            text.append("\tKC:i:");
+            append_int((*kc)[(size_t)i], text);
         }
         text.push_back('\n');
     }
@@ -1324,6 +1329,126 @@ int dump_unitigs_colored(const plain_matrix_sbwt_t &index, const string &indexfi
     return 0;
 }
 
+// sbwt thread: the reads threaded through the unitig graph of the index.  One line per read, in read
+// order: the 0-based read number, then one `read_pos:unitig:offset:n_kmers` per step, space-separated.  --colors threads
+// through the coloured graph; --coverage writes `unitig<TAB>n_kmers<TAB>kmer_hits` per unitig; --gfa writes the graph as
+// `dump-unitigs --gfa` does with a KC:i: tag (the k-mer hits) on every segment.
+int thread_main(int argc, char **argv) {
+    int64_t micros_start = cur_time_micros();
+    set_log_level(LogLevel::MINOR);
+    Options opts({
+        {"out-file", 'o', true, "Output filename.", ""},
+        {"index-file", 'i', true, "Index input file.", ""},
+        {"query-file", 'q', true, "The reads in FASTA or FASTQ format, possibly gzipped.", ""},
+        {"gzip-output", 'z', false, "Writes the walks in gzipped form.", ""},
+        {"colors", 0, true, "Colour file or colour-set file of the index: thread through the coloured unitigs.", ""},
+        {"coverage", 0, true, "Write one line per unitig: unitig, its k-mers, the k-mer hits of the reads on it (tab-separated).", ""},
+        {"gfa", 0, true, "Write the graph as GFA 1, as dump-unitigs --gfa does, with the k-mer hits as a KC:i: tag per segment.", ""},
+        {"gpu", 0, true, "HIP device to run on.", "0"},
+        {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
+        {"help", 'h', false, "Print usage", ""},
+    });
+    opts.parse(argc, argv);
+    if (argc == 1 || opts.count("help")) {
+        std::cerr << opts.help(argv[0], "Per read: the unitigs of the de Bruijn graph it runs along, as read_pos:unitig:offset:n_kmers steps.") << std::endl;
+        exit(1);
+    }
+    const string indexfile = opts.get("index-file"), queryfile = opts.get("query-file"), outfile = opts.get("out-file");
+    const bool colored = opts.count("colors");
+    const string colorsfile = colored ? opts.get("colors") : string();
+    const string covfile = opts.count("coverage") ? opts.get("coverage") : string(), gfafile = opts.count("gfa") ? opts.get("gfa") : string();
+    check_readable(indexfile);
+    check_readable(queryfile);
+    if (colored) check_readable(colorsfile);
+    check_writable(outfile);
+    if (!covfile.empty()) check_writable(covfile);
+    if (!gfafile.empty()) check_writable(gfafile);
+    const bool gzip_output = opts.count("gzip-output"), coverage = !covfile.empty() || !gfafile.empty();
+    set_default_device(atoi(opts.get("gpu").c_str()));
+    int64_t batch_bases = atoll(opts.get("batch-bases").c_str());
+    if (batch_bases < 1) batch_bases = 1;
+
+    std::ifstream in(indexfile, std::ios::binary);
+    if (!in.good()) throw std::runtime_error("Error opening file: " + indexfile);
+    const string variant = load_string(in);
+    if (variant != "plain-matrix")
+        throw std::runtime_error("Error: only the plain-matrix variant is supported by the GPU path (got " + variant + ")");
+    plain_matrix_sbwt_t index;
+    index.load(in);
+    ColorSetsHandle sets;
+    if (colored) load_colorsets(colorsfile, indexfile, index, sets);
+    const plain_matrix_sbwt_t::UnitigGraph graph = index.unitig_graph(colored ? sets.h : nullptr);
+    vector<int64_t> kmer_hits;
+    int64_t total_reads = 0, total_steps = 0;
+    {
+        write_log("Threading the reads of " + queryfile + " to output file " + outfile, LogLevel::MAJOR);
+        seq_io::Reader reader(queryfile);
+        seq_io::Buffered_ofstream writer(outfile, gzip_output);
+        bool more = true;
+        vector<char> bases;
+        vector<int64_t> read_off;
+        string text;
+        while (more) {
+            bases.clear();
+            read_off.assign(1, 0);
+            more = reader.read_batch(bases, read_off, batch_bases);
+            const int64_t n_reads = (int64_t)read_off.size() - 1;
+            if (n_reads <= 0) continue;
+            const plain_matrix_sbwt_t::Walks w = index.walks(graph, bases.data(), read_off.data(), n_reads, coverage);
+            text.clear();
+            for (int64_t r = 0; r < n_reads; r++) {
+                append_int(total_reads + r, text);
+                for (int64_t s = w.step_off[(size_t)r]; s < w.step_off[(size_t)r + 1]; s++) {
+                    const sbwtgpu_walk_step &st = w.steps[(size_t)s];
+                    text.push_back(' ');
+                    append_int(st.read_pos, text);
+                    text.push_back(':');
+                    append_int((int64_t)st.unitig, text);
+                    text.push_back(':');
+                    append_int((int64_t)st.offset, text);
+                    text.push_back(':');
+                    append_int(st.n_kmers, text);
+                }
+                text.push_back('\n');
+            }
+            writer.write(text.data(), (int64_t)text.size());
+            if (coverage) {
+                if (kmer_hits.empty()) kmer_hits = w.unitig_kmers;
+                else for (size_t i = 0; i < kmer_hits.size(); i++) kmer_hits[i] += w.unitig_kmers[i];
+            }
+            total_reads += n_reads;
+            total_steps += (int64_t)w.steps.size();
+        }
+    }
+    if (coverage) {
+        const plain_matrix_sbwt_t::ColoredUnitigs u = graph.unitigs();
+        const int64_t n = (int64_t)u.first_col.size(), k = index.get_k();
+        kmer_hits.resize((size_t)n, 0);                  // (no read at all: zeros)
+        if (!covfile.empty()) {
+            string lines;
+            for (int64_t i = 0; i < n; i++) {
+                append_int(i, lines);
+                lines.push_back('\t');
+                append_int(u.off[(size_t)i + 1] - u.off[(size_t)i] - (k - 1), lines);
+                lines.push_back('\t');
+                append_int(kmer_hits[(size_t)i], lines);
+                lines.push_back('\n');
+            }
+            if (sbwthost_write_file(covfile.c_str(), lines.data(), (int64_t)lines.size(), 0, 0) != 0)
+                throw std::runtime_error(string("Error writing ") + covfile + ": " + sbwthost_last_error());
+        }
+        if (!gfafile.empty()) {
+            const string text = gfa_text(u.bases, u.off, u.link_off, u.link_to, colored ? &u.set_id : nullptr, k, &kmer_hits);
+            if (sbwthost_write_file(gfafile.c_str(), text.data(), (int64_t)text.size(), 0, 0) != 0)
+                throw std::runtime_error(string("Error writing ") + gfafile + ": " + sbwthost_last_error());
+        }
+    }
+    write_log("Threaded " + std::to_string(total_reads) + " reads: " + std::to_string(total_steps) + " steps; us/read end-to-end: " +
+                  std::to_string((double)(cur_time_micros() - micros_start) / (double)std::max<int64_t>(1, total_reads)),
+              LogLevel::MAJOR);
+    return 0;
+}
+
 // sbwt merge-colors: the colour sets of one or two coloured indexes carried onto index U (the output of `sbwt set-op`, for
 // one), without any sequence file: the "SBWTCOL3" file that build-colors --compress writes for U and the same colouring
 int merge_colors_main(int argc, char **argv) {
@@ -1633,7 +1758,7 @@ int pseudoalign_main(int argc, char **argv) {
     return 0;
 }
 
-const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "set-op", "read-hits", "build-colors", "compress-colors", "merge-colors", "color-matrix", "color-select", "pseudoalign"};
+const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "thread", "set-op", "read-hits", "build-colors", "compress-colors", "merge-colors", "color-matrix", "color-select", "pseudoalign"};
 
 void print_help(char **argv) {
     std::cerr << "Available commands: " << std::endl;
@@ -1664,6 +1789,7 @@ int main(int argc, char **argv) {   // sbwt.cpp:19-57
         }
         else if (command == "matching-statistics") return matching_statistics_main(argc, argv);
         else if (command == "dump-unitigs") return dump_unitigs_main(argc, argv);
+        else if (command == "thread") return thread_main(argc, argv);
         else if (command == "set-op") return set_op_main(argc, argv);
         else if (command == "read-hits") return read_hits_main(argc, argv);
         else if (command == "build-colors") return build_colors_main(argc, argv);

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <atomic>
 #include <mutex>
 #include <cstddef>
 #include <cstring>
@@ -23,6 +24,7 @@
 #include "sbwt_unitigs.h"
 #include "sbwt_setops.h"
 #include "sbwt_readhits.h"
+#include "sbwt_walks.h"
 #include "sbwt_colors.h"
 #include "sbwt_colorsets.h"
 #include "sbwt_colormerge.h"
@@ -186,6 +188,7 @@ static int g_sparse_buckets_pct = [] { const int v = env_int("SBWTGPU_SPARSE_BUC
 static int g_rh_wave_min = SBWT_RH_WAVE_MIN;
 static int64_t g_rh_chunk_bases = 0;
 static int g_rh_wide = 0;
+static int64_t g_wk_chunk_bases = 0;      // "walks_chunk_bases": 0 = the default of 64 Mi
 static int64_t g_pa_chunk_bases = 0;      // "pseudoalign_chunk_bases": 0 = the default of 64 Mi
 // shared k-mers (sbwt_colormatrix.hip): objects of this many sets or more go to the matrix cores, smaller ones to the plain
 // kernel; the sets a wave adds up in 32 bits before it adds into the 64-bit matrix.  Neither shows in a result.
@@ -296,6 +299,7 @@ int sbwtgpu_set_tuning(const char *key, int64_t value) {
     if (!strcmp(key, "read_hits_wave_min")) { g_rh_wave_min = value < 1 ? SBWT_RH_WAVE_MIN : value > 0x7fffffff ? 0x7fffffff : (int)value; return SBWTGPU_OK; }
     if (!strcmp(key, "read_hits_chunk_bases")) { g_rh_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "read_hits_wide")) { g_rh_wide = (int)value; return SBWTGPU_OK; }
+    if (!strcmp(key, "walks_chunk_bases")) { g_wk_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "pseudoalign_chunk_bases")) { g_pa_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "gram_mfma_min_sets")) { g_gram_mfma_min_sets = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "gram_flush_sets")) {
@@ -2582,6 +2586,10 @@ struct sbwtgpu_unitigs {
     // a graph handle (sbwtgpu_unitigs_create_graph): the SBWTGPU_UNITIGS_* flags it was made with, and what locate checks against
     unsigned graph = 0;
     int64_t n_nodes = 0;
+    // the walks' start bitmap (sbwtgpu_unitigs_walks_prepare): one bit per column, made once from the
+    // column map under the mutex and then only read
+    mutable std::mutex walks_mutex;
+    mutable std::atomic<unsigned long long *> d_walk_start{nullptr};
 };
 
 // the plain call, or with a colour view (ids, table, words) the coloured one; graph: SBWTGPU_UNITIGS_* flags
@@ -2640,6 +2648,7 @@ void sbwtgpu_unitigs_destroy(sbwtgpu_unitigs *u) {
     if (u->run.d_link_to) (void)hipFree(u->run.d_link_to);
     if (u->run.d_col_unitig) (void)hipFree(u->run.d_col_unitig);
     if (u->run.d_col_offset) (void)hipFree(u->run.d_col_offset);
+    if (u->d_walk_start.load()) (void)hipFree(u->d_walk_start.load());
     delete u;
 }
 
@@ -2951,6 +2960,216 @@ int sbwtgpu_read_hits_batch(const sbwtgpu_index *idx, const char *bases, const i
     park_slots(idx->device, S, n_slots, rc);
     if (rc != SBWTGPU_OK) return rc;
     if (bug) return fail_status(bug);
+    return SBWTGPU_OK;
+}
+
+// ---- reads threaded through the unitig graph (sbwt_walks.hip) -----------------------
+static_assert(sizeof(sbwtgpu_walk_step) == sizeof(SbwtWalkStep), "the record of the ABI is the kernels' record");
+
+int sbwtgpu_unitigs_walks_prepare(sbwtgpu_unitigs *u) {
+    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_COLUMN_MAP, "SBWTGPU_UNITIGS_COLUMN_MAP");
+    if (rc != SBWTGPU_OK) return rc;
+    if (u->d_walk_start.load(std::memory_order_acquire)) return SBWTGPU_OK;
+    std::lock_guard<std::mutex> lock(u->walks_mutex);
+    if (u->d_walk_start.load(std::memory_order_acquire)) return SBWTGPU_OK;
+    DeviceGuard guard(u->device);
+    DevBuf bits;
+    Stream st;
+    hipError_t e = bits.alloc((size_t)((u->n_nodes + 63) / 64 + 1) * 8);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
+    if (e == hipSuccess) {
+        sbwt_launch_walk_startbits(u->run.d_col_offset, u->n_nodes, static_cast<unsigned long long *>(bits.p), st.s);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st.s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "walks: start bitmap: %s", hipGetErrorString(e));
+    }
+    u->d_walk_start.store(static_cast<unsigned long long *>(bits.p), std::memory_order_release);
+    bits.p = nullptr;
+    return SBWTGPU_OK;
+}
+
+int64_t sbwtgpu_unitigs_walks_workspace_bytes(int64_t total_bases, int64_t n_reads) {
+    if (total_bases < 0) total_bases = 0;
+    if (n_reads < 0) n_reads = 0;
+    return sbwt_walk_layout(sbwtgpu_search_workspace_bytes(total_bases), total_bases, n_reads).total;
+}
+
+static int walks_check(const sbwtgpu_index *idx, const sbwtgpu_unitigs *u, int64_t n_reads) {
+    if (!idx) return fail(SBWTGPU_ERR_INVALID_ARG, "idx is NULL");
+    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    // (the size first, as the colour layer does: an index of that size is refused for it whatever else is wrong with the call)
+    if (idx->h.n_nodes >= ((int64_t)1 << 31))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "walks: the index has %lld columns, the walks read int32 search results (fewer than 2^31 columns)",
+                    (long long)idx->h.n_nodes);
+    int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_COLUMN_MAP, "SBWTGPU_UNITIGS_COLUMN_MAP");
+    if (rc != SBWTGPU_OK) return rc;
+    if (idx->h.rank_only) return fail(SBWTGPU_ERR_INVALID_ARG, "%s", RANK_ONLY_MSG);
+    if (u->n_nodes != idx->h.n_nodes || u->k != idx->h.k || u->device != idx->device)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "walks: the handle (%lld columns, k = %lld, device %d) was not made from this index (%lld columns, k = %lld, device %d)",
+                    (long long)u->n_nodes, (long long)u->k, u->device, (long long)idx->h.n_nodes, (long long)idx->h.k, idx->device);
+    if (n_reads < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative n_reads");
+    if (n_reads >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_INVALID_ARG, "2^31 reads or more in one call: split the batch");
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_unitigs_walks_dev(const sbwtgpu_index *idx, const sbwtgpu_unitigs *u, const char *d_bases, int64_t total_bases,
+                              const int64_t *d_read_off, int64_t n_reads, int64_t *d_step_off, sbwtgpu_walk_step *d_steps,
+                              int64_t steps_cap, int64_t *d_unitig_kmers, void *d_ws, int64_t ws_bytes, void *stream) {
+    int rc = walks_check(idx, u, n_reads);
+    if (rc != SBWTGPU_OK) return rc;
+    if (steps_cap < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative steps_cap");
+    if (total_bases < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative size");
+    if (total_bases >= ((int64_t)1 << 36))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "more than 2^36 bases in one call: split the batch");
+    const unsigned long long *start = u->d_walk_start.load(std::memory_order_acquire);
+    if (!start)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "walks: the handle is not prepared (sbwtgpu_unitigs_walks_prepare builds its start bitmap)");
+    const int64_t need = sbwtgpu_unitigs_walks_workspace_bytes(total_bases, n_reads);
+    if (!d_ws || ws_bytes < need)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "workspace missing or too small (%lld < %lld)", (long long)ws_bytes, (long long)need);
+    if (((uintptr_t)d_ws & 15) != 0) return fail(SBWTGPU_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+    if (!d_step_off || (steps_cap > 0 && !d_steps)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
+    DeviceGuard guard(idx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n_reads == 0) {
+        HIP_TRY(hipMemsetAsync(d_step_off, 0, 8, st));
+        return SBWTGPU_OK;
+    }
+    if (!d_read_off || (total_bases > 0 && !d_bases)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
+    const int64_t search_ws = sbwtgpu_search_workspace_bytes(total_bases);
+    const SbwtWalkLayout L = sbwt_walk_layout(search_ws, total_bases, n_reads);
+    char *w = static_cast<char *>(d_ws);
+    int32_t *res = reinterpret_cast<int32_t *>(w + L.res);
+    long long *ooff = reinterpret_cast<long long *>(w + L.ooff);
+    const int k = (int)idx->h.k;
+    sbwt_launch_rh_offsets(reinterpret_cast<const long long *>(d_read_off), n_reads, k, reinterpret_cast<long long *>(w + L.cnt),
+                           reinterpret_cast<long long *>(w + L.bsum), ooff, st);
+    // (a batch of fewer than k bases has no window: nothing to search, W = 0 and no pass below reads a result; the status
+    // word that sbwtgpu_workspace_status looks at is then cleared here)
+    if (total_bases >= k) {
+        rc = search_dev_i32(idx, d_bases, total_bases, d_read_off, n_reads, res, reinterpret_cast<const int64_t *>(ooff), d_ws, search_ws,
+                            stream, 0);
+        if (rc != SBWTGPU_OK) return rc;
+    } else {
+        HIP_TRY(hipMemsetAsync(d_ws, 0, sizeof(SbwtWorkHeader), st));
+    }
+    const hipError_t e = sbwt_launch_walks(res, ooff, n_reads, total_bases, start, u->run.d_col_unitig, u->run.d_col_offset, u->n_nodes, w, L,
+                                           reinterpret_cast<long long *>(d_step_off), reinterpret_cast<SbwtWalkStep *>(d_steps), steps_cap,
+                                           reinterpret_cast<long long *>(d_unitig_kmers), st);
+    if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "walks passes: %s", hipGetErrorString(e));
+    return SBWTGPU_OK;
+}
+
+// Host buffers: the batch is cut into chunks of whole reads of at most "walks_chunk_bases" bases (a chunk always takes one
+// read), one after the other on a parked slot of the search pipeline: a chunk's step count decides how many records come
+// back, so its offsets are read before its records are fetched.  step_off is stitched: a chunk's offsets plus the steps of
+// the chunks before it.
+int sbwtgpu_unitigs_walks_batch(const sbwtgpu_index *idx, const sbwtgpu_unitigs *u, const char *bases, const int64_t *read_off,
+                                int64_t n_reads, int64_t *step_off, sbwtgpu_walk_step **steps_out, int64_t *n_steps,
+                                int64_t *unitig_kmers) {
+    int rc = walks_check(idx, u, n_reads);
+    if (rc != SBWTGPU_OK) return rc;
+    if (!step_off || !steps_out || !n_steps) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    *steps_out = nullptr;
+    *n_steps = 0;
+    step_off[0] = 0;
+    const int64_t n_unitigs = u->run.n_unitigs;
+    if (unitig_kmers && n_unitigs > 0) memset(unitig_kmers, 0, (size_t)n_unitigs * 8);
+    if (n_reads == 0) return SBWTGPU_OK;
+    if (!read_off) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    if (read_off[n_reads] > read_off[0] && !bases) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
+    if ((rc = sbwtgpu_unitigs_walks_prepare(const_cast<sbwtgpu_unitigs *>(u))) != SBWTGPU_OK) return rc;
+    const int64_t budget = g_wk_chunk_bases > 0 ? g_wk_chunk_bases : (int64_t)64 << 20, CH_READS = (int64_t)1 << 24, k = idx->h.k;
+    std::vector<int64_t> cuts{0};
+    int64_t max_bases = 0, max_reads = 0, max_windows = 0, windows = 0;
+    try {
+        for (int64_t lo = 0, r = 0; r < n_reads; r++) {
+            if ((rc = check_read_length(read_off, r)) != SBWTGPU_OK) return rc;
+            if (r > lo && (read_off[r + 1] - read_off[lo] > budget || r - lo >= CH_READS)) {
+                cuts.push_back(r);
+                lo = r;
+                windows = 0;
+            }
+            windows += std::max<int64_t>(0, read_off[r + 1] - read_off[r] - k + 1);
+            max_bases = std::max(max_bases, read_off[r + 1] - read_off[lo]);
+            max_reads = std::max(max_reads, r + 1 - lo);
+            max_windows = std::max(max_windows, windows);
+        }
+        cuts.push_back(n_reads);
+    } catch (const std::bad_alloc &) {
+        return fail(SBWTGPU_ERR_OOM, "out of host memory");
+    }
+    const int64_t n_chunks = (int64_t)cuts.size() - 1;
+    const bool pin_in = is_pinned(bases);
+    const int64_t ws_bytes = sbwtgpu_unitigs_walks_workspace_bytes(max_bases, max_reads);
+    // device: [bases][read_off][step_off][coverage][steps][workspace]; pinned: bases and offsets down, step_off (and coverage) back
+    const int64_t o_roff = align256(max_bases + 16), o_soff = o_roff + align256((max_reads + 1) * 8),
+                  o_cov = o_soff + align256((max_reads + 1) * 8), o_steps = o_cov + (unitig_kmers ? align256(n_unitigs * 8 + 8) : 0),
+                  o_ws = o_steps + align256(max_windows * 16 + 16), need_dev = o_ws + align256(ws_bytes);
+    const int64_t need_in = o_soff, need_out = align256((max_reads + 1) * 8);
+    DeviceGuard guard(idx->device);
+    PipeSlot S[1];
+    if ((rc = take_slots(idx->device, S, 1, need_in, need_out, need_dev, "walks buffers")) != SBWTGPU_OK) return rc;
+    PipeSlot &P = S[0];
+    int bug = 0;                    // the first nonzero device status of a chunk
+    sbwtgpu_walk_step *steps = nullptr;
+    int64_t total = 0, cap = 0;
+    auto run = [&]() -> int {
+        hipError_t e;
+        if (unitig_kmers && n_unitigs > 0 && (e = hipMemsetAsync(P.d_mem + o_cov, 0, (size_t)n_unitigs * 8, P.st)) != hipSuccess)
+            return fail(SBWTGPU_ERR_HIP, "memset: %s", hipGetErrorString(e));
+        for (int64_t c = 0; c < n_chunks; c++) {
+            const int64_t lo = cuts[(size_t)c], hi = cuts[(size_t)c + 1], nr = hi - lo, nb = read_off[hi] - read_off[lo];
+            int64_t *hro = (int64_t *)(P.h_in + o_roff);
+            for (int64_t r = 0; r <= nr; r++) hro[r] = read_off[lo + r] - read_off[lo];
+            const char *hb = bases + read_off[lo];
+            if (!pin_in && nb > 0) { parallel_memcpy(P.h_in, hb, (size_t)nb); hb = P.h_in; }
+            if ((nb > 0 && (e = hipMemcpyAsync(P.d_mem, hb, (size_t)nb, hipMemcpyHostToDevice, P.st)) != hipSuccess) ||
+                (e = hipMemcpyAsync(P.d_mem + o_roff, hro, (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, P.st)) != hipSuccess)
+                return fail(SBWTGPU_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
+            const int r2 = sbwtgpu_unitigs_walks_dev(idx, u, P.d_mem, nb, (const int64_t *)(P.d_mem + o_roff), nr, (int64_t *)(P.d_mem + o_soff),
+                                                     (sbwtgpu_walk_step *)(P.d_mem + o_steps), max_windows,
+                                                     unitig_kmers ? (int64_t *)(P.d_mem + o_cov) : nullptr, P.d_mem + o_ws, ws_bytes, P.st);
+            if (r2 != SBWTGPU_OK) return r2;
+            if ((e = hipMemcpyAsync(P.h_out, P.d_mem + o_soff, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, P.st)) != hipSuccess ||
+                (e = hipMemcpyAsync(P.h_status, P.d_mem + o_ws + offsetof(SbwtWorkHeader, status), 4, hipMemcpyDeviceToHost, P.st)) != hipSuccess ||
+                (e = hipStreamSynchronize(P.st)) != hipSuccess)
+                return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
+            if (P.h_status[0] != 0 && bug == 0) bug = P.h_status[0];
+            const int64_t *so = (const int64_t *)P.h_out, ns = so[nr];
+            for (int64_t r = 1; r <= nr; r++) step_off[lo + r] = total + so[r];
+            if (ns > 0) {
+                if (total + ns > cap) {
+                    const int64_t want = std::max(total + ns, cap + cap / 2);
+                    void *q = realloc(steps, (size_t)want * sizeof(sbwtgpu_walk_step));
+                    if (!q) return fail(SBWTGPU_ERR_OOM, "out of host memory");
+                    steps = static_cast<sbwtgpu_walk_step *>(q);
+                    cap = want;
+                }
+                if ((e = hipMemcpyAsync(steps + total, P.d_mem + o_steps, (size_t)ns * sizeof(sbwtgpu_walk_step), hipMemcpyDeviceToHost, P.st)) != hipSuccess ||
+                    (e = hipStreamSynchronize(P.st)) != hipSuccess)
+                    return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
+                total += ns;
+            }
+        }
+        if (unitig_kmers && n_unitigs > 0 &&
+            ((e = hipMemcpyAsync(unitig_kmers, P.d_mem + o_cov, (size_t)n_unitigs * 8, hipMemcpyDeviceToHost, P.st)) != hipSuccess ||
+             (e = hipStreamSynchronize(P.st)) != hipSuccess))
+            return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
+        return SBWTGPU_OK;
+    };
+    rc = run();
+    park_slots(idx->device, S, 1, rc);
+    if (rc == SBWTGPU_OK && bug) rc = fail_status(bug);
+    if (rc != SBWTGPU_OK) {
+        free(steps);
+        return rc;
+    }
+    *steps_out = steps;
+    *n_steps = total;
     return SBWTGPU_OK;
 }
 

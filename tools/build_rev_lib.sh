@@ -7,7 +7,8 @@ REV=$1; NAME=$2
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 W=$(mktemp -d /tmp/sbwt_rev_XXXX)
 git -C "$ROOT" worktree add -f "$W" "$REV" > /dev/null
-( cd "$W/sbwt_amd/csrc" && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -o "$ROOT/sbwt_amd/lib/$NAME.so" \
-    sbwt_search.hip sbwt_search_fused.hip sbwt_api_kernels.hip sbwt_derived.hip sbwt_build.hip sbwt_sort.hip sbwt_format.hip sbwtgpu_capi.cpp -ldl )
+# (compiler, flags and sources are those of the revision's own build driver, read as a file: its package is not imported)
+CMD=$(cd "$W" && python -c "import runpy, sys; print(' '.join(runpy.run_path('sbwt_amd/build.py')['_hipcc_cmd'](sys.argv[1])))" "$ROOT/sbwt_amd/lib/$NAME.so")
+$CMD
 git -C "$ROOT" worktree remove --force "$W"
 echo "built $ROOT/sbwt_amd/lib/$NAME.so from $REV"
