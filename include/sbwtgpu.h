@@ -118,6 +118,8 @@ int         sbwtgpu_device_count(int *count);
  *                        always takes one read); 0 (default) = 64 Mi
  *   "pseudoalign_chunk_bases" sbwtgpu_pseudoalign_batch (_wide_batch, _sets_batch) and sbwtgpu_colors_add_batch cut their batch
  *                        into chunks of whole reads of at most this many bases (a chunk always takes one read); 0 (default) = 64 Mi
+ *   "screen_chunk_bases" sbwtgpu_screen_add_batch cuts its batch into chunks of whole reads of at most this many bases (a chunk
+ *                        always takes one read); 0 (default) = 64 Mi
  *   "trans_ext", "trans_wide"   accepted and ignored (round-2 table formats)
  * Read when an index is CREATED (derived acceleration structures inside the device image; environment
  * variables of the same meaning: SBWTGPU_SPARSE_PRECALC, SBWTGPU_PROBE_FILTER, SBWTGPU_PATH_ORDER):
@@ -986,6 +988,68 @@ int  sbwtgpu_colorsets_match_sets(const sbwtgpu_colorsets *s, const sbwtgpu_colo
 int  sbwtgpu_colorsets_select_counts(const sbwtgpu_colorsets *s, const sbwtgpu_color_predicate *p, sbwtgpu_color_select_info *info);
 int  sbwtgpu_colorsets_select(const sbwtgpu_colorsets *s, const sbwtgpu_color_predicate *p, int build_streaming_support,
                               sbwtgpu_plain_matrix_bits *out, sbwtgpu_color_select_info *info /* may be NULL */);
+
+/* ---- screen: which references are in a read set, and how much of each ----
+ * The sample-level counterpart of the per-read hit profiles and of the shared k-mers: per reference the number of its
+ * k-mers, how many distinct ones the sample contains (breadth: the exact containment) and how many of the sample's windows
+ * fall on it (depth).  A screen object is an accumulator on the device that lives across batches.
+ * Inputs: a colour-set object s of an index of n columns, with n_sets, ids, table, C = n_colors and W words per row, and
+ * batches of reads in the form sbwtgpu_read_hits_* takes them.
+ * The sample M is the multiset of the windows of all reads added so far.  A window counts under the rule of
+ * sbwtgpu_search_batch: a byte other than upper-case A/C/G/T in it means no hit.  With strands = 2, M also holds the
+ * reverse complement of every window (the complement rule of the read-hit profiles): a window is then two occurrences, and
+ * a palindromic window two occurrences of one k-mer.  A window whose search result is >= 0 is one HIT on that column; with
+ * two strands each of its two k-mers is.  The object holds
+ *   - n_windows, the size of M, misses counted (strands = 2: twice the windows);
+ *   - n_hits, the number of hits;
+ *   - seen, one bit per column: bit v is set when column v has a hit.  uint64 words, bit v % 64 of word v / 64; n_seen is
+ *     its popcount;
+ *   - set_hits[t], int64[n_sets]: the hits on columns with ids[v] = t.  Set 0, the empty set, is counted like any other;
+ *     the entries sum to n_hits.
+ * Derived on demand -- the object stays usable, and more batches may follow:
+ *   - set_kmers[t] = size[t] of sbwtgpu_colorsets_set_sizes (size[0] includes the dummy columns);
+ *   - set_seen[t] = #{ v : ids[v] = t and seen[v] }; the entries sum to n_seen;
+ *   - per colour c and X one of kmers, seen, hits: ref_X[c] = the sum of set_X[t] over the sets t >= 1 whose row has bit c.
+ *     ref_kmers[c] is the number of index k-mers of reference c (the diagonal of the shared matrix), ref_seen[c] /
+ *     ref_kmers[c] the containment of c in the sample, ref_hits[c] / ref_kmers[c] its mean k-mer depth.
+ * Everything is exact int64; there is no floating point anywhere.  The state is a function of the index, of what the
+ * object s MEANS and of the multiset of reads added: it does not depend on batch boundaries, chunking, tuning, image level,
+ * stream, or the order of concurrent adds.  For an uploaded s with duplicate rows or another numbering the per-set vectors
+ * follow its ids, the per-colour vectors are those of its canonical form.
+ * sbwtgpu_screen_create allocates n / 8 + 8 n_sets bytes and a few words, zeroed; s and its index must outlive the object.
+ * sbwtgpu_screen_reset zeroes it again (it waits for the device first).
+ * sbwtgpu_screen_add_dev takes device pointers with the preconditions of sbwtgpu_read_hits_dev, is asynchronous on `stream`,
+ * never synchronises and never allocates.  Its workspace, of sbwtgpu_screen_workspace_bytes (non-decreasing in total_bases
+ * and n_reads), is 16-byte aligned and begins with the search workspace: sbwtgpu_workspace_status on it reports the
+ * search's status word.  After the searches (the forward batch and, for two strands, the mirrored batch of the read-hit
+ * profiles; int32 results: colour sets exist below 2^31 columns only) one kernel launch feeds the accumulator.
+ * sbwtgpu_screen_add_batch takes host buffers and cuts the batch into chunks of whole reads of at most
+ * "screen_chunk_bases" bases (sbwtgpu_set_tuning; 0 = the default of 64 Mi; a chunk always takes one read), two in flight.
+ * Only bases and offsets go to the device; nothing but each chunk's status word comes back.
+ * sbwtgpu_screen_info, _sets, _colors and _seen_copy run on a stream of the object's own; they see every add that has
+ * returned from sbwtgpu_screen_add_batch, which finishes its streams before it returns.  A caller of sbwtgpu_screen_add_dev
+ * on a stream of their own finishes that stream first.  They leave the object unchanged; any output may be NULL.
+ * sbwtgpu_screen_seen_dev gives the bitmap in place: ceil(n / 64) words that live as long as x.
+ * Adds from several host threads or streams on one object are safe -- the object is built on atomics -- as long as each
+ * caller brings a workspace of its own; the queries serialise on the object.
+ * Refusals (SBWTGPU_ERR_INVALID_ARG with a message that names the cause): NULL arguments; strands not 1 or 2; n_reads < 0
+ * or >= 2^31; a workspace that is too small; and what the colour-set queries refuse for the object's index.  A read of 2^31
+ * bases or more: SBWTGPU_ERR_READ_TOO_LONG.  SBWTGPU_ERR_OOM leaves index and colour sets usable and nothing allocated.
+ * Scratch of _sets and _colors, released before they return: 16 n_sets + 24 C bytes. */
+typedef struct sbwtgpu_screen sbwtgpu_screen;
+int     sbwtgpu_screen_create(const sbwtgpu_colorsets *s, sbwtgpu_screen **out);
+int     sbwtgpu_screen_reset(sbwtgpu_screen *x);
+void    sbwtgpu_screen_destroy(sbwtgpu_screen *x);
+int64_t sbwtgpu_screen_workspace_bytes(int64_t total_bases, int64_t n_reads, int strands);
+int     sbwtgpu_screen_add_dev(sbwtgpu_screen *x, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                               int64_t n_reads, int strands, void *d_workspace, int64_t workspace_bytes, void *stream);
+int     sbwtgpu_screen_add_batch(sbwtgpu_screen *x, const char *bases, const int64_t *read_off, int64_t n_reads, int strands);
+int     sbwtgpu_screen_info(const sbwtgpu_screen *x, int64_t *n_windows, int64_t *n_hits, int64_t *n_seen, int64_t *n_sets,
+                            int32_t *n_colors);
+int     sbwtgpu_screen_sets(const sbwtgpu_screen *x, int64_t *set_kmers, int64_t *set_seen, int64_t *set_hits /* n_sets each */);
+int     sbwtgpu_screen_colors(const sbwtgpu_screen *x, int64_t *ref_kmers, int64_t *ref_seen, int64_t *ref_hits /* n_colors each */);
+int     sbwtgpu_screen_seen_dev(const sbwtgpu_screen *x, const uint64_t **d_seen);
+int     sbwtgpu_screen_seen_copy(const sbwtgpu_screen *x, uint64_t *seen /* ceil(n / 64) */);
 
 #ifdef __cplusplus
 }

@@ -70,6 +70,9 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_colorsets_set_sizes", "sbwtgpu_colorsets_shared_kmers", "sbwtgpu_colorsets_shared_workspace_bytes",
     "sbwtgpu_colorsets_shared_kmers_dev",
     "sbwtgpu_colorsets_match_sets", "sbwtgpu_colorsets_select_counts", "sbwtgpu_colorsets_select",
+    "sbwtgpu_screen_create", "sbwtgpu_screen_reset", "sbwtgpu_screen_destroy", "sbwtgpu_screen_workspace_bytes",
+    "sbwtgpu_screen_add_dev", "sbwtgpu_screen_add_batch", "sbwtgpu_screen_info", "sbwtgpu_screen_sets", "sbwtgpu_screen_colors",
+    "sbwtgpu_screen_seen_dev", "sbwtgpu_screen_seen_copy",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -346,6 +349,19 @@ def lib() -> C.CDLL:
         L.sbwtgpu_unitigs_walks_workspace_bytes.restype = i64
         L.sbwtgpu_unitigs_walks_dev.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp]
         L.sbwtgpu_unitigs_walks_batch.argtypes = [vp, vp, vp, vp, i64, vp, C.POINTER(vp), C.POINTER(i64), vp]
+        L.sbwtgpu_screen_create.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_screen_reset.argtypes = [vp]
+        L.sbwtgpu_screen_destroy.argtypes = [vp]
+        L.sbwtgpu_screen_destroy.restype = None
+        L.sbwtgpu_screen_workspace_bytes.argtypes = [i64, i64, ci]
+        L.sbwtgpu_screen_workspace_bytes.restype = i64
+        L.sbwtgpu_screen_add_dev.argtypes = [vp, vp, i64, vp, i64, ci, vp, i64, vp]
+        L.sbwtgpu_screen_add_batch.argtypes = [vp, vp, vp, i64, ci]
+        L.sbwtgpu_screen_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_int32)]
+        L.sbwtgpu_screen_sets.argtypes = [vp, vp, vp, vp]
+        L.sbwtgpu_screen_colors.argtypes = [vp, vp, vp, vp]
+        L.sbwtgpu_screen_seen_dev.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_screen_seen_copy.argtypes = [vp, vp]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -1265,6 +1281,12 @@ class ColorSets:
                                                         stream or None))
 
     # ---- colour select: k-mers by a predicate over their colour sets (include/sbwtgpu.h) ----
+    def screen(self) -> "Screen":
+        """sbwtgpu_screen_create: an empty accumulator for screening read sets against this object's references."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_screen_create(self._h, C.byref(h)))
+        return Screen(h, self)
+
     def color_mask(self, colors) -> np.ndarray:
         """uint64[W] with the bits of `colors`: an iterable of colour numbers, or a ready array of W uint64 words (taken as it
         is; the library refuses bits at or above n_colors)."""
@@ -1344,6 +1366,88 @@ class ColorSets:
         """sbwtgpu_pseudoalign_sets_dev (raw device pointers, as WideColors.pseudoalign_dev)."""
         _check(lib().sbwtgpu_pseudoalign_sets_dev(self._h, d_bases, total_bases, d_read_off, n_reads, 2 if both_strands else 1,
                                                   threshold_ppm, denominator, d_out, d_colors, d_counts or None, d_ws, ws_bytes, stream))
+
+
+class Screen:
+    """Owns an sbwtgpu_screen handle: the accumulator of a read set screened against the references of a colour-set object
+    (include/sbwtgpu.h, "screen") -- per set and per colour the index k-mers, the distinct ones the sample holds and the hits.
+    Everything is exact int64.  The colour sets (and through them the index) are kept referenced."""
+
+    def __init__(self, handle, sets: "ColorSets"):
+        self._h = handle
+        self.sets_object = sets
+        self.n_sets, self.n_colors = sets.n_sets, sets.n_colors
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        if self._h:
+            lib().sbwtgpu_screen_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def add(self, bases, read_off, strands: int = 1) -> None:
+        """sbwtgpu_screen_add_batch: the reads (uint8 bases, int64 offsets) join the sample; strands = 2 adds the reverse
+        complement of every window too."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        _check(lib().sbwtgpu_screen_add_batch(self._h, bases.ctypes.data, read_off.ctypes.data, len(read_off) - 1, strands))
+
+    def add_reads(self, reads: Sequence[bytes], strands: int = 1) -> None:
+        bases, off = concat_reads(reads)
+        self.add(bases, off, strands)
+
+    def add_dev(self, d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_ws: int, ws_bytes: int, strands: int = 1,
+                stream: int = 0) -> None:
+        """sbwtgpu_screen_add_dev (raw device pointers; workspace of screen_workspace_bytes): asynchronous on stream."""
+        _check(lib().sbwtgpu_screen_add_dev(self._h, d_bases or None, total_bases, d_read_off or None, n_reads, strands, d_ws or None,
+                                            ws_bytes, stream or None))
+
+    def info(self) -> dict:
+        """n_windows, n_hits, n_seen, n_sets and n_colors."""
+        nw, nh, ns, nt = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        nc = C.c_int32()
+        _check(lib().sbwtgpu_screen_info(self._h, C.byref(nw), C.byref(nh), C.byref(ns), C.byref(nt), C.byref(nc)))
+        return {"n_windows": nw.value, "n_hits": nh.value, "n_seen": ns.value, "n_sets": nt.value, "n_colors": nc.value}
+
+    def sets(self):
+        """(set_kmers, set_seen, set_hits): int64[n_sets] each."""
+        out = [np.full(self.n_sets, -12345, dtype=np.int64) for _ in range(3)]
+        _check(lib().sbwtgpu_screen_sets(self._h, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data))
+        return tuple(out)
+
+    def colors(self):
+        """(ref_kmers, ref_seen, ref_hits): int64[n_colors] each."""
+        out = [np.full(self.n_colors, -12345, dtype=np.int64) for _ in range(3)]
+        _check(lib().sbwtgpu_screen_colors(self._h, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data))
+        return tuple(out)
+
+    def seen(self) -> np.ndarray:
+        """uint64[ceil(n / 64)]: bit v % 64 of word v // 64 says whether column v has a hit."""
+        out = np.zeros((self.sets_object.index.n_nodes + 63) // 64, dtype=np.uint64)
+        _check(lib().sbwtgpu_screen_seen_copy(self._h, out.ctypes.data))
+        return out
+
+    def seen_dev(self) -> int:
+        p = C.c_void_p()
+        _check(lib().sbwtgpu_screen_seen_dev(self._h, C.byref(p)))
+        return p.value or 0
+
+    def reset(self) -> None:
+        _check(lib().sbwtgpu_screen_reset(self._h))
 
 
 class ColorSetsBuilder:
@@ -1440,6 +1544,10 @@ def read_hits_workspace_bytes(total_bases: int, n_reads: int, both_strands: bool
 
 def walks_workspace_bytes(total_bases: int, n_reads: int) -> int:
     return int(lib().sbwtgpu_unitigs_walks_workspace_bytes(total_bases, n_reads))
+
+
+def screen_workspace_bytes(total_bases: int, n_reads: int, strands: int = 1) -> int:
+    return int(lib().sbwtgpu_screen_workspace_bytes(total_bases, n_reads, strands))
 
 
 def pseudoalign_workspace_bytes(total_bases: int, n_reads: int, both_strands: bool = False) -> int:

@@ -596,6 +596,57 @@ public:
         link_to.resize((size_t)n_links);
         return sbwtgpu_unitigs_links_copy(u, link_off.data(), link_to.data());
     }
+    // A read set screened against the references of a colour-set object of THIS index (include/sbwtgpu.h, "screen"): the
+    // accumulator is kept for as many batches as the caller has; the vectors are exact int64.
+    class Screen {
+    public:
+        Screen() = default;
+        Screen(const Screen &) = delete;
+        Screen &operator=(const Screen &) = delete;
+        Screen(Screen &&o) noexcept : h(o.h) { o.h = nullptr; }
+        Screen &operator=(Screen &&o) noexcept {
+            if (this != &o) { sbwtgpu_screen_destroy(h); h = o.h; o.h = nullptr; }
+            return *this;
+        }
+        ~Screen() { sbwtgpu_screen_destroy(h); }
+        void add(const char *bases, const int64_t *read_off, int64_t n_reads, int strands = 1) {
+            detail::gpu_check(sbwtgpu_screen_add_batch(h, bases, read_off, n_reads, strands));
+        }
+        void reset() { detail::gpu_check(sbwtgpu_screen_reset(h)); }
+        struct Info { int64_t n_windows = 0, n_hits = 0, n_seen = 0, n_sets = 0; int32_t n_colors = 0; };
+        Info info() const {
+            Info i;
+            detail::gpu_check(sbwtgpu_screen_info(h, &i.n_windows, &i.n_hits, &i.n_seen, &i.n_sets, &i.n_colors));
+            return i;
+        }
+        // kmers, seen, hits: per set (n_sets entries each) or per colour (n_colors entries each)
+        struct Vectors { std::vector<int64_t> kmers, seen, hits; };
+        Vectors sets() const {
+            Vectors v;
+            int64_t n_sets = 0;
+            detail::gpu_check(sbwtgpu_screen_info(h, nullptr, nullptr, nullptr, &n_sets, nullptr));
+            const size_t n = (size_t)n_sets;
+            v.kmers.resize(n); v.seen.resize(n); v.hits.resize(n);
+            detail::gpu_check(sbwtgpu_screen_sets(h, v.kmers.data(), v.seen.data(), v.hits.data()));
+            return v;
+        }
+        Vectors colors() const {
+            Vectors v;
+            int32_t n_colors = 0;
+            detail::gpu_check(sbwtgpu_screen_info(h, nullptr, nullptr, nullptr, nullptr, &n_colors));
+            const size_t n = (size_t)n_colors;
+            v.kmers.resize(n); v.seen.resize(n); v.hits.resize(n);
+            detail::gpu_check(sbwtgpu_screen_colors(h, v.kmers.data(), v.seen.data(), v.hits.data()));
+            return v;
+        }
+        sbwtgpu_screen *h = nullptr;
+    };
+    Screen screen(const sbwtgpu_colorsets *sets) const {
+        need_device();
+        Screen s;
+        detail::gpu_check(sbwtgpu_screen_create(sets, &s.h));
+        return s;
+    }
     // the k-mers of the index whose colour set satisfies the predicate, as the columns of their index (include/sbwtgpu.h,
     // "colour select"): bit for bit what the builder gives for the selected k-mers.  The object is one of THIS index;
     // 2 <= k <= 64.  `info` (optional) receives the counts and pass times.

@@ -13,6 +13,9 @@
 //   sbwt compress-colors -i <index> -c <colours> -o <colour sets>
 //   sbwt color-matrix -i <index> -c <colours> -o <shared.tsv> [--jaccard-ppm]
 //               the colour-set file of a colour file written with or without --wide
+//   sbwt screen -i <index> -c <colours> -q <reads> -o <screen.tsv> [--both-strands] [--sets-out <sets.tsv>]
+//               a read set screened against the references: per colour its index k-mers, those the reads contain, and the
+//               hits on them; the accumulator stays on the GPU across batches
 //   sbwt merge-colors -u <index U> -a <index A> --colors-a <colours of A> [-b <index B> --colors-b <colours of B>]
 //               [--color-offset <n>] -o <colour sets of U>
 //               the colour sets of A (and B, its colours moved up by the offset) carried onto U's k-mers: run set-op first,
@@ -1277,6 +1280,94 @@ int color_matrix_main(int argc, char **argv) {
     return 0;
 }
 
+// sbwt screen: which references are in a read set, and how much of each (include/sbwtgpu.h, "screen").  The output starts with
+// "# windows <n_windows> hits <n_hits> seen <n_seen>", then one line per colour: colour, ref_kmers, ref_seen, ref_hits,
+// tab-separated; --sets-out: one line per set id: id, set_kmers, set_seen, set_hits.  Batches go to the GPU one at a time and
+// nothing comes back until the end.
+int screen_main(int argc, char **argv) {
+    int64_t micros_start = cur_time_micros();
+    set_log_level(LogLevel::MINOR);
+    Options opts({
+        {"index-file", 'i', true, "Index input file.", ""},
+        {"colors-file", 'c', true, "Colour file of the index (sbwt build-colors with or without --wide or --compress, compress-colors, merge-colors).", ""},
+        {"query-file", 'q', true, "The reads in FASTA or FASTQ format, possibly gzipped.", ""},
+        {"out-file", 'o', true, "Output file: a header line, then per colour its k-mers, the k-mers the reads contain, and the hits.", ""},
+        {"sets-out", 0, true, "Also write the same three numbers per colour set, one line per set id.", ""},
+        {"both-strands", 0, false, "The reverse complement of every window counts as a window too.", ""},
+        {"gpu", 0, true, "HIP device to run on.", "0"},
+        {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
+        {"help", 'h', false, "Print usage", ""},
+    });
+    opts.parse(argc, argv);
+    if (argc == 1 || opts.count("help")) {
+        std::cerr << opts.help(argv[0], "Screen a read set against the references: per colour k-mers, k-mers seen, hits.") << std::endl;
+        exit(1);
+    }
+    const string indexfile = opts.get("index-file"), colorsfile = opts.get("colors-file"), queryfile = opts.get("query-file"),
+                 outfile = opts.get("out-file"), setsfile = opts.count("sets-out") ? opts.get("sets-out") : string();
+    check_readable(indexfile);
+    check_readable(colorsfile);
+    check_readable(queryfile);
+    check_writable(outfile);
+    if (!setsfile.empty()) check_writable(setsfile);
+    const int strands = opts.count("both-strands") ? 2 : 1;
+    set_default_device(atoi(opts.get("gpu").c_str()));
+    int64_t batch_bases = atoll(opts.get("batch-bases").c_str());
+    if (batch_bases < 1) batch_bases = 1;
+    plain_matrix_sbwt_t index;
+    load_plain_matrix(indexfile, index);
+    ColorSetsHandle sets;
+    load_colorsets(colorsfile, indexfile, index, sets);
+    plain_matrix_sbwt_t::Screen screen = index.screen(sets.h);
+    int64_t total_reads = 0;
+    {
+        seq_io::Reader reader(queryfile);
+        bool more = true;
+        vector<char> bases;
+        vector<int64_t> read_off;
+        while (more) {
+            bases.clear();
+            read_off.assign(1, 0);
+            more = reader.read_batch(bases, read_off, batch_bases);
+            const int64_t n_reads = (int64_t)read_off.size() - 1;
+            if (n_reads <= 0) continue;
+            screen.add(bases.data(), read_off.data(), n_reads, strands);
+            total_reads += n_reads;
+        }
+    }
+    const plain_matrix_sbwt_t::Screen::Info info = screen.info();
+    auto table = [](const plain_matrix_sbwt_t::Screen::Vectors &v, string &text) {
+        for (size_t i = 0; i < v.kmers.size(); i++) {
+            append_int((int64_t)i, text);
+            text.push_back('\t');
+            append_int(v.kmers[i], text);
+            text.push_back('\t');
+            append_int(v.seen[i], text);
+            text.push_back('\t');
+            append_int(v.hits[i], text);
+            text.push_back('\n');
+        }
+    };
+    string text = "# windows " + std::to_string(info.n_windows) + " hits " + std::to_string(info.n_hits) + " seen " +
+                  std::to_string(info.n_seen) + "\n";
+    table(screen.colors(), text);
+    if (sbwthost_write_file(outfile.c_str(), text.data(), (int64_t)text.size(), 0, 0) != 0)
+        throw std::runtime_error(string("Error writing ") + outfile + ": " + sbwthost_last_error());
+    if (!setsfile.empty()) {
+        text.clear();
+        table(screen.sets(), text);
+        if (sbwthost_write_file(setsfile.c_str(), text.data(), (int64_t)text.size(), 0, 0) != 0)
+            throw std::runtime_error(string("Error writing ") + setsfile + ": " + sbwthost_last_error());
+    }
+    write_log("Screened " + std::to_string(total_reads) + " reads against " + std::to_string(info.n_colors) + " references: " +
+                  std::to_string(info.n_hits) + " hits in " + std::to_string(info.n_windows) + " windows, " +
+                  std::to_string(info.n_seen) + " k-mers seen",
+              LogLevel::MAJOR);
+    write_log("us/read end-to-end: " + std::to_string((double)(cur_time_micros() - micros_start) / (double)std::max<int64_t>(1, total_reads)),
+              LogLevel::MAJOR);
+    return 0;
+}
+
 // dump-unitigs --colors: coloured unitigs as FASTA, the header "number set-id" (a parser that takes the id up to the first
 // blank still sees the number); --sets-out: line i = "i c1 c2 ..." for set id i = 0 .. n_sets - 1, the line of set 0 is "0"
 int dump_unitigs_colored(const plain_matrix_sbwt_t &index, const string &indexfile, const string &colorsfile, const string &outfile,
@@ -1758,7 +1849,7 @@ int pseudoalign_main(int argc, char **argv) {
     return 0;
 }
 
-const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "thread", "set-op", "read-hits", "build-colors", "compress-colors", "merge-colors", "color-matrix", "color-select", "pseudoalign"};
+const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "thread", "set-op", "read-hits", "build-colors", "compress-colors", "merge-colors", "color-matrix", "color-select", "screen", "pseudoalign"};
 
 void print_help(char **argv) {
     std::cerr << "Available commands: " << std::endl;
@@ -1797,6 +1888,7 @@ int main(int argc, char **argv) {   // sbwt.cpp:19-57
         else if (command == "merge-colors") return merge_colors_main(argc, argv);
         else if (command == "color-matrix") return color_matrix_main(argc, argv);
         else if (command == "color-select") return color_select_main(argc, argv);
+        else if (command == "screen") return screen_main(argc, argv);
         else if (command == "pseudoalign") return pseudoalign_main(argc, argv);
         else throw std::runtime_error("Invalid command: " + command);
     } catch (const std::runtime_error &e) {

@@ -30,6 +30,7 @@
 #include "sbwt_colormerge.h"
 #include "sbwt_colormatrix.h"
 #include "sbwt_colorselect.h"
+#include "sbwt_screen.h"
 
 namespace {
 
@@ -190,6 +191,7 @@ static int64_t g_rh_chunk_bases = 0;
 static int g_rh_wide = 0;
 static int64_t g_wk_chunk_bases = 0;      // "walks_chunk_bases": 0 = the default of 64 Mi
 static int64_t g_pa_chunk_bases = 0;      // "pseudoalign_chunk_bases": 0 = the default of 64 Mi
+static int64_t g_screen_chunk_bases = 0;  // "screen_chunk_bases": 0 = the default of 64 Mi
 // shared k-mers (sbwt_colormatrix.hip): objects of this many sets or more go to the matrix cores, smaller ones to the plain
 // kernel; the sets a wave adds up in 32 bits before it adds into the 64-bit matrix.  Neither shows in a result.
 static int64_t g_gram_mfma_min_sets = SBWT_GM_MIN_SETS_DEFAULT;
@@ -301,6 +303,7 @@ int sbwtgpu_set_tuning(const char *key, int64_t value) {
     if (!strcmp(key, "read_hits_wide")) { g_rh_wide = (int)value; return SBWTGPU_OK; }
     if (!strcmp(key, "walks_chunk_bases")) { g_wk_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "pseudoalign_chunk_bases")) { g_pa_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
+    if (!strcmp(key, "screen_chunk_bases")) { g_screen_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "gram_mfma_min_sets")) { g_gram_mfma_min_sets = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "gram_flush_sets")) {
         if (value < 1 || value > SBWT_GM_FLUSH_MAX)
@@ -4261,6 +4264,263 @@ int sbwtgpu_colorsets_shared_kmers(const sbwtgpu_colorsets *s, const int64_t *we
         for (uint64_t x = hdr.max_w; x; x >>= 7) info->n_limbs++;
         for (int i = 0; i < 4; i++) info->pass_ms[i] = ms[i];
     }
+    return SBWTGPU_OK;
+}
+
+// ---- screen: per-colour k-mer containment of a read set (sbwt_screen.hip) -----------
+}  // extern "C"
+// One device allocation: the counters (256 bytes), set_hits (n_sets int64) and the seen bitmap.  The adds only ever add to it
+// with atomics; the queries take `mu`, run on `stream` and bring their scratch with them.
+struct sbwtgpu_screen {
+    const sbwtgpu_colorsets *s = nullptr;
+    int device = 0;
+    int64_t n_nodes = 0, n_sets = 0, n_words = 0;       // n_words = ceil(n_nodes / 64)
+    DevBuf mem;
+    size_t bytes = 0;
+    SbwtScreenCounters *d_ctr = nullptr;
+    unsigned long long *d_set_hits = nullptr, *d_seen = nullptr;
+    Stream stream;
+    mutable std::mutex mu;
+};
+static int screen_check(const sbwtgpu_screen *x) {
+    if (!x) return fail(SBWTGPU_ERR_INVALID_ARG, "screen: the object is NULL");
+    return colorsets_check(x->s);
+}
+extern "C" {
+
+int sbwtgpu_screen_create(const sbwtgpu_colorsets *s, sbwtgpu_screen **out) {
+    if (!s || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "screen: NULL argument (s and out are needed)");
+    *out = nullptr;
+    const int rc = colorsets_check(s);
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(s->base.device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", s->base.device);
+    sbwtgpu_screen *x = new (std::nothrow) sbwtgpu_screen();
+    if (!x) return fail(SBWTGPU_ERR_OOM, "out of host memory");
+    x->s = s;
+    x->device = s->base.device;
+    x->n_nodes = s->base.n_nodes;
+    x->n_sets = s->n_sets;
+    x->n_words = (x->n_nodes + 63) / 64;
+    const size_t o_hits = 256, o_seen = o_hits + align256((size_t)x->n_sets * 8);
+    x->bytes = o_seen + align256((size_t)x->n_words * 8 + 8);
+    hipError_t e = hipStreamCreateWithFlags(&x->stream.s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = x->mem.alloc(x->bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(x->mem.p, 0, x->bytes, x->stream.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(x->stream.s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        delete x;
+        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "screen: %s", hipGetErrorString(e));
+    }
+    char *m = static_cast<char *>(x->mem.p);
+    x->d_ctr = reinterpret_cast<SbwtScreenCounters *>(m);
+    x->d_set_hits = reinterpret_cast<unsigned long long *>(m + o_hits);
+    x->d_seen = reinterpret_cast<unsigned long long *>(m + o_seen);
+    *out = x;
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_screen_reset(sbwtgpu_screen *x) {
+    const int rc = screen_check(x);
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(x->device);
+    std::lock_guard<std::mutex> lock(x->mu);
+    // (adds of the caller's on other streams have to be over, as for the queries: the device is waited for, then zeroed)
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemsetAsync(x->mem.p, 0, x->bytes, x->stream.s));
+    HIP_TRY(hipStreamSynchronize(x->stream.s));
+    return SBWTGPU_OK;
+}
+
+void sbwtgpu_screen_destroy(sbwtgpu_screen *x) {
+    if (!x) return;
+    DeviceGuard guard(x->device);
+    delete x;
+}
+
+int64_t sbwtgpu_screen_workspace_bytes(int64_t total_bases, int64_t n_reads, int strands) {
+    return sbwtgpu_pseudoalign_workspace_bytes(total_bases, n_reads, strands);
+}
+
+int sbwtgpu_screen_add_dev(sbwtgpu_screen *x, const char *d_bases, int64_t total_bases, const int64_t *d_read_off, int64_t n_reads,
+                           int strands, void *d_ws, int64_t ws_bytes, void *stream) {
+    int rc = screen_check(x);
+    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc != SBWTGPU_OK) return rc;
+    const sbwtgpu_colorsets *s = x->s;
+    return colors_dev_common(&s->base, d_bases, total_bases, d_read_off, n_reads, strands, d_ws, ws_bytes, stream,
+                             [&](const int *res, const int *res2, const long long *ooff, SbwtPaHeader *, hipStream_t st) {
+                                 sbwt_launch_screen_add(res, res2, ooff, n_reads, total_bases, s->d_ids, x->n_nodes, x->n_sets, x->d_seen,
+                                                        x->d_set_hits, x->d_ctr, st);
+                             });
+}
+
+// Host buffers: read_hits_batch's chunks of whole reads under "screen_chunk_bases", two in flight on the parked slots of the
+// search pipeline.  Bases and offsets go down; only each chunk's status word comes back.
+int sbwtgpu_screen_add_batch(sbwtgpu_screen *x, const char *bases, const int64_t *read_off, int64_t n_reads, int strands) {
+    int rc = screen_check(x);
+    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_reads == 0) return SBWTGPU_OK;
+    if (!read_off) return fail(SBWTGPU_ERR_INVALID_ARG, "screen: NULL argument (read_off)");
+    if (read_off[n_reads] > read_off[0] && !bases) return fail(SBWTGPU_ERR_INVALID_ARG, "screen: NULL argument (bases)");
+    const int64_t budget = g_screen_chunk_bases > 0 ? g_screen_chunk_bases : (int64_t)64 << 20, CH_READS = (int64_t)1 << 24;
+    std::vector<int64_t> cuts{0};
+    int64_t max_bases = 0, max_reads = 0;
+    try {
+        for (int64_t lo = 0, r = 0; r < n_reads; r++) {
+            if ((rc = check_read_length(read_off, r)) != SBWTGPU_OK) return rc;
+            if (r > lo && (read_off[r + 1] - read_off[lo] > budget || r - lo >= CH_READS)) {
+                cuts.push_back(r);
+                lo = r;
+            }
+            max_bases = std::max(max_bases, read_off[r + 1] - read_off[lo]);
+            max_reads = std::max(max_reads, r + 1 - lo);
+        }
+        cuts.push_back(n_reads);
+    } catch (const std::bad_alloc &) {
+        return fail(SBWTGPU_ERR_OOM, "out of host memory");
+    }
+    const int64_t n_chunks = (int64_t)cuts.size() - 1;
+    const bool pin_in = is_pinned(bases);
+    const int64_t ws_bytes = sbwtgpu_screen_workspace_bytes(max_bases, max_reads, strands);
+    const int64_t need_in = align256(max_bases + 16) + align256((max_reads + 1) * 8);
+    const int64_t need_dev = need_in + align256(ws_bytes);
+    DeviceGuard guard(x->device);
+    const int n_slots = n_chunks > 1 ? 2 : 1;
+    PipeSlot S[2];
+    if ((rc = take_slots(x->device, S, n_slots, need_in, 0, need_dev, "screen buffers")) != SBWTGPU_OK) return rc;
+    int bug = 0;                    // the first nonzero device status of a chunk
+    const int64_t o_roff = align256(max_bases + 16), o_ws = need_in;
+    auto submit = [&](int64_t c) -> int {
+        PipeSlot &P = S[c % n_slots];
+        const int64_t lo = cuts[(size_t)c], hi = cuts[(size_t)c + 1], nr = hi - lo, nb = read_off[hi] - read_off[lo];
+        int64_t *hro = (int64_t *)(P.h_in + o_roff);
+        for (int64_t r = 0; r <= nr; r++) hro[r] = read_off[lo + r] - read_off[lo];
+        const char *hb = bases + read_off[lo];
+        if (!pin_in && nb > 0) { parallel_memcpy(P.h_in, hb, (size_t)nb); hb = P.h_in; }
+        hipError_t e;
+        if ((nb > 0 && (e = hipMemcpyAsync(P.d_mem, hb, (size_t)nb, hipMemcpyHostToDevice, P.st)) != hipSuccess) ||
+            (e = hipMemcpyAsync(P.d_mem + o_roff, hro, (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, P.st)) != hipSuccess)
+            return fail(SBWTGPU_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
+        const int r2 = sbwtgpu_screen_add_dev(x, P.d_mem, nb, (const int64_t *)(P.d_mem + o_roff), nr, strands, P.d_mem + o_ws, ws_bytes, P.st);
+        if (r2 != SBWTGPU_OK) return r2;
+        const SbwtPaLayout L = sbwt_pa_layout(sbwtgpu_search_workspace_bytes(nb), nb, nr, strands);
+        if ((e = hipMemcpyAsync(P.h_status, P.d_mem + o_ws + L.hdr, 4, hipMemcpyDeviceToHost, P.st)) != hipSuccess)
+            return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
+        return SBWTGPU_OK;
+    };
+    auto collect = [&](int64_t c) -> int {
+        PipeSlot &P = S[c % n_slots];
+        hipError_t e = hipStreamSynchronize(P.st);
+        if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "stream synchronize: %s", hipGetErrorString(e));
+        if (P.h_status[0] != 0 && bug == 0) bug = P.h_status[0];
+        return SBWTGPU_OK;
+    };
+    rc = two_in_flight(n_chunks, submit, collect);
+    park_slots(x->device, S, n_slots, rc);
+    if (rc != SBWTGPU_OK) return rc;
+    if (bug) return fail_status(bug);
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_screen_info(const sbwtgpu_screen *x, int64_t *n_windows, int64_t *n_hits, int64_t *n_seen, int64_t *n_sets,
+                        int32_t *n_colors) {
+    const int rc = screen_check(x);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_sets) *n_sets = x->n_sets;
+    if (n_colors) *n_colors = x->s->base.n_colors;
+    if (!n_windows && !n_hits && !n_seen) return SBWTGPU_OK;
+    DeviceGuard guard(x->device);
+    std::lock_guard<std::mutex> lock(x->mu);
+    hipStream_t st = x->stream.s;
+    SbwtScreenCounters h;
+    unsigned long long seen = 0;
+    DevBuf d;
+    if (n_seen) {
+        HIP_TRY(d.alloc(8));
+        sbwt_launch_screen_popcount(x->d_seen, x->n_words, static_cast<unsigned long long *>(d.p), st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&seen, d.p, 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(&h, x->d_ctr, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (n_windows) *n_windows = (int64_t)h.n_windows;
+    if (n_hits) *n_hits = (int64_t)h.n_hits;
+    if (n_seen) *n_seen = (int64_t)seen;
+    return SBWTGPU_OK;
+}
+
+}  // extern "C"
+// what _sets and _colors share: the per-set vectors on the device (d: [set_kmers][set_seen], n_sets int64 each; set_hits is the
+// object's own), enqueued on the object's stream under its mutex
+static int screen_set_vectors(const sbwtgpu_screen *x, DevBuf &d) {
+    HIP_TRY(d.alloc((size_t)x->n_sets * 16));
+    unsigned long long *kmers = static_cast<unsigned long long *>(d.p);
+    sbwt_launch_screen_sets(x->s->d_ids, x->n_nodes, x->n_sets, x->d_seen, kmers, kmers + x->n_sets, x->stream.s);
+    HIP_TRY(hipGetLastError());
+    return SBWTGPU_OK;
+}
+extern "C" {
+
+int sbwtgpu_screen_sets(const sbwtgpu_screen *x, int64_t *set_kmers, int64_t *set_seen, int64_t *set_hits) {
+    int rc = screen_check(x);
+    if (rc != SBWTGPU_OK) return rc;
+    if (!set_kmers && !set_seen && !set_hits) return SBWTGPU_OK;
+    DeviceGuard guard(x->device);
+    std::lock_guard<std::mutex> lock(x->mu);
+    hipStream_t st = x->stream.s;
+    const size_t nb = (size_t)x->n_sets * 8;
+    DevBuf d;
+    if (set_kmers || set_seen) {
+        if ((rc = screen_set_vectors(x, d)) != SBWTGPU_OK) return rc;
+        if (set_kmers) HIP_TRY(hipMemcpyAsync(set_kmers, d.p, nb, hipMemcpyDeviceToHost, st));
+        if (set_seen) HIP_TRY(hipMemcpyAsync(set_seen, static_cast<char *>(d.p) + nb, nb, hipMemcpyDeviceToHost, st));
+    }
+    if (set_hits) HIP_TRY(hipMemcpyAsync(set_hits, x->d_set_hits, nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_screen_colors(const sbwtgpu_screen *x, int64_t *ref_kmers, int64_t *ref_seen, int64_t *ref_hits) {
+    int rc = screen_check(x);
+    if (rc != SBWTGPU_OK) return rc;
+    if (!ref_kmers && !ref_seen && !ref_hits) return SBWTGPU_OK;
+    DeviceGuard guard(x->device);
+    std::lock_guard<std::mutex> lock(x->mu);
+    hipStream_t st = x->stream.s;
+    const sbwtgpu_colorsets *s = x->s;
+    const int C = s->base.n_colors;
+    const size_t cb = (size_t)C * 8;
+    DevBuf d, ref;
+    if ((rc = screen_set_vectors(x, d)) != SBWTGPU_OK) return rc;
+    HIP_TRY(ref.alloc(3 * cb));
+    unsigned long long *kmers = static_cast<unsigned long long *>(d.p);
+    sbwt_launch_screen_expand(s->d_table, x->n_sets, s->base.words, C, kmers, kmers + x->n_sets, x->d_set_hits,
+                              static_cast<unsigned long long *>(ref.p), st);
+    HIP_TRY(hipGetLastError());
+    if (ref_kmers) HIP_TRY(hipMemcpyAsync(ref_kmers, ref.p, cb, hipMemcpyDeviceToHost, st));
+    if (ref_seen) HIP_TRY(hipMemcpyAsync(ref_seen, static_cast<char *>(ref.p) + cb, cb, hipMemcpyDeviceToHost, st));
+    if (ref_hits) HIP_TRY(hipMemcpyAsync(ref_hits, static_cast<char *>(ref.p) + 2 * cb, cb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_screen_seen_dev(const sbwtgpu_screen *x, const uint64_t **d_seen) {
+    if (!x || !d_seen) return fail(SBWTGPU_ERR_INVALID_ARG, "screen: NULL argument");
+    *d_seen = reinterpret_cast<const uint64_t *>(x->d_seen);
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_screen_seen_copy(const sbwtgpu_screen *x, uint64_t *seen) {
+    const int rc = screen_check(x);
+    if (rc != SBWTGPU_OK) return rc;
+    if (!seen) return fail(SBWTGPU_ERR_INVALID_ARG, "screen: NULL argument (seen)");
+    DeviceGuard guard(x->device);
+    std::lock_guard<std::mutex> lock(x->mu);
+    HIP_TRY(hipMemcpyAsync(seen, x->d_seen, (size_t)x->n_words * 8, hipMemcpyDeviceToHost, x->stream.s));
+    HIP_TRY(hipStreamSynchronize(x->stream.s));
     return SBWTGPU_OK;
 }
 
