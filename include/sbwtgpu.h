@@ -1051,6 +1051,62 @@ int     sbwtgpu_screen_colors(const sbwtgpu_screen *x, int64_t *ref_kmers, int64
 int     sbwtgpu_screen_seen_dev(const sbwtgpu_screen *x, const uint64_t **d_seen);
 int     sbwtgpu_screen_seen_copy(const sbwtgpu_screen *x, uint64_t *seen /* ceil(n / 64) */);
 
+/* ---- bubbles: where the references differ, and which reference carries which allele ----
+ * Variant sites of the PLAIN unitig graph: a handle u of sbwtgpu_unitigs_create_graph(idx, NULL, flags, ...) with
+ * SBWTGPU_UNITIGS_LINKS.  The terms unitig, link, link_off, link_to, column map, real column and S(v) (the colour row of
+ * column v, table[ids[v]]) are those of the sections on unitigs, coloured unitigs and the unitig graph.  In the plain graph a
+ * unitig with one in-link and one out-link is never followed by another such unitig (that edge would be internal), so every
+ * branch of a bubble is one unitig.  A coloured handle cuts branches at colour breaks and is refused: pass the plain handle
+ * plus the colour-set object.
+ *   in-degree       of unitig j: the number of entries of link_to equal to j.
+ *   out-degree      of unitig i: link_off[i+1] - link_off[i].
+ *   bubble          four unitigs (s, a, b, t) with: outdeg(s) = 2 and its links in CSR order are a, b (a is reached by the
+ *                   smaller edge character; a != b); indeg(a) = indeg(b) = 1 and outdeg(a) = outdeg(b) = 1; the link of a
+ *                   and the link of b go to the same unitig t, and indeg(t) = 2; a, b are neither s nor t.  s = t is
+ *                   allowed: a bubble on a cycle, and it is reported.
+ *   no bubble       deliberately: sites with three or four branches; a branch that is an edge s -> t with no unitig on it
+ *                   (a deletion against the other branch); nested structures (superbubbles); tips.
+ *   n_kmers[j]      the k-mers of branch[j]: its length - k + 1.
+ *   kind            SBWTGPU_BUBBLE_SNP when n_kmers[0] = n_kmers[1] = k (both paths add k + 1 characters of which the last k
+ *                   spell t's first k-mer: one free character, a single-base substitution), else SBWTGPU_BUBBLE_OTHER.
+ *   allele          of branch j: the last n_kmers[j] characters of its spelling (what its k-mers add); for an SNP the variant
+ *                   base is allele[0].  The caller cuts them from sbwtgpu_unitigs_copy's bases.
+ *   order           records ascend by source.  The result is a function of the index alone and, with colours, of the matrix
+ *                   the object means: byte-identical between runs, image levels, layouts, and marks given or derived.
+ *   branch colours  with a colour-set object s of W-word rows (and SBWTGPU_UNITIGS_COLUMN_MAP on the handle), two rows for
+ *                   branch j of bubble i at uint64[(2 i + j) W + w]: inter = AND of S(v) over the columns v of unitig
+ *                   branch[j] (the references that hold the whole allele), uni = OR over the same columns (those that hold
+ *                   any of its k-mers).  An object with duplicate rows or another numbering gives the same rows; bits at or
+ *                   above n_colors are 0.
+ *   strands         the graph is directed: on an index that holds reverse complements every bubble appears twice, once per
+ *                   strand, with s and t swapped and the alleles reverse-complemented (the convention of
+ *                   sbwtgpu_unitigs_create).  Pairing them is left to the caller.
+ * sbwtgpu_bubbles_create runs on a stream of its own (in-degrees, detection, a scan, a fill, and with s one pass over the
+ * column map), with 24 bytes of scratch per unitig that it frees before it returns; the result takes 32 n_bubbles bytes and
+ * with colours 32 W n_bubbles more.  Nothing proportional to the number of columns is allocated.  Zero unitigs or zero links
+ * give zero bubbles and success.  _info: n_colors = words = 0 without an object; n_bubbles must not be NULL, the others may.
+ * _dev: d_rec must not be NULL; the pointers are NULL where there is nothing (no bubble; rows without an object) and live
+ * as long as b.  _copy: rec may be NULL when there is no bubble, inter / uni when there is no bubble or no object.
+ * sbwtgpu_bubbles_in_degrees_copy is the first pass alone.  The handle, the object and the index stay unchanged, and b
+ * holds no reference to them: they may be destroyed before b.  The calls are thread-safe on immutable handles.
+ * Refusals (SBWTGPU_ERR_INVALID_ARG with a message that names the cause): NULL u or out; a handle made without
+ * SBWTGPU_UNITIGS_LINKS; a coloured handle; an object given with a handle made without SBWTGPU_UNITIGS_COLUMN_MAP; an object
+ * whose index has another number of columns or another k than the handle's; NULL outputs where a value exists.
+ * SBWTGPU_ERR_OOM leaves the handle, the object and the index usable and nothing allocated. */
+#define SBWTGPU_BUBBLE_OTHER 0u
+#define SBWTGPU_BUBBLE_SNP   1u
+typedef struct { uint32_t source, branch[2], sink, n_kmers[2], kind, reserved /* 0 */; } sbwtgpu_bubble;   /* 32 bytes */
+typedef struct sbwtgpu_bubbles sbwtgpu_bubbles;
+int  sbwtgpu_bubbles_create(const sbwtgpu_unitigs *u, const sbwtgpu_colorsets *s_or_null, sbwtgpu_bubbles **out);
+int  sbwtgpu_bubbles_info  (const sbwtgpu_bubbles *b, int64_t *n_bubbles, int64_t *n_snps, int32_t *n_colors, int32_t *words);
+int  sbwtgpu_bubbles_dev   (const sbwtgpu_bubbles *b, const sbwtgpu_bubble **d_rec, const uint64_t **d_inter, const uint64_t **d_union);
+int  sbwtgpu_bubbles_copy  (const sbwtgpu_bubbles *b, sbwtgpu_bubble *rec, uint64_t *inter, uint64_t *uni);
+/* pass 1 alone: indeg[n_unitigs] (may be NULL when there is no unitig) */
+int  sbwtgpu_bubbles_in_degrees_copy(const sbwtgpu_unitigs *u, uint32_t *indeg);
+/* measurement aid (tools/bubbles_bench.py): device-event times in ms of in-degrees, detect, compact, branch colours */
+int  sbwtgpu_bubbles_stats (const sbwtgpu_bubbles *b, double pass_ms[4]);
+void sbwtgpu_bubbles_destroy(sbwtgpu_bubbles *b);
+
 #ifdef __cplusplus
 }
 #endif

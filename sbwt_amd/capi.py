@@ -30,6 +30,10 @@ UNITIGS_LINKS = 1               # SBWTGPU_UNITIGS_* (sbwtgpu_unitigs_create_grap
 UNITIGS_COLUMN_MAP = 2
 # sbwtgpu_walk_step: one step of a read through the unitig graph (Unitigs.walks)
 WALK_STEP = np.dtype([("unitig", np.uint32), ("offset", np.uint32), ("read_pos", np.int32), ("n_kmers", np.int32)])
+# sbwtgpu_bubble: one variant site of the plain unitig graph (Unitigs.bubbles)
+BUBBLE = np.dtype([("source", np.uint32), ("branch", np.uint32, (2,)), ("sink", np.uint32), ("n_kmers", np.uint32, (2,)),
+                   ("kind", np.uint32), ("reserved", np.uint32)])
+BUBBLE_OTHER, BUBBLE_SNP = 0, 1
 
 # every symbol include/sbwtgpu.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = [
@@ -73,6 +77,8 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_screen_create", "sbwtgpu_screen_reset", "sbwtgpu_screen_destroy", "sbwtgpu_screen_workspace_bytes",
     "sbwtgpu_screen_add_dev", "sbwtgpu_screen_add_batch", "sbwtgpu_screen_info", "sbwtgpu_screen_sets", "sbwtgpu_screen_colors",
     "sbwtgpu_screen_seen_dev", "sbwtgpu_screen_seen_copy",
+    "sbwtgpu_bubbles_create", "sbwtgpu_bubbles_info", "sbwtgpu_bubbles_dev", "sbwtgpu_bubbles_copy",
+    "sbwtgpu_bubbles_in_degrees_copy", "sbwtgpu_bubbles_stats", "sbwtgpu_bubbles_destroy",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -362,6 +368,14 @@ def lib() -> C.CDLL:
         L.sbwtgpu_screen_colors.argtypes = [vp, vp, vp, vp]
         L.sbwtgpu_screen_seen_dev.argtypes = [vp, C.POINTER(vp)]
         L.sbwtgpu_screen_seen_copy.argtypes = [vp, vp]
+        L.sbwtgpu_bubbles_create.argtypes = [vp, vp, C.POINTER(vp)]
+        L.sbwtgpu_bubbles_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.sbwtgpu_bubbles_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.sbwtgpu_bubbles_copy.argtypes = [vp, vp, vp, vp]
+        L.sbwtgpu_bubbles_in_degrees_copy.argtypes = [vp, vp]
+        L.sbwtgpu_bubbles_stats.argtypes = [vp, C.POINTER(C.c_double)]
+        L.sbwtgpu_bubbles_destroy.argtypes = [vp]
+        L.sbwtgpu_bubbles_destroy.restype = None
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -931,6 +945,20 @@ class Unitigs:
         _check(lib().sbwtgpu_unitigs_walks_dev(index._h, self._h, d_bases, total_bases, d_read_off, n_reads, d_step_off, d_steps,
                                                steps_cap, d_unitig_kmers or None, d_ws, ws_bytes, stream))
 
+    # ---- bubbles (a plain handle with the links) ----
+    def in_degrees(self) -> np.ndarray:
+        """sbwtgpu_bubbles_in_degrees_copy: uint32[n_unitigs], the number of links that end at every unitig."""
+        indeg = np.empty(self.n_unitigs, dtype=np.uint32)
+        _check(lib().sbwtgpu_bubbles_in_degrees_copy(self._h, indeg.ctypes.data if self.n_unitigs else None))
+        return indeg
+
+    def bubbles(self, colorsets: Optional["ColorSets"] = None) -> "Bubbles":
+        """sbwtgpu_bubbles_create: the bubbles of the graph and, with a colour-set object of the same index (the handle then
+        needs the column map), the colours of every branch."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_bubbles_create(self._h, colorsets._h if colorsets is not None else None, C.byref(h)))
+        return Bubbles(h)
+
     # ---- a coloured handle only (ColorSets.unitigs_dev) ----
     def set_ids_dev(self) -> int:
         """d_set_id (n_unitigs uint32) as an integer; valid until close()."""
@@ -948,6 +976,67 @@ class Unitigs:
         nb, ns, nc = C.c_int64(0), C.c_int64(0), C.c_int32(0)
         _check(lib().sbwtgpu_unitigs_color_info(self._h, C.byref(nb), C.byref(ns), C.byref(nc)))
         return {"n_color_breaks": int(nb.value), "n_sets": int(ns.value), "n_colors": int(nc.value)}
+
+
+class Bubbles:
+    """Owns an sbwtgpu_bubbles handle: the variant sites of a plain unitig graph (Unitigs.bubbles)."""
+
+    def __init__(self, handle):
+        self._h = handle
+        i = self.info()
+        self.n_bubbles, self.n_snps, self.n_colors, self.words = i["n_bubbles"], i["n_snps"], i["n_colors"], i["words"]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        if self._h:
+            lib().sbwtgpu_bubbles_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        nb, ns, nc, w = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
+        _check(lib().sbwtgpu_bubbles_info(self._h, C.byref(nb), C.byref(ns), C.byref(nc), C.byref(w)))
+        return {"n_bubbles": int(nb.value), "n_snps": int(ns.value), "n_colors": int(nc.value), "words": int(w.value)}
+
+    def _copy(self):
+        rec = np.zeros(self.n_bubbles, dtype=BUBBLE)
+        inter = np.zeros((self.n_bubbles, 2, self.words), dtype=np.uint64)
+        uni = np.zeros((self.n_bubbles, 2, self.words), dtype=np.uint64)
+        rows = self.n_bubbles > 0 and self.words > 0
+        _check(lib().sbwtgpu_bubbles_copy(self._h, rec.ctypes.data if self.n_bubbles else None, inter.ctypes.data if rows else None,
+                                          uni.ctypes.data if rows else None))
+        return rec, inter, uni
+
+    def records(self) -> np.ndarray:
+        """BUBBLE[n_bubbles], ascending by source: source, branch[2], sink, n_kmers[2], kind, reserved."""
+        return self._copy()[0]
+
+    def branch_colors(self):
+        """(inter, uni): uint64[n_bubbles, 2, W] each -- the references that hold the whole allele of a branch, and those that
+        hold any of its k-mers.  W = 0 for an object made without colour sets."""
+        return self._copy()[1:]
+
+    def dev_ptrs(self):
+        """(d_rec, d_inter, d_union) as integers (0 where there is nothing); valid until close()."""
+        r, a, b = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().sbwtgpu_bubbles_dev(self._h, C.byref(r), C.byref(a), C.byref(b)))
+        return r.value or 0, a.value or 0, b.value or 0
+
+    def stats(self) -> dict:
+        """Device-event times of the passes (ms)."""
+        ms = (C.c_double * 4)()
+        _check(lib().sbwtgpu_bubbles_stats(self._h, ms))
+        return {"pass_ms": dict(zip(("in_degrees", "detect", "compact", "branch_colors"), (float(x) for x in ms)))}
 
 
 class Colors:

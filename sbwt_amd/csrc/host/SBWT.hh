@@ -587,6 +587,31 @@ public:
         }
         return walks(g, bases.data(), read_off.data(), (int64_t)reads.size(), coverage);
     }
+    // The bubbles of a PLAIN graph handle (include/sbwtgpu.h, "bubbles"): the records by ascending source and, with a
+    // colour-set object of THIS index, the rows of branch j of bubble i at inter / uni[(2 i + j) words ..).
+    struct Bubbles {
+        std::vector<sbwtgpu_bubble> rec;
+        std::vector<uint64_t> inter, uni;
+        int64_t n_snps = 0;
+        int32_t n_colors = 0, words = 0;
+    };
+    Bubbles bubbles(const UnitigGraph &g, const sbwtgpu_colorsets *sets = nullptr) const {
+        need_device();
+        sbwtgpu_bubbles *b = nullptr;
+        detail::gpu_check(sbwtgpu_bubbles_create(g.h, sets, &b));
+        Bubbles r;
+        int64_t n = 0;
+        int rc = sbwtgpu_bubbles_info(b, &n, &r.n_snps, &r.n_colors, &r.words);
+        if (rc == SBWTGPU_OK) {
+            r.rec.resize((size_t)n);
+            r.inter.resize((size_t)n * 2 * (size_t)r.words);
+            r.uni.resize(r.inter.size());
+            rc = sbwtgpu_bubbles_copy(b, r.rec.data(), r.inter.data(), r.uni.data());
+        }
+        sbwtgpu_bubbles_destroy(b);
+        detail::gpu_check(rc);
+        return r;
+    }
     // the links of a graph handle of n unitigs into host vectors
     static int copy_links(const sbwtgpu_unitigs *u, int64_t n, std::vector<int64_t> &link_off, std::vector<uint32_t> &link_to) {
         int64_t n_links = 0;

@@ -1540,6 +1540,96 @@ int thread_main(int argc, char **argv) {
     return 0;
 }
 
+// the set bits of a `words`-word row as comma-separated ascending colours, "-" for none
+void append_color_list(const uint64_t *row, int32_t words, string &text) {
+    bool any = false;
+    for (int32_t w = 0; w < words; w++)
+        for (uint64_t x = row[w]; x; x &= x - 1) {
+            if (any) text.push_back(',');
+            append_int((int64_t)w * 64 + __builtin_ctzll(x), text);
+            any = true;
+        }
+    if (!any) text.push_back('-');
+}
+
+// sbwt bubbles: the variant sites of the plain unitig graph (include/sbwtgpu.h, "bubbles").  The output starts with
+// "# unitigs U links L bubbles B snps S", then one line per bubble in record order: source, branch_a, branch_b, sink, n_a,
+// n_b, SNP|OTHER, allele_a, allele_b, tab-separated; with -c two more fields, the colours of each branch: those of inter,
+// comma-separated ascending ("-" for none), and "|" and those of uni where the two differ.  --snps-only keeps the SNP lines.
+int bubbles_main(int argc, char **argv) {
+    set_log_level(LogLevel::MINOR);
+    Options opts({
+        {"index-file", 'i', true, "Index input file.", ""},
+        {"colors-file", 'c', true, "Colour file of the index (sbwt build-colors with or without --wide or --compress, compress-colors, merge-colors): adds the colours of each branch.", ""},
+        {"out-file", 'o', true, "Output file: a header line, then one tab-separated line per bubble.", ""},
+        {"gzip-output", 'z', false, "Writes the output in gzipped form.", ""},
+        {"snps-only", 0, false, "Write only the bubbles of kind SNP (the header still counts all).", ""},
+        {"gpu", 0, true, "HIP device to run on.", "0"},
+        {"help", 'h', false, "Print usage", ""},
+    });
+    opts.parse(argc, argv);
+    if (argc == 1 || opts.count("help")) {
+        std::cerr << opts.help(argv[0], "Find the bubbles of the unitig graph: where the references differ, and which reference carries which allele.") << std::endl;
+        exit(1);
+    }
+    const string indexfile = opts.get("index-file"), outfile = opts.get("out-file");
+    const bool colored = opts.count("colors-file") > 0, gzip_output = opts.count("gzip-output") > 0, snps_only = opts.count("snps-only") > 0;
+    const string colorsfile = colored ? opts.get("colors-file") : string();
+    check_readable(indexfile);
+    if (colored) check_readable(colorsfile);
+    check_writable(outfile);
+    set_default_device(atoi(opts.get("gpu").c_str()));
+    plain_matrix_sbwt_t index;
+    load_plain_matrix(indexfile, index);
+    ColorSetsHandle sets;
+    if (colored) load_colorsets(colorsfile, indexfile, index, sets);
+    const plain_matrix_sbwt_t::UnitigGraph graph = index.unitig_graph();
+    const plain_matrix_sbwt_t::Bubbles bb = index.bubbles(graph, colored ? sets.h : nullptr);
+    const plain_matrix_sbwt_t::ColoredUnitigs u = graph.unitigs();
+    string text = "# unitigs ";
+    append_int((int64_t)u.first_col.size(), text);
+    text += " links ";
+    append_int((int64_t)u.link_to.size(), text);
+    text += " bubbles ";
+    append_int((int64_t)bb.rec.size(), text);
+    text += " snps ";
+    append_int(bb.n_snps, text);
+    text.push_back('\n');
+    const size_t W = (size_t)bb.words;
+    for (size_t i = 0; i < bb.rec.size(); i++) {
+        const sbwtgpu_bubble &r = bb.rec[i];
+        if (snps_only && r.kind != SBWTGPU_BUBBLE_SNP) continue;
+        const int64_t f[6] = {r.source, r.branch[0], r.branch[1], r.sink, r.n_kmers[0], r.n_kmers[1]};
+        for (int j = 0; j < 6; j++) {
+            append_int(f[j], text);
+            text.push_back('\t');
+        }
+        text += r.kind == SBWTGPU_BUBBLE_SNP ? "SNP" : "OTHER";
+        for (int j = 0; j < 2; j++) {                      // the allele: the last n_kmers characters of the branch
+            text.push_back('\t');
+            const int64_t end = u.off[(size_t)r.branch[j] + 1];
+            text.append(u.bases.data() + (end - (int64_t)r.n_kmers[j]), (size_t)r.n_kmers[j]);
+        }
+        for (int j = 0; colored && j < 2; j++) {
+            text.push_back('\t');
+            const uint64_t *in = bb.inter.data() + (2 * i + (size_t)j) * W, *un = bb.uni.data() + (2 * i + (size_t)j) * W;
+            append_color_list(in, bb.words, text);
+            if (!std::equal(in, in + W, un)) {
+                text.push_back('|');
+                append_color_list(un, bb.words, text);
+            }
+        }
+        text.push_back('\n');
+    }
+    {
+        seq_io::Buffered_ofstream writer(outfile, gzip_output);
+        writer.write(text.data(), (int64_t)text.size());
+    }
+    write_log("Wrote " + std::to_string(bb.rec.size()) + " bubbles (" + std::to_string(bb.n_snps) + " SNPs) of " +
+                  std::to_string(u.first_col.size()) + " unitigs", LogLevel::MAJOR);
+    return 0;
+}
+
 // sbwt merge-colors: the colour sets of one or two coloured indexes carried onto index U (the output of `sbwt set-op`, for
 // one), without any sequence file: the "SBWTCOL3" file that build-colors --compress writes for U and the same colouring
 int merge_colors_main(int argc, char **argv) {
@@ -1849,7 +1939,7 @@ int pseudoalign_main(int argc, char **argv) {
     return 0;
 }
 
-const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "thread", "set-op", "read-hits", "build-colors", "compress-colors", "merge-colors", "color-matrix", "color-select", "screen", "pseudoalign"};
+const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "thread", "bubbles", "set-op", "read-hits", "build-colors", "compress-colors", "merge-colors", "color-matrix", "color-select", "screen", "pseudoalign"};
 
 void print_help(char **argv) {
     std::cerr << "Available commands: " << std::endl;
@@ -1881,6 +1971,7 @@ int main(int argc, char **argv) {   // sbwt.cpp:19-57
         else if (command == "matching-statistics") return matching_statistics_main(argc, argv);
         else if (command == "dump-unitigs") return dump_unitigs_main(argc, argv);
         else if (command == "thread") return thread_main(argc, argv);
+        else if (command == "bubbles") return bubbles_main(argc, argv);
         else if (command == "set-op") return set_op_main(argc, argv);
         else if (command == "read-hits") return read_hits_main(argc, argv);
         else if (command == "build-colors") return build_colors_main(argc, argv);

@@ -31,6 +31,7 @@
 #include "sbwt_colormatrix.h"
 #include "sbwt_colorselect.h"
 #include "sbwt_screen.h"
+#include "sbwt_bubbles.h"
 
 namespace {
 
@@ -4657,6 +4658,151 @@ int sbwtgpu_colorsets_select(const sbwtgpu_colorsets *s, const sbwtgpu_color_pre
     }
     info->pass_ms[2] = ms_since(t0);
     return rc;
+}
+
+
+// ---- bubbles: variant sites of the plain unitig graph and the colours of each allele (sbwt_bubbles.hip) ----
+}  // extern "C"
+static_assert(sizeof(sbwtgpu_bubble) == sizeof(SbwtBubble), "the record of the ABI is the kernels' record");
+struct sbwtgpu_bubbles {
+    int device = 0;
+    int n_colors = 0, words = 0;
+    SbwtBubbleRun run;
+};
+// what both bubble calls ask of the handle
+static int bubbles_check_handle(const sbwtgpu_unitigs *u) {
+    if (!(u->graph & SBWTGPU_UNITIGS_LINKS))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: the handle was made without SBWTGPU_UNITIGS_LINKS (sbwtgpu_unitigs_create_graph takes the flag)");
+    if (u->colored)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: a coloured handle cuts the branches at colour breaks: pass the plain handle "
+                    "(sbwtgpu_unitigs_create_graph with idx) plus the colour-set object");
+    return SBWTGPU_OK;
+}
+extern "C" {
+
+int sbwtgpu_bubbles_create(const sbwtgpu_unitigs *u, const sbwtgpu_colorsets *s, sbwtgpu_bubbles **out) {
+    if (!u || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: NULL argument (u and out are needed)");
+    *out = nullptr;
+    int rc = bubbles_check_handle(u);
+    if (rc != SBWTGPU_OK) return rc;
+    if (s) {
+        if (!(u->graph & SBWTGPU_UNITIGS_COLUMN_MAP))
+            return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: branch colours need the column map, and the handle was made without "
+                        "SBWTGPU_UNITIGS_COLUMN_MAP (sbwtgpu_unitigs_create_graph takes the flag)");
+        if ((rc = colorsets_check(s)) != SBWTGPU_OK) return rc;
+        if (s->base.n_nodes != u->n_nodes || s->base.k != u->k)
+            return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: colour sets of %lld columns at k = %lld used with unitigs of an index of %lld columns at k = %lld",
+                        (long long)s->base.n_nodes, (long long)s->base.k, (long long)u->n_nodes, (long long)u->k);
+        if (s->base.device != u->device)
+            return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: the colour sets are on device %d, the unitigs on device %d", s->base.device, u->device);
+    }
+    DeviceGuard guard(u->device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", u->device);
+    sbwtgpu_bubbles *b = new (std::nothrow) sbwtgpu_bubbles();
+    if (!b) return fail(SBWTGPU_ERR_OOM, "out of host memory");
+    b->device = u->device;
+    SbwtBubbleGraph g;
+    g.d_link_off = u->run.d_link_off;
+    g.d_link_to = u->run.d_link_to;
+    g.d_off = u->run.d_off;
+    g.n_unitigs = u->run.n_unitigs;
+    g.n_links = u->run.n_links;
+    g.k = u->k;
+    if (s) {
+        b->n_colors = s->base.n_colors;
+        b->words = s->base.words;
+        g.d_col_unitig = u->run.d_col_unitig;
+        g.n_nodes = u->n_nodes;
+        g.d_ids = s->d_ids;
+        g.d_table = s->d_table;
+        g.words = s->base.words;
+        g.n_colors = s->base.n_colors;
+    }
+    Stream st;
+    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = sbwt_bubbles_run(g, &b->run, st.s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        delete b;
+        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "bubbles: %s", hipGetErrorString(e));
+    }
+    *out = b;
+    return SBWTGPU_OK;
+}
+
+void sbwtgpu_bubbles_destroy(sbwtgpu_bubbles *b) {
+    if (!b) return;
+    DeviceGuard guard(b->device);
+    if (b->run.d_rec) (void)hipFree(b->run.d_rec);
+    if (b->run.d_inter) (void)hipFree(b->run.d_inter);
+    if (b->run.d_uni) (void)hipFree(b->run.d_uni);
+    delete b;
+}
+
+int sbwtgpu_bubbles_info(const sbwtgpu_bubbles *b, int64_t *n_bubbles, int64_t *n_snps, int32_t *n_colors, int32_t *words) {
+    if (!b) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: the object is NULL");
+    if (!n_bubbles) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: NULL argument (n_bubbles)");
+    *n_bubbles = b->run.n_bubbles;
+    if (n_snps) *n_snps = b->run.n_snps;
+    if (n_colors) *n_colors = b->n_colors;
+    if (words) *words = b->words;
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_bubbles_dev(const sbwtgpu_bubbles *b, const sbwtgpu_bubble **d_rec, const uint64_t **d_inter, const uint64_t **d_union) {
+    if (!b) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: the object is NULL");
+    if (!d_rec) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: NULL argument (d_rec)");
+    *d_rec = reinterpret_cast<const sbwtgpu_bubble *>(b->run.d_rec);
+    if (d_inter) *d_inter = reinterpret_cast<const uint64_t *>(b->run.d_inter);
+    if (d_union) *d_union = reinterpret_cast<const uint64_t *>(b->run.d_uni);
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_bubbles_copy(const sbwtgpu_bubbles *b, sbwtgpu_bubble *rec, uint64_t *inter, uint64_t *uni) {
+    if (!b) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: the object is NULL");
+    const int64_t n = b->run.n_bubbles;
+    if (n == 0) return SBWTGPU_OK;
+    if (!rec) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: NULL argument (rec, for %lld bubbles)", (long long)n);
+    if (b->words > 0 && (!inter || !uni))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: NULL argument (inter and uni: the object carries branch colours)");
+    DeviceGuard guard(b->device);
+    HIP_TRY(hipMemcpy(rec, b->run.d_rec, (size_t)n * sizeof(sbwtgpu_bubble), hipMemcpyDeviceToHost));
+    if (b->words > 0) {
+        const size_t bytes = (size_t)n * 2 * (size_t)b->words * 8;
+        HIP_TRY(hipMemcpy(inter, b->run.d_inter, bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(uni, b->run.d_uni, bytes, hipMemcpyDeviceToHost));
+    }
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_bubbles_in_degrees_copy(const sbwtgpu_unitigs *u, uint32_t *indeg) {
+    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: NULL argument (u)");
+    const int rc = bubbles_check_handle(u);
+    if (rc != SBWTGPU_OK) return rc;
+    const int64_t n = u->run.n_unitigs;
+    if (n == 0) return SBWTGPU_OK;
+    if (!indeg) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: NULL argument (indeg, for %lld unitigs)", (long long)n);
+    DeviceGuard guard(u->device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", u->device);
+    DevBuf d;
+    Stream st;
+    hipError_t e = d.alloc((size_t)n * 4);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = sbwt_bubbles_in_degrees(u->run.d_link_to, u->run.n_links, n, static_cast<unsigned *>(d.p), st.s);
+    if (e == hipSuccess) e = hipMemcpyAsync(indeg, d.p, (size_t)n * 4, hipMemcpyDeviceToHost, st.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(st.s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "bubbles: %s", hipGetErrorString(e));
+    }
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_bubbles_stats(const sbwtgpu_bubbles *b, double pass_ms[4]) {
+    if (!b) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: the object is NULL");
+    if (pass_ms)
+        for (int i = 0; i < SBWT_BB_N_PASSES; i++) pass_ms[i] = (double)b->run.ms[i];
+    return SBWTGPU_OK;
 }
 
 }  // extern "C"
