@@ -18,48 +18,28 @@
 #include <vector>
 #include <thread>
 
-#include "../../include/sbwtgpu.h"
-#include "sbwt_device.h"
-#include "sbwt_ms.h"
-#include "sbwt_unitigs.h"
-#include "sbwt_setops.h"
-#include "sbwt_readhits.h"
-#include "sbwt_walks.h"
-#include "sbwt_colors.h"
-#include "sbwt_colorsets.h"
-#include "sbwt_colormerge.h"
+#include "sbwtgpu_internal.h"
+#include "sbwt_readhits.h"          // (the defaults and bounds of knobs that sbwtgpu_set_tuning sets for the other files)
 #include "sbwt_colormatrix.h"
-#include "sbwt_colorselect.h"
-#include "sbwt_screen.h"
-#include "sbwt_bubbles.h"
 
-namespace {
+using namespace sbwt_capi;
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
+// the one definition of the error text and of what writes it: every file of the C ABI fails through these
+static thread_local char g_err[512] = "";
+int sbwt_capi::fail(int code, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return code;
 }
-
-// a search's device status word (SbwtWorkHeader::status) as the call's result: a k-mer search that did not end on one column,
-// or the sorted fused kernel's stall detector (a workgroup that made no progress for 2^20 waits)
-static int fail_status(int status) {
+int sbwt_capi::fail_status(int status) {
     if (status == SBWTGPU_ERR_STALLED)
         return fail(SBWTGPU_ERR_STALLED, "Bug: the sorted fused search kernel stalled (no progress in a workgroup)");
     return fail(SBWTGPU_ERR_NOT_SINGLETON, "Bug: k-mer search did not give a singleton interval");
 }
 
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(e_ == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP,         \
-                        "%s failed: %s", #expr, hipGetErrorString(e_));                        \
-    } while (0)
+namespace {
 
 // Depth of the device-side prefix table: deep enough that most walks start with a nearly unique
 // interval (ceil(log4(n_nodes)) + 2), capped at 14 (4 GiB of the 288 GB of HBM) unless
@@ -89,28 +69,6 @@ int default_device_precalc(int64_t n_nodes, bool derived) {
     return v;
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = (hipSetDevice(dev) == hipSuccess);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-template <typename T>
-inline T align256(T x) { return (x + 255) & ~(T)255; }
-
 // a knob's initial value: the environment variable when it is set, else the default
 int env_int(const char *name, int dflt) {
     const char *e = getenv(name);
@@ -134,12 +92,19 @@ static int g_variant_override = -1, g_probe_override = -1, g_debug = 0, g_derive
 static int g_fused_table = 1;      // the fused route's ticket table for batches with many long reads ("fused_table")
 // the fused kernel with its lanes sorted by state ("fused_sort": 0 off, 1 on; env SBWTGPU_FUSED_SORT; sbwt_search_fused.hip)
 static int g_fused_sort = env_int("SBWTGPU_FUSED_SORT", SBWT_FUSED_SORT_DEFAULT);
-// set around a search call by the *_i32 entry points: the kernels of this call write int32 results (SbwtIndexView::out32)
+// set around a search call by the *_i32 entry points: the kernels of this call write int32 results (SbwtIndexView::out32).
+// Only Out32 writes it, so it is 0 again on every way out of the call.
 static thread_local int t_out32 = 0;
+struct Out32 {
+    explicit Out32(int on) { t_out32 = on; }
+    ~Out32() { t_out32 = 0; }
+    Out32(const Out32 &) = delete;
+    Out32 &operator=(const Out32 &) = delete;
+};
 static int64_t g_ev_count = 0;
 // debug aid for the parity tests: fill the result range with a poison pattern before every search and every
 // matching-statistics call, so that a result the kernel never writes cannot inherit a correct value from an earlier launch
-static int g_poison = env_int("SBWTGPU_POISON_RESULTS", 0);
+int sbwt_capi::g_poison = env_int("SBWTGPU_POISON_RESULTS", 0);
 static int g_probe_filter = env_int("SBWTGPU_PROBE_FILTER", 1);
 static int g_image_level = env_int("SBWTGPU_IMAGE_LEVEL", 0);
 static int64_t g_max_image_bytes = env_i64("SBWTGPU_MAX_IMAGE_BYTES", 0);
@@ -185,78 +150,54 @@ static int g_path_stitch_min = env_int("SBWTGPU_PATH_STITCH_MIN", 1);
 // 100 for k <= 31 (round 5, one box: config 2 4.74 vs 4.90 ms, config 3 6.39 vs 6.54 ms -- the smaller table is no slower), 125 where
 // whole k-mers take two levels (k = 63: 4.18 ms at 125, 4.26 at 110, 4.29 at 100)
 static int g_sparse_buckets_pct = [] { const int v = env_int("SBWTGPU_SPARSE_BUCKETS_PCT", 0); return v <= 0 ? 0 : v < 60 ? 60 : v > 400 ? 400 : v; }();
-// per-read hit profiles (sbwt_readhits.hip): reads of this many windows or more are reduced by a wave instead of a lane; the
-// host entry point's chunk budget in bases (0: 64 Mi); 1: int64 results on indexes that would take int32 (tests)
-static int g_rh_wave_min = SBWT_RH_WAVE_MIN;
-static int64_t g_rh_chunk_bases = 0;
-static int g_rh_wide = 0;
-static int64_t g_wk_chunk_bases = 0;      // "walks_chunk_bases": 0 = the default of 64 Mi
-static int64_t g_pa_chunk_bases = 0;      // "pseudoalign_chunk_bases": 0 = the default of 64 Mi
-static int64_t g_screen_chunk_bases = 0;  // "screen_chunk_bases": 0 = the default of 64 Mi
-// shared k-mers (sbwt_colormatrix.hip): objects of this many sets or more go to the matrix cores, smaller ones to the plain
-// kernel; the sets a wave adds up in 32 bits before it adds into the 64-bit matrix.  Neither shows in a result.
-static int64_t g_gram_mfma_min_sets = SBWT_GM_MIN_SETS_DEFAULT;
-static int64_t g_gram_flush_sets = SBWT_GM_FLUSH_DEFAULT;
 // depth of the sparse (hashed) prefix table built at index creation (capped at k and at 31 = one 62-bit key)
 static int g_sparse_depth = env_int("SBWTGPU_SPARSE_PRECALC", 31);
 
-struct sbwtgpu_index {
-    SbwtBlobHeader h;
-    int device = 0;
-    char *blob = nullptr;       // device
-    bool owns_blob = true;
-    // the LCS array of matching statistics (sbwt_ms.hip): its own allocation, outside the blob and its byte cap, built on
-    // the first call that needs it (sbwtgpu_index_build_lcs); replicas (adopt / bcast) build their own
-    mutable std::mutex lcs_mu;
-    mutable unsigned char *lcs = nullptr;
-    // probe length of the certificate walks: long enough that a random string of that length is almost
-    // surely absent (log4(#k-mers) + 4), at least one char longer than the device prefix table
-    int probe_len(bool allow_override = true) const {
-        if (allow_override && g_probe_override >= 0) return g_probe_override < h.k ? g_probe_override : 0;
-        int64_t nk = h.n_kmers > 0 ? h.n_kmers : h.n_nodes;
-        int L = 4;
-        while (L < 40 && ((int64_t)1 << (2 * L)) < nk) L++;
-        L += 4;
-        if (L < h.p_dev + 2) L = (int)h.p_dev + 2;
-        if (L > h.k - 1) return 0;
-        return L;
-    }
-    SbwtIndexView view() const {
-        SbwtIndexView v;
-        v.blocks = reinterpret_cast<const uint4 *>(blob + h.off_blocks);
-        v.ptab = h.p_dev > 0 ? reinterpret_cast<const longlong2 *>(blob + h.off_ptab) : nullptr;
-        v.mega = reinterpret_cast<const unsigned long long *>(blob + h.off_mega);
-        v.n_nodes = h.n_nodes;
-        v.n_pos = h.n_pos > 0 ? h.n_pos : h.n_nodes;
-        for (int i = 0; i < 4; i++) v.C[i] = h.C[i];
-        v.k = (int)h.k;
-        v.p_dev = (int)h.p_dev;
-        v.n_mega = (int)h.n_mega;
-        v.has_ssup = h.has_ssup;
-        v.probe_len = probe_len();
-        v.debug = g_debug;
-        v.fused_sort = g_fused_sort;
-        v.big = h.big_layout;
-        v.out32 = t_out32;
-        v.force_mega = h.force_mega;
-        v.p_sparse = (int)h.p_sparse;
-        v.n_sb = (unsigned)h.n_sb;
-        v.stab = h.p_sparse > 0 ? reinterpret_cast<const uint4 *>(blob + h.off_stab) : nullptr;
-        v.col = h.has_path ? reinterpret_cast<const unsigned *>(blob + h.off_col) : nullptr;
-        v.pos = h.has_path ? reinterpret_cast<const unsigned *>(blob + h.off_pos) : nullptr;
-        v.pq = h.has_path ? reinterpret_cast<const uint4 *>(blob + h.off_pq) : nullptr;
-        v.trans = (h.has_path && h.n_tslots > 0) ? reinterpret_cast<const uint4 *>(blob + h.off_trans) : nullptr;
-        v.stab_pos = h.stab_pos;
-        v.n_tslots = (unsigned)h.n_tslots;
-        v.has_safe = h.has_safe;
-        v.stab2 = h.n_sb2 > 0 ? reinterpret_cast<const uint4 *>(blob + h.off_stab2) : nullptr;
-        v.n_sb2 = (unsigned)h.n_sb2;
-        v.pfil = h.p_filter > 0 ? reinterpret_cast<const uint4 *>(blob + h.off_pfil) : nullptr;
-        v.p_filter = (int)h.p_filter;
-        v.log2f = (int)h.log2f;
-        return v;
-    }
-};
+int sbwtgpu_index::probe_len(bool allow_override) const {
+    if (allow_override && g_probe_override >= 0) return g_probe_override < h.k ? g_probe_override : 0;
+    int64_t nk = h.n_kmers > 0 ? h.n_kmers : h.n_nodes;
+    int L = 4;
+    while (L < 40 && ((int64_t)1 << (2 * L)) < nk) L++;
+    L += 4;
+    if (L < h.p_dev + 2) L = (int)h.p_dev + 2;
+    if (L > h.k - 1) return 0;
+    return L;
+}
+SbwtIndexView sbwtgpu_index::view() const {
+    SbwtIndexView v;
+    v.blocks = reinterpret_cast<const uint4 *>(blob + h.off_blocks);
+    v.ptab = h.p_dev > 0 ? reinterpret_cast<const longlong2 *>(blob + h.off_ptab) : nullptr;
+    v.mega = reinterpret_cast<const unsigned long long *>(blob + h.off_mega);
+    v.n_nodes = h.n_nodes;
+    v.n_pos = h.n_pos > 0 ? h.n_pos : h.n_nodes;
+    for (int i = 0; i < 4; i++) v.C[i] = h.C[i];
+    v.k = (int)h.k;
+    v.p_dev = (int)h.p_dev;
+    v.n_mega = (int)h.n_mega;
+    v.has_ssup = h.has_ssup;
+    v.probe_len = probe_len();
+    v.debug = g_debug;
+    v.fused_sort = g_fused_sort;
+    v.big = h.big_layout;
+    v.out32 = t_out32;
+    v.force_mega = h.force_mega;
+    v.p_sparse = (int)h.p_sparse;
+    v.n_sb = (unsigned)h.n_sb;
+    v.stab = h.p_sparse > 0 ? reinterpret_cast<const uint4 *>(blob + h.off_stab) : nullptr;
+    v.col = h.has_path ? reinterpret_cast<const unsigned *>(blob + h.off_col) : nullptr;
+    v.pos = h.has_path ? reinterpret_cast<const unsigned *>(blob + h.off_pos) : nullptr;
+    v.pq = h.has_path ? reinterpret_cast<const uint4 *>(blob + h.off_pq) : nullptr;
+    v.trans = (h.has_path && h.n_tslots > 0) ? reinterpret_cast<const uint4 *>(blob + h.off_trans) : nullptr;
+    v.stab_pos = h.stab_pos;
+    v.n_tslots = (unsigned)h.n_tslots;
+    v.has_safe = h.has_safe;
+    v.stab2 = h.n_sb2 > 0 ? reinterpret_cast<const uint4 *>(blob + h.off_stab2) : nullptr;
+    v.n_sb2 = (unsigned)h.n_sb2;
+    v.pfil = h.p_filter > 0 ? reinterpret_cast<const uint4 *>(blob + h.off_pfil) : nullptr;
+    v.p_filter = (int)h.p_filter;
+    v.log2f = (int)h.log2f;
+    return v;
+}
 
 // Which path-order route by default: the fused one (equal-length batches in one kernel, everything else through the
 // general kernel behind it).
@@ -1100,9 +1041,6 @@ static SbwtTickTab ws_tick_tab(void *d_ws, int64_t total_bases) {
     return tt;
 }
 
-static const char *RANK_ONLY_MSG =
-    "the index columns are not a valid SBWT (set bits != n_nodes - 1): only rank() is available";
-
 // SBWT::search through streaming steps on the device (the marks given with the index, or derived): exact where a streaming step
 // and a full search agree on every k-mer of valid bases (tests/test_large.hh:104-115).  Not for k = 1: there every column is in
 // the root's suffix group while the edges sit on the first k-mer's column (NodeBOSSInMemoryConstructor.hh:98-154), so the
@@ -1222,9 +1160,10 @@ int sbwtgpu_kernel_times(double *ms, int64_t cap, int64_t *n) {
     return SBWTGPU_OK;
 }
 
-static int search_dev_common(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases,
-                             const int64_t *d_read_off, int64_t n_reads, int64_t *d_out, const int64_t *d_out_off,
-                             void *d_ws, int64_t ws_bytes, void *stream, int streaming) {
+}  // extern "C"
+int sbwt_capi::search_dev_common(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases,
+                                 const int64_t *d_read_off, int64_t n_reads, int64_t *d_out, const int64_t *d_out_off,
+                                 void *d_ws, int64_t ws_bytes, void *stream, int streaming) {
     int rc = search_dev_check(idx, total_bases, n_reads, d_ws, ws_bytes, streaming);
     if (rc != SBWTGPU_OK) return rc;
     if (n_reads == 0) return SBWTGPU_OK;
@@ -1297,6 +1236,7 @@ static int search_dev_common(const sbwtgpu_index *idx, const char *d_bases, int6
     return sbwtgpu_search_encoded_dev(idx, total_bases, d_read_off, n_reads, d_out, d_out_off, d_ws, ws_bytes,
                                       streaming, stream);
 }
+extern "C" {
 
 int sbwtgpu_streaming_search_dev(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases,
                                  const int64_t *d_read_off, int64_t n_reads, int64_t *d_out,
@@ -1314,19 +1254,19 @@ int sbwtgpu_search_dev(const sbwtgpu_index *idx, const char *d_bases, int64_t to
 
 // The same two calls with int32 results (result compaction): every kernel of the route writes 4 bytes per k-mer
 // instead of 8 -- half the write requests of a launch, which are 40 % of its time.
-static int search_dev_i32(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
-                          int64_t n_reads, int32_t *d_out, const int64_t *d_out_off, void *d_ws, int64_t ws_bytes, void *stream,
-                          int streaming) {
+}  // extern "C"
+int sbwt_capi::search_dev_i32(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                              int64_t n_reads, int32_t *d_out, const int64_t *d_out_off, void *d_ws, int64_t ws_bytes, void *stream,
+                              int streaming) {
     if (!idx) return fail(SBWTGPU_ERR_INVALID_ARG, "idx is NULL");
     if (idx->h.n_nodes >= ((int64_t)1 << 31))
         return fail(SBWTGPU_ERR_INVALID_ARG, "int32 results need an index of fewer than 2^31 columns (this one has %lld)",
                     (long long)idx->h.n_nodes);
-    t_out32 = 1;
-    const int rc = search_dev_common(idx, d_bases, total_bases, d_read_off, n_reads, reinterpret_cast<int64_t *>(d_out), d_out_off,
-                                     d_ws, ws_bytes, stream, streaming);
-    t_out32 = 0;
-    return rc;
+    const Out32 scope(1);
+    return search_dev_common(idx, d_bases, total_bases, d_read_off, n_reads, reinterpret_cast<int64_t *>(d_out), d_out_off, d_ws,
+                             ws_bytes, stream, streaming);
 }
+extern "C" {
 int sbwtgpu_streaming_search_dev_i32(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases,
                                      const int64_t *d_read_off, int64_t n_reads, int32_t *d_out, const int64_t *d_out_off,
                                      void *d_ws, int64_t ws_bytes, void *stream) {
@@ -1379,40 +1319,22 @@ int sbwtgpu_workspace_stats(const void *d_ws, void *stream, int64_t stats[8]) {
 // ---- host-buffer entry points --------------------------------------------------------------
 }  // extern "C"
 namespace {
-struct Stream {
-    hipStream_t s = nullptr;
-    ~Stream() {
-        if (s) (void)hipStreamDestroy(s);
-    }
-};
-
-// Small calls (the scalar API of the reference -- SBWT::search(kmer), rank(pos, c), one update_sbwt_interval -- arrives
-// here as batches of one): no hipMalloc / hipStreamCreate per call.  Every host thread keeps, per device, one stream,
-// one pinned host buffer and one device buffer of SLOT_CAP bytes; a call whose data fits stages its inputs in the pinned
-// buffer, moves them with ONE H2D copy, runs its kernels, and brings the results back with ONE D2H copy + one sync.
-constexpr size_t SLOT_CAP = (size_t)1 << 20;
 bool g_exiting = false;                                  // set at process exit: HIP may be gone, leak instead of freeing
-struct SmallSlot {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    char *host = nullptr, *dev = nullptr;
-    void release() {
-        if (device < 0 || g_exiting) return;
-        DeviceGuard guard(device);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (host) (void)hipHostFree(host);
-        if (dev) (void)hipFree(dev);
-        stream = nullptr; host = dev = nullptr; device = -1;
-    }
-};
 struct SlotSet {
     std::vector<SmallSlot> v;
     ~SlotSet() { for (auto &s : v) s.release(); }
 };
 thread_local SlotSet t_slots;
-// The calling thread's slot on `device` (the current device must already be `device`), or nullptr when `need` does not
-// fit or the buffers cannot be allocated (the caller then takes the general path).
-SmallSlot *small_slot(int device, size_t need) {
+}  // namespace
+void sbwt_capi::SmallSlot::release() {
+    if (device < 0 || g_exiting) return;
+    DeviceGuard guard(device);
+    if (stream) (void)hipStreamDestroy(stream);
+    if (host) (void)hipHostFree(host);
+    if (dev) (void)hipFree(dev);
+    stream = nullptr; host = dev = nullptr; device = -1;
+}
+SmallSlot *sbwt_capi::small_slot(int device, size_t need) {
     if (need > SLOT_CAP) return nullptr;
     static const bool once = [] { atexit([] { g_exiting = true; }); return true; }();
     (void)once;
@@ -1432,100 +1354,7 @@ SmallSlot *small_slot(int device, size_t need) {
     return &t_slots.v.back();
 }
 
-// One host-buffer call that is not pipelined: the caller lays its inputs, results and workspace out in one range of
-// `bytes` bytes (every part 256-byte aligned) and names the parts by their offsets.  A call that fits SLOT_CAP runs on the
-// thread's SmallSlot: in() copies into the pinned buffer, upload() is the ONE H2D copy, finish() the ONE D2H copy, the
-// ONE synchronise and the copies out to the caller.  A larger call gets a temporary stream and one device allocation,
-// and in() / out() copy straight between the caller's memory and the device: no host-side bounce.
-struct Staging {
-    std::vector<std::vector<int64_t>> kept;     // large calls: computed inputs, alive until the synchronise
-    Stream tmp_stream;
-    DevBuf tmp_dev;
-    SmallSlot *sl = nullptr;
-    char *dev = nullptr;
-    hipStream_t stream = nullptr;
-    size_t in_lo = SIZE_MAX, in_hi = 0, out_lo = SIZE_MAX, out_hi = 0;    // slot: the byte ranges of the two copies
-    struct Back { void *dst; size_t off, n; } back[4];
-    int n_back = 0;
-
-    int open(int device, size_t bytes) {       // (the current device must already be `device`)
-        sl = small_slot(device, bytes);
-        if (sl) { dev = sl->dev; stream = sl->stream; return SBWTGPU_OK; }
-        HIP_TRY(hipStreamCreateWithFlags(&tmp_stream.s, hipStreamNonBlocking));
-        HIP_TRY(tmp_dev.alloc(bytes));
-        dev = static_cast<char *>(tmp_dev.p);
-        stream = tmp_stream.s;
-        return SBWTGPU_OK;
-    }
-    template <typename T>
-    T *at(size_t off) const { return reinterpret_cast<T *>(dev + off); }
-    // n bytes of the caller's at src are the input at `off`
-    int in(size_t off, const void *src, size_t n) {
-        if (n == 0) return SBWTGPU_OK;
-        if (!sl) {
-            HIP_TRY(hipMemcpyAsync(dev + off, src, n, hipMemcpyHostToDevice, stream));
-            return SBWTGPU_OK;
-        }
-        if (src != sl->host + off) memcpy(sl->host + off, src, n);
-        in_lo = std::min(in_lo, off);
-        in_hi = std::max(in_hi, off + n);
-        return SBWTGPU_OK;
-    }
-    // the input at `off` is the n offsets src[0 .. n) rebased to start at 0 (device buffers start at their first base)
-    int in_rebased(size_t off, const int64_t *src, int64_t n) {
-        int64_t *o = nullptr;
-        if (sl) {
-            o = reinterpret_cast<int64_t *>(sl->host + off);
-        } else {
-            try {
-                kept.emplace_back((size_t)n);
-            } catch (const std::bad_alloc &) {
-                return fail(SBWTGPU_ERR_OOM, "out of host memory");
-            }
-            o = kept.back().data();
-        }
-        for (int64_t t = 0; t < n; t++) o[t] = src[t] - src[0];
-        return in(off, o, (size_t)n * 8);
-    }
-    int upload() {
-        if (sl && in_hi > in_lo) HIP_TRY(hipMemcpyAsync(dev + in_lo, sl->host + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, stream));
-        return SBWTGPU_OK;
-    }
-    // after the kernels: the n bytes at `off` are a result and go to dst (written by the time finish() returns)
-    int out(size_t off, void *dst, size_t n) {
-        if (n == 0) return SBWTGPU_OK;
-        if (!sl) {
-            HIP_TRY(hipMemcpyAsync(dst, dev + off, n, hipMemcpyDeviceToHost, stream));
-            return SBWTGPU_OK;
-        }
-        if (n_back == (int)(sizeof(back) / sizeof(back[0]))) return fail(SBWTGPU_ERR_HIP, "internal: too many results in one staged call");
-        back[n_back++] = Back{dst, off, n};
-        out_lo = std::min(out_lo, off);
-        out_hi = std::max(out_hi, off + n);
-        return SBWTGPU_OK;
-    }
-    int finish() {
-        if (sl && out_hi > out_lo) HIP_TRY(hipMemcpyAsync(sl->host + out_lo, dev + out_lo, out_hi - out_lo, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        for (int i = 0; i < n_back; i++) memcpy(back[i].dst, sl->host + back[i].off, back[i].n);
-        return SBWTGPU_OK;
-    }
-};
-#define STG_TRY(expr)                                                                          \
-    do {                                                                                       \
-        const int rc_ = (expr);                                                                \
-        if (rc_ != SBWTGPU_OK) return rc_;                                                     \
-    } while (0)
-}  // namespace
 extern "C" {
-
-// The length of read r as every host entry point checks it while it walks the offsets: not negative, below 2^31
-static inline int check_read_length(const int64_t *read_off, int64_t r) {
-    const int64_t len = read_off[r + 1] - read_off[r];
-    if (len < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "read_off is not non-decreasing at read %lld", (long long)r);
-    if (len >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_READ_TOO_LONG, "read %lld has >= 2^31 bases", (long long)r);
-    return SBWTGPU_OK;
-}
 
 // (*any_long: some read has more than 2 * PIECE k-mers -- the host entry points cut those into pieces, below)
 static int check_reads(const int64_t *read_off, const int64_t *out_off, int64_t n_reads, int64_t k, bool *any_long = nullptr) {
@@ -1603,49 +1432,13 @@ static inline int64_t pieces_bases_bound(int64_t len, int64_t k) {   // bytes ap
 // threads.  The rate is then PCIe's: 8 bytes of results per k-mer.
 }  // extern "C"
 namespace {
-// One slot of a pipeline: a stream, pinned staging buffers for what goes down and what comes back, a pinned status word
-// and one device allocation, which the entry point carves for its chunk.  Pinned and device buffers are expensive to
-// create (page pinning), so finished calls park their slots and later calls on the same device take them again, whichever
-// entry point parked them; ensure() grows only what is too small for the taker.
-struct PipeSlot {
-    hipStream_t st = nullptr;
-    char *h_in = nullptr, *h_out = nullptr;     // pinned staging: inputs; results (search: only for pageable callers)
-    int *h_status = nullptr;                    // pinned, 64 bytes: the chunk's device status (text: and its text length)
-    char *d_mem = nullptr;
-    int64_t cap_in = 0, cap_out = 0, cap_dev = 0;
-    hipError_t ensure(int64_t need_in, int64_t need_out, int64_t need_dev) {
-        hipError_t e = hipSuccess;
-        if (!st) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-        if (e == hipSuccess && !h_status) e = hipHostMalloc((void **)&h_status, 64, hipHostMallocDefault);
-        auto grow = [&e](char *&p, int64_t &cap, int64_t need, bool device) {
-            if (e != hipSuccess || cap >= need) return;
-            if (p) (void)(device ? hipFree(p) : hipHostFree(p));
-            p = nullptr; cap = 0;
-            e = device ? hipMalloc((void **)&p, (size_t)need) : hipHostMalloc((void **)&p, (size_t)need, hipHostMallocDefault);
-            if (e == hipSuccess) cap = need;
-        };
-        grow(h_in, cap_in, need_in, false);
-        grow(h_out, cap_out, need_out, false);
-        grow(d_mem, cap_dev, need_dev, true);
-        return e;
-    }
-    void release() {
-        if (st) (void)hipStreamDestroy(st);
-        if (h_in) (void)hipHostFree(h_in);
-        if (h_out) (void)hipHostFree(h_out);
-        if (h_status) (void)hipHostFree(h_status);
-        if (d_mem) (void)hipFree(d_mem);
-        *this = PipeSlot();
-    }
-};
-std::mutex g_park_mutex;
+std::mutex g_park_mutex;             // the parked slots of every file's calls (PipeSlot, sbwtgpu_internal.h)
 struct Parked { int device; PipeSlot slot; };
 std::vector<Parked> g_parked;
 const size_t PARK_CAP = 8;                      // parked slots per device; a call that finishes beyond it frees its slots
 
-// n slots for a call on `device` (the current device), each grown to the call's needs: parked ones first, the most
-// recently parked first.  On failure nothing is left allocated.
-int take_slots(int device, PipeSlot *S, int n, int64_t need_in, int64_t need_out, int64_t need_dev, const char *what) {
+}  // namespace
+int sbwt_capi::take_slots(int device, PipeSlot *S, int n, int64_t need_in, int64_t need_out, int64_t need_dev, const char *what) {
     {
         std::lock_guard<std::mutex> lock(g_park_mutex);
         int got = 0;
@@ -1664,8 +1457,7 @@ int take_slots(int device, PipeSlot *S, int n, int64_t need_in, int64_t need_out
     }
     return SBWTGPU_OK;
 }
-// The end of a call on its slots: parked for the next one, or, after an error, freed once the device is idle.
-void park_slots(int device, PipeSlot *S, int n, int rc) {
+void sbwt_capi::park_slots(int device, PipeSlot *S, int n, int rc) {
     if (rc != SBWTGPU_OK) (void)hipDeviceSynchronize();
     std::lock_guard<std::mutex> lock(g_park_mutex);
     size_t there = 0;
@@ -1675,23 +1467,12 @@ void park_slots(int device, PipeSlot *S, int n, int rc) {
         else S[q].release();
     }
 }
-// Two chunks in flight: chunk c is submitted once chunk c - 2 has been collected from the slot it takes
-template <typename Submit, typename Collect>
-int two_in_flight(int64_t n_chunks, Submit submit, Collect collect) {
-    int rc = SBWTGPU_OK;
-    for (int64_t c = 0; c < n_chunks && rc == SBWTGPU_OK; c++) {
-        if (c >= 2) rc = collect(c - 2);
-        if (rc == SBWTGPU_OK) rc = submit(c);
-    }
-    for (int64_t c = std::max<int64_t>(0, n_chunks - 2); c < n_chunks && rc == SBWTGPU_OK; c++) rc = collect(c);
-    return rc;
-}
-bool is_pinned(const void *p) {
+bool sbwt_capi::is_pinned(const void *p) {
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
     return a.type == hipMemoryTypeHost;
 }
-void parallel_memcpy(char *dst, const char *src, size_t n) {
+void sbwt_capi::parallel_memcpy(char *dst, const char *src, size_t n) {
     const int T = n >= ((size_t)8 << 20) ? 4 : 1;
     if (T == 1) { memcpy(dst, src, n); return; }
     std::vector<std::thread> th;
@@ -1702,8 +1483,7 @@ void parallel_memcpy(char *dst, const char *src, size_t n) {
     }
     for (auto &x : th) x.join();
 }
-const int64_t PIPE_MIN = (int64_t)64 << 20;
-}  // namespace
+static const int64_t PIPE_MIN = (int64_t)64 << 20;
 extern "C" {
 
 // ro / oo: nv + 1 offsets into src_bases / out (rebased to 0 or not: only ro[0], oo[0] and differences are used)
@@ -1766,10 +1546,11 @@ static int search_host_pipelined(const sbwtgpu_index *idx, const char *src_bases
             (e = hipMemcpyAsync(d.roff, hro, (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, P.st)) != hipSuccess ||
             (e = hipMemcpyAsync(d.ooff, hoo, (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, P.st)) != hipSuccess)
             return fail(SBWTGPU_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
-        t_out32 = out32 ? 1 : 0;                        // (int32 results: the kernels write them into the same device range)
-        int r2 = search_dev_common(idx, d.bases, nb, d.roff, nr, d.out, d.ooff, d.ws, ws_bytes, P.st, streaming);
-        t_out32 = 0;
-        if (r2 != SBWTGPU_OK) return r2;
+        {
+            const Out32 scope(out32 ? 1 : 0);           // (int32 results: the kernels write them into the same device range)
+            const int r2 = search_dev_common(idx, d.bases, nb, d.roff, nr, d.out, d.ooff, d.ws, ws_bytes, P.st, streaming);
+            if (r2 != SBWTGPU_OK) return r2;
+        }
         char *target = pin_out ? (out32 ? (char *)(out32 + oo[lo]) : (char *)(out + oo[lo])) : P.h_out;
         const void *from = d.out;
         if ((e = hipMemcpyAsync(target, from, (size_t)(nvals * vb), hipMemcpyDeviceToHost, P.st)) != hipSuccess ||
@@ -2124,6 +1905,10 @@ int build_columns_t(SbwtBuildState &S, int64_t k, int build_streaming_support, s
     return SBWTGPU_OK;
 }
 }  // namespace
+int sbwt_capi::build_columns(SbwtBuildState &S, int64_t k, int build_streaming_support, sbwtgpu_plain_matrix_bits *out) {
+    return (k <= 32) ? build_columns_t<unsigned long long>(S, k, build_streaming_support, out)
+                     : build_columns_t<unsigned __int128>(S, k, build_streaming_support, out);
+}
 extern "C" {
 
 int sbwtgpu_build_plain_matrix(const char *const *seqs, const int64_t *seq_len, int64_t n_seqs, int64_t k, int add_revcomp,
@@ -2167,8 +1952,7 @@ int sbwtgpu_build_plain_matrix(const char *const *seqs, const int64_t *seq_len, 
                         "use the host builder for inputs with this many sequences", (long long)S.n_nopred,
                         (long long)S.n_nopred * (long long)k);
         }
-        rc = (k <= 32) ? build_columns_t<unsigned long long>(S, k, build_streaming_support, out)
-                       : build_columns_t<unsigned __int128>(S, k, build_streaming_support, out);
+        rc = build_columns(S, k, build_streaming_support, out);
     } catch (const std::bad_alloc &) {
         sbwt_build_release(&S);
         rc = fail(SBWTGPU_ERR_OOM, "out of host memory");
@@ -2427,2381 +2211,6 @@ int sbwtgpu_search_text_batch(const sbwtgpu_index *idx, const char *bases, const
     char *shrunk = (char *)realloc(acc.buf, (size_t)(acc.len ? acc.len : 1));
     *text = shrunk ? shrunk : acc.buf;
     *text_bytes = acc.len;
-    return SBWTGPU_OK;
-}
-
-// ---- matching statistics (sbwt_ms.hip) ------------------------------------------------------------
-namespace {
-int lcs_build_locked(const sbwtgpu_index *idx) {
-    if (idx->lcs) return SBWTGPU_OK;
-    DeviceGuard guard(idx->device);
-    const int64_t n = idx->h.n_nodes;
-    DevBuf scratch;
-    unsigned char *d_lcs = nullptr;
-    // n + 1 entries (lcs[n] = 0), rounded up to whole 64-byte lines: the contraction reads aligned 8-byte words
-    const size_t lcs_bytes = (size_t)((n + 1 + 63) & ~(int64_t)63) + 64;
-    hipError_t e = hipMalloc((void **)&d_lcs, lcs_bytes);
-    if (e == hipSuccess) e = scratch.alloc((size_t)sbwt_lcs_scratch_bytes(n));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (d_lcs) (void)hipFree(d_lcs);
-        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "LCS array: hipMalloc failed: %s",
-                    hipGetErrorString(e));
-    }
-    Stream st;
-    e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMemsetAsync(d_lcs, 0, lcs_bytes, st.s);
-    if (e == hipSuccess) e = hipMemsetAsync(scratch.p, 0, (size_t)sbwt_lcs_scratch_bytes(n), st.s);
-    if (e == hipSuccess) {
-        sbwt_launch_build_lcs(idx->view(), scratch.p, d_lcs, st.s);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st.s);
-    if (e != hipSuccess) {
-        (void)hipFree(d_lcs);
-        return fail(SBWTGPU_ERR_HIP, "LCS build: %s", hipGetErrorString(e));
-    }
-    idx->lcs = d_lcs;
-    return SBWTGPU_OK;
-}
-int lcs_ensure(const sbwtgpu_index *idx) {
-    if (!idx) return fail(SBWTGPU_ERR_INVALID_ARG, "idx is NULL");
-    if (idx->h.rank_only) return fail(SBWTGPU_ERR_INVALID_ARG, "%s", RANK_ONLY_MSG);
-    std::lock_guard<std::mutex> lock(idx->lcs_mu);
-    return lcs_build_locked(idx);
-}
-int ms_check_ptrs(const int64_t *first, const int64_t *second) {
-    if ((first == nullptr) != (second == nullptr)) return fail(SBWTGPU_ERR_INVALID_ARG, "first and second must be both NULL or both non-NULL");
-    return SBWTGPU_OK;
-}
-}  // namespace
-
-int sbwtgpu_index_build_lcs(sbwtgpu_index *idx) { return lcs_ensure(idx); }
-
-int sbwtgpu_index_get_lcs(const sbwtgpu_index *idx, uint8_t *out) {
-    if (!out) return fail(SBWTGPU_ERR_INVALID_ARG, "out is NULL");
-    int rc = lcs_ensure(idx);
-    if (rc != SBWTGPU_OK) return rc;
-    DeviceGuard guard(idx->device);
-    HIP_TRY(hipMemcpy(out, idx->lcs, (size_t)idx->h.n_nodes, hipMemcpyDeviceToHost));
-    return SBWTGPU_OK;
-}
-
-int64_t sbwtgpu_ms_workspace_bytes(int64_t total_bases) {
-    (void)total_bases;
-    return (int64_t)sizeof(SbwtMsWork);
-}
-
-int sbwtgpu_matching_statistics_dev(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases,
-                                    const int64_t *d_read_off, int64_t n_reads, uint8_t *d_len, int64_t *d_first,
-                                    int64_t *d_second, void *d_ws, int64_t ws_bytes, void *stream) {
-    int rc = lcs_ensure(idx);
-    if (rc != SBWTGPU_OK) return rc;
-    if ((rc = ms_check_ptrs(d_first, d_second)) != SBWTGPU_OK) return rc;
-    if (n_reads < 0 || total_bases < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative size");
-    if (total_bases >= ((int64_t)1 << 36))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "more than 2^36 bases in one call: split the batch");
-    if (!d_ws || ws_bytes < sbwtgpu_ms_workspace_bytes(total_bases))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "workspace missing or too small (%lld < %lld)", (long long)ws_bytes,
-                    (long long)sbwtgpu_ms_workspace_bytes(total_bases));
-    if (((uintptr_t)d_ws & 15) != 0) return fail(SBWTGPU_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
-    if (n_reads > 0 && !d_read_off) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
-    if (total_bases > 0 && (!d_bases || !d_len)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
-    DeviceGuard guard(idx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(d_ws, 0, sizeof(SbwtMsWork), st));
-    if (g_poison && n_reads > 0 && total_bases > 0) {
-        // len 0xFF is above every k, so a slot the kernel skips cannot pass for an answer
-        int64_t b0 = 0;
-        HIP_TRY(hipMemcpyAsync(&b0, d_read_off, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemsetAsync(d_len + b0, 0xFF, (size_t)total_bases, st));
-        if (d_first) {
-            HIP_TRY(hipMemsetAsync(d_first + b0, 0xA5, (size_t)total_bases * 8, st));
-            HIP_TRY(hipMemsetAsync(d_second + b0, 0xA5, (size_t)total_bases * 8, st));
-        }
-    }
-    sbwt_launch_ms(idx->view(), idx->lcs, d_bases, total_bases, reinterpret_cast<const long long *>(d_read_off), n_reads,
-                   d_len, reinterpret_cast<long long *>(d_first), reinterpret_cast<long long *>(d_second),
-                   static_cast<SbwtMsWork *>(d_ws), st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_ms_workspace_stats(const void *d_ws, void *stream, int64_t stats[5]) {
-    if (!d_ws || !stats) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    SbwtMsWork w;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemcpyAsync(&w, d_ws, sizeof(w), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    stats[0] = (int64_t)w.n_out;
-    stats[1] = (int64_t)w.n_walk;
-    stats[2] = (int64_t)w.n_full;
-    stats[3] = (int64_t)w.n_contract;
-    stats[4] = (int64_t)w.n_recompute;
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_matching_statistics_batch(const sbwtgpu_index *idx, const char *bases, const int64_t *read_off,
-                                      int64_t n_reads, uint8_t *len, int64_t *first, int64_t *second) {
-    int rc = lcs_ensure(idx);
-    if (rc != SBWTGPU_OK) return rc;
-    if ((rc = ms_check_ptrs(first, second)) != SBWTGPU_OK) return rc;
-    if (n_reads < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative n_reads");
-    if (n_reads == 0) return SBWTGPU_OK;
-    if (!read_off) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    for (int64_t r = 0; r < n_reads; r++)
-        if ((rc = check_read_length(read_off, r)) != SBWTGPU_OK) return rc;
-    const int64_t base0 = read_off[0], total = read_off[n_reads] - base0;
-    if (total == 0) return SBWTGPU_OK;
-    if (!bases || !len) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    DeviceGuard guard(idx->device);
-    // [bases][read_off][len][first][second][workspace], every part 256-byte aligned
-    const size_t o_off = align256((size_t)total + 8), o_len = o_off + align256((size_t)(n_reads + 1) * 8),
-                 o_f = o_len + align256((size_t)total), o_s = o_f + (first ? align256((size_t)total * 8) : 0),
-                 o_ws = o_s + (first ? align256((size_t)total * 8) : 0);
-    const int64_t ws_bytes = sbwtgpu_ms_workspace_bytes(total);
-    Staging sg;
-    STG_TRY(sg.open(idx->device, o_ws + (size_t)ws_bytes));
-    STG_TRY(sg.in(0, bases + base0, (size_t)total));
-    STG_TRY(sg.in_rebased(o_off, read_off, n_reads + 1));
-    STG_TRY(sg.upload());
-    STG_TRY(sbwtgpu_matching_statistics_dev(idx, sg.at<const char>(0), total, sg.at<const int64_t>(o_off), n_reads, sg.at<uint8_t>(o_len),
-                                            first ? sg.at<int64_t>(o_f) : nullptr, first ? sg.at<int64_t>(o_s) : nullptr,
-                                            sg.at<char>(o_ws), ws_bytes, sg.stream));
-    STG_TRY(sg.out(o_len, len + base0, (size_t)total));
-    if (first) {
-        STG_TRY(sg.out(o_f, first + base0, (size_t)total * 8));
-        STG_TRY(sg.out(o_s, second + base0, (size_t)total * 8));
-    }
-    return sg.finish();
-}
-
-// ---- unitigs (sbwt_unitigs.hip) ---------------------------------------------------------------------
-struct sbwtgpu_unitigs {
-    int device = 0;
-    int64_t k = 0;
-    SbwtUnitigRun run;
-    // a coloured handle (sbwtgpu_unitigs_create_colored): what its colour-set object said of itself
-    bool colored = false;
-    int64_t n_sets = 0;
-    int n_colors = 0;
-    // a graph handle (sbwtgpu_unitigs_create_graph): the SBWTGPU_UNITIGS_* flags it was made with, and what locate checks against
-    unsigned graph = 0;
-    int64_t n_nodes = 0;
-    // the walks' start bitmap (sbwtgpu_unitigs_walks_prepare): one bit per column, made once from the
-    // column map under the mutex and then only read
-    mutable std::mutex walks_mutex;
-    mutable std::atomic<unsigned long long *> d_walk_start{nullptr};
-};
-
-// the plain call, or with a colour view (ids, table, words) the coloured one; graph: SBWTGPU_UNITIGS_* flags
-static int unitigs_create_common(const sbwtgpu_index *idx, const unsigned *d_ids, const unsigned long long *d_table, int words,
-                                 int64_t n_sets, int n_colors, unsigned graph, sbwtgpu_unitigs **out) {
-    if (idx->h.rank_only) return fail(SBWTGPU_ERR_INVALID_ARG, "%s", RANK_ONLY_MSG);
-    if (idx->h.k < 2) return fail(SBWTGPU_ERR_INVALID_ARG, "unitigs need k >= 2");
-    if (idx->h.n_nodes >= ((int64_t)1 << 32) - ((int64_t)1 << 24))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "unitigs: columns are 32-bit unsigned values (%lld columns)", (long long)idx->h.n_nodes);
-    DeviceGuard guard(idx->device);
-    sbwtgpu_unitigs *u = new (std::nothrow) sbwtgpu_unitigs();
-    if (!u) return fail(SBWTGPU_ERR_OOM, "out of host memory");
-    u->device = idx->device;
-    u->k = idx->h.k;
-    u->colored = d_ids != nullptr;
-    u->n_sets = n_sets;
-    u->n_colors = n_colors;
-    u->graph = graph;
-    u->n_nodes = idx->h.n_nodes;
-    DevBuf scratch;
-    Stream st;
-    hipError_t e = scratch.alloc((size_t)sbwt_unitigs_scratch_bytes(idx->h.n_nodes));
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e == hipSuccess)
-        e = sbwt_unitigs_run(idx->view(), idx->h.has_ssup || idx->h.ssup_derived, scratch.p, &u->run, st.s, d_ids, d_table, words,
-                             graph);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        delete u;
-        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "unitigs: %s", hipGetErrorString(e));
-    }
-    const int64_t nk = u->run.total_bases - u->run.n_unitigs * (u->k - 1);
-    if (idx->h.n_kmers > 0 && nk != idx->h.n_kmers) {
-        sbwtgpu_unitigs_destroy(u);
-        return fail(SBWTGPU_ERR_INVALID_ARG, "unitigs: the index has %lld real columns, its n_kmers says %lld", (long long)nk,
-                    (long long)idx->h.n_kmers);
-    }
-    *out = u;
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_unitigs_create(const sbwtgpu_index *idx, sbwtgpu_unitigs **out) {
-    if (!idx || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    return unitigs_create_common(idx, nullptr, nullptr, 0, 0, 0, 0u, out);
-}
-
-void sbwtgpu_unitigs_destroy(sbwtgpu_unitigs *u) {
-    if (!u) return;
-    DeviceGuard guard(u->device);
-    if (u->run.d_bases) (void)hipFree(u->run.d_bases);
-    if (u->run.d_off) (void)hipFree(u->run.d_off);
-    if (u->run.d_first_col) (void)hipFree(u->run.d_first_col);
-    if (u->run.d_set_id) (void)hipFree(u->run.d_set_id);
-    if (u->run.d_link_off) (void)hipFree(u->run.d_link_off);
-    if (u->run.d_link_to) (void)hipFree(u->run.d_link_to);
-    if (u->run.d_col_unitig) (void)hipFree(u->run.d_col_unitig);
-    if (u->run.d_col_offset) (void)hipFree(u->run.d_col_offset);
-    if (u->d_walk_start.load()) (void)hipFree(u->d_walk_start.load());
-    delete u;
-}
-
-int sbwtgpu_unitigs_info(const sbwtgpu_unitigs *u, int64_t *n_unitigs, int64_t *total_bases, int64_t *n_kmers) {
-    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    if (n_unitigs) *n_unitigs = u->run.n_unitigs;
-    if (total_bases) *total_bases = u->run.total_bases;
-    if (n_kmers) *n_kmers = u->run.total_bases - u->run.n_unitigs * (u->k - 1);
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_unitigs_dev(const sbwtgpu_unitigs *u, const char **d_bases, const int64_t **d_off, const int64_t **d_first_col) {
-    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    if (d_bases) *d_bases = u->run.d_bases;
-    if (d_off) *d_off = reinterpret_cast<const int64_t *>(u->run.d_off);
-    if (d_first_col) *d_first_col = reinterpret_cast<const int64_t *>(u->run.d_first_col);
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_unitigs_copy(const sbwtgpu_unitigs *u, char *bases, int64_t *off, int64_t *first_col) {
-    if (!u || !off || (!bases && u->run.total_bases > 0)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    DeviceGuard guard(u->device);
-    if (u->run.total_bases > 0) HIP_TRY(hipMemcpy(bases, u->run.d_bases, (size_t)u->run.total_bases, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(off, u->run.d_off, (size_t)(u->run.n_unitigs + 1) * 8, hipMemcpyDeviceToHost));
-    if (first_col && u->run.n_unitigs > 0)
-        HIP_TRY(hipMemcpy(first_col, u->run.d_first_col, (size_t)u->run.n_unitigs * 8, hipMemcpyDeviceToHost));
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_unitigs_stats(const sbwtgpu_unitigs *u, double pass_ms[6], int64_t *jump_rounds) {
-    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    if (pass_ms)
-        for (int i = 0; i < SBWT_UT_N_PASSES; i++) pass_ms[i] = (double)u->run.ms[i];
-    if (jump_rounds) *jump_rounds = u->run.jump_rounds;
-    return SBWTGPU_OK;
-}
-
-static int unitigs_check_colored(const sbwtgpu_unitigs *u) {
-    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    if (!u->colored)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "unitigs: a handle of sbwtgpu_unitigs_create carries no colours (sbwtgpu_unitigs_create_colored does)");
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_unitigs_set_ids_dev(const sbwtgpu_unitigs *u, const uint32_t **d_set_id) {
-    const int rc = unitigs_check_colored(u);
-    if (rc != SBWTGPU_OK) return rc;
-    if (!d_set_id) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *d_set_id = reinterpret_cast<const uint32_t *>(u->run.d_set_id);
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_unitigs_set_ids_copy(const sbwtgpu_unitigs *u, uint32_t *set_id) {
-    const int rc = unitigs_check_colored(u);
-    if (rc != SBWTGPU_OK) return rc;
-    if (!set_id && u->run.n_unitigs > 0) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    DeviceGuard guard(u->device);
-    if (u->run.n_unitigs > 0) HIP_TRY(hipMemcpy(set_id, u->run.d_set_id, (size_t)u->run.n_unitigs * 4, hipMemcpyDeviceToHost));
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_unitigs_color_info(const sbwtgpu_unitigs *u, int64_t *n_color_breaks, int64_t *n_sets, int32_t *n_colors) {
-    const int rc = unitigs_check_colored(u);
-    if (rc != SBWTGPU_OK) return rc;
-    if (n_color_breaks) *n_color_breaks = u->run.n_color_breaks;
-    if (n_sets) *n_sets = u->n_sets;
-    if (n_colors) *n_colors = u->n_colors;
-    return SBWTGPU_OK;
-}
-
-// ---- the unitig graph: links, column map, locate (sbwtgpu_unitigs_create_graph is with the colour sets) ----
-static int unitigs_check_graph(const sbwtgpu_unitigs *u, unsigned need, const char *what) {
-    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    if (!(u->graph & need))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "unitigs: the handle was made without %s (sbwtgpu_unitigs_create_graph takes the flag)", what);
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_unitigs_links_info(const sbwtgpu_unitigs *u, int64_t *n_links) {
-    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_LINKS, "SBWTGPU_UNITIGS_LINKS");
-    if (rc != SBWTGPU_OK) return rc;
-    if (!n_links) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *n_links = u->run.n_links;
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_unitigs_links_dev(const sbwtgpu_unitigs *u, const int64_t **d_link_off, const uint32_t **d_link_to) {
-    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_LINKS, "SBWTGPU_UNITIGS_LINKS");
-    if (rc != SBWTGPU_OK) return rc;
-    if (!d_link_off || !d_link_to) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *d_link_off = reinterpret_cast<const int64_t *>(u->run.d_link_off);
-    *d_link_to = reinterpret_cast<const uint32_t *>(u->run.d_link_to);
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_unitigs_links_copy(const sbwtgpu_unitigs *u, int64_t *link_off, uint32_t *link_to) {
-    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_LINKS, "SBWTGPU_UNITIGS_LINKS");
-    if (rc != SBWTGPU_OK) return rc;
-    if (!link_off || (!link_to && u->run.n_links > 0)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    DeviceGuard guard(u->device);
-    HIP_TRY(hipMemcpy(link_off, u->run.d_link_off, (size_t)(u->run.n_unitigs + 1) * 8, hipMemcpyDeviceToHost));
-    if (u->run.n_links > 0) HIP_TRY(hipMemcpy(link_to, u->run.d_link_to, (size_t)u->run.n_links * 4, hipMemcpyDeviceToHost));
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_unitigs_column_map_dev(const sbwtgpu_unitigs *u, const uint32_t **d_col_unitig, const uint32_t **d_col_offset) {
-    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_COLUMN_MAP, "SBWTGPU_UNITIGS_COLUMN_MAP");
-    if (rc != SBWTGPU_OK) return rc;
-    if (!d_col_unitig || !d_col_offset) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *d_col_unitig = reinterpret_cast<const uint32_t *>(u->run.d_col_unitig);
-    *d_col_offset = reinterpret_cast<const uint32_t *>(u->run.d_col_offset);
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_unitigs_column_map_copy(const sbwtgpu_unitigs *u, uint32_t *col_unitig, uint32_t *col_offset) {
-    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_COLUMN_MAP, "SBWTGPU_UNITIGS_COLUMN_MAP");
-    if (rc != SBWTGPU_OK) return rc;
-    if (!col_unitig || !col_offset) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    DeviceGuard guard(u->device);
-    HIP_TRY(hipMemcpy(col_unitig, u->run.d_col_unitig, (size_t)u->n_nodes * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(col_offset, u->run.d_col_offset, (size_t)u->n_nodes * 4, hipMemcpyDeviceToHost));
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_unitigs_locate_dev(const sbwtgpu_unitigs *u, const int64_t *d_cols, int64_t n, uint32_t *d_unitig, uint32_t *d_offset,
-                               void *stream) {
-    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_COLUMN_MAP, "SBWTGPU_UNITIGS_COLUMN_MAP");
-    if (rc != SBWTGPU_OK) return rc;
-    if (n < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative n");
-    if (n == 0) return SBWTGPU_OK;
-    if (!d_cols || !d_unitig || !d_offset) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    DeviceGuard guard(u->device);
-    HIP_TRY(sbwt_unitigs_locate(u->run.d_col_unitig, u->run.d_col_offset, u->n_nodes, reinterpret_cast<const long long *>(d_cols), n,
-                                d_unitig, d_offset, static_cast<hipStream_t>(stream)));
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_unitigs_locate_batch(const sbwtgpu_unitigs *u, const int64_t *cols, int64_t n, uint32_t *unitig, uint32_t *offset) {
-    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_COLUMN_MAP, "SBWTGPU_UNITIGS_COLUMN_MAP");
-    if (rc != SBWTGPU_OK) return rc;
-    if (n < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative n");
-    if (n == 0) return SBWTGPU_OK;
-    if (!cols || !unitig || !offset) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    DeviceGuard guard(u->device);
-    // [cols] in, [unitig][offset] back
-    const size_t o_u = align256((size_t)n * 8), o_o = o_u + align256((size_t)n * 4);
-    Staging sg;
-    STG_TRY(sg.open(u->device, o_o + (size_t)n * 4));
-    STG_TRY(sg.in(0, cols, (size_t)n * 8));
-    STG_TRY(sg.upload());
-    STG_TRY(sbwtgpu_unitigs_locate_dev(u, sg.at<const int64_t>(0), n, sg.at<uint32_t>(o_u), sg.at<uint32_t>(o_o), sg.stream));
-    STG_TRY(sg.out(o_u, unitig, (size_t)n * 4));
-    STG_TRY(sg.out(o_o, offset, (size_t)n * 4));
-    return sg.finish();
-}
-
-int sbwtgpu_unitigs_graph_stats(const sbwtgpu_unitigs *u, double *links_ms, double *map_ms) {
-    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    if (links_ms) *links_ms = (double)u->run.links_ms;
-    if (map_ms) *map_ms = (double)u->run.map_ms;
-    return SBWTGPU_OK;
-}
-
-// ---- per-read hit profiles (sbwt_readhits.hip) --------------------------------------------------------
-static_assert(sizeof(sbwtgpu_read_hits) == sizeof(SbwtReadHits), "the record of the ABI is the kernels' record");
-
-int64_t sbwtgpu_read_hits_workspace_bytes(int64_t total_bases, int64_t n_reads, int strands) {
-    if (total_bases < 0) total_bases = 0;
-    if (n_reads < 0) n_reads = 0;
-    return sbwt_rh_layout(sbwtgpu_search_workspace_bytes(total_bases), total_bases, n_reads, strands == 2 ? 2 : 1).total;
-}
-
-static int read_hits_check(const sbwtgpu_index *idx, int64_t n_reads, int strands) {
-    if (!idx) return fail(SBWTGPU_ERR_INVALID_ARG, "idx is NULL");
-    if (idx->h.rank_only) return fail(SBWTGPU_ERR_INVALID_ARG, "%s", RANK_ONLY_MSG);
-    if (strands != 1 && strands != 2) return fail(SBWTGPU_ERR_INVALID_ARG, "strands must be 1 (forward) or 2 (either strand), not %d", strands);
-    if (n_reads < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative n_reads");
-    if (n_reads >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_INVALID_ARG, "2^31 reads or more in one call: split the batch");
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_read_hits_dev(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
-                          int64_t n_reads, int strands, sbwtgpu_read_hits *d_out, void *d_ws, int64_t ws_bytes, void *stream) {
-    int rc = read_hits_check(idx, n_reads, strands);
-    if (rc != SBWTGPU_OK) return rc;
-    if (total_bases < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative size");
-    if (total_bases >= ((int64_t)1 << 36))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "more than 2^36 bases in one call: split the batch");
-    const int64_t need = sbwtgpu_read_hits_workspace_bytes(total_bases, n_reads, strands);
-    if (!d_ws || ws_bytes < need)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "workspace missing or too small (%lld < %lld)", (long long)ws_bytes, (long long)need);
-    if (((uintptr_t)d_ws & 15) != 0) return fail(SBWTGPU_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
-    if (n_reads == 0) return SBWTGPU_OK;
-    if (!d_read_off || !d_out || (total_bases > 0 && !d_bases)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
-    DeviceGuard guard(idx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t search_ws = sbwtgpu_search_workspace_bytes(total_bases);
-    const SbwtRhLayout L = sbwt_rh_layout(search_ws, total_bases, n_reads, strands);
-    char *w = static_cast<char *>(d_ws);
-    SbwtRhHeader *hdr = reinterpret_cast<SbwtRhHeader *>(w + L.hdr);
-    int64_t *res = reinterpret_cast<int64_t *>(w + L.res);
-    unsigned long long *bits = reinterpret_cast<unsigned long long *>(w + L.bits);
-    long long *ooff = reinterpret_cast<long long *>(w + L.ooff);
-    // int32 results where the index allows them: half the bytes written and read back ("read_hits_wide": tests of the other)
-    const int wide = (idx->h.n_nodes >= ((int64_t)1 << 31) || g_rh_wide) ? 1 : 0;
-    const int k = (int)idx->h.k;
-    HIP_TRY(hipMemsetAsync(hdr, 0, sizeof(SbwtRhHeader), st));
-    if (g_poison) HIP_TRY(hipMemsetAsync(d_out, 0xA5, (size_t)n_reads * sizeof(sbwtgpu_read_hits), st));
-    sbwt_launch_rh_offsets(reinterpret_cast<const long long *>(d_read_off), n_reads, k, reinterpret_cast<long long *>(w + L.cnt),
-                           reinterpret_cast<long long *>(w + L.bsum), ooff, st);
-    // (a batch of fewer than k bases has no window: nothing to search and no bit to write -- the reducer reads no word of
-    // the bit vector for a read without windows -- and the records are zeros)
-    const bool any = total_bases >= k;
-    const SbwtWorkHeader *sws = reinterpret_cast<const SbwtWorkHeader *>(w);
-    if (any) {
-        t_out32 = wide ? 0 : 1;
-        rc = search_dev_common(idx, d_bases, total_bases, d_read_off, n_reads, res, reinterpret_cast<const int64_t *>(ooff), d_ws,
-                               search_ws, stream, 0);
-        t_out32 = 0;
-        if (rc != SBWTGPU_OK) return rc;
-        sbwt_launch_rh_bits(res, wide, ooff, n_reads, total_bases, 0, bits, sws, hdr, st);
-    }
-    if (strands == 2 && any) {
-        char *rcb = w + L.rc;
-        long long *roff2 = reinterpret_cast<long long *>(w + L.roff2), *ooff2 = reinterpret_cast<long long *>(w + L.ooff2);
-        sbwt_launch_rh_mirror(d_bases, total_bases, reinterpret_cast<const long long *>(d_read_off), ooff, n_reads, rcb, roff2, ooff2, st);
-        t_out32 = wide ? 0 : 1;
-        rc = search_dev_common(idx, rcb, total_bases, reinterpret_cast<const int64_t *>(roff2), n_reads, res,
-                               reinterpret_cast<const int64_t *>(ooff2), d_ws, search_ws, stream, 0);
-        t_out32 = 0;
-        if (rc != SBWTGPU_OK) return rc;
-        sbwt_launch_rh_bits(res, wide, ooff, n_reads, total_bases, 1, bits, sws, hdr, st);
-    }
-    sbwt_launch_rh_reduce(bits, ooff, n_reads, k, g_rh_wave_min, reinterpret_cast<SbwtReadHits *>(d_out), st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-    return SBWTGPU_OK;
-}
-
-// Host buffers: the batch is cut into chunks of whole reads of at most "read_hits_chunk_bases" bases (a chunk always takes
-// one read), two chunks in flight on the parked slots of the search pipeline.  Bases and offsets go down, records come back.
-int sbwtgpu_read_hits_batch(const sbwtgpu_index *idx, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
-                            sbwtgpu_read_hits *out) {
-    int rc = read_hits_check(idx, n_reads, strands);
-    if (rc != SBWTGPU_OK) return rc;
-    if (n_reads == 0) return SBWTGPU_OK;
-    if (!read_off || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    if (read_off[n_reads] > read_off[0] && !bases) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    const int64_t budget = g_rh_chunk_bases > 0 ? g_rh_chunk_bases : (int64_t)64 << 20, CH_READS = (int64_t)1 << 24;
-    std::vector<int64_t> cuts{0};
-    int64_t max_bases = 0, max_reads = 0;
-    try {
-        for (int64_t lo = 0, r = 0; r < n_reads; r++) {
-            if ((rc = check_read_length(read_off, r)) != SBWTGPU_OK) return rc;
-            if (r > lo && (read_off[r + 1] - read_off[lo] > budget || r - lo >= CH_READS)) {
-                cuts.push_back(r);
-                lo = r;
-            }
-            max_bases = std::max(max_bases, read_off[r + 1] - read_off[lo]);
-            max_reads = std::max(max_reads, r + 1 - lo);
-        }
-        cuts.push_back(n_reads);
-    } catch (const std::bad_alloc &) {
-        return fail(SBWTGPU_ERR_OOM, "out of host memory");
-    }
-    const int64_t n_chunks = (int64_t)cuts.size() - 1;
-    const bool pin_in = is_pinned(bases), pin_out = is_pinned(out);
-    const int64_t ws_bytes = sbwtgpu_read_hits_workspace_bytes(max_bases, max_reads, strands);
-    const int64_t need_in = align256(max_bases + 16) + align256((max_reads + 1) * 8);
-    const int64_t need_out = pin_out ? 0 : align256(max_reads * 16);
-    const int64_t need_dev = align256(max_bases + 16) + align256((max_reads + 1) * 8) + align256(max_reads * 16) + align256(ws_bytes);
-    DeviceGuard guard(idx->device);
-    const int n_slots = n_chunks > 1 ? 2 : 1;
-    PipeSlot S[2];
-    if ((rc = take_slots(idx->device, S, n_slots, need_in, need_out, need_dev, "read-hits buffers")) != SBWTGPU_OK) return rc;
-    int bug = 0;                    // the first nonzero device status of a chunk
-    const int64_t o_roff = align256(max_bases + 16), o_rec = o_roff + align256((max_reads + 1) * 8), o_ws = o_rec + align256(max_reads * 16);
-    auto submit = [&](int64_t c) -> int {
-        PipeSlot &P = S[c % n_slots];
-        const int64_t lo = cuts[(size_t)c], hi = cuts[(size_t)c + 1], nr = hi - lo, nb = read_off[hi] - read_off[lo];
-        int64_t *hro = (int64_t *)(P.h_in + align256(max_bases + 16));
-        for (int64_t r = 0; r <= nr; r++) hro[r] = read_off[lo + r] - read_off[lo];
-        const char *hb = bases + read_off[lo];
-        if (!pin_in && nb > 0) { parallel_memcpy(P.h_in, hb, (size_t)nb); hb = P.h_in; }
-        hipError_t e;
-        if ((nb > 0 && (e = hipMemcpyAsync(P.d_mem, hb, (size_t)nb, hipMemcpyHostToDevice, P.st)) != hipSuccess) ||
-            (e = hipMemcpyAsync(P.d_mem + o_roff, hro, (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, P.st)) != hipSuccess)
-            return fail(SBWTGPU_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
-        const int r2 = sbwtgpu_read_hits_dev(idx, P.d_mem, nb, (const int64_t *)(P.d_mem + o_roff), nr, strands,
-                                             (sbwtgpu_read_hits *)(P.d_mem + o_rec), P.d_mem + o_ws, ws_bytes, P.st);
-        if (r2 != SBWTGPU_OK) return r2;
-        const SbwtRhLayout L = sbwt_rh_layout(sbwtgpu_search_workspace_bytes(nb), nb, nr, strands);
-        char *target = pin_out ? (char *)(out + lo) : P.h_out;
-        if ((e = hipMemcpyAsync(target, P.d_mem + o_rec, (size_t)nr * 16, hipMemcpyDeviceToHost, P.st)) != hipSuccess ||
-            (e = hipMemcpyAsync(P.h_status, P.d_mem + o_ws + L.hdr, 4, hipMemcpyDeviceToHost, P.st)) != hipSuccess)
-            return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
-        return SBWTGPU_OK;
-    };
-    auto collect = [&](int64_t c) -> int {
-        PipeSlot &P = S[c % n_slots];
-        hipError_t e = hipStreamSynchronize(P.st);
-        if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "stream synchronize: %s", hipGetErrorString(e));
-        if (P.h_status[0] != 0 && bug == 0) bug = P.h_status[0];
-        const int64_t lo = cuts[(size_t)c], hi = cuts[(size_t)c + 1];
-        if (!pin_out) memcpy(out + lo, P.h_out, (size_t)(hi - lo) * 16);
-        return SBWTGPU_OK;
-    };
-    rc = two_in_flight(n_chunks, submit, collect);
-    park_slots(idx->device, S, n_slots, rc);
-    if (rc != SBWTGPU_OK) return rc;
-    if (bug) return fail_status(bug);
-    return SBWTGPU_OK;
-}
-
-// ---- reads threaded through the unitig graph (sbwt_walks.hip) -----------------------
-static_assert(sizeof(sbwtgpu_walk_step) == sizeof(SbwtWalkStep), "the record of the ABI is the kernels' record");
-
-int sbwtgpu_unitigs_walks_prepare(sbwtgpu_unitigs *u) {
-    const int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_COLUMN_MAP, "SBWTGPU_UNITIGS_COLUMN_MAP");
-    if (rc != SBWTGPU_OK) return rc;
-    if (u->d_walk_start.load(std::memory_order_acquire)) return SBWTGPU_OK;
-    std::lock_guard<std::mutex> lock(u->walks_mutex);
-    if (u->d_walk_start.load(std::memory_order_acquire)) return SBWTGPU_OK;
-    DeviceGuard guard(u->device);
-    DevBuf bits;
-    Stream st;
-    hipError_t e = bits.alloc((size_t)((u->n_nodes + 63) / 64 + 1) * 8);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e == hipSuccess) {
-        sbwt_launch_walk_startbits(u->run.d_col_offset, u->n_nodes, static_cast<unsigned long long *>(bits.p), st.s);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st.s);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "walks: start bitmap: %s", hipGetErrorString(e));
-    }
-    u->d_walk_start.store(static_cast<unsigned long long *>(bits.p), std::memory_order_release);
-    bits.p = nullptr;
-    return SBWTGPU_OK;
-}
-
-int64_t sbwtgpu_unitigs_walks_workspace_bytes(int64_t total_bases, int64_t n_reads) {
-    if (total_bases < 0) total_bases = 0;
-    if (n_reads < 0) n_reads = 0;
-    return sbwt_walk_layout(sbwtgpu_search_workspace_bytes(total_bases), total_bases, n_reads).total;
-}
-
-static int walks_check(const sbwtgpu_index *idx, const sbwtgpu_unitigs *u, int64_t n_reads) {
-    if (!idx) return fail(SBWTGPU_ERR_INVALID_ARG, "idx is NULL");
-    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    // (the size first, as the colour layer does: an index of that size is refused for it whatever else is wrong with the call)
-    if (idx->h.n_nodes >= ((int64_t)1 << 31))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "walks: the index has %lld columns, the walks read int32 search results (fewer than 2^31 columns)",
-                    (long long)idx->h.n_nodes);
-    int rc = unitigs_check_graph(u, SBWTGPU_UNITIGS_COLUMN_MAP, "SBWTGPU_UNITIGS_COLUMN_MAP");
-    if (rc != SBWTGPU_OK) return rc;
-    if (idx->h.rank_only) return fail(SBWTGPU_ERR_INVALID_ARG, "%s", RANK_ONLY_MSG);
-    if (u->n_nodes != idx->h.n_nodes || u->k != idx->h.k || u->device != idx->device)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "walks: the handle (%lld columns, k = %lld, device %d) was not made from this index (%lld columns, k = %lld, device %d)",
-                    (long long)u->n_nodes, (long long)u->k, u->device, (long long)idx->h.n_nodes, (long long)idx->h.k, idx->device);
-    if (n_reads < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative n_reads");
-    if (n_reads >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_INVALID_ARG, "2^31 reads or more in one call: split the batch");
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_unitigs_walks_dev(const sbwtgpu_index *idx, const sbwtgpu_unitigs *u, const char *d_bases, int64_t total_bases,
-                              const int64_t *d_read_off, int64_t n_reads, int64_t *d_step_off, sbwtgpu_walk_step *d_steps,
-                              int64_t steps_cap, int64_t *d_unitig_kmers, void *d_ws, int64_t ws_bytes, void *stream) {
-    int rc = walks_check(idx, u, n_reads);
-    if (rc != SBWTGPU_OK) return rc;
-    if (steps_cap < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative steps_cap");
-    if (total_bases < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative size");
-    if (total_bases >= ((int64_t)1 << 36))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "more than 2^36 bases in one call: split the batch");
-    const unsigned long long *start = u->d_walk_start.load(std::memory_order_acquire);
-    if (!start)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "walks: the handle is not prepared (sbwtgpu_unitigs_walks_prepare builds its start bitmap)");
-    const int64_t need = sbwtgpu_unitigs_walks_workspace_bytes(total_bases, n_reads);
-    if (!d_ws || ws_bytes < need)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "workspace missing or too small (%lld < %lld)", (long long)ws_bytes, (long long)need);
-    if (((uintptr_t)d_ws & 15) != 0) return fail(SBWTGPU_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
-    if (!d_step_off || (steps_cap > 0 && !d_steps)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
-    DeviceGuard guard(idx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n_reads == 0) {
-        HIP_TRY(hipMemsetAsync(d_step_off, 0, 8, st));
-        return SBWTGPU_OK;
-    }
-    if (!d_read_off || (total_bases > 0 && !d_bases)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
-    const int64_t search_ws = sbwtgpu_search_workspace_bytes(total_bases);
-    const SbwtWalkLayout L = sbwt_walk_layout(search_ws, total_bases, n_reads);
-    char *w = static_cast<char *>(d_ws);
-    int32_t *res = reinterpret_cast<int32_t *>(w + L.res);
-    long long *ooff = reinterpret_cast<long long *>(w + L.ooff);
-    const int k = (int)idx->h.k;
-    sbwt_launch_rh_offsets(reinterpret_cast<const long long *>(d_read_off), n_reads, k, reinterpret_cast<long long *>(w + L.cnt),
-                           reinterpret_cast<long long *>(w + L.bsum), ooff, st);
-    // (a batch of fewer than k bases has no window: nothing to search, W = 0 and no pass below reads a result; the status
-    // word that sbwtgpu_workspace_status looks at is then cleared here)
-    if (total_bases >= k) {
-        rc = search_dev_i32(idx, d_bases, total_bases, d_read_off, n_reads, res, reinterpret_cast<const int64_t *>(ooff), d_ws, search_ws,
-                            stream, 0);
-        if (rc != SBWTGPU_OK) return rc;
-    } else {
-        HIP_TRY(hipMemsetAsync(d_ws, 0, sizeof(SbwtWorkHeader), st));
-    }
-    const hipError_t e = sbwt_launch_walks(res, ooff, n_reads, total_bases, start, u->run.d_col_unitig, u->run.d_col_offset, u->n_nodes, w, L,
-                                           reinterpret_cast<long long *>(d_step_off), reinterpret_cast<SbwtWalkStep *>(d_steps), steps_cap,
-                                           reinterpret_cast<long long *>(d_unitig_kmers), st);
-    if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "walks passes: %s", hipGetErrorString(e));
-    return SBWTGPU_OK;
-}
-
-// Host buffers: the batch is cut into chunks of whole reads of at most "walks_chunk_bases" bases (a chunk always takes one
-// read), one after the other on a parked slot of the search pipeline: a chunk's step count decides how many records come
-// back, so its offsets are read before its records are fetched.  step_off is stitched: a chunk's offsets plus the steps of
-// the chunks before it.
-int sbwtgpu_unitigs_walks_batch(const sbwtgpu_index *idx, const sbwtgpu_unitigs *u, const char *bases, const int64_t *read_off,
-                                int64_t n_reads, int64_t *step_off, sbwtgpu_walk_step **steps_out, int64_t *n_steps,
-                                int64_t *unitig_kmers) {
-    int rc = walks_check(idx, u, n_reads);
-    if (rc != SBWTGPU_OK) return rc;
-    if (!step_off || !steps_out || !n_steps) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *steps_out = nullptr;
-    *n_steps = 0;
-    step_off[0] = 0;
-    const int64_t n_unitigs = u->run.n_unitigs;
-    if (unitig_kmers && n_unitigs > 0) memset(unitig_kmers, 0, (size_t)n_unitigs * 8);
-    if (n_reads == 0) return SBWTGPU_OK;
-    if (!read_off) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    if (read_off[n_reads] > read_off[0] && !bases) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    if ((rc = sbwtgpu_unitigs_walks_prepare(const_cast<sbwtgpu_unitigs *>(u))) != SBWTGPU_OK) return rc;
-    const int64_t budget = g_wk_chunk_bases > 0 ? g_wk_chunk_bases : (int64_t)64 << 20, CH_READS = (int64_t)1 << 24, k = idx->h.k;
-    std::vector<int64_t> cuts{0};
-    int64_t max_bases = 0, max_reads = 0, max_windows = 0, windows = 0;
-    try {
-        for (int64_t lo = 0, r = 0; r < n_reads; r++) {
-            if ((rc = check_read_length(read_off, r)) != SBWTGPU_OK) return rc;
-            if (r > lo && (read_off[r + 1] - read_off[lo] > budget || r - lo >= CH_READS)) {
-                cuts.push_back(r);
-                lo = r;
-                windows = 0;
-            }
-            windows += std::max<int64_t>(0, read_off[r + 1] - read_off[r] - k + 1);
-            max_bases = std::max(max_bases, read_off[r + 1] - read_off[lo]);
-            max_reads = std::max(max_reads, r + 1 - lo);
-            max_windows = std::max(max_windows, windows);
-        }
-        cuts.push_back(n_reads);
-    } catch (const std::bad_alloc &) {
-        return fail(SBWTGPU_ERR_OOM, "out of host memory");
-    }
-    const int64_t n_chunks = (int64_t)cuts.size() - 1;
-    const bool pin_in = is_pinned(bases);
-    const int64_t ws_bytes = sbwtgpu_unitigs_walks_workspace_bytes(max_bases, max_reads);
-    // device: [bases][read_off][step_off][coverage][steps][workspace]; pinned: bases and offsets down, step_off (and coverage) back
-    const int64_t o_roff = align256(max_bases + 16), o_soff = o_roff + align256((max_reads + 1) * 8),
-                  o_cov = o_soff + align256((max_reads + 1) * 8), o_steps = o_cov + (unitig_kmers ? align256(n_unitigs * 8 + 8) : 0),
-                  o_ws = o_steps + align256(max_windows * 16 + 16), need_dev = o_ws + align256(ws_bytes);
-    const int64_t need_in = o_soff, need_out = align256((max_reads + 1) * 8);
-    DeviceGuard guard(idx->device);
-    PipeSlot S[1];
-    if ((rc = take_slots(idx->device, S, 1, need_in, need_out, need_dev, "walks buffers")) != SBWTGPU_OK) return rc;
-    PipeSlot &P = S[0];
-    int bug = 0;                    // the first nonzero device status of a chunk
-    sbwtgpu_walk_step *steps = nullptr;
-    int64_t total = 0, cap = 0;
-    auto run = [&]() -> int {
-        hipError_t e;
-        if (unitig_kmers && n_unitigs > 0 && (e = hipMemsetAsync(P.d_mem + o_cov, 0, (size_t)n_unitigs * 8, P.st)) != hipSuccess)
-            return fail(SBWTGPU_ERR_HIP, "memset: %s", hipGetErrorString(e));
-        for (int64_t c = 0; c < n_chunks; c++) {
-            const int64_t lo = cuts[(size_t)c], hi = cuts[(size_t)c + 1], nr = hi - lo, nb = read_off[hi] - read_off[lo];
-            int64_t *hro = (int64_t *)(P.h_in + o_roff);
-            for (int64_t r = 0; r <= nr; r++) hro[r] = read_off[lo + r] - read_off[lo];
-            const char *hb = bases + read_off[lo];
-            if (!pin_in && nb > 0) { parallel_memcpy(P.h_in, hb, (size_t)nb); hb = P.h_in; }
-            if ((nb > 0 && (e = hipMemcpyAsync(P.d_mem, hb, (size_t)nb, hipMemcpyHostToDevice, P.st)) != hipSuccess) ||
-                (e = hipMemcpyAsync(P.d_mem + o_roff, hro, (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, P.st)) != hipSuccess)
-                return fail(SBWTGPU_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
-            const int r2 = sbwtgpu_unitigs_walks_dev(idx, u, P.d_mem, nb, (const int64_t *)(P.d_mem + o_roff), nr, (int64_t *)(P.d_mem + o_soff),
-                                                     (sbwtgpu_walk_step *)(P.d_mem + o_steps), max_windows,
-                                                     unitig_kmers ? (int64_t *)(P.d_mem + o_cov) : nullptr, P.d_mem + o_ws, ws_bytes, P.st);
-            if (r2 != SBWTGPU_OK) return r2;
-            if ((e = hipMemcpyAsync(P.h_out, P.d_mem + o_soff, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, P.st)) != hipSuccess ||
-                (e = hipMemcpyAsync(P.h_status, P.d_mem + o_ws + offsetof(SbwtWorkHeader, status), 4, hipMemcpyDeviceToHost, P.st)) != hipSuccess ||
-                (e = hipStreamSynchronize(P.st)) != hipSuccess)
-                return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
-            if (P.h_status[0] != 0 && bug == 0) bug = P.h_status[0];
-            const int64_t *so = (const int64_t *)P.h_out, ns = so[nr];
-            for (int64_t r = 1; r <= nr; r++) step_off[lo + r] = total + so[r];
-            if (ns > 0) {
-                if (total + ns > cap) {
-                    const int64_t want = std::max(total + ns, cap + cap / 2);
-                    void *q = realloc(steps, (size_t)want * sizeof(sbwtgpu_walk_step));
-                    if (!q) return fail(SBWTGPU_ERR_OOM, "out of host memory");
-                    steps = static_cast<sbwtgpu_walk_step *>(q);
-                    cap = want;
-                }
-                if ((e = hipMemcpyAsync(steps + total, P.d_mem + o_steps, (size_t)ns * sizeof(sbwtgpu_walk_step), hipMemcpyDeviceToHost, P.st)) != hipSuccess ||
-                    (e = hipStreamSynchronize(P.st)) != hipSuccess)
-                    return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
-                total += ns;
-            }
-        }
-        if (unitig_kmers && n_unitigs > 0 &&
-            ((e = hipMemcpyAsync(unitig_kmers, P.d_mem + o_cov, (size_t)n_unitigs * 8, hipMemcpyDeviceToHost, P.st)) != hipSuccess ||
-             (e = hipStreamSynchronize(P.st)) != hipSuccess))
-            return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
-        return SBWTGPU_OK;
-    };
-    rc = run();
-    park_slots(idx->device, S, 1, rc);
-    if (rc == SBWTGPU_OK && bug) rc = fail_status(bug);
-    if (rc != SBWTGPU_OK) {
-        free(steps);
-        return rc;
-    }
-    *steps_out = steps;
-    *n_steps = total;
-    return SBWTGPU_OK;
-}
-
-// ---- colours and pseudoalignment (sbwt_colors.hip) ----------------------------------------------------
-static_assert(sizeof(sbwtgpu_pseudoalignment) == sizeof(SbwtPseudoalignment), "the record of the ABI is the kernels' record");
-static_assert(sizeof(sbwtgpu_read_found) == sizeof(SbwtReadFound), "the wide record of the ABI is the kernels' record");
-
-struct sbwtgpu_colors {
-    const sbwtgpu_index *idx = nullptr;
-    int device = 0;
-    int64_t n_nodes = 0, k = 0;
-    int n_colors = 0;
-    int words = 1;                      // 64-bit words per row: ceil(n_colors / 64)
-    unsigned long long *d_rows = nullptr;
-};
-// deduplicated colour sets (sbwt_colorsets.hip): `base` binds the object to its index as a colours object is bound (no rows)
-struct sbwtgpu_colorsets {
-    sbwtgpu_colors base;
-    int64_t n_sets = 0, n_colored = 0;
-    unsigned *d_ids = nullptr;
-    unsigned long long *d_table = nullptr;
-};
-
-// a colour-set builder (sbwt_colorsets.hip, "the builder"): `base` binds it to its index; a colour is new, open or closed
-struct sbwtgpu_colorsets_builder {
-    sbwtgpu_colors base;
-    SbwtCsbState st;
-    Stream stream;                      // of the closes and of finish, for the builder's life: a stream costs milliseconds to make
-    std::vector<unsigned char> state;   // per colour: CSB_NEW, CSB_OPEN, CSB_CLOSED
-    std::vector<int64_t> per_color;     // the columns marked when the colour was closed
-    int open = -1;                      // the open colour, or -1
-    bool finished = false, broken = false;
-};
-enum { CSB_NEW = 0, CSB_OPEN = 1, CSB_CLOSED = 2 };
-
-static int colors_check_index(const sbwtgpu_index *idx) {
-    if (idx->h.n_nodes >= ((int64_t)1 << 31))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "colours: the index has %lld columns, the colour layer reads int32 search results (fewer than 2^31 columns)",
-                    (long long)idx->h.n_nodes);
-    if (idx->h.rank_only) return fail(SBWTGPU_ERR_INVALID_ARG, "%s", RANK_ONLY_MSG);
-    return SBWTGPU_OK;
-}
-// the object and the index it was made for still agree (a colours object is bound to its index at creation)
-static int colors_check(const sbwtgpu_colors *c) {
-    if (!c || !c->idx) return fail(SBWTGPU_ERR_INVALID_ARG, "colours object is NULL");
-    if (c->idx->h.n_nodes != c->n_nodes || c->idx->h.k != c->k)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "colours of %lld columns at k = %lld used with an index of %lld columns at k = %lld",
-                    (long long)c->n_nodes, (long long)c->k, (long long)c->idx->h.n_nodes, (long long)c->idx->h.k);
-    return colors_check_index(c->idx);
-}
-static int colors_check_batch(int64_t n_reads, int strands) {
-    if (strands != 1 && strands != 2) return fail(SBWTGPU_ERR_INVALID_ARG, "strands must be 1 (forward) or 2 (either strand), not %d", strands);
-    if (n_reads < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative n_reads");
-    if (n_reads >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_INVALID_ARG, "2^31 reads or more in one call: split the batch");
-    return SBWTGPU_OK;
-}
-static int colors_check_query(int threshold_ppm, int denominator) {
-    if (threshold_ppm < 1 || threshold_ppm > 1000000)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "threshold_ppm must be in 1 .. 1000000, not %d", threshold_ppm);
-    if (denominator != 0 && denominator != 1)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "denominator must be 0 (the found k-mers) or 1 (all k-mers), not %d", denominator);
-    return SBWTGPU_OK;
-}
-
-// what both creates do once n_colors has passed their own bound
-static int colors_create_checked(const sbwtgpu_index *idx, int n_colors, const uint64_t *rows_or_null, sbwtgpu_colors **out) {
-    DeviceGuard guard(idx->device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", idx->device);
-    sbwtgpu_colors *c = new (std::nothrow) sbwtgpu_colors();
-    if (!c) return fail(SBWTGPU_ERR_OOM, "out of host memory");
-    c->idx = idx;
-    c->device = idx->device;
-    c->n_nodes = idx->h.n_nodes;
-    c->k = idx->h.k;
-    c->n_colors = n_colors;
-    c->words = (n_colors + 63) / 64;
-    const size_t bytes = (size_t)c->n_nodes * (size_t)c->words * 8;
-    Stream st;
-    hipError_t e = hipMalloc((void **)&c->d_rows, bytes ? bytes : 16);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e == hipSuccess && !rows_or_null) e = hipMemsetAsync(c->d_rows, 0, bytes, st.s);
-    if (e == hipSuccess && rows_or_null) e = hipMemcpyAsync(c->d_rows, rows_or_null, bytes, hipMemcpyHostToDevice, st.s);
-    if (e == hipSuccess) e = rows_or_null ? sbwt_colors_clean(idx->view(), c->d_rows, n_colors, st.s) : hipStreamSynchronize(st.s);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        sbwtgpu_colors_destroy(c);
-        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "colours: %s", hipGetErrorString(e));
-    }
-    *out = c;
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_colors_create(const sbwtgpu_index *idx, int n_colors, const uint64_t *rows_or_null, sbwtgpu_colors **out) {
-    if (!idx || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    int rc = colors_check_index(idx);
-    if (rc != SBWTGPU_OK) return rc;
-    if (n_colors < 1 || n_colors > 64)
-        return fail(SBWTGPU_ERR_INVALID_ARG,
-                    "n_colors must be in 1 .. 64, not %d (more than 64 colours are out of scope here: sbwtgpu_colors_create_wide takes up to %d)",
-                    n_colors, SBWTGPU_MAX_COLORS);
-    return colors_create_checked(idx, n_colors, rows_or_null, out);
-}
-
-int sbwtgpu_colors_create_wide(const sbwtgpu_index *idx, int n_colors, const uint64_t *rows_or_null, sbwtgpu_colors **out) {
-    if (!idx || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    int rc = colors_check_index(idx);
-    if (rc != SBWTGPU_OK) return rc;
-    if (n_colors < 1 || n_colors > SBWTGPU_MAX_COLORS)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "n_colors must be in 1 .. %d, not %d", SBWTGPU_MAX_COLORS, n_colors);
-    return colors_create_checked(idx, n_colors, rows_or_null, out);
-}
-
-int sbwtgpu_colors_words(const sbwtgpu_colors *c) { return c ? c->words : 0; }
-
-void sbwtgpu_colors_destroy(sbwtgpu_colors *c) {
-    if (!c) return;
-    DeviceGuard guard(c->device);
-    if (c->d_rows) (void)hipFree(c->d_rows);
-    delete c;
-}
-
-// h: 64 words + 1 entries -- the coloured columns per colour, then those of any colour
-static int colors_stats(const sbwtgpu_colors *c, unsigned long long *h) {
-    const size_t bytes = ((size_t)c->words * 64 + 1) * 8;
-    DeviceGuard guard(c->device);
-    DevBuf stats;
-    Stream st;
-    HIP_TRY(stats.alloc(bytes));
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    HIP_TRY(hipMemsetAsync(stats.p, 0, bytes, st.s));
-    sbwt_launch_col_stats(c->d_rows, c->n_nodes, c->words, static_cast<unsigned long long *>(stats.p), st.s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h, stats.p, bytes, hipMemcpyDeviceToHost, st.s));
-    HIP_TRY(hipStreamSynchronize(st.s));
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_colors_info(const sbwtgpu_colors *c, sbwtgpu_colors_info_t *info) {
-    if (!c || !info) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    memset(info, 0, sizeof(*info));
-    if (c->n_colors > 64)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "the colours object has %d colours, sbwtgpu_colors_info_t holds 64: use sbwtgpu_colors_info_wide",
-                    c->n_colors);
-    info->n_columns = c->n_nodes;
-    info->k = c->k;
-    info->n_colors = c->n_colors;
-    unsigned long long h[65];
-    const int rc = colors_stats(c, h);
-    if (rc != SBWTGPU_OK) return rc;
-    for (int i = 0; i < 64; i++) info->per_color[i] = (int64_t)h[i];
-    info->n_colored_columns = (int64_t)h[64];
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_colors_info_wide(const sbwtgpu_colors *c, int64_t *n_columns, int64_t *k, int32_t *n_colors, int64_t *n_colored_columns,
-                             int64_t *per_color) {
-    if (!c) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    if (n_columns) *n_columns = c->n_nodes;
-    if (k) *k = c->k;
-    if (n_colors) *n_colors = c->n_colors;
-    if (!n_colored_columns && !per_color) return SBWTGPU_OK;
-    unsigned long long h[SBWTGPU_MAX_COLORS + 1];
-    const int rc = colors_stats(c, h);
-    if (rc != SBWTGPU_OK) return rc;
-    if (per_color)
-        for (int i = 0; i < c->n_colors; i++) per_color[i] = (int64_t)h[i];
-    if (n_colored_columns) *n_colored_columns = (int64_t)h[(size_t)c->words * 64];
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_colors_copy(const sbwtgpu_colors *c, uint64_t *rows_out) {
-    if (!c || !rows_out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    DeviceGuard guard(c->device);
-    HIP_TRY(hipMemcpy(rows_out, c->d_rows, (size_t)c->n_nodes * (size_t)c->words * 8, hipMemcpyDeviceToHost));
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_colors_dev(const sbwtgpu_colors *c, const uint64_t **d_rows) {
-    if (!c || !d_rows) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *d_rows = reinterpret_cast<const uint64_t *>(c->d_rows);
-    return SBWTGPU_OK;
-}
-
-int64_t sbwtgpu_pseudoalign_workspace_bytes(int64_t total_bases, int64_t n_reads, int strands) {
-    if (total_bases < 0) total_bases = 0;
-    if (n_reads < 0) n_reads = 0;
-    return sbwt_pa_layout(sbwtgpu_search_workspace_bytes(total_bases), total_bases, n_reads, strands == 2 ? 2 : 1).total;
-}
-
-// What colouring and the query share: the result offsets, the int32 search of the batch and, for two strands, of the mirrored
-// batch into the second result buffer; `tail` enqueues what turns the results into bits or records (res2: NULL with one strand,
-// and for a batch without any window, whose result buffers nobody wrote).
-}  // extern "C"
-template <typename Tail>
-static int colors_dev_common(const sbwtgpu_colors *c, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
-                             int64_t n_reads, int strands, void *d_ws, int64_t ws_bytes, void *stream, Tail tail) {
-    if (total_bases < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative size");
-    if (total_bases >= ((int64_t)1 << 36))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "more than 2^36 bases in one call: split the batch");
-    const int64_t need = sbwtgpu_pseudoalign_workspace_bytes(total_bases, n_reads, strands);
-    if (!d_ws || ws_bytes < need)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "workspace missing or too small (%lld < %lld)", (long long)ws_bytes, (long long)need);
-    if (((uintptr_t)d_ws & 15) != 0) return fail(SBWTGPU_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
-    if (n_reads == 0) return SBWTGPU_OK;
-    if (!d_read_off || (total_bases > 0 && !d_bases)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
-    const sbwtgpu_index *idx = c->idx;
-    DeviceGuard guard(idx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t search_ws = sbwtgpu_search_workspace_bytes(total_bases);
-    const SbwtPaLayout L = sbwt_pa_layout(search_ws, total_bases, n_reads, strands);
-    char *w = static_cast<char *>(d_ws);
-    SbwtPaHeader *hdr = reinterpret_cast<SbwtPaHeader *>(w + L.hdr);
-    int *res = reinterpret_cast<int *>(w + L.res);
-    long long *ooff = reinterpret_cast<long long *>(w + L.ooff);
-    const int k = (int)idx->h.k;
-    HIP_TRY(hipMemsetAsync(hdr, 0, sizeof(SbwtPaHeader), st));
-    sbwt_launch_rh_offsets(reinterpret_cast<const long long *>(d_read_off), n_reads, k, reinterpret_cast<long long *>(w + L.cnt),
-                           reinterpret_cast<long long *>(w + L.bsum), ooff, st);
-    // (a batch of fewer than k bases has no window: nothing to search, and `tail` reads no result)
-    const bool any = total_bases >= k;
-    const SbwtWorkHeader *sws = reinterpret_cast<const SbwtWorkHeader *>(w);
-    int *res2 = nullptr;
-    int rc;
-    if (any) {
-        t_out32 = 1;
-        rc = search_dev_common(idx, d_bases, total_bases, d_read_off, n_reads, reinterpret_cast<int64_t *>(res),
-                               reinterpret_cast<const int64_t *>(ooff), d_ws, search_ws, stream, 0);
-        t_out32 = 0;
-        if (rc != SBWTGPU_OK) return rc;
-        sbwt_launch_pa_note_status(sws, hdr, st);
-    }
-    if (strands == 2 && any) {
-        res2 = reinterpret_cast<int *>(w + L.res2);
-        char *rcb = w + L.rc;
-        long long *roff2 = reinterpret_cast<long long *>(w + L.roff2), *ooff2 = reinterpret_cast<long long *>(w + L.ooff2);
-        sbwt_launch_rh_mirror(d_bases, total_bases, reinterpret_cast<const long long *>(d_read_off), ooff, n_reads, rcb, roff2, ooff2, st);
-        t_out32 = 1;
-        rc = search_dev_common(idx, rcb, total_bases, reinterpret_cast<const int64_t *>(roff2), n_reads, reinterpret_cast<int64_t *>(res2),
-                               reinterpret_cast<const int64_t *>(ooff2), d_ws, search_ws, stream, 0);
-        t_out32 = 0;
-        if (rc != SBWTGPU_OK) return rc;
-        sbwt_launch_pa_note_status(sws, hdr, st);
-    }
-    tail(res, res2, ooff, hdr, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-    return SBWTGPU_OK;
-}
-extern "C" {
-
-int sbwtgpu_pseudoalign_dev(const sbwtgpu_colors *c, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
-                            int64_t n_reads, int strands, int threshold_ppm, int denominator, sbwtgpu_pseudoalignment *d_out,
-                            int32_t *d_counts_or_null, void *d_ws, int64_t ws_bytes, void *stream) {
-    int rc = colors_check(c);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
-    if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
-    if (rc != SBWTGPU_OK) return rc;
-    if (c->n_colors > 64)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "the colours object has %d colours, a 16-byte record holds 64: use sbwtgpu_pseudoalign_wide_dev",
-                    c->n_colors);
-    if (n_reads > 0 && !d_out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
-    return colors_dev_common(c, d_bases, total_bases, d_read_off, n_reads, strands, d_ws, ws_bytes, stream,
-                             [&](const int *res, const int *res2, const long long *ooff, SbwtPaHeader *, hipStream_t st) {
-                                 sbwt_launch_pa_reduce(res, res2, ooff, n_reads, c->d_rows, c->n_nodes, c->n_colors, threshold_ppm,
-                                                       denominator, reinterpret_cast<SbwtPseudoalignment *>(d_out), d_counts_or_null, st);
-                             });
-}
-
-int sbwtgpu_pseudoalign_wide_dev(const sbwtgpu_colors *c, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
-                                 int64_t n_reads, int strands, int threshold_ppm, int denominator, sbwtgpu_read_found *d_out,
-                                 uint64_t *d_colors, int32_t *d_counts_or_null, void *d_ws, int64_t ws_bytes, void *stream) {
-    int rc = colors_check(c);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
-    if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
-    if (rc != SBWTGPU_OK) return rc;
-    if (n_reads > 0 && (!d_out || !d_colors)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
-    return colors_dev_common(c, d_bases, total_bases, d_read_off, n_reads, strands, d_ws, ws_bytes, stream,
-                             [&](const int *res, const int *res2, const long long *ooff, SbwtPaHeader *, hipStream_t st) {
-                                 sbwt_launch_pa_reduce_wide(res, res2, ooff, n_reads, c->d_rows, c->n_nodes, c->words, c->n_colors,
-                                                            threshold_ppm, denominator, reinterpret_cast<SbwtReadFound *>(d_out),
-                                                            reinterpret_cast<unsigned long long *>(d_colors), d_counts_or_null, st);
-                             });
-}
-
-// Host buffers, for colouring (out == NULL: bit `color` is set, *n_hit the windows with a hit) and for the query alike: the batch
-// is cut into chunks of whole reads of at most "pseudoalign_chunk_bases" bases (a chunk always takes one read), two chunks in
-// flight on the parked slots of the search pipeline.  Bases and offsets go down; records, and counts if asked for, come back.
-// wide_colors != NULL: the wide query -- `out` holds 8-byte records (sbwtgpu_read_found) and wide_colors the reads' colour
-// words, 8 + 8 words bytes per read instead of 16; a chunk then also ends where its results would outgrow what 2^24 reads of
-// 64 colours with counts bring back.  sets != NULL: the wide query over a colour-set object, whose `base` is c.  marks != NULL:
-// colouring for a colour-set builder, whose `base` is c -- a hit sets its column's bit in the builder's mark bitmap.
-static int colors_host_batch(const sbwtgpu_colors *c, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
-                             int color, int threshold_ppm, int denominator, void *out, uint64_t *wide_colors, int32_t *counts,
-                             int64_t *n_windows, int64_t *n_hit, const sbwtgpu_colorsets *sets = nullptr,
-                             unsigned long long *marks = nullptr) {
-    const sbwtgpu_index *idx = c->idx;
-    if (n_windows) *n_windows = 0;
-    if (n_hit) *n_hit = 0;
-    if (n_reads == 0) return SBWTGPU_OK;
-    if (!read_off) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    if (read_off[n_reads] > read_off[0] && !bases) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    const int64_t nc = c->n_colors, k = c->k, nw = c->words;
-    const int64_t rec_bytes = wide_colors ? 8 : 16, per_read = rec_bytes + (wide_colors ? 8 * nw : 0) + (counts ? 4 * nc : 0);
-    const int64_t budget = g_pa_chunk_bases > 0 ? g_pa_chunk_bases : (int64_t)64 << 20;
-    const int64_t CH_READS = std::min((int64_t)1 << 24, std::max<int64_t>(1, (((int64_t)1 << 24) * 272) / per_read));
-    std::vector<int64_t> cuts{0};
-    int64_t max_bases = 0, max_reads = 0, windows = 0;
-    int rc;
-    try {
-        for (int64_t lo = 0, r = 0; r < n_reads; r++) {
-            if ((rc = check_read_length(read_off, r)) != SBWTGPU_OK) return rc;
-            if (r > lo && (read_off[r + 1] - read_off[lo] > budget || r - lo >= CH_READS)) {
-                cuts.push_back(r);
-                lo = r;
-            }
-            max_bases = std::max(max_bases, read_off[r + 1] - read_off[lo]);
-            max_reads = std::max(max_reads, r + 1 - lo);
-            windows += std::max<int64_t>(0, read_off[r + 1] - read_off[r] - k + 1);
-        }
-        cuts.push_back(n_reads);
-    } catch (const std::bad_alloc &) {
-        return fail(SBWTGPU_ERR_OOM, "out of host memory");
-    }
-    const int64_t n_chunks = (int64_t)cuts.size() - 1;
-    const bool pin_in = is_pinned(bases);
-    const int64_t ws_bytes = sbwtgpu_pseudoalign_workspace_bytes(max_bases, max_reads, strands);
-    const int64_t b_rec = out ? align256(max_reads * rec_bytes) : 0, b_col = wide_colors ? align256(max_reads * nw * 8) : 0,
-                  b_cnt = counts ? align256(max_reads * nc * 4) : 0;
-    const int64_t need_in = align256(max_bases + 16) + align256((max_reads + 1) * 8);
-    const int64_t need_out = b_rec + b_col + b_cnt;
-    const int64_t need_dev = align256(max_bases + 16) + align256((max_reads + 1) * 8) + b_rec + b_col + b_cnt + align256(ws_bytes);
-    DeviceGuard guard(idx->device);
-    const int n_slots = n_chunks > 1 ? 2 : 1;
-    PipeSlot S[2];
-    if ((rc = take_slots(idx->device, S, n_slots, need_in, need_out, need_dev, "pseudoalignment buffers")) != SBWTGPU_OK) return rc;
-    int bug = 0;                    // the first nonzero device status of a chunk
-    int64_t hits = 0;
-    const int64_t o_roff = align256(max_bases + 16), o_rec = o_roff + align256((max_reads + 1) * 8), o_col = o_rec + b_rec,
-                  o_cnt = o_col + b_col, o_ws = o_cnt + b_cnt;
-    auto submit = [&](int64_t ch) -> int {
-        PipeSlot &P = S[ch % n_slots];
-        const int64_t lo = cuts[(size_t)ch], hi = cuts[(size_t)ch + 1], nr = hi - lo, nb = read_off[hi] - read_off[lo];
-        int64_t *hro = (int64_t *)(P.h_in + align256(max_bases + 16));
-        for (int64_t r = 0; r <= nr; r++) hro[r] = read_off[lo + r] - read_off[lo];
-        const char *hb = bases + read_off[lo];
-        if (!pin_in && nb > 0) { parallel_memcpy(P.h_in, hb, (size_t)nb); hb = P.h_in; }
-        hipError_t e;
-        if ((nb > 0 && (e = hipMemcpyAsync(P.d_mem, hb, (size_t)nb, hipMemcpyHostToDevice, P.st)) != hipSuccess) ||
-            (e = hipMemcpyAsync(P.d_mem + o_roff, hro, (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, P.st)) != hipSuccess)
-            return fail(SBWTGPU_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
-        int r2;
-        const int64_t *d_roff = (const int64_t *)(P.d_mem + o_roff);
-        if (sets) {
-            r2 = sbwtgpu_pseudoalign_sets_dev(sets, P.d_mem, nb, d_roff, nr, strands, threshold_ppm, denominator,
-                                              (sbwtgpu_read_found *)(P.d_mem + o_rec), (uint64_t *)(P.d_mem + o_col),
-                                              counts ? (int32_t *)(P.d_mem + o_cnt) : nullptr, P.d_mem + o_ws, ws_bytes, P.st);
-        } else if (wide_colors) {
-            r2 = sbwtgpu_pseudoalign_wide_dev(c, P.d_mem, nb, d_roff, nr, strands, threshold_ppm, denominator,
-                                              (sbwtgpu_read_found *)(P.d_mem + o_rec), (uint64_t *)(P.d_mem + o_col),
-                                              counts ? (int32_t *)(P.d_mem + o_cnt) : nullptr, P.d_mem + o_ws, ws_bytes, P.st);
-        } else if (out) {
-            r2 = sbwtgpu_pseudoalign_dev(c, P.d_mem, nb, d_roff, nr, strands, threshold_ppm, denominator,
-                                         (sbwtgpu_pseudoalignment *)(P.d_mem + o_rec), counts ? (int32_t *)(P.d_mem + o_cnt) : nullptr,
-                                         P.d_mem + o_ws, ws_bytes, P.st);
-        } else if (marks) {
-            r2 = colors_dev_common(c, P.d_mem, nb, d_roff, nr, strands, P.d_mem + o_ws, ws_bytes, P.st,
-                                   [&](const int *res, const int *res2, const long long *ooff, SbwtPaHeader *hdr, hipStream_t st) {
-                                       sbwt_launch_csb_mark(res, res2, ooff, nr, nb, marks, c->n_nodes, 1, hdr, st);
-                                       if (res2) sbwt_launch_csb_mark(res2, nullptr, ooff, nr, nb, marks, c->n_nodes, 0, hdr, st);
-                                   });
-        } else {
-            r2 = colors_dev_common(c, P.d_mem, nb, d_roff, nr, strands, P.d_mem + o_ws, ws_bytes, P.st,
-                                   [&](const int *res, const int *res2, const long long *ooff, SbwtPaHeader *hdr, hipStream_t st) {
-                                       sbwt_launch_col_mark(res, res2, ooff, nr, nb, c->d_rows, c->n_nodes, c->words, color, 1, hdr, st);
-                                       if (res2)
-                                           sbwt_launch_col_mark(res2, nullptr, ooff, nr, nb, c->d_rows, c->n_nodes, c->words, color, 0, hdr, st);
-                                   });
-        }
-        if (r2 != SBWTGPU_OK) return r2;
-        const SbwtPaLayout L = sbwt_pa_layout(sbwtgpu_search_workspace_bytes(nb), nb, nr, strands);
-        if ((out && (e = hipMemcpyAsync(P.h_out, P.d_mem + o_rec, (size_t)(nr * rec_bytes), hipMemcpyDeviceToHost, P.st)) != hipSuccess) ||
-            (wide_colors &&
-             (e = hipMemcpyAsync(P.h_out + b_rec, P.d_mem + o_col, (size_t)(nr * nw) * 8, hipMemcpyDeviceToHost, P.st)) != hipSuccess) ||
-            (counts && nr * nc > 0 &&
-             (e = hipMemcpyAsync(P.h_out + b_rec + b_col, P.d_mem + o_cnt, (size_t)(nr * nc) * 4, hipMemcpyDeviceToHost, P.st)) != hipSuccess) ||
-            (e = hipMemcpyAsync(P.h_status, P.d_mem + o_ws + L.hdr, 16, hipMemcpyDeviceToHost, P.st)) != hipSuccess)
-            return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
-        return SBWTGPU_OK;
-    };
-    auto collect = [&](int64_t ch) -> int {
-        PipeSlot &P = S[ch % n_slots];
-        hipError_t e = hipStreamSynchronize(P.st);
-        if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "stream synchronize: %s", hipGetErrorString(e));
-        if (P.h_status[0] != 0 && bug == 0) bug = P.h_status[0];
-        unsigned long long nh;
-        memcpy(&nh, P.h_status + 2, 8);                  // (SbwtPaHeader::n_hit)
-        hits += (int64_t)nh;
-        const int64_t lo = cuts[(size_t)ch], hi = cuts[(size_t)ch + 1];
-        if (out) memcpy((char *)out + lo * rec_bytes, P.h_out, (size_t)((hi - lo) * rec_bytes));
-        if (wide_colors) memcpy(wide_colors + lo * nw, P.h_out + b_rec, (size_t)((hi - lo) * nw) * 8);
-        if (counts && (hi - lo) * nc > 0) memcpy(counts + lo * nc, P.h_out + b_rec + b_col, (size_t)((hi - lo) * nc) * 4);
-        return SBWTGPU_OK;
-    };
-    rc = two_in_flight(n_chunks, submit, collect);
-    park_slots(idx->device, S, n_slots, rc);
-    if (rc != SBWTGPU_OK) return rc;
-    if (bug) return fail_status(bug);
-    if (n_windows) *n_windows = windows;
-    if (n_hit) *n_hit = hits;
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_colors_add_batch(sbwtgpu_colors *c, int color, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
-                             int64_t *n_windows, int64_t *n_hit_windows) {
-    int rc = colors_check(c);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
-    if (rc != SBWTGPU_OK) return rc;
-    if (color < 0 || color >= c->n_colors)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "color %d is out of range: the colours object has %d colours", color, c->n_colors);
-    return colors_host_batch(c, bases, read_off, n_reads, strands, color, 0, 0, nullptr, nullptr, nullptr, n_windows, n_hit_windows);
-}
-
-int sbwtgpu_pseudoalign_batch(const sbwtgpu_colors *c, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
-                              int threshold_ppm, int denominator, sbwtgpu_pseudoalignment *out, int32_t *counts_or_null) {
-    int rc = colors_check(c);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
-    if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
-    if (rc != SBWTGPU_OK) return rc;
-    if (c->n_colors > 64)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "the colours object has %d colours, a 16-byte record holds 64: use sbwtgpu_pseudoalign_wide_batch",
-                    c->n_colors);
-    if (n_reads > 0 && !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    return colors_host_batch(c, bases, read_off, n_reads, strands, 0, threshold_ppm, denominator, out, nullptr, counts_or_null, nullptr,
-                             nullptr);
-}
-
-int sbwtgpu_pseudoalign_wide_batch(const sbwtgpu_colors *c, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
-                                   int threshold_ppm, int denominator, sbwtgpu_read_found *out, uint64_t *colors_out,
-                                   int32_t *counts_or_null) {
-    int rc = colors_check(c);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
-    if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
-    if (rc != SBWTGPU_OK) return rc;
-    if (n_reads > 0 && (!out || !colors_out)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    return colors_host_batch(c, bases, read_off, n_reads, strands, 0, threshold_ppm, denominator, out, colors_out, counts_or_null,
-                             nullptr, nullptr);
-}
-
-// ---- deduplicated colour sets (sbwt_colorsets.hip) -----------------------------------------------------
-static int colorsets_check(const sbwtgpu_colorsets *s) {
-    if (!s) return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set object is NULL");
-    return colors_check(&s->base);
-}
-
-static sbwtgpu_colorsets *colorsets_new(const sbwtgpu_index *idx, int n_colors) {
-    sbwtgpu_colorsets *s = new (std::nothrow) sbwtgpu_colorsets();
-    if (!s) return nullptr;
-    s->base.idx = idx;
-    s->base.device = idx->device;
-    s->base.n_nodes = idx->h.n_nodes;
-    s->base.k = idx->h.k;
-    s->base.n_colors = n_colors;
-    s->base.words = (n_colors + 63) / 64;
-    return s;
-}
-
-// n_colored = the ids that are not 0
-static hipError_t colorsets_count(sbwtgpu_colorsets *s, hipStream_t st) {
-    DevBuf count;
-    unsigned long long h = 0;
-    hipError_t e = count.alloc(8);
-    if (e == hipSuccess) e = hipMemsetAsync(count.p, 0, 8, st);
-    if (e == hipSuccess) {
-        sbwt_launch_cs_count(s->d_ids, s->base.n_nodes, static_cast<unsigned long long *>(count.p), st);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, count.p, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    s->n_colored = (int64_t)h;
-    return e;
-}
-
-static int colorsets_hip_failed(sbwtgpu_colorsets *s, hipError_t e) {
-    (void)hipGetLastError();
-    sbwtgpu_colorsets_destroy(s);
-    return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "colour sets: %s", hipGetErrorString(e));
-}
-
-int sbwtgpu_colorsets_compress(const sbwtgpu_colors *c, sbwtgpu_colorsets **out) {
-    if (!c || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    const int rc = colors_check(c);
-    if (rc != SBWTGPU_OK) return rc;
-    DeviceGuard guard(c->device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", c->device);
-    sbwtgpu_colorsets *s = colorsets_new(c->idx, c->n_colors);
-    if (!s) return fail(SBWTGPU_ERR_OOM, "out of host memory");
-    Stream st;
-    long long n_sets = 0;
-    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = sbwt_colorsets_compress(c->d_rows, c->n_nodes, c->words, &s->d_ids, &s->d_table, &n_sets, st.s);
-    s->n_sets = n_sets;
-    if (e == hipSuccess) e = colorsets_count(s, st.s);
-    if (e != hipSuccess) return colorsets_hip_failed(s, e);
-    *out = s;
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_colorsets_create(const sbwtgpu_index *idx, int n_colors, const uint32_t *ids, int64_t n_sets, const uint64_t *table,
-                             sbwtgpu_colorsets **out) {
-    if (!idx || !out || !ids || !table) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    const int rc = colors_check_index(idx);
-    if (rc != SBWTGPU_OK) return rc;
-    if (n_colors < 1 || n_colors > SBWTGPU_MAX_COLORS)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "n_colors must be in 1 .. %d, not %d", SBWTGPU_MAX_COLORS, n_colors);
-    if (n_sets < 1 || n_sets > (int64_t)0xFFFFFFFFll)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "n_sets must be in 1 .. 2^32 - 1, not %lld (row 0, the empty set, is always there)", (long long)n_sets);
-    DeviceGuard guard(idx->device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", idx->device);
-    sbwtgpu_colorsets *s = colorsets_new(idx, n_colors);
-    if (!s) return fail(SBWTGPU_ERR_OOM, "out of host memory");
-    s->n_sets = n_sets;
-    const size_t id_bytes = (size_t)s->base.n_nodes * 4, table_bytes = (size_t)n_sets * (size_t)s->base.words * 8;
-    Stream st;
-    unsigned long long report[2] = {~0ull, ~0ull};
-    hipError_t e = hipMalloc((void **)&s->d_ids, id_bytes + 16);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_table, table_bytes);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_ids, ids, id_bytes, hipMemcpyHostToDevice, st.s);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_table, table, table_bytes, hipMemcpyHostToDevice, st.s);
-    if (e == hipSuccess) e = sbwt_colorsets_validate(idx->view(), s->d_ids, s->d_table, n_sets, n_colors, report, st.s);
-    if (e == hipSuccess && report[0] == ~0ull && report[1] == ~0ull) e = colorsets_count(s, st.s);
-    if (e != hipSuccess) return colorsets_hip_failed(s, e);
-    if (report[1] != ~0ull || report[0] != ~0ull) {
-        sbwtgpu_colorsets_destroy(s);
-        const long long row = (long long)(report[1] >> 8);
-        if (report[1] == ~0ull)
-            return fail(SBWTGPU_ERR_INVALID_ARG, "colour sets: the id of column %lld is not below n_sets = %lld", (long long)report[0],
-                        (long long)n_sets);
-        switch ((int)(report[1] & 255)) {
-        case SBWT_CS_ROW0_NOT_ZERO:
-            return fail(SBWTGPU_ERR_INVALID_ARG, "colour sets: row 0 of the table is not all zero (id 0 is the empty set)");
-        case SBWT_CS_ZERO_ROW:
-            return fail(SBWTGPU_ERR_INVALID_ARG, "colour sets: row %lld of the table is all zero (only row 0 may be)", row);
-        default:
-            return fail(SBWTGPU_ERR_INVALID_ARG, "colour sets: row %lld of the table has a bit >= n_colors = %d", row, n_colors);
-        }
-    }
-    *out = s;
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_colorsets_expand(const sbwtgpu_colorsets *s, sbwtgpu_colors **out) {
-    if (!s || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    int rc = colorsets_check(s);
-    if (rc != SBWTGPU_OK) return rc;
-    sbwtgpu_colors *c = nullptr;
-    if ((rc = colors_create_checked(s->base.idx, s->base.n_colors, nullptr, &c)) != SBWTGPU_OK) return rc;
-    DeviceGuard guard(s->base.device);
-    Stream st;
-    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e == hipSuccess) {
-        sbwt_launch_cs_expand(s->d_ids, s->d_table, s->base.n_nodes, s->base.words, c->d_rows, st.s);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st.s);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        sbwtgpu_colors_destroy(c);
-        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "colour sets: %s", hipGetErrorString(e));
-    }
-    *out = c;
-    return SBWTGPU_OK;
-}
-
-void sbwtgpu_colorsets_destroy(sbwtgpu_colorsets *s) {
-    if (!s) return;
-    DeviceGuard guard(s->base.device);
-    if (s->d_ids) (void)hipFree(s->d_ids);
-    if (s->d_table) (void)hipFree(s->d_table);
-    delete s;
-}
-
-int sbwtgpu_colorsets_info(const sbwtgpu_colorsets *s, int64_t *n_columns, int64_t *k, int32_t *n_colors, int32_t *words, int64_t *n_sets,
-                           int64_t *n_colored_columns, int64_t *device_bytes) {
-    if (!s) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    if (n_columns) *n_columns = s->base.n_nodes;
-    if (k) *k = s->base.k;
-    if (n_colors) *n_colors = s->base.n_colors;
-    if (words) *words = s->base.words;
-    if (n_sets) *n_sets = s->n_sets;
-    if (n_colored_columns) *n_colored_columns = s->n_colored;
-    if (device_bytes) *device_bytes = s->base.n_nodes * 4 + s->n_sets * (int64_t)s->base.words * 8;
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_colorsets_copy(const sbwtgpu_colorsets *s, uint32_t *ids_out, uint64_t *table_out) {
-    if (!s) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    DeviceGuard guard(s->base.device);
-    if (ids_out && s->base.n_nodes > 0) HIP_TRY(hipMemcpy(ids_out, s->d_ids, (size_t)s->base.n_nodes * 4, hipMemcpyDeviceToHost));
-    if (table_out) HIP_TRY(hipMemcpy(table_out, s->d_table, (size_t)s->n_sets * (size_t)s->base.words * 8, hipMemcpyDeviceToHost));
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_colorsets_dev(const sbwtgpu_colorsets *s, const uint32_t **d_ids, const uint64_t **d_table) {
-    if (!s) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    if (d_ids) *d_ids = reinterpret_cast<const uint32_t *>(s->d_ids);
-    if (d_table) *d_table = reinterpret_cast<const uint64_t *>(s->d_table);
-    return SBWTGPU_OK;
-}
-
-// coloured unitigs (sbwt_unitigs.hip with a colour view): the object's ids and table are read in place during the call only
-int sbwtgpu_unitigs_create_colored(const sbwtgpu_colorsets *s, sbwtgpu_unitigs **out) {
-    if (!s || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    const int rc = colorsets_check(s);
-    if (rc != SBWTGPU_OK) return rc;
-    return unitigs_create_common(s->base.idx, s->d_ids, s->d_table, s->base.words, s->n_sets, s->base.n_colors, 0u, out);
-}
-
-// the unitigs as a graph (section 21): the plain run of idx or the coloured run of s, with the links and the column map asked for
-int sbwtgpu_unitigs_create_graph(const sbwtgpu_index *idx, const sbwtgpu_colorsets *s, unsigned flags, sbwtgpu_unitigs **out) {
-    if (!out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    if ((idx != nullptr) == (s != nullptr))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "unitig graph: give exactly one of idx (a plain run) and s (a coloured run), %s were given",
-                    idx ? "both" : "neither");
-    if (flags & ~(unsigned)(SBWTGPU_UNITIGS_LINKS | SBWTGPU_UNITIGS_COLUMN_MAP))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "unitig graph: unknown flag bits 0x%x", flags & ~(unsigned)(SBWTGPU_UNITIGS_LINKS | SBWTGPU_UNITIGS_COLUMN_MAP));
-    if (idx) return unitigs_create_common(idx, nullptr, nullptr, 0, 0, 0, flags, out);
-    const int rc = colorsets_check(s);
-    if (rc != SBWTGPU_OK) return rc;
-    return unitigs_create_common(s->base.idx, s->d_ids, s->d_table, s->base.words, s->n_sets, s->base.n_colors, flags, out);
-}
-
-int sbwtgpu_pseudoalign_sets_dev(const sbwtgpu_colorsets *s, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
-                                 int64_t n_reads, int strands, int threshold_ppm, int denominator, sbwtgpu_read_found *d_out,
-                                 uint64_t *d_colors, int32_t *d_counts_or_null, void *d_ws, int64_t ws_bytes, void *stream) {
-    int rc = colorsets_check(s);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
-    if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
-    if (rc != SBWTGPU_OK) return rc;
-    if (n_reads > 0 && (!d_out || !d_colors)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
-    const sbwtgpu_colors *c = &s->base;
-    return colors_dev_common(c, d_bases, total_bases, d_read_off, n_reads, strands, d_ws, ws_bytes, stream,
-                             [&](const int *res, const int *res2, const long long *ooff, SbwtPaHeader *, hipStream_t st) {
-                                 sbwt_launch_pa_reduce_sets(res, res2, ooff, n_reads, s->d_ids, s->d_table, c->n_nodes, s->n_sets, c->words,
-                                                            c->n_colors, threshold_ppm, denominator, reinterpret_cast<SbwtReadFound *>(d_out),
-                                                            reinterpret_cast<unsigned long long *>(d_colors), d_counts_or_null, st);
-                             });
-}
-
-int sbwtgpu_pseudoalign_sets_batch(const sbwtgpu_colorsets *s, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
-                                   int threshold_ppm, int denominator, sbwtgpu_read_found *out, uint64_t *colors_out,
-                                   int32_t *counts_or_null) {
-    int rc = colorsets_check(s);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
-    if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
-    if (rc != SBWTGPU_OK) return rc;
-    if (n_reads > 0 && (!out || !colors_out)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    return colors_host_batch(&s->base, bases, read_off, n_reads, strands, 0, threshold_ppm, denominator, out, colors_out, counts_or_null,
-                             nullptr, nullptr, s);
-}
-
-// ---- the colour-set builder (sbwt_colorsets.hip, "the builder") -----------------------------------------
-static int builder_check(const sbwtgpu_colorsets_builder *b) {
-    if (!b) return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set builder is NULL");
-    if (b->finished) return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set builder: finish has consumed it, only destroy is left");
-    if (b->broken) return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set builder is broken by an earlier error, only destroy is left");
-    return colors_check(&b->base);
-}
-
-static int builder_failed(sbwtgpu_colorsets_builder *b, hipError_t e) {
-    (void)hipGetLastError();
-    b->broken = true;
-    return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "colour-set builder: %s", hipGetErrorString(e));
-}
-
-// merges the open colour's marks into (ids, table); nothing open: nothing to do
-static int builder_close_open(sbwtgpu_colorsets_builder *b) {
-    if (b->open < 0) return SBWTGPU_OK;
-    long long marked = 0;
-    const hipError_t e = sbwt_csb_close(&b->st, b->open, &marked, b->stream.s);
-    if (e != hipSuccess) return builder_failed(b, e);
-    b->per_color[(size_t)b->open] = marked;
-    b->state[(size_t)b->open] = CSB_CLOSED;
-    b->open = -1;
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_colorsets_builder_create(const sbwtgpu_index *idx, int n_colors, sbwtgpu_colorsets_builder **out) {
-    if (!idx || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    const int rc = colors_check_index(idx);
-    if (rc != SBWTGPU_OK) return rc;
-    if (n_colors < 1 || n_colors > SBWTGPU_MAX_COLORS)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "n_colors must be in 1 .. %d, not %d", SBWTGPU_MAX_COLORS, n_colors);
-    DeviceGuard guard(idx->device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", idx->device);
-    sbwtgpu_colorsets_builder *b = new (std::nothrow) sbwtgpu_colorsets_builder();
-    if (!b) return fail(SBWTGPU_ERR_OOM, "out of host memory");
-    try {
-        b->state.assign((size_t)n_colors, CSB_NEW);
-        b->per_color.assign((size_t)n_colors, 0);
-    } catch (const std::bad_alloc &) {
-        delete b;
-        return fail(SBWTGPU_ERR_OOM, "out of host memory");
-    }
-    b->base.idx = idx;
-    b->base.device = idx->device;
-    b->base.n_nodes = idx->h.n_nodes;
-    b->base.k = idx->h.k;
-    b->base.n_colors = n_colors;
-    b->base.words = (n_colors + 63) / 64;
-    hipError_t e = hipStreamCreateWithFlags(&b->stream.s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = sbwt_csb_init(&b->st, b->base.n_nodes, b->base.words, b->stream.s);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        delete b;
-        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "colour-set builder: %s", hipGetErrorString(e));
-    }
-    *out = b;
-    return SBWTGPU_OK;
-}
-
-void sbwtgpu_colorsets_builder_destroy(sbwtgpu_colorsets_builder *b) {
-    if (!b) return;
-    DeviceGuard guard(b->base.device);
-    sbwt_csb_free(&b->st);
-    delete b;
-}
-
-int sbwtgpu_colorsets_builder_add_batch(sbwtgpu_colorsets_builder *b, int color, const char *bases, const int64_t *read_off,
-                                        int64_t n_reads, int strands, int64_t *n_windows, int64_t *n_hit_windows) {
-    int rc = builder_check(b);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
-    if (rc != SBWTGPU_OK) return rc;
-    if (color < 0 || color >= b->base.n_colors)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "color %d is out of range: the colour-set builder has %d colours", color, b->base.n_colors);
-    if (b->state[(size_t)color] == CSB_CLOSED)
-        return fail(SBWTGPU_ERR_INVALID_ARG,
-                    "colour %d is closed: the sequences of one colour must come in consecutive calls (another colour was added after it)", color);
-    // (what colors_host_batch would refuse is refused here, before the call closes a colour)
-    if (n_reads > 0 && (!read_off || (read_off[n_reads] > read_off[0] && !bases))) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    for (int64_t r = 0; r < n_reads; r++)
-        if ((rc = check_read_length(read_off, r)) != SBWTGPU_OK) return rc;
-    DeviceGuard guard(b->base.device);
-    if (b->open != color) {
-        if ((rc = builder_close_open(b)) != SBWTGPU_OK) return rc;
-        b->open = color;
-        b->state[(size_t)color] = CSB_OPEN;
-    }
-    rc = colors_host_batch(&b->base, bases, read_off, n_reads, strands, color, 0, 0, nullptr, nullptr, nullptr, n_windows, n_hit_windows,
-                           nullptr, b->st.d_marks);
-    if (rc == SBWTGPU_ERR_OOM || rc == SBWTGPU_ERR_HIP) b->broken = true;          // (some of the batch may be marked, some not)
-    return rc;
-}
-
-int sbwtgpu_colorsets_builder_info(const sbwtgpu_colorsets_builder *b, int64_t *n_columns, int64_t *k, int32_t *n_colors, int32_t *words,
-                                   int64_t *n_sets, int64_t *n_colored_columns, int64_t *per_color, int64_t *device_bytes) {
-    const int rc = builder_check(b);
-    if (rc != SBWTGPU_OK) return rc;
-    if (n_columns) *n_columns = b->base.n_nodes;
-    if (k) *k = b->base.k;
-    if (n_colors) *n_colors = b->base.n_colors;
-    if (words) *words = b->base.words;
-    if (n_sets) *n_sets = b->st.n_sets;
-    if (n_colored_columns) *n_colored_columns = b->st.n_colored;
-    if (per_color) std::copy(b->per_color.begin(), b->per_color.end(), per_color);
-    if (device_bytes) *device_bytes = sbwt_csb_device_bytes(&b->st);
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_colorsets_builder_finish(sbwtgpu_colorsets_builder *b, sbwtgpu_colorsets **out) {
-    if (!out) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    int rc = builder_check(b);
-    if (rc != SBWTGPU_OK) return rc;
-    DeviceGuard guard(b->base.device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", b->base.device);
-    if ((rc = builder_close_open(b)) != SBWTGPU_OK) return rc;
-    sbwtgpu_colorsets *s = colorsets_new(b->base.idx, b->base.n_colors);
-    if (!s) return fail(SBWTGPU_ERR_OOM, "out of host memory");
-    long long n_sets = 0;
-    s->n_colored = b->st.n_colored;
-    const hipError_t e = sbwt_csb_finish(&b->st, &s->d_ids, &s->d_table, &n_sets, b->stream.s);
-    s->n_sets = n_sets;
-    if (e != hipSuccess) {
-        sbwtgpu_colorsets_destroy(s);
-        return builder_failed(b, e);
-    }
-    b->finished = true;
-    *out = s;
-    return SBWTGPU_OK;
-}
-
-// ---- set operations (sbwt_setops.hip) ---------------------------------------------------------------
-}  // extern "C"
-namespace {
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-// what the label extraction needs of an index: the unitig pass's conditions, and a key of 64 or 128 bits
-int setop_check_index(const sbwtgpu_index *idx, const char *who) {
-    if (idx->h.rank_only) return fail(SBWTGPU_ERR_INVALID_ARG, "%s", RANK_ONLY_MSG);
-    if (idx->h.k < 2 || idx->h.k > 64)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "%s: k = %lld, the keys of the device builder hold 2 <= k <= 64", who, (long long)idx->h.k);
-    if (idx->h.n_nodes >= ((int64_t)1 << 32) - ((int64_t)1 << 24))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "%s: columns are 32-bit unsigned values (%lld columns)", who, (long long)idx->h.n_nodes);
-    return SBWTGPU_OK;
-}
-int setop_check_pair(const sbwtgpu_index *a, const sbwtgpu_index *b, int op) {
-    if (!a || !b) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    if (op < SBWTGPU_SETOP_UNION || op > SBWTGPU_SETOP_SYMMETRIC_DIFFERENCE)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "set operation %d: 0 union, 1 intersection, 2 difference, 3 symmetric difference", op);
-    if (a->h.k != b->h.k)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "set operation: the indexes differ in k (%lld and %lld)", (long long)a->h.k, (long long)b->h.k);
-    if (a->device != b->device)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "set operation: the indexes are on different devices (%d and %d)", a->device, b->device);
-    int rc = setop_check_index(a, "set operation, a");
-    if (rc == SBWTGPU_OK && b != a) rc = setop_check_index(b, "set operation, b");
-    return rc;
-}
-int setop_hip_fail(hipError_t e, const char *what) {
-    (void)hipGetLastError();
-    return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "set operation, %s: %s", what, hipGetErrorString(e));
-}
-// keys of a, keys of b, merge + select.  With d_res: the result's keys (a device allocation the caller owns).
-int setop_merge(const sbwtgpu_index *a, const sbwtgpu_index *b, int op, hipStream_t st, void **d_res, sbwtgpu_setop_info *info) {
-    DevBuf ka, kb;
-    long long na = 0, nb = 0;
-    const int key_bytes = a->h.k <= 32 ? 8 : 16;
-    auto t0 = std::chrono::steady_clock::now();
-    hipError_t e = sbwt_setops_keys(a->view(), &ka.p, &na, st);
-    if (e != hipSuccess) return setop_hip_fail(e, "keys of a");
-    info->pass_ms[0] = ms_since(t0);
-    t0 = std::chrono::steady_clock::now();
-    if (b != a) {
-        e = sbwt_setops_keys(b->view(), &kb.p, &nb, st);
-        if (e != hipSuccess) return setop_hip_fail(e, "keys of b");
-    } else {
-        nb = na;
-    }
-    info->pass_ms[1] = ms_since(t0);
-    if (na + nb >= ((int64_t)1 << 32) - ((int64_t)1 << 24))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "set operation: %lld + %lld k-mers exceed the 2^32 work-items of one launch", na, nb);
-    t0 = std::chrono::steady_clock::now();
-    SbwtSetopCounts c;
-    e = sbwt_setops_merge(ka.p, na, b != a ? kb.p : ka.p, nb, key_bytes, op, d_res, &c, st);
-    if (e != hipSuccess) return setop_hip_fail(e, "merge");
-    info->pass_ms[2] = ms_since(t0);
-    info->n_a = c.n_a; info->n_b = c.n_b; info->n_both = c.n_both; info->n_either = c.n_either; info->n_result = c.n_result;
-    return SBWTGPU_OK;
-}
-}  // namespace
-extern "C" {
-
-int sbwtgpu_index_setop(const sbwtgpu_index *a, const sbwtgpu_index *b, int op, int build_streaming_support,
-                        sbwtgpu_plain_matrix_bits *out, sbwtgpu_setop_info *info) {
-    sbwtgpu_setop_info local;
-    if (!info) info = &local;
-    memset(info, 0, sizeof(*info));
-    if (!out) return fail(SBWTGPU_ERR_INVALID_ARG, "out is NULL");
-    memset(out, 0, sizeof(*out));
-    int rc = setop_check_pair(a, b, op);
-    if (rc != SBWTGPU_OK) return rc;
-    DeviceGuard guard(a->device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", a->device);
-    Stream st;
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    const int64_t k = a->h.k;
-    void *d_res = nullptr;
-    rc = setop_merge(a, b, op, st.s, &d_res, info);
-    if (rc != SBWTGPU_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    SbwtBuildState S;
-    try {
-        const int ra = sbwt_build_from_keys(d_res, info->n_result, (int)k, &S, st.s);       // (S owns d_res now)
-        if (ra != 0) { sbwt_build_release(&S); return fail(ra == -8 ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "set operation: builder tail"); }
-        info->n_nopred = S.n_nopred;
-        if ((long long)S.n_nopred * (long long)k > (1ll << 26)) {
-            sbwt_build_release(&S);
-            return fail(SBWTGPU_ERR_OOM, "set operation: the result has %lld predecessor-less k-mers x k = %lld dummy records (limit 2^26; "
-                        "the dummies are expanded on the host).  Intersections and differences of fragmented sets reach this limit "
-                        "sooner than genomes do: dump the unitigs of both indexes and use the host builder",
-                        (long long)S.n_nopred, (long long)S.n_nopred * (long long)k);
-        }
-        rc = (k <= 32) ? build_columns_t<unsigned long long>(S, k, build_streaming_support, out)
-                       : build_columns_t<unsigned __int128>(S, k, build_streaming_support, out);
-    } catch (const std::bad_alloc &) {
-        sbwt_build_release(&S);
-        rc = fail(SBWTGPU_ERR_OOM, "out of host memory");
-    }
-    info->pass_ms[3] = ms_since(t0);
-    return rc;
-}
-
-int sbwtgpu_index_setop_counts(const sbwtgpu_index *a, const sbwtgpu_index *b, sbwtgpu_setop_info *info) {
-    if (!info) return fail(SBWTGPU_ERR_INVALID_ARG, "info is NULL");
-    memset(info, 0, sizeof(*info));
-    int rc = setop_check_pair(a, b, SBWTGPU_SETOP_UNION);
-    if (rc != SBWTGPU_OK) return rc;
-    DeviceGuard guard(a->device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", a->device);
-    Stream st;
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    return setop_merge(a, b, SBWTGPU_SETOP_UNION, st.s, nullptr, info);
-}
-
-int sbwtgpu_index_kmer_keys(const sbwtgpu_index *idx, void *out_keys, int64_t cap_bytes, int64_t *n_keys, int *key_bytes) {
-    if (!idx) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
-    if (cap_bytes < 0 || (!out_keys && cap_bytes > 0)) return fail(SBWTGPU_ERR_INVALID_ARG, "out_keys is NULL");
-    int rc = setop_check_index(idx, "k-mer keys");
-    if (rc != SBWTGPU_OK) return rc;
-    DeviceGuard guard(idx->device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", idx->device);
-    Stream st;
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    DevBuf keys;
-    long long n = 0;
-    const int kb = idx->h.k <= 32 ? 8 : 16;
-    hipError_t e = sbwt_setops_keys(idx->view(), &keys.p, &n, st.s);
-    if (e != hipSuccess) return setop_hip_fail(e, "keys");
-    if (n_keys) *n_keys = n;
-    if (key_bytes) *key_bytes = kb;
-    if (!out_keys && cap_bytes == 0) return SBWTGPU_OK;
-    if (cap_bytes < n * kb)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "k-mer keys: %lld keys of %d bytes need %lld bytes, cap_bytes is %lld", n, kb, n * kb,
-                    (long long)cap_bytes);
-    if (n > 0) HIP_TRY(hipMemcpy(out_keys, keys.p, (size_t)(n * kb), hipMemcpyDeviceToHost));
-    return SBWTGPU_OK;
-}
-
-// ---- colour sets carried onto another index (sbwt_colormerge.hip) ---------------------------------------
-int sbwtgpu_colorsets_merge(const sbwtgpu_index *u, const sbwtgpu_colorsets *sa, const sbwtgpu_colorsets *sb, int color_offset_b,
-                            sbwtgpu_colorsets **out, sbwtgpu_colorsets_merge_info *info) {
-    if (info) memset(info, 0, sizeof(*info));
-    if (out) *out = nullptr;
-    if (!u || !sa || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set merge: NULL argument (u, sa and out are needed)");
-    int rc = colorsets_check(sa);
-    if (rc == SBWTGPU_OK && sb) rc = colorsets_check(sb);
-    if (rc != SBWTGPU_OK) return rc;
-    const sbwtgpu_index *a = sa->base.idx, *b = sb ? sb->base.idx : nullptr;
-    if (u->h.n_nodes >= ((int64_t)1 << 31))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set merge: u has %lld columns, a colour-set object needs fewer than 2^31 columns",
-                    (long long)u->h.n_nodes);
-    if (u->h.k != a->h.k || (b && b->h.k != a->h.k))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set merge: the indexes differ in k (u %lld, a %lld, b %lld)", (long long)u->h.k,
-                    (long long)a->h.k, (long long)(b ? b->h.k : a->h.k));
-    if ((rc = setop_check_index(u, "colour-set merge, u")) != SBWTGPU_OK) return rc;
-    if (a != u && (rc = setop_check_index(a, "colour-set merge, a")) != SBWTGPU_OK) return rc;
-    if (b && b != u && b != a && (rc = setop_check_index(b, "colour-set merge, b")) != SBWTGPU_OK) return rc;
-    if (u->device != a->device || (b && b->device != a->device))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set merge: the indexes are on different devices (u %d, a %d, b %d)", u->device,
-                    a->device, b ? b->device : a->device);
-    if (color_offset_b < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set merge: color_offset_b must not be negative, not %d", color_offset_b);
-    if (!sb && color_offset_b != 0)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set merge: color_offset_b = %d without sb (it must be 0 then)", color_offset_b);
-    const int64_t n_colors_out = std::max<int64_t>(sa->base.n_colors, sb ? (int64_t)color_offset_b + sb->base.n_colors : 0);
-    if (n_colors_out > SBWTGPU_MAX_COLORS)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "colour-set merge: color_offset_b %d + %d colours of b = %lld colours, more than %d",
-                    color_offset_b, sb ? sb->base.n_colors : 0, (long long)n_colors_out, SBWTGPU_MAX_COLORS);
-    DeviceGuard guard(u->device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", u->device);
-    sbwtgpu_colorsets *s = colorsets_new(u, (int)n_colors_out);
-    if (!s) return fail(SBWTGPU_ERR_OOM, "out of host memory");
-    SbwtCmSide A{a->view()}, B{a->view()};
-    A.d_ids = sa->d_ids; A.d_table = sa->d_table; A.n_sets = sa->n_sets; A.words = sa->base.words;
-    if (sb) { B.ix = b->view(); B.d_ids = sb->d_ids; B.d_table = sb->d_table; B.n_sets = sb->n_sets; B.words = sb->base.words; }
-    SbwtCmInfo ci;
-    Stream st;
-    long long n_sets = 0;
-    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e == hipSuccess)
-        e = sbwt_colormerge(u->view(), A, sb ? &B : nullptr, u == a ? 1 : (b && u == b) ? 2 : 0, b == a, color_offset_b, s->base.words,
-                            &s->d_ids, &s->d_table, &n_sets, &ci, st.s);
-    s->n_sets = n_sets;
-    if (e == hipSuccess) e = colorsets_count(s, st.s);
-    if (e != hipSuccess) return colorsets_hip_failed(s, e);
-    if (info) {
-        info->n_real_u = ci.n_real_u; info->n_from_a = ci.n_from_a; info->n_from_b = ci.n_from_b; info->n_from_both = ci.n_from_both;
-        info->n_pairs = ci.n_pairs; info->n_sets = ci.n_sets;
-        for (int i = 0; i < 4; i++) info->pass_ms[i] = ci.pass_ms[i];
-    }
-    *out = s;
-    return SBWTGPU_OK;
-}
-
-// ---- shared k-mers: the colours' weighted Gram matrix (sbwt_colormatrix.hip) -----------------------------
-int sbwtgpu_colorsets_set_sizes(const sbwtgpu_colorsets *s, int64_t *sizes_out) {
-    if (!s || !sizes_out) return fail(SBWTGPU_ERR_INVALID_ARG, "set sizes: NULL argument (s and sizes_out are needed)");
-    const int rc = colorsets_check(s);
-    if (rc != SBWTGPU_OK) return rc;
-    DeviceGuard guard(s->base.device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", s->base.device);
-    Stream st;
-    DevBuf d;
-    std::vector<uint32_t> h;
-    try { h.resize((size_t)s->n_sets); } catch (const std::bad_alloc &) { return fail(SBWTGPU_ERR_OOM, "out of host memory"); }
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    HIP_TRY(d.alloc((size_t)s->n_sets * 4));
-    sbwt_launch_gm_sizes(s->d_ids, s->base.n_nodes, s->n_sets, static_cast<unsigned *>(d.p), st.s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h.data(), d.p, (size_t)s->n_sets * 4, hipMemcpyDeviceToHost, st.s));
-    HIP_TRY(hipStreamSynchronize(st.s));
-    for (int64_t t = 0; t < s->n_sets; t++) sizes_out[t] = (int64_t)h[(size_t)t];
-    return SBWTGPU_OK;
-}
-
-int64_t sbwtgpu_colorsets_shared_workspace_bytes(const sbwtgpu_colorsets *s) {
-    if (!s) return 0;
-    DeviceGuard guard(s->base.device);
-    return sbwt_gm_workspace_bytes(s->n_sets, s->base.n_colors);
-}
-
-int sbwtgpu_colorsets_shared_kmers_dev(const sbwtgpu_colorsets *s, const int64_t *d_weights_or_null, int64_t *d_matrix, void *d_workspace,
-                                       int64_t workspace_bytes, void *stream) {
-    if (!s || !d_matrix || !d_workspace)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "shared k-mers: NULL argument (s, d_matrix and d_workspace are needed)");
-    const int rc = colorsets_check(s);
-    if (rc != SBWTGPU_OK) return rc;
-    DeviceGuard guard(s->base.device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", s->base.device);
-    const int64_t need = sbwt_gm_workspace_bytes(s->n_sets, s->base.n_colors);
-    if (need < 0) return fail(SBWTGPU_ERR_HIP, "shared k-mers: the sort's storage size could not be asked");
-    if (workspace_bytes < need)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "shared k-mers: the workspace has %lld bytes, %lld sets of %d colours need %lld "
-                    "(sbwtgpu_colorsets_shared_workspace_bytes)", (long long)workspace_bytes, (long long)s->n_sets, s->base.n_colors,
-                    (long long)need);
-    const hipError_t e = sbwt_gm_enqueue(s->d_ids, s->base.n_nodes, s->d_table, s->n_sets, s->base.n_colors,
-                                         reinterpret_cast<const long long *>(d_weights_or_null), reinterpret_cast<long long *>(d_matrix),
-                                         d_workspace, workspace_bytes, s->n_sets >= g_gram_mfma_min_sets, g_gram_flush_sets, nullptr,
-                                         static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "shared k-mers: %s", hipGetErrorString(e));
-    }
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_colorsets_shared_kmers(const sbwtgpu_colorsets *s, const int64_t *weights_or_null, int64_t *matrix_out,
-                                   sbwtgpu_shared_info *info) {
-    if (info) memset(info, 0, sizeof(*info));
-    if (!s || !matrix_out) return fail(SBWTGPU_ERR_INVALID_ARG, "shared k-mers: NULL argument (s and matrix_out are needed)");
-    const int rc = colorsets_check(s);
-    if (rc != SBWTGPU_OK) return rc;
-    DeviceGuard guard(s->base.device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", s->base.device);
-    const int C = s->base.n_colors;
-    const bool use_mfma = s->n_sets >= g_gram_mfma_min_sets;
-    const int64_t ws_bytes = sbwt_gm_workspace_bytes(s->n_sets, C);
-    if (ws_bytes < 0) return fail(SBWTGPU_ERR_HIP, "shared k-mers: the sort's storage size could not be asked");
-    const size_t m_bytes = (size_t)C * (size_t)C * 8;
-    Stream st;
-    DevBuf ws, w, m;
-    SbwtGmHeader hdr;
-    double ms[4] = {0, 0, 0, 0};
-    // (the plain route touches the header and the weights only: its workspace need not hold the planes)
-    const int64_t ws_alloc = use_mfma ? ws_bytes : sbwt_gm_plain_workspace_bytes(s->n_sets);
-    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = ws.alloc((size_t)ws_alloc);
-    if (e == hipSuccess) e = m.alloc(m_bytes);
-    if (e == hipSuccess && weights_or_null) e = w.alloc((size_t)s->n_sets * 8);
-    if (e == hipSuccess && weights_or_null) e = hipMemcpyAsync(w.p, weights_or_null, (size_t)s->n_sets * 8, hipMemcpyHostToDevice, st.s);
-    if (e == hipSuccess)
-        e = sbwt_gm_enqueue(s->d_ids, s->base.n_nodes, s->d_table, s->n_sets, C, static_cast<const long long *>(w.p),
-                            static_cast<long long *>(m.p), ws.p, ws_alloc, use_mfma, g_gram_flush_sets, ms, st.s);
-    const auto t0 = std::chrono::steady_clock::now();
-    if (e == hipSuccess) e = hipMemcpyAsync(&hdr, ws.p, sizeof(hdr), hipMemcpyDeviceToHost, st.s);
-    if (e == hipSuccess) e = hipStreamSynchronize(st.s);
-    if (e == hipSuccess && hdr.status == ~0ull) e = hipMemcpy(matrix_out, m.p, m_bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "shared k-mers: %s", hipGetErrorString(e));
-    }
-    if (hdr.status != ~0ull)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "shared k-mers: the weight of set %llu is %lld, weights must be in 0 .. 2^31 - 1",
-                    hdr.status, (long long)weights_or_null[hdr.status]);
-    ms[3] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (info) {
-        info->n_sets_used = (int64_t)hdr.n_used;
-        info->n_colors = C;
-        info->words = s->base.words;
-        info->used_mfma = use_mfma ? 1 : 0;
-        for (uint64_t x = hdr.max_w; x; x >>= 7) info->n_limbs++;
-        for (int i = 0; i < 4; i++) info->pass_ms[i] = ms[i];
-    }
-    return SBWTGPU_OK;
-}
-
-// ---- screen: per-colour k-mer containment of a read set (sbwt_screen.hip) -----------
-}  // extern "C"
-// One device allocation: the counters (256 bytes), set_hits (n_sets int64) and the seen bitmap.  The adds only ever add to it
-// with atomics; the queries take `mu`, run on `stream` and bring their scratch with them.
-struct sbwtgpu_screen {
-    const sbwtgpu_colorsets *s = nullptr;
-    int device = 0;
-    int64_t n_nodes = 0, n_sets = 0, n_words = 0;       // n_words = ceil(n_nodes / 64)
-    DevBuf mem;
-    size_t bytes = 0;
-    SbwtScreenCounters *d_ctr = nullptr;
-    unsigned long long *d_set_hits = nullptr, *d_seen = nullptr;
-    Stream stream;
-    mutable std::mutex mu;
-};
-static int screen_check(const sbwtgpu_screen *x) {
-    if (!x) return fail(SBWTGPU_ERR_INVALID_ARG, "screen: the object is NULL");
-    return colorsets_check(x->s);
-}
-extern "C" {
-
-int sbwtgpu_screen_create(const sbwtgpu_colorsets *s, sbwtgpu_screen **out) {
-    if (!s || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "screen: NULL argument (s and out are needed)");
-    *out = nullptr;
-    const int rc = colorsets_check(s);
-    if (rc != SBWTGPU_OK) return rc;
-    DeviceGuard guard(s->base.device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", s->base.device);
-    sbwtgpu_screen *x = new (std::nothrow) sbwtgpu_screen();
-    if (!x) return fail(SBWTGPU_ERR_OOM, "out of host memory");
-    x->s = s;
-    x->device = s->base.device;
-    x->n_nodes = s->base.n_nodes;
-    x->n_sets = s->n_sets;
-    x->n_words = (x->n_nodes + 63) / 64;
-    const size_t o_hits = 256, o_seen = o_hits + align256((size_t)x->n_sets * 8);
-    x->bytes = o_seen + align256((size_t)x->n_words * 8 + 8);
-    hipError_t e = hipStreamCreateWithFlags(&x->stream.s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = x->mem.alloc(x->bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(x->mem.p, 0, x->bytes, x->stream.s);
-    if (e == hipSuccess) e = hipStreamSynchronize(x->stream.s);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        delete x;
-        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "screen: %s", hipGetErrorString(e));
-    }
-    char *m = static_cast<char *>(x->mem.p);
-    x->d_ctr = reinterpret_cast<SbwtScreenCounters *>(m);
-    x->d_set_hits = reinterpret_cast<unsigned long long *>(m + o_hits);
-    x->d_seen = reinterpret_cast<unsigned long long *>(m + o_seen);
-    *out = x;
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_screen_reset(sbwtgpu_screen *x) {
-    const int rc = screen_check(x);
-    if (rc != SBWTGPU_OK) return rc;
-    DeviceGuard guard(x->device);
-    std::lock_guard<std::mutex> lock(x->mu);
-    // (adds of the caller's on other streams have to be over, as for the queries: the device is waited for, then zeroed)
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemsetAsync(x->mem.p, 0, x->bytes, x->stream.s));
-    HIP_TRY(hipStreamSynchronize(x->stream.s));
-    return SBWTGPU_OK;
-}
-
-void sbwtgpu_screen_destroy(sbwtgpu_screen *x) {
-    if (!x) return;
-    DeviceGuard guard(x->device);
-    delete x;
-}
-
-int64_t sbwtgpu_screen_workspace_bytes(int64_t total_bases, int64_t n_reads, int strands) {
-    return sbwtgpu_pseudoalign_workspace_bytes(total_bases, n_reads, strands);
-}
-
-int sbwtgpu_screen_add_dev(sbwtgpu_screen *x, const char *d_bases, int64_t total_bases, const int64_t *d_read_off, int64_t n_reads,
-                           int strands, void *d_ws, int64_t ws_bytes, void *stream) {
-    int rc = screen_check(x);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
-    if (rc != SBWTGPU_OK) return rc;
-    const sbwtgpu_colorsets *s = x->s;
-    return colors_dev_common(&s->base, d_bases, total_bases, d_read_off, n_reads, strands, d_ws, ws_bytes, stream,
-                             [&](const int *res, const int *res2, const long long *ooff, SbwtPaHeader *, hipStream_t st) {
-                                 sbwt_launch_screen_add(res, res2, ooff, n_reads, total_bases, s->d_ids, x->n_nodes, x->n_sets, x->d_seen,
-                                                        x->d_set_hits, x->d_ctr, st);
-                             });
-}
-
-// Host buffers: read_hits_batch's chunks of whole reads under "screen_chunk_bases", two in flight on the parked slots of the
-// search pipeline.  Bases and offsets go down; only each chunk's status word comes back.
-int sbwtgpu_screen_add_batch(sbwtgpu_screen *x, const char *bases, const int64_t *read_off, int64_t n_reads, int strands) {
-    int rc = screen_check(x);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
-    if (rc != SBWTGPU_OK) return rc;
-    if (n_reads == 0) return SBWTGPU_OK;
-    if (!read_off) return fail(SBWTGPU_ERR_INVALID_ARG, "screen: NULL argument (read_off)");
-    if (read_off[n_reads] > read_off[0] && !bases) return fail(SBWTGPU_ERR_INVALID_ARG, "screen: NULL argument (bases)");
-    const int64_t budget = g_screen_chunk_bases > 0 ? g_screen_chunk_bases : (int64_t)64 << 20, CH_READS = (int64_t)1 << 24;
-    std::vector<int64_t> cuts{0};
-    int64_t max_bases = 0, max_reads = 0;
-    try {
-        for (int64_t lo = 0, r = 0; r < n_reads; r++) {
-            if ((rc = check_read_length(read_off, r)) != SBWTGPU_OK) return rc;
-            if (r > lo && (read_off[r + 1] - read_off[lo] > budget || r - lo >= CH_READS)) {
-                cuts.push_back(r);
-                lo = r;
-            }
-            max_bases = std::max(max_bases, read_off[r + 1] - read_off[lo]);
-            max_reads = std::max(max_reads, r + 1 - lo);
-        }
-        cuts.push_back(n_reads);
-    } catch (const std::bad_alloc &) {
-        return fail(SBWTGPU_ERR_OOM, "out of host memory");
-    }
-    const int64_t n_chunks = (int64_t)cuts.size() - 1;
-    const bool pin_in = is_pinned(bases);
-    const int64_t ws_bytes = sbwtgpu_screen_workspace_bytes(max_bases, max_reads, strands);
-    const int64_t need_in = align256(max_bases + 16) + align256((max_reads + 1) * 8);
-    const int64_t need_dev = need_in + align256(ws_bytes);
-    DeviceGuard guard(x->device);
-    const int n_slots = n_chunks > 1 ? 2 : 1;
-    PipeSlot S[2];
-    if ((rc = take_slots(x->device, S, n_slots, need_in, 0, need_dev, "screen buffers")) != SBWTGPU_OK) return rc;
-    int bug = 0;                    // the first nonzero device status of a chunk
-    const int64_t o_roff = align256(max_bases + 16), o_ws = need_in;
-    auto submit = [&](int64_t c) -> int {
-        PipeSlot &P = S[c % n_slots];
-        const int64_t lo = cuts[(size_t)c], hi = cuts[(size_t)c + 1], nr = hi - lo, nb = read_off[hi] - read_off[lo];
-        int64_t *hro = (int64_t *)(P.h_in + o_roff);
-        for (int64_t r = 0; r <= nr; r++) hro[r] = read_off[lo + r] - read_off[lo];
-        const char *hb = bases + read_off[lo];
-        if (!pin_in && nb > 0) { parallel_memcpy(P.h_in, hb, (size_t)nb); hb = P.h_in; }
-        hipError_t e;
-        if ((nb > 0 && (e = hipMemcpyAsync(P.d_mem, hb, (size_t)nb, hipMemcpyHostToDevice, P.st)) != hipSuccess) ||
-            (e = hipMemcpyAsync(P.d_mem + o_roff, hro, (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, P.st)) != hipSuccess)
-            return fail(SBWTGPU_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
-        const int r2 = sbwtgpu_screen_add_dev(x, P.d_mem, nb, (const int64_t *)(P.d_mem + o_roff), nr, strands, P.d_mem + o_ws, ws_bytes, P.st);
-        if (r2 != SBWTGPU_OK) return r2;
-        const SbwtPaLayout L = sbwt_pa_layout(sbwtgpu_search_workspace_bytes(nb), nb, nr, strands);
-        if ((e = hipMemcpyAsync(P.h_status, P.d_mem + o_ws + L.hdr, 4, hipMemcpyDeviceToHost, P.st)) != hipSuccess)
-            return fail(SBWTGPU_ERR_HIP, "D2H copy: %s", hipGetErrorString(e));
-        return SBWTGPU_OK;
-    };
-    auto collect = [&](int64_t c) -> int {
-        PipeSlot &P = S[c % n_slots];
-        hipError_t e = hipStreamSynchronize(P.st);
-        if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "stream synchronize: %s", hipGetErrorString(e));
-        if (P.h_status[0] != 0 && bug == 0) bug = P.h_status[0];
-        return SBWTGPU_OK;
-    };
-    rc = two_in_flight(n_chunks, submit, collect);
-    park_slots(x->device, S, n_slots, rc);
-    if (rc != SBWTGPU_OK) return rc;
-    if (bug) return fail_status(bug);
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_screen_info(const sbwtgpu_screen *x, int64_t *n_windows, int64_t *n_hits, int64_t *n_seen, int64_t *n_sets,
-                        int32_t *n_colors) {
-    const int rc = screen_check(x);
-    if (rc != SBWTGPU_OK) return rc;
-    if (n_sets) *n_sets = x->n_sets;
-    if (n_colors) *n_colors = x->s->base.n_colors;
-    if (!n_windows && !n_hits && !n_seen) return SBWTGPU_OK;
-    DeviceGuard guard(x->device);
-    std::lock_guard<std::mutex> lock(x->mu);
-    hipStream_t st = x->stream.s;
-    SbwtScreenCounters h;
-    unsigned long long seen = 0;
-    DevBuf d;
-    if (n_seen) {
-        HIP_TRY(d.alloc(8));
-        sbwt_launch_screen_popcount(x->d_seen, x->n_words, static_cast<unsigned long long *>(d.p), st);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&seen, d.p, 8, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipMemcpyAsync(&h, x->d_ctr, sizeof(h), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (n_windows) *n_windows = (int64_t)h.n_windows;
-    if (n_hits) *n_hits = (int64_t)h.n_hits;
-    if (n_seen) *n_seen = (int64_t)seen;
-    return SBWTGPU_OK;
-}
-
-}  // extern "C"
-// what _sets and _colors share: the per-set vectors on the device (d: [set_kmers][set_seen], n_sets int64 each; set_hits is the
-// object's own), enqueued on the object's stream under its mutex
-static int screen_set_vectors(const sbwtgpu_screen *x, DevBuf &d) {
-    HIP_TRY(d.alloc((size_t)x->n_sets * 16));
-    unsigned long long *kmers = static_cast<unsigned long long *>(d.p);
-    sbwt_launch_screen_sets(x->s->d_ids, x->n_nodes, x->n_sets, x->d_seen, kmers, kmers + x->n_sets, x->stream.s);
-    HIP_TRY(hipGetLastError());
-    return SBWTGPU_OK;
-}
-extern "C" {
-
-int sbwtgpu_screen_sets(const sbwtgpu_screen *x, int64_t *set_kmers, int64_t *set_seen, int64_t *set_hits) {
-    int rc = screen_check(x);
-    if (rc != SBWTGPU_OK) return rc;
-    if (!set_kmers && !set_seen && !set_hits) return SBWTGPU_OK;
-    DeviceGuard guard(x->device);
-    std::lock_guard<std::mutex> lock(x->mu);
-    hipStream_t st = x->stream.s;
-    const size_t nb = (size_t)x->n_sets * 8;
-    DevBuf d;
-    if (set_kmers || set_seen) {
-        if ((rc = screen_set_vectors(x, d)) != SBWTGPU_OK) return rc;
-        if (set_kmers) HIP_TRY(hipMemcpyAsync(set_kmers, d.p, nb, hipMemcpyDeviceToHost, st));
-        if (set_seen) HIP_TRY(hipMemcpyAsync(set_seen, static_cast<char *>(d.p) + nb, nb, hipMemcpyDeviceToHost, st));
-    }
-    if (set_hits) HIP_TRY(hipMemcpyAsync(set_hits, x->d_set_hits, nb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_screen_colors(const sbwtgpu_screen *x, int64_t *ref_kmers, int64_t *ref_seen, int64_t *ref_hits) {
-    int rc = screen_check(x);
-    if (rc != SBWTGPU_OK) return rc;
-    if (!ref_kmers && !ref_seen && !ref_hits) return SBWTGPU_OK;
-    DeviceGuard guard(x->device);
-    std::lock_guard<std::mutex> lock(x->mu);
-    hipStream_t st = x->stream.s;
-    const sbwtgpu_colorsets *s = x->s;
-    const int C = s->base.n_colors;
-    const size_t cb = (size_t)C * 8;
-    DevBuf d, ref;
-    if ((rc = screen_set_vectors(x, d)) != SBWTGPU_OK) return rc;
-    HIP_TRY(ref.alloc(3 * cb));
-    unsigned long long *kmers = static_cast<unsigned long long *>(d.p);
-    sbwt_launch_screen_expand(s->d_table, x->n_sets, s->base.words, C, kmers, kmers + x->n_sets, x->d_set_hits,
-                              static_cast<unsigned long long *>(ref.p), st);
-    HIP_TRY(hipGetLastError());
-    if (ref_kmers) HIP_TRY(hipMemcpyAsync(ref_kmers, ref.p, cb, hipMemcpyDeviceToHost, st));
-    if (ref_seen) HIP_TRY(hipMemcpyAsync(ref_seen, static_cast<char *>(ref.p) + cb, cb, hipMemcpyDeviceToHost, st));
-    if (ref_hits) HIP_TRY(hipMemcpyAsync(ref_hits, static_cast<char *>(ref.p) + 2 * cb, cb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_screen_seen_dev(const sbwtgpu_screen *x, const uint64_t **d_seen) {
-    if (!x || !d_seen) return fail(SBWTGPU_ERR_INVALID_ARG, "screen: NULL argument");
-    *d_seen = reinterpret_cast<const uint64_t *>(x->d_seen);
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_screen_seen_copy(const sbwtgpu_screen *x, uint64_t *seen) {
-    const int rc = screen_check(x);
-    if (rc != SBWTGPU_OK) return rc;
-    if (!seen) return fail(SBWTGPU_ERR_INVALID_ARG, "screen: NULL argument (seen)");
-    DeviceGuard guard(x->device);
-    std::lock_guard<std::mutex> lock(x->mu);
-    HIP_TRY(hipMemcpyAsync(seen, x->d_seen, (size_t)x->n_words * 8, hipMemcpyDeviceToHost, x->stream.s));
-    HIP_TRY(hipStreamSynchronize(x->stream.s));
-    return SBWTGPU_OK;
-}
-
-// ---- colour select: k-mers by a predicate over their colour sets (sbwt_colorselect.hip) ------------------
-}  // extern "C"
-namespace {
-// the checks of all three calls; masks: include, then exclude (2 W words, what the kernels read)
-int colorselect_check(const sbwtgpu_colorsets *s, const sbwtgpu_color_predicate *p, bool needs_keys, std::vector<uint64_t> &masks) {
-    if (!s || !p || !p->include) return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: NULL argument (s, the predicate and its include mask are needed)");
-    int rc = colorsets_check(s);
-    if (rc != SBWTGPU_OK) return rc;
-    const int W = s->base.words, C = s->base.n_colors;
-    try { masks.assign((size_t)2 * W, 0); } catch (const std::bad_alloc &) { return fail(SBWTGPU_ERR_OOM, "out of host memory"); }
-    for (int w = 0; w < W; w++) {
-        masks[(size_t)w] = p->include[w];
-        masks[(size_t)W + w] = p->exclude_or_null ? p->exclude_or_null[w] : 0;
-    }
-    if (C & 63) {
-        const uint64_t high = ~0ull << (C & 63);
-        if (masks[(size_t)W - 1] & high)
-            return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: the include mask has a bit at or above n_colors = %d", C);
-        if (masks[(size_t)2 * W - 1] & high)
-            return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: the exclude mask has a bit at or above n_colors = %d", C);
-    }
-    if (p->min_in < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: min_in must not be negative, not %d", p->min_in);
-    if (p->max_in < p->min_in) return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: max_in = %d is below min_in = %d", p->max_in, p->min_in);
-    if (needs_keys) rc = setop_check_index(s->base.idx, "colour select");
-    return rc;
-}
-int colorselect_hip_fail(hipError_t e, const char *what) {
-    (void)hipGetLastError();
-    if (e == hipErrorUnknown)
-        return fail(SBWTGPU_ERR_HIP, "colour select, %s: the ids and the keys disagree about the selected columns (a broken object)", what);
-    return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "colour select, %s: %s", what, hipGetErrorString(e));
-}
-// keys of the index, verdicts, counts and -- with d_res -- the selected keys (a device allocation the caller owns)
-int colorselect_run(const sbwtgpu_colorsets *s, const sbwtgpu_color_predicate *p, const std::vector<uint64_t> &masks, hipStream_t st,
-                    void **d_res, sbwtgpu_color_select_info *info) {
-    const sbwtgpu_index *idx = s->base.idx;
-    const int key_bytes = idx->h.k <= 32 ? 8 : 16;
-    DevBuf keys, cols, dm;
-    long long nk = 0;
-    auto t0 = std::chrono::steady_clock::now();
-    hipError_t e = sbwt_setops_keys(idx->view(), &keys.p, &nk, st, reinterpret_cast<unsigned **>(&cols.p));
-    if (e != hipSuccess) return colorselect_hip_fail(e, "keys");
-    info->pass_ms[0] = ms_since(t0);
-    info->n_real = nk;
-    t0 = std::chrono::steady_clock::now();
-    e = dm.alloc(masks.size() * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(dm.p, masks.data(), masks.size() * 8, hipMemcpyHostToDevice, st);
-    SbwtCselCounts c;
-    if (e == hipSuccess)
-        e = sbwt_colorselect(s->d_ids, s->base.n_nodes, s->d_table, s->n_sets, s->base.words, static_cast<const unsigned long long *>(dm.p),
-                             p->min_in, p->max_in, keys.p, static_cast<const unsigned *>(cols.p), nk, key_bytes, d_res, &c, st);
-    if (e != hipSuccess) return colorselect_hip_fail(e, "verdicts and select");
-    info->pass_ms[1] = ms_since(t0);
-    info->n_selected = c.n_selected;
-    info->n_sets_matched = c.n_sets_matched;
-    return SBWTGPU_OK;
-}
-}  // namespace
-extern "C" {
-
-int sbwtgpu_colorsets_match_sets(const sbwtgpu_colorsets *s, const sbwtgpu_color_predicate *p, uint8_t *match_out) {
-    if (!match_out) return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: match_out is NULL");
-    std::vector<uint64_t> masks;
-    const int rc = colorselect_check(s, p, false, masks);
-    if (rc != SBWTGPU_OK) return rc;
-    DeviceGuard guard(s->base.device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", s->base.device);
-    Stream st;
-    DevBuf dm, dv;
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    HIP_TRY(dm.alloc(masks.size() * 8));
-    HIP_TRY(dv.alloc((size_t)s->n_sets));
-    HIP_TRY(hipMemcpyAsync(dm.p, masks.data(), masks.size() * 8, hipMemcpyHostToDevice, st.s));
-    sbwt_launch_csel_verdict(s->d_table, s->n_sets, s->base.words, static_cast<const unsigned long long *>(dm.p), p->min_in, p->max_in,
-                             static_cast<unsigned char *>(dv.p), st.s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(match_out, dv.p, (size_t)s->n_sets, hipMemcpyDeviceToHost, st.s));
-    HIP_TRY(hipStreamSynchronize(st.s));
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_colorsets_select_counts(const sbwtgpu_colorsets *s, const sbwtgpu_color_predicate *p, sbwtgpu_color_select_info *info) {
-    if (!info) return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: info is NULL");
-    memset(info, 0, sizeof(*info));
-    std::vector<uint64_t> masks;
-    const int rc = colorselect_check(s, p, true, masks);
-    if (rc != SBWTGPU_OK) return rc;
-    DeviceGuard guard(s->base.device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", s->base.device);
-    Stream st;
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    return colorselect_run(s, p, masks, st.s, nullptr, info);
-}
-
-int sbwtgpu_colorsets_select(const sbwtgpu_colorsets *s, const sbwtgpu_color_predicate *p, int build_streaming_support,
-                             sbwtgpu_plain_matrix_bits *out, sbwtgpu_color_select_info *info) {
-    sbwtgpu_color_select_info local;
-    if (!info) info = &local;
-    memset(info, 0, sizeof(*info));
-    if (!out) return fail(SBWTGPU_ERR_INVALID_ARG, "colour select: out is NULL");
-    memset(out, 0, sizeof(*out));
-    std::vector<uint64_t> masks;
-    int rc = colorselect_check(s, p, true, masks);
-    if (rc != SBWTGPU_OK) return rc;
-    DeviceGuard guard(s->base.device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", s->base.device);
-    Stream st;
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    const int64_t k = s->base.k;
-    void *d_res = nullptr;
-    rc = colorselect_run(s, p, masks, st.s, &d_res, info);
-    if (rc != SBWTGPU_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    SbwtBuildState S;
-    try {
-        const int ra = sbwt_build_from_keys(d_res, info->n_selected, (int)k, &S, st.s);     // (S owns d_res now)
-        if (ra != 0) { sbwt_build_release(&S); return fail(ra == -8 ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "colour select: builder tail"); }
-        info->n_nopred = S.n_nopred;
-        if ((long long)S.n_nopred * (long long)k > (1ll << 26)) {
-            sbwt_build_release(&S);
-            return fail(SBWTGPU_ERR_OOM, "colour select: the result has %lld predecessor-less k-mers x k = %lld dummy records (limit 2^26; "
-                        "the dummies are expanded on the host).  Selections are fragmented sets and reach this limit sooner than "
-                        "genomes do: dump the unitigs and use the host builder",
-                        (long long)S.n_nopred, (long long)S.n_nopred * (long long)k);
-        }
-        rc = (k <= 32) ? build_columns_t<unsigned long long>(S, k, build_streaming_support, out)
-                       : build_columns_t<unsigned __int128>(S, k, build_streaming_support, out);
-    } catch (const std::bad_alloc &) {
-        sbwt_build_release(&S);
-        rc = fail(SBWTGPU_ERR_OOM, "out of host memory");
-    }
-    info->pass_ms[2] = ms_since(t0);
-    return rc;
-}
-
-
-// ---- bubbles: variant sites of the plain unitig graph and the colours of each allele (sbwt_bubbles.hip) ----
-}  // extern "C"
-static_assert(sizeof(sbwtgpu_bubble) == sizeof(SbwtBubble), "the record of the ABI is the kernels' record");
-struct sbwtgpu_bubbles {
-    int device = 0;
-    int n_colors = 0, words = 0;
-    SbwtBubbleRun run;
-};
-// what both bubble calls ask of the handle
-static int bubbles_check_handle(const sbwtgpu_unitigs *u) {
-    if (!(u->graph & SBWTGPU_UNITIGS_LINKS))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: the handle was made without SBWTGPU_UNITIGS_LINKS (sbwtgpu_unitigs_create_graph takes the flag)");
-    if (u->colored)
-        return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: a coloured handle cuts the branches at colour breaks: pass the plain handle "
-                    "(sbwtgpu_unitigs_create_graph with idx) plus the colour-set object");
-    return SBWTGPU_OK;
-}
-extern "C" {
-
-int sbwtgpu_bubbles_create(const sbwtgpu_unitigs *u, const sbwtgpu_colorsets *s, sbwtgpu_bubbles **out) {
-    if (!u || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: NULL argument (u and out are needed)");
-    *out = nullptr;
-    int rc = bubbles_check_handle(u);
-    if (rc != SBWTGPU_OK) return rc;
-    if (s) {
-        if (!(u->graph & SBWTGPU_UNITIGS_COLUMN_MAP))
-            return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: branch colours need the column map, and the handle was made without "
-                        "SBWTGPU_UNITIGS_COLUMN_MAP (sbwtgpu_unitigs_create_graph takes the flag)");
-        if ((rc = colorsets_check(s)) != SBWTGPU_OK) return rc;
-        if (s->base.n_nodes != u->n_nodes || s->base.k != u->k)
-            return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: colour sets of %lld columns at k = %lld used with unitigs of an index of %lld columns at k = %lld",
-                        (long long)s->base.n_nodes, (long long)s->base.k, (long long)u->n_nodes, (long long)u->k);
-        if (s->base.device != u->device)
-            return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: the colour sets are on device %d, the unitigs on device %d", s->base.device, u->device);
-    }
-    DeviceGuard guard(u->device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", u->device);
-    sbwtgpu_bubbles *b = new (std::nothrow) sbwtgpu_bubbles();
-    if (!b) return fail(SBWTGPU_ERR_OOM, "out of host memory");
-    b->device = u->device;
-    SbwtBubbleGraph g;
-    g.d_link_off = u->run.d_link_off;
-    g.d_link_to = u->run.d_link_to;
-    g.d_off = u->run.d_off;
-    g.n_unitigs = u->run.n_unitigs;
-    g.n_links = u->run.n_links;
-    g.k = u->k;
-    if (s) {
-        b->n_colors = s->base.n_colors;
-        b->words = s->base.words;
-        g.d_col_unitig = u->run.d_col_unitig;
-        g.n_nodes = u->n_nodes;
-        g.d_ids = s->d_ids;
-        g.d_table = s->d_table;
-        g.words = s->base.words;
-        g.n_colors = s->base.n_colors;
-    }
-    Stream st;
-    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = sbwt_bubbles_run(g, &b->run, st.s);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        delete b;
-        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "bubbles: %s", hipGetErrorString(e));
-    }
-    *out = b;
-    return SBWTGPU_OK;
-}
-
-void sbwtgpu_bubbles_destroy(sbwtgpu_bubbles *b) {
-    if (!b) return;
-    DeviceGuard guard(b->device);
-    if (b->run.d_rec) (void)hipFree(b->run.d_rec);
-    if (b->run.d_inter) (void)hipFree(b->run.d_inter);
-    if (b->run.d_uni) (void)hipFree(b->run.d_uni);
-    delete b;
-}
-
-int sbwtgpu_bubbles_info(const sbwtgpu_bubbles *b, int64_t *n_bubbles, int64_t *n_snps, int32_t *n_colors, int32_t *words) {
-    if (!b) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: the object is NULL");
-    if (!n_bubbles) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: NULL argument (n_bubbles)");
-    *n_bubbles = b->run.n_bubbles;
-    if (n_snps) *n_snps = b->run.n_snps;
-    if (n_colors) *n_colors = b->n_colors;
-    if (words) *words = b->words;
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_bubbles_dev(const sbwtgpu_bubbles *b, const sbwtgpu_bubble **d_rec, const uint64_t **d_inter, const uint64_t **d_union) {
-    if (!b) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: the object is NULL");
-    if (!d_rec) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: NULL argument (d_rec)");
-    *d_rec = reinterpret_cast<const sbwtgpu_bubble *>(b->run.d_rec);
-    if (d_inter) *d_inter = reinterpret_cast<const uint64_t *>(b->run.d_inter);
-    if (d_union) *d_union = reinterpret_cast<const uint64_t *>(b->run.d_uni);
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_bubbles_copy(const sbwtgpu_bubbles *b, sbwtgpu_bubble *rec, uint64_t *inter, uint64_t *uni) {
-    if (!b) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: the object is NULL");
-    const int64_t n = b->run.n_bubbles;
-    if (n == 0) return SBWTGPU_OK;
-    if (!rec) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: NULL argument (rec, for %lld bubbles)", (long long)n);
-    if (b->words > 0 && (!inter || !uni))
-        return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: NULL argument (inter and uni: the object carries branch colours)");
-    DeviceGuard guard(b->device);
-    HIP_TRY(hipMemcpy(rec, b->run.d_rec, (size_t)n * sizeof(sbwtgpu_bubble), hipMemcpyDeviceToHost));
-    if (b->words > 0) {
-        const size_t bytes = (size_t)n * 2 * (size_t)b->words * 8;
-        HIP_TRY(hipMemcpy(inter, b->run.d_inter, bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(uni, b->run.d_uni, bytes, hipMemcpyDeviceToHost));
-    }
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_bubbles_in_degrees_copy(const sbwtgpu_unitigs *u, uint32_t *indeg) {
-    if (!u) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: NULL argument (u)");
-    const int rc = bubbles_check_handle(u);
-    if (rc != SBWTGPU_OK) return rc;
-    const int64_t n = u->run.n_unitigs;
-    if (n == 0) return SBWTGPU_OK;
-    if (!indeg) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: NULL argument (indeg, for %lld unitigs)", (long long)n);
-    DeviceGuard guard(u->device);
-    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", u->device);
-    DevBuf d;
-    Stream st;
-    hipError_t e = d.alloc((size_t)n * 4);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = sbwt_bubbles_in_degrees(u->run.d_link_to, u->run.n_links, n, static_cast<unsigned *>(d.p), st.s);
-    if (e == hipSuccess) e = hipMemcpyAsync(indeg, d.p, (size_t)n * 4, hipMemcpyDeviceToHost, st.s);
-    if (e == hipSuccess) e = hipStreamSynchronize(st.s);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "bubbles: %s", hipGetErrorString(e));
-    }
-    return SBWTGPU_OK;
-}
-
-int sbwtgpu_bubbles_stats(const sbwtgpu_bubbles *b, double pass_ms[4]) {
-    if (!b) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: the object is NULL");
-    if (pass_ms)
-        for (int i = 0; i < SBWT_BB_N_PASSES; i++) pass_ms[i] = (double)b->run.ms[i];
     return SBWTGPU_OK;
 }
 

@@ -468,3 +468,35 @@ def test_one_parking_lot(gpu, case_idx):
     capi.lib().sbwtgpu_release_cached_buffers()
     again = [text(), hits(), search()][::-1]
     assert np.array_equal(again[0], first[0]) and np.array_equal(again[1], first[1]) and again[2] == first[2]
+
+
+def test_errors_of_every_translation_unit_reach_last_error(gpu):
+    """The C ABI is three source files with one error text between them: an error raised in the reads file (read_hits_batch
+    with strands = 3) and one raised in the colour file (pseudoalign_batch on a 65-colour object) are what
+    sbwtgpu_last_error() says afterwards, not the text an earlier error of the main file left there."""
+    orc = OracleIndex.build([synth.random_genome(300, 21).tobytes()], 15, True, False, 4)
+    idx = gpu_index_from_oracle(orc)
+    L = capi.lib()
+    bases, off = capi.concat_reads([b"ACGTACGTACGTACGTACGT", b"TTTTGGGGCCCCAAAATTTTG"])
+    n = len(off) - 1
+
+    def stale():
+        assert L.sbwtgpu_set_tuning(b"no_such_key", 0) == capi.ERR_INVALID_ARG
+        assert b"no_such_key" in L.sbwtgpu_last_error()
+
+    stale()
+    out = np.zeros((n, 4), dtype=np.int32)
+    assert L.sbwtgpu_read_hits_batch(idx.handle, bases.ctypes.data, off.ctypes.data, n, 3, out.ctypes.data) == capi.ERR_INVALID_ARG
+    msg = L.sbwtgpu_last_error().decode()
+    assert msg and "strands" in msg and "3" in msg and "no_such_key" not in msg, msg
+
+    stale()
+    wide = capi.WideColors.create(idx, 65)
+    with pytest.raises(capi.SbwtGpuError) as err:
+        capi.Colors.pseudoalign(wide, bases, off)
+    msg = L.sbwtgpu_last_error().decode()
+    assert err.value.code == capi.ERR_INVALID_ARG and err.value.msg == msg
+    assert msg and "65 colours" in msg and "sbwtgpu_pseudoalign_wide_batch" in msg, msg
+    # and a call that succeeds in each file after them
+    assert len(idx.read_hits(bases, off)) == n and len(wide.pseudoalign(bases, off)[0]) == n
+    wide.close()
