@@ -2,33 +2,50 @@
 // lines (reference src/CLI/sbwt_search.cpp, src/CLI/sbwt.cpp), running the queries on the GPU in
 // batches; plus a minimal in-memory `build` so that indexes can be produced without KMC.
 //
+//   sbwt build  -i <in> -o <index> -k <k> [-p <precalc>] [--add-reverse-complements]
+//               [--no-streaming-support] [-t <threads>]      (subset of sbwt_build.cpp:40-55)
 //   sbwt search -o <out> -i <index> -q <query> [-z]        (sbwt_search.cpp:151-157)
 //   sbwt matching-statistics -i <index> -q <query> -o <out> [-z] [--intervals]
 //               k-bounded matching statistics: one line per read, one token per base ("d", or "d,first,second")
+//   sbwt dump-unitigs -i <index> -o <out> [-z] [--gfa] [--colors <colours> [--sets-out <sets.txt>]]
+//               the index turned back into sequence: FASTA, one record per unitig, the header the unitig's number; --colors
+//               cuts the unitigs where the colour set changes (header "number set-id"); --gfa writes GFA 1, the unitigs as
+//               segments and the links between them
+//   sbwt thread -i <index> -q <reads> -o <walks> [-z] [--colors <colours>] [--coverage <cov.tsv>] [--gfa <graph.gfa>]
+//               the reads threaded through the unitig graph: one line per read, its number, then one
+//               `read_pos:unitig:offset:n_kmers` per step; --coverage: `unitig n_kmers kmer_hits` per unitig
+//   sbwt bubbles -i <index> [-c <colours>] -o <bubbles.tsv> [-z] [--snps-only]
+//               the variant sites of the unitig graph: a header line, then per bubble source, branches, sink, k-mers of each
+//               branch, SNP|OTHER and the two alleles; with -c the colours of each branch
+//   sbwt set-op -a <index A> -b <index B> [--op union|intersection|difference|symmetric-difference] -o <index> [--counts-only]
+//               two index files combined on the GPU without their input sequences: the index `sbwt build` would write for
+//               the result's k-mers
+//   sbwt read-hits -i <index> -q <query> -o <out> [-z] [--both-strands]
+//               one line per read: n_kmers n_found covered_bases longest_run
 //   sbwt build-colors -i <index> -r <refs.txt> -o <colours> [--both-strands] [--wide | --compress [--stream]]
 //               one colour per listed reference file, set on the columns of the index's k-mers that the file holds
 //               (--wide: up to 4096 files, a colour file of several words per column; --compress: up to 4096 files, a
 //               colour-set file of one id per column and the distinct colour sets; --compress --stream: the same file, built
 //               one reference at a time without the wide matrix on the device)
 //   sbwt compress-colors -i <index> -c <colours> -o <colour sets>
-//   sbwt color-matrix -i <index> -c <colours> -o <shared.tsv> [--jaccard-ppm]
 //               the colour-set file of a colour file written with or without --wide
-//   sbwt screen -i <index> -c <colours> -q <reads> -o <screen.tsv> [--both-strands] [--sets-out <sets.tsv>]
-//               a read set screened against the references: per colour its index k-mers, those the reads contain, and the
-//               hits on them; the accumulator stays on the GPU across batches
 //   sbwt merge-colors -u <index U> -a <index A> --colors-a <colours of A> [-b <index B> --colors-b <colours of B>]
 //               [--color-offset <n>] -o <colour sets of U>
 //               the colour sets of A (and B, its colours moved up by the offset) carried onto U's k-mers: run set-op first,
 //               then merge-colors on its output
+//   sbwt color-matrix -i <index> -c <colours> -o <shared.tsv> [--jaccard-ppm]
+//               the k-mers each pair of references shares, C lines of C tab-separated integers; --jaccard-ppm: the Jaccard
+//               index of each pair in parts per million instead
 //   sbwt color-select -i <index> -c <colours> [--include 0,3-5|all] [--exclude <list>] [--min <n>] [--max <n>]
 //               -o <sub-index> [--colors-out <colour sets of the sub-index>] [--counts-only]
 //               the k-mers whose colour set has none of the excluded colours and between min and max of the included ones,
 //               as an index: core (--include g --min |g|), unique (--include g --exclude the others), accessory
 //               (--max C-1), soft core (--include g --min p)
+//   sbwt screen -i <index> -c <colours> -q <reads> -o <screen.tsv> [--both-strands] [--sets-out <sets.tsv>]
+//               a read set screened against the references: per colour its index k-mers, those the reads contain, and the
+//               hits on them; the accumulator stays on the GPU across batches
 //   sbwt pseudoalign -i <index> -c <colours> -q <query> -o <out> [-z] [--threshold 0.7] [--all-kmers] [--both-strands]
 //               one line per read: its number, then the colours that hold it
-//   sbwt build  -i <in> -o <index> -k <k> [-p <precalc>] [--add-reverse-complements]
-//               [--no-streaming-support] [-t <threads>]      (subset of sbwt_build.cpp:40-55)
 // Extra, GPU-only flags of `search` (defaults keep the reference behaviour and output):
 //   --gpu <id>            HIP device to use (default 0)
 //   --gpus <n>            shard every batch over HIP devices 0..n-1 (index replicated by one RCCL broadcast)
@@ -128,6 +145,107 @@ private:
     vector<OptSpec> specs_;
     std::map<string, string> values_;
 };
+
+// ---- what the subcommands share ----
+// Parses the command line (first, so that a bad option is reported before any usage text); without arguments or with --help
+// prints the usage text and leaves with status 1.
+void parse_or_usage(Options &opts, int argc, char **argv, const string &description) {
+    opts.parse(argc, argv);
+    if (argc == 1 || opts.count("help")) {
+        std::cerr << opts.help(argv[0], description) << std::endl;
+        exit(1);
+    }
+}
+// --gpu and --batch-bases (at least 1); the defaults are the strings in each command's spec
+void use_gpu_option(const Options &opts) { set_default_device(atoi(opts.get("gpu").c_str())); }
+int64_t batch_bases_option(const Options &opts) { return std::max<int64_t>(1, atoll(opts.get("batch-bases").c_str())); }
+
+// `refusal` names the path in the sentence that refuses another variant ("GPU path", "GPU search path")
+void load_plain_matrix(const string &indexfile, plain_matrix_sbwt_t &index, const char *refusal = "GPU path") {
+    std::ifstream in(indexfile, std::ios::binary);
+    if (!in.good()) throw std::runtime_error("Error opening file: " + indexfile);
+    const string variant = load_string(in);
+    if (variant != "plain-matrix")
+        throw std::runtime_error(string("Error: only the plain-matrix variant is supported by the ") + refusal + " (got " + variant + ")");
+    index.load(in);
+}
+
+// --precalc-length of the commands that write an index, at most k (sbwt_build.cpp:101-105)
+int64_t precalc_option(const Options &opts, int64_t k) {
+    const int64_t precalc = atoll(opts.get("precalc-length").c_str());
+    if (precalc <= k) return precalc;
+    write_log("Warning: precalc length " + std::to_string(precalc) + " is longer than k = " + std::to_string(k), LogLevel::MAJOR);
+    write_log("Setting precalc length to " + std::to_string(k), LogLevel::MAJOR);
+    return k;
+}
+// the index file of `sbwt build`: the variant's name (sbwt_build.cpp:142), then the index with the intervals of all strings
+// of `precalc` characters (sbwt_build.cpp:157); the bytes the index took come back
+int64_t write_index_file(plain_matrix_sbwt_t &index, const string &file, int64_t precalc) {
+    std::ofstream out(file, std::ios::binary);
+    if (!out.good()) throw std::runtime_error("Error opening file: " + file);
+    serialize_string("plain-matrix", out);
+    index.do_kmer_prefix_precalc(precalc);
+    return index.serialize(out);
+}
+
+// --query-file and --out-file of search, matching-statistics and read-hits: one file each, or with a query file named *.txt
+// two lists of files, one per line.  Every input is checked for reading, then every output for writing (which creates it);
+// --out-file is looked at after the inputs (sbwt_search.cpp:170-190).
+struct QueryFiles { vector<string> in, out; };
+QueryFiles query_and_output_files(const Options &opts) {
+    const string queryfile = opts.get("query-file");
+    const bool multi_file = queryfile.size() >= 4 && queryfile.substr(queryfile.size() - 4) == ".txt";
+    QueryFiles f;
+    f.in = multi_file ? readlines(queryfile) : vector<string>{queryfile};
+    for (const string &file : f.in) check_readable(file);
+    const string outfile = opts.get("out-file");
+    f.out = multi_file ? readlines(outfile) : vector<string>{outfile};
+    for (const string &file : f.out) check_writable(file);
+    return f;
+}
+void check_same_count(const QueryFiles &f) {   // run_queries, sbwt_search.cpp:111-115
+    if (f.in.size() != f.out.size())
+        throw std::runtime_error("Number of input and output files does not match (" + std::to_string(f.in.size()) + " vs " +
+                                 std::to_string(f.out.size()) + ")");
+}
+
+// Reads `reader` to its end in batches of about batch_bases bases: fn(bases, read_off, n_reads) for every batch that holds a
+// read.  The caller opens the reader, since where it is opened relative to the log line and to the output file shows.
+template <typename Fn>
+void for_each_batch(seq_io::Reader &reader, int64_t batch_bases, Fn &&fn) {
+    vector<char> bases;
+    vector<int64_t> read_off;
+    for (bool more = true; more;) {
+        bases.clear();
+        read_off.assign(1, 0);
+        more = reader.read_batch(bases, read_off, batch_bases);
+        const int64_t n_reads = (int64_t)read_off.size() - 1;
+        if (n_reads > 0) fn(bases, read_off, n_reads);
+    }
+}
+
+void write_text_file(const string &path, const string &text, bool gzip) {
+    if (sbwthost_write_file(path.c_str(), text.data(), (int64_t)text.size(), gzip ? 1 : 0, 0) != 0)
+        throw std::runtime_error(string("Error writing ") + path + ": " + sbwthost_last_error());
+}
+
+void append_int(int64_t x, string &out) {
+    char buf[24];
+    int i = 0;
+    if (x == 0) buf[i++] = '0';
+    while (x > 0) { buf[i++] = (char)('0' + x % 10); x /= 10; }
+    while (i > 0) out.push_back(buf[--i]);
+}
+// the set bits of a `words`-word row as ascending colour numbers: `first` before the first one, `sep` before every other
+void append_set_bits(const uint64_t *row, int64_t words, const char *first, const char *sep, string &out) {
+    const char *lead = first;
+    for (int64_t w = 0; w < words; w++)
+        for (uint64_t bits = row[w]; bits; bits &= bits - 1) {
+            out.append(lead);
+            append_int(w * 64 + __builtin_ctzll(bits), out);
+            lead = sep;
+        }
+}
 
 // print_vector, sbwt_search.cpp:21-43: each value followed by one space, '\n' per read; -1 special
 // cased; 0 prints as an empty token (kept: that is what the reference emits)
@@ -431,27 +549,11 @@ int search_main(int argc, char **argv) {
         {"host-format", 0, false, "Format the output on the CPU (print_vector) instead of on the GPU.", ""},
         {"help", 'h', false, "Print usage", ""},
     });
-    opts.parse(argc, argv);
-    if (argc == 1 || opts.count("help")) {
-        std::cerr << opts.help(argv[0], "Query all k-mers of all input reads.") << std::endl;
-        exit(1);
-    }
+    parse_or_usage(opts, argc, argv, "Query all k-mers of all input reads.");
     string indexfile = opts.get("index-file");
     check_readable(indexfile);
-
-    string queryfile = opts.get("query-file");
-    vector<string> input_files;
-    bool multi_file = queryfile.size() >= 4 && queryfile.substr(queryfile.size() - 4) == ".txt";
-    if (multi_file) input_files = readlines(queryfile);
-    else input_files = {queryfile};
-    for (const string &file : input_files) check_readable(file);
-
-    string outfile = opts.get("out-file");
+    const QueryFiles files = query_and_output_files(opts);
     bool gzip_output = opts.count("gzip-output");
-    vector<string> output_files;
-    if (multi_file) output_files = readlines(outfile);
-    else output_files = {outfile};
-    for (const string &file : output_files) check_writable(file);
 
     vector<int> devices;
     if (opts.get("gpu-list") != "-") {
@@ -468,8 +570,7 @@ int search_main(int argc, char **argv) {
         else devices.push_back(atoi(opts.get("gpu").c_str()));
     }
     set_default_device(devices[0]);
-    int64_t batch_bases = atoll(opts.get("batch-bases").c_str());
-    if (batch_bases < 1) batch_bases = 1;
+    const int64_t batch_bases = batch_bases_option(opts);
 
     std::ifstream in(indexfile, std::ios::binary);
     if (!in.good()) throw std::runtime_error("Error opening file: " + indexfile);
@@ -484,9 +585,7 @@ int search_main(int argc, char **argv) {
     if (variant != "plain-matrix")
         throw std::runtime_error("Error: only the plain-matrix variant is supported by the GPU search path (got " +
                                  variant + ")");
-    if (input_files.size() != output_files.size())   // run_queries, sbwt_search.cpp:111-115
-        throw std::runtime_error("Number of input and output files does not match (" +
-                                 std::to_string(input_files.size()) + " vs " + std::to_string(output_files.size()) + ")");
+    check_same_count(files);
     // The index loads (file, HIP start-up, device image: a few tenths of a second) on a thread of its own while the first
     // input file is already being parsed; the search waits for it.
     plain_matrix_sbwt_t index;
@@ -516,8 +615,8 @@ int search_main(int argc, char **argv) {
     };
     int64_t number_of_queries = 0;
     try {
-        for (size_t i = 0; i < input_files.size(); i++)
-            number_of_queries += run_file(input_files[i], output_files[i], get_index, gzip_output, batch_bases,
+        for (size_t i = 0; i < files.in.size(); i++)
+            number_of_queries += run_file(files.in[i], files.out[i], get_index, gzip_output, batch_bases,
                                           opts.count("host-format")).queries;
     } catch (...) {
         if (!joined) { loader.join(); joined = true; }
@@ -548,11 +647,7 @@ int build_main(int argc, char **argv) {
         {"gpu", 0, true, "HIP device used for the prefix table.", "0"},
         {"help", 'h', false, "Print usage", ""},
     });
-    opts.parse(argc, argv);
-    if (argc == 1 || opts.count("help")) {
-        std::cerr << opts.help(argv[0], "Construct a plain-matrix SBWT (in memory).") << std::endl;
-        exit(1);
-    }
+    parse_or_usage(opts, argc, argv, "Construct a plain-matrix SBWT (in memory).");
     string variant = opts.get("variant");
     if (variant != "plain-matrix") {
         std::cerr << "Error: unknown variant: " << variant << std::endl;
@@ -566,13 +661,8 @@ int build_main(int argc, char **argv) {
     else input_files = {in_file};
     for (const string &f : input_files) check_readable(f);
     int64_t k = atoll(opts.get("kmer-length").c_str());
-    int64_t precalc = atoll(opts.get("precalc-length").c_str());
-    if (precalc > k) {   // sbwt_build.cpp:101-105
-        write_log("Warning: precalc length " + std::to_string(precalc) + " is longer than k = " + std::to_string(k), LogLevel::MAJOR);
-        write_log("Setting precalc length to " + std::to_string(k), LogLevel::MAJOR);
-        precalc = k;
-    }
-    set_default_device(atoi(opts.get("gpu").c_str()));
+    const int64_t precalc = precalc_option(opts, k);
+    use_gpu_option(opts);
     vector<string> seqs;
     for (const string &f : input_files) {
         seq_io::Reader reader(f);
@@ -588,11 +678,7 @@ int build_main(int argc, char **argv) {
     plain_matrix_sbwt_t index(bits, 0);
     write_log("Build SBWT for " + std::to_string(index.number_of_kmers()) + " distinct k-mers", LogLevel::MAJOR);
     write_log("SBWT has " + std::to_string(index.number_of_subsets()) + " subsets", LogLevel::MAJOR);
-    std::ofstream out(out_file, std::ios::binary);
-    if (!out.good()) throw std::runtime_error("Error opening file: " + out_file);
-    serialize_string(variant, out);                       // sbwt_build.cpp:142
-    index.do_kmer_prefix_precalc(precalc);                // sbwt_build.cpp:157
-    int64_t bytes_written = index.serialize(out);
+    const int64_t bytes_written = write_index_file(index, out_file, precalc);
     write_log("Built variant " + variant + " to file " + out_file, LogLevel::MAJOR);
     write_log("Space on disk: " + std::to_string(bytes_written * 8.0 / (double)index.number_of_subsets()) +
                   " bits per column, " + std::to_string(bytes_written * 8.0 / (double)index.number_of_kmers()) +
@@ -604,14 +690,6 @@ int build_main(int argc, char **argv) {
 // `sbwt matching-statistics`: the query handling of `search` (FASTA / FASTQ, gzipped, .txt lists of files), one line per
 // read with one token per base, each followed by a space (print_vector's layout): the match length d, or "d,first,second"
 // with --intervals.  Batches go to the GPU one at a time; the text is formatted on the host.
-void append_int(int64_t x, string &out) {
-    char buf[24];
-    int i = 0;
-    if (x == 0) buf[i++] = '0';
-    while (x > 0) { buf[i++] = (char)('0' + x % 10); x /= 10; }
-    while (i > 0) out.push_back(buf[--i]);
-}
-
 int matching_statistics_main(int argc, char **argv) {
     int64_t micros_start = cur_time_micros();
     set_log_level(LogLevel::MINOR);
@@ -627,52 +705,28 @@ int matching_statistics_main(int argc, char **argv) {
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "67108864"},
         {"help", 'h', false, "Print usage", ""},
     });
-    opts.parse(argc, argv);
-    if (argc == 1 || opts.count("help")) {
-        std::cerr << opts.help(argv[0], "k-bounded matching statistics of every base of all input reads.") << std::endl;
-        exit(1);
-    }
+    parse_or_usage(opts, argc, argv, "k-bounded matching statistics of every base of all input reads.");
     const string indexfile = opts.get("index-file");
     check_readable(indexfile);
-    const string queryfile = opts.get("query-file"), outfile = opts.get("out-file");
-    const bool multi_file = queryfile.size() >= 4 && queryfile.substr(queryfile.size() - 4) == ".txt";
-    const vector<string> input_files = multi_file ? readlines(queryfile) : vector<string>{queryfile};
-    const vector<string> output_files = multi_file ? readlines(outfile) : vector<string>{outfile};
-    for (const string &file : input_files) check_readable(file);
-    for (const string &file : output_files) check_writable(file);
-    if (input_files.size() != output_files.size())
-        throw std::runtime_error("Number of input and output files does not match (" + std::to_string(input_files.size()) +
-                                 " vs " + std::to_string(output_files.size()) + ")");
+    const QueryFiles files = query_and_output_files(opts);
+    check_same_count(files);
     const bool gzip_output = opts.count("gzip-output"), intervals = opts.count("intervals");
-    set_default_device(atoi(opts.get("gpu").c_str()));
-    int64_t batch_bases = atoll(opts.get("batch-bases").c_str());
-    if (batch_bases < 1) batch_bases = 1;
+    use_gpu_option(opts);
+    const int64_t batch_bases = batch_bases_option(opts);
 
-    std::ifstream in(indexfile, std::ios::binary);
-    if (!in.good()) throw std::runtime_error("Error opening file: " + indexfile);
-    const string variant = load_string(in);
-    if (variant != "plain-matrix")
-        throw std::runtime_error("Error: only the plain-matrix variant is supported by the GPU search path (got " + variant + ")");
     plain_matrix_sbwt_t index;
-    index.load(in);
+    load_plain_matrix(indexfile, index, "GPU search path");
     int64_t positions = 0;
-    for (size_t f = 0; f < input_files.size(); f++) {
-        write_log("Running matching statistics from input file " + input_files[f] + " to output file " + output_files[f],
+    for (size_t f = 0; f < files.in.size(); f++) {
+        write_log("Running matching statistics from input file " + files.in[f] + " to output file " + files.out[f],
                   LogLevel::MAJOR);
-        seq_io::Reader reader(input_files[f]);
-        seq_io::Buffered_ofstream writer(output_files[f], gzip_output);
-        bool more = true;
-        vector<char> bases;
-        vector<int64_t> read_off;
+        seq_io::Reader reader(files.in[f]);
+        seq_io::Buffered_ofstream writer(files.out[f], gzip_output);
         vector<uint8_t> len;
         vector<int64_t> first, second;
         string text;
-        while (more) {
-            bases.clear();
-            read_off.assign(1, 0);
-            more = reader.read_batch(bases, read_off, batch_bases);
-            const int64_t n_reads = (int64_t)read_off.size() - 1, total = read_off.back();
-            if (n_reads <= 0) continue;
+        for_each_batch(reader, batch_bases, [&](const vector<char> &bases, const vector<int64_t> &read_off, int64_t n_reads) {
+            const int64_t total = read_off.back();
             len.resize((size_t)total);
             if (intervals) { first.resize((size_t)total); second.resize((size_t)total); }
             index.matching_statistics_batch(bases.data(), read_off.data(), n_reads, len.data(), intervals ? first.data() : nullptr,
@@ -693,7 +747,7 @@ int matching_statistics_main(int argc, char **argv) {
             }
             writer.write(text.data(), (int64_t)text.size());
             positions += total;
-        }
+        });
     }
     write_log("us/base end-to-end: " + std::to_string((double)(cur_time_micros() - micros_start) / (double)std::max<int64_t>(1, positions)),
               LogLevel::MAJOR);
@@ -718,51 +772,26 @@ int read_hits_main(int argc, char **argv) {
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
     });
-    opts.parse(argc, argv);
-    if (argc == 1 || opts.count("help")) {
-        std::cerr << opts.help(argv[0], "Per read: k-mers, k-mers found in the index, bases they cover, longest run of found k-mers.") << std::endl;
-        exit(1);
-    }
+    parse_or_usage(opts, argc, argv, "Per read: k-mers, k-mers found in the index, bases they cover, longest run of found k-mers.");
     const string indexfile = opts.get("index-file");
     check_readable(indexfile);
-    const string queryfile = opts.get("query-file"), outfile = opts.get("out-file");
-    const bool multi_file = queryfile.size() >= 4 && queryfile.substr(queryfile.size() - 4) == ".txt";
-    const vector<string> input_files = multi_file ? readlines(queryfile) : vector<string>{queryfile};
-    const vector<string> output_files = multi_file ? readlines(outfile) : vector<string>{outfile};
-    for (const string &file : input_files) check_readable(file);
-    for (const string &file : output_files) check_writable(file);
-    if (input_files.size() != output_files.size())
-        throw std::runtime_error("Number of input and output files does not match (" + std::to_string(input_files.size()) +
-                                 " vs " + std::to_string(output_files.size()) + ")");
+    const QueryFiles files = query_and_output_files(opts);
+    check_same_count(files);
     const bool gzip_output = opts.count("gzip-output");
     const int strands = opts.count("both-strands") ? 2 : 1;
-    set_default_device(atoi(opts.get("gpu").c_str()));
-    int64_t batch_bases = atoll(opts.get("batch-bases").c_str());
-    if (batch_bases < 1) batch_bases = 1;
+    use_gpu_option(opts);
+    const int64_t batch_bases = batch_bases_option(opts);
 
-    std::ifstream in(indexfile, std::ios::binary);
-    if (!in.good()) throw std::runtime_error("Error opening file: " + indexfile);
-    const string variant = load_string(in);
-    if (variant != "plain-matrix")
-        throw std::runtime_error("Error: only the plain-matrix variant is supported by the GPU search path (got " + variant + ")");
     plain_matrix_sbwt_t index;
-    index.load(in);
+    load_plain_matrix(indexfile, index, "GPU search path");
     int64_t total_reads = 0;
-    for (size_t f = 0; f < input_files.size(); f++) {
-        write_log("Running read-hits from input file " + input_files[f] + " to output file " + output_files[f], LogLevel::MAJOR);
-        seq_io::Reader reader(input_files[f]);
-        seq_io::Buffered_ofstream writer(output_files[f], gzip_output);
-        bool more = true;
-        vector<char> bases;
-        vector<int64_t> read_off;
+    for (size_t f = 0; f < files.in.size(); f++) {
+        write_log("Running read-hits from input file " + files.in[f] + " to output file " + files.out[f], LogLevel::MAJOR);
+        seq_io::Reader reader(files.in[f]);
+        seq_io::Buffered_ofstream writer(files.out[f], gzip_output);
         vector<sbwtgpu_read_hits> rec;
         string text;
-        while (more) {
-            bases.clear();
-            read_off.assign(1, 0);
-            more = reader.read_batch(bases, read_off, batch_bases);
-            const int64_t n_reads = (int64_t)read_off.size() - 1;
-            if (n_reads <= 0) continue;
+        for_each_batch(reader, batch_bases, [&](const vector<char> &bases, const vector<int64_t> &read_off, int64_t n_reads) {
             rec.resize((size_t)n_reads);
             index.read_hits_batch(bases.data(), read_off.data(), n_reads, strands, rec.data());
             text.clear();
@@ -778,7 +807,7 @@ int read_hits_main(int argc, char **argv) {
             }
             writer.write(text.data(), (int64_t)text.size());
             total_reads += n_reads;
-        }
+        });
     }
     write_log("us/read end-to-end: " + std::to_string((double)(cur_time_micros() - micros_start) / (double)std::max<int64_t>(1, total_reads)),
               LogLevel::MAJOR);
@@ -840,11 +869,7 @@ int dump_unitigs_main(int argc, char **argv) {
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"help", 'h', false, "Print usage", ""},
     });
-    opts.parse(argc, argv);
-    if (argc == 1 || opts.count("help")) {
-        std::cerr << opts.help(argv[0], "Write the unitigs of the de Bruijn graph of the indexed k-mers as FASTA.") << std::endl;
-        exit(1);
-    }
+    parse_or_usage(opts, argc, argv, "Write the unitigs of the de Bruijn graph of the indexed k-mers as FASTA.");
     const string indexfile = opts.get("index-file"), outfile = opts.get("out-file");
     const bool colored = opts.count("colors");
     if (opts.count("sets-out") && !colored) throw std::runtime_error("Error: --sets-out needs --colors");
@@ -853,14 +878,9 @@ int dump_unitigs_main(int argc, char **argv) {
     if (colored) check_readable(colorsfile);
     check_writable(outfile);
     if (!setsfile.empty()) check_writable(setsfile);
-    set_default_device(atoi(opts.get("gpu").c_str()));
-    std::ifstream in(indexfile, std::ios::binary);
-    if (!in.good()) throw std::runtime_error("Error opening file: " + indexfile);
-    const string variant = load_string(in);
-    if (variant != "plain-matrix")
-        throw std::runtime_error("Error: only the plain-matrix variant is supported by the GPU path (got " + variant + ")");
+    use_gpu_option(opts);
     plain_matrix_sbwt_t index;
-    index.load(in);
+    load_plain_matrix(indexfile, index);
     const bool gfa = opts.count("gfa");
     if (colored) return dump_unitigs_colored(index, indexfile, colorsfile, outfile, setsfile, opts.count("gzip-output"), gfa);
     const plain_matrix_sbwt_t::Unitigs u = index.unitigs(gfa);
@@ -878,8 +898,7 @@ int dump_unitigs_main(int argc, char **argv) {
             text.push_back('\n');
         }
     }
-    if (sbwthost_write_file(outfile.c_str(), text.data(), (int64_t)text.size(), opts.count("gzip-output") ? 1 : 0, 0) != 0)
-        throw std::runtime_error(string("Error writing ") + outfile + ": " + sbwthost_last_error());
+    write_text_file(outfile, text, opts.count("gzip-output"));
     write_log("Wrote " + std::to_string(n) + " unitigs, " + std::to_string(u.bases.size()) + " bases" +
                   (gfa ? ", " + std::to_string(u.link_to.size()) + " links" : string()),
               LogLevel::MAJOR);
@@ -901,11 +920,7 @@ int set_op_main(int argc, char **argv) {
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"help", 'h', false, "Print usage", ""},
     });
-    opts.parse(argc, argv);
-    if (argc == 1 || opts.count("help")) {
-        std::cerr << opts.help(argv[0], "Union, intersection or difference of the k-mer sets of two indexes, as an index.") << std::endl;
-        exit(1);
-    }
+    parse_or_usage(opts, argc, argv, "Union, intersection or difference of the k-mer sets of two indexes, as an index.");
     static const vector<string> names = {"union", "intersection", "difference", "symmetric-difference"};
     const string opname = opts.get("op");
     int op = -1;
@@ -918,17 +933,10 @@ int set_op_main(int argc, char **argv) {
     check_readable(file_a);
     check_readable(file_b);
     if (!counts_only) check_writable(out_file);
-    set_default_device(atoi(opts.get("gpu").c_str()));
+    use_gpu_option(opts);
     plain_matrix_sbwt_t A, B;
-    for (int i = 0; i < 2; i++) {
-        const string &f = i ? file_b : file_a;
-        std::ifstream in(f, std::ios::binary);
-        if (!in.good()) throw std::runtime_error("Error opening file: " + f);
-        const string variant = load_string(in);
-        if (variant != "plain-matrix")
-            throw std::runtime_error("Error: only the plain-matrix variant is supported by the GPU path (got " + variant + ")");
-        (i ? B : A).load(in);
-    }
+    load_plain_matrix(file_a, A);
+    load_plain_matrix(file_b, B);
     auto log_counts = [](const sbwtgpu_setop_info &c) {
         write_log("k-mers: " + std::to_string(c.n_a) + " in a, " + std::to_string(c.n_b) + " in b, " + std::to_string(c.n_both) +
                       " in both, " + std::to_string(c.n_either) + " in either; Jaccard index " +
@@ -941,24 +949,14 @@ int set_op_main(int argc, char **argv) {
         std::cout << c.n_a << " " << c.n_b << " " << c.n_both << " " << c.n_either << std::endl;
         return 0;
     }
-    const int64_t k = A.get_k();
-    int64_t precalc = atoll(opts.get("precalc-length").c_str());
-    if (precalc > k) {
-        write_log("Warning: precalc length " + std::to_string(precalc) + " is longer than k = " + std::to_string(k), LogLevel::MAJOR);
-        write_log("Setting precalc length to " + std::to_string(k), LogLevel::MAJOR);
-        precalc = k;
-    }
+    const int64_t precalc = precalc_option(opts, A.get_k());
     sbwtgpu_setop_info info;
     PlainMatrixBits bits = plain_matrix_sbwt_t::set_operation(A, B, op, !opts.count("no-streaming-support"), &info);
     log_counts(info);
     plain_matrix_sbwt_t index(bits, 0);
     write_log("The " + opname + " has " + std::to_string(index.number_of_kmers()) + " distinct k-mers, " +
                   std::to_string(index.number_of_subsets()) + " subsets", LogLevel::MAJOR);
-    std::ofstream out(out_file, std::ios::binary);
-    if (!out.good()) throw std::runtime_error("Error opening file: " + out_file);
-    serialize_string("plain-matrix", out);
-    index.do_kmer_prefix_precalc(precalc);
-    index.serialize(out);
+    write_index_file(index, out_file, precalc);
     write_log("Wrote the index to " + out_file, LogLevel::MAJOR);
     return 0;
 }
@@ -1009,6 +1007,52 @@ bool file_has_magic(const string &file, const char *magic) {
     return in.gcount() == 8 && memcmp(got, magic, 8) == 0;
 }
 
+void host_check(int rc) {
+    if (rc != 0) throw std::runtime_error(sbwthost_last_error());
+}
+
+// A colour file of `index` read and put on the device; a file of another index is refused.  What the file may be:
+//   ROWS_ONLY    an "SBWTCOL1" or "SBWTCOL2" file, both through the wide reader into a wide colours object (compress-colors)
+//   ANY_AS_WIDE  the same, or an "SBWTCOL3" file into a colour-set object (load_colorsets)
+//   ANY          "SBWTCOL3" into a colour-set object, "SBWTCOL2" into a wide colours object, anything else through the
+//                narrow reader into a narrow one: the three routes of pseudoalign
+struct ColorFile {
+    enum Accept { ROWS_ONLY, ANY_AS_WIDE, ANY };
+    ColorsHandle col;          // one of col.h and sets.h is set
+    ColorSetsHandle sets;
+    bool wide = true;          // col holds rows of `words` words (sbwtgpu_colors_create_wide)
+    int64_t words = 1;
+};
+void load_color_file(const string &colorsfile, const string &indexfile, const plain_matrix_sbwt_t &index, ColorFile::Accept accept,
+                     ColorFile &out) {
+    const char *file = colorsfile.c_str();
+    const bool sets = accept != ColorFile::ROWS_ONLY && file_has_magic(colorsfile, "SBWTCOL3");
+    const bool wide = sets || accept != ColorFile::ANY || file_has_magic(colorsfile, "SBWTCOL2");
+    int64_t n_columns = 0, n_colors = 0, ck = 0, words = 1, n_sets = 0;
+    host_check(sets   ? sbwthost_colorsets_read(file, &n_columns, &n_colors, &ck, &words, &n_sets, nullptr, 0, nullptr, 0)
+               : wide ? sbwthost_colors_read_wide(file, &n_columns, &n_colors, &ck, &words, nullptr, 0)
+                      : sbwthost_colors_read(file, &n_columns, &n_colors, &ck, nullptr, 0));
+    if (n_columns != index.number_of_subsets() || ck != index.get_k())
+        throw std::runtime_error("Error: " + colorsfile + " colours an index of " + std::to_string(n_columns) + " columns at k = " +
+                                 std::to_string(ck) + ", " + indexfile + " has " + std::to_string(index.number_of_subsets()) +
+                                 " columns at k = " + std::to_string(index.get_k()));
+    if (sets) {
+        vector<uint32_t> ids((size_t)n_columns);
+        vector<uint64_t> table((size_t)(n_sets * words));
+        host_check(sbwthost_colorsets_read(file, &n_columns, &n_colors, &ck, &words, &n_sets, ids.data(), n_columns, table.data(),
+                                           n_sets * words));
+        colors_check(sbwtgpu_colorsets_create(index.device_handle(), (int)n_colors, ids.data(), n_sets, table.data(), &out.sets.h));
+    } else {
+        vector<uint64_t> rows((size_t)(n_columns * words));
+        host_check(wide ? sbwthost_colors_read_wide(file, &n_columns, &n_colors, &ck, &words, rows.data(), n_columns * words)
+                        : sbwthost_colors_read(file, &n_columns, &n_colors, &ck, rows.data(), n_columns));
+        if (wide) colors_check(sbwtgpu_colors_create_wide(index.device_handle(), (int)n_colors, rows.data(), &out.col.h));
+        else colors_check(sbwtgpu_colors_create(index.device_handle(), (int)n_colors, rows.data(), &out.col.h));
+    }
+    out.wide = wide;
+    out.words = words;
+}
+
 // writes a colour-set object as an "SBWTCOL3" file; count_color >= 0: *count_out = the columns whose set holds that colour
 void write_colorsets(const sbwtgpu_colorsets *sets, const string &outfile, int count_color = -1, int64_t *count_out = nullptr) {
     int64_t n_columns = 0, ck = 0, n_sets = 0, n_colored = 0, bytes = 0;
@@ -1021,8 +1065,7 @@ void write_colorsets(const sbwtgpu_colorsets *sets, const string &outfile, int c
         *count_out = 0;
         for (uint32_t id : ids) *count_out += (int64_t)((table[(size_t)id * words + (count_color >> 6)] >> (count_color & 63)) & 1u);
     }
-    if (sbwthost_colorsets_write(outfile.c_str(), ids.data(), table.data(), n_columns, n_colors, ck, n_sets) != 0)
-        throw std::runtime_error(sbwthost_last_error());
+    host_check(sbwthost_colorsets_write(outfile.c_str(), ids.data(), table.data(), n_columns, n_colors, ck, n_sets));
     write_log("Wrote " + std::to_string(n_sets) + " colour sets of " + std::to_string(n_colors) + " colours over " +
                   std::to_string(n_colored) + " coloured columns (" + std::to_string(bytes) + " bytes on the device) to " + outfile,
               LogLevel::MAJOR);
@@ -1033,15 +1076,6 @@ void compress_and_write(const sbwtgpu_colors *col, const string &outfile) {
     ColorSetsHandle sets;
     colors_check(sbwtgpu_colorsets_compress(col, &sets.h));
     write_colorsets(sets.h, outfile);
-}
-
-void load_plain_matrix(const string &indexfile, plain_matrix_sbwt_t &index) {
-    std::ifstream in(indexfile, std::ios::binary);
-    if (!in.good()) throw std::runtime_error("Error opening file: " + indexfile);
-    const string variant = load_string(in);
-    if (variant != "plain-matrix")
-        throw std::runtime_error("Error: only the plain-matrix variant is supported by the GPU path (got " + variant + ")");
-    index.load(in);
 }
 
 // sbwt build-colors: refs.txt holds one sequence file per line, colour = 0-based line number (at most 64, with --wide at most
@@ -1060,11 +1094,7 @@ int build_colors_main(int argc, char **argv) {
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
     });
-    opts.parse(argc, argv);
-    if (argc == 1 || opts.count("help")) {
-        std::cerr << opts.help(argv[0], "Colour the k-mers of an index by the reference files that hold them.") << std::endl;
-        exit(1);
-    }
+    parse_or_usage(opts, argc, argv, "Colour the k-mers of an index by the reference files that hold them.");
     const string indexfile = opts.get("index-file"), refsfile = opts.get("refs"), outfile = opts.get("out-file");
     check_readable(indexfile);
     check_readable(refsfile);
@@ -1083,9 +1113,8 @@ int build_colors_main(int argc, char **argv) {
     for (const string &file : refs) check_readable(file);
     check_writable(outfile);
     const int strands = opts.count("both-strands") ? 2 : 1;
-    set_default_device(atoi(opts.get("gpu").c_str()));
-    int64_t batch_bases = atoll(opts.get("batch-bases").c_str());
-    if (batch_bases < 1) batch_bases = 1;
+    use_gpu_option(opts);
+    const int64_t batch_bases = batch_bases_option(opts);
     plain_matrix_sbwt_t index;
     load_plain_matrix(indexfile, index);
     ColorsHandle col;
@@ -1097,15 +1126,7 @@ int build_colors_main(int argc, char **argv) {
     int open_color = -1;            // --stream: the colour that only finish closes
     for (size_t c = 0; c < refs.size(); c++) {
         seq_io::Reader reader(refs[c]);
-        bool more = true;
-        vector<char> bases;
-        vector<int64_t> read_off;
-        while (more) {
-            bases.clear();
-            read_off.assign(1, 0);
-            more = reader.read_batch(bases, read_off, batch_bases);
-            const int64_t n_reads = (int64_t)read_off.size() - 1;
-            if (n_reads <= 0) continue;
+        for_each_batch(reader, batch_bases, [&](const vector<char> &bases, const vector<int64_t> &read_off, int64_t n_reads) {
             int64_t w = 0, h = 0;
             if (stream) {
                 colors_check(sbwtgpu_colorsets_builder_add_batch(builder.h, (int)c, bases.data(), read_off.data(), n_reads, strands, &w, &h));
@@ -1115,7 +1136,7 @@ int build_colors_main(int argc, char **argv) {
             }
             windows[c] += w;
             hit_windows[c] += h;
-        }
+        });
     }
     int64_t n_columns = 0, ck = 0, n_colored = 0;
     int32_t n_colors = 0;
@@ -1147,9 +1168,8 @@ int build_colors_main(int argc, char **argv) {
     }
     vector<uint64_t> rows((size_t)n_columns * (size_t)sbwtgpu_colors_words(col.h));
     colors_check(sbwtgpu_colors_copy(col.h, rows.data()));
-    if ((wide ? sbwthost_colors_write_wide(outfile.c_str(), rows.data(), n_columns, n_colors, ck)
-              : sbwthost_colors_write(outfile.c_str(), rows.data(), n_columns, n_colors, ck)) != 0)
-        throw std::runtime_error(sbwthost_last_error());
+    host_check(wide ? sbwthost_colors_write_wide(outfile.c_str(), rows.data(), n_columns, n_colors, ck)
+                    : sbwthost_colors_write(outfile.c_str(), rows.data(), n_columns, n_colors, ck));
     write_log("Wrote " + std::to_string(n_colors) + " colours of " + std::to_string(n_colored) + " coloured columns to " + outfile,
               LogLevel::MAJOR);
     return 0;
@@ -1166,63 +1186,27 @@ int compress_colors_main(int argc, char **argv) {
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"help", 'h', false, "Print usage", ""},
     });
-    opts.parse(argc, argv);
-    if (argc == 1 || opts.count("help")) {
-        std::cerr << opts.help(argv[0], "Deduplicate the colour sets of a colour file: one id per column and a table of the distinct sets.") << std::endl;
-        exit(1);
-    }
+    parse_or_usage(opts, argc, argv, "Deduplicate the colour sets of a colour file: one id per column and a table of the distinct sets.");
     const string indexfile = opts.get("index-file"), colorsfile = opts.get("colors-file"), outfile = opts.get("out-file");
     check_readable(indexfile);
     check_readable(colorsfile);
     check_writable(outfile);
-    set_default_device(atoi(opts.get("gpu").c_str()));
+    use_gpu_option(opts);
     plain_matrix_sbwt_t index;
     load_plain_matrix(indexfile, index);
-    int64_t n_columns = 0, n_colors = 0, ck = 0, words = 1;
-    if (sbwthost_colors_read_wide(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, nullptr, 0) != 0)
-        throw std::runtime_error(sbwthost_last_error());
-    if (n_columns != index.number_of_subsets() || ck != index.get_k())
-        throw std::runtime_error("Error: " + colorsfile + " colours an index of " + std::to_string(n_columns) + " columns at k = " +
-                                 std::to_string(ck) + ", " + indexfile + " has " + std::to_string(index.number_of_subsets()) +
-                                 " columns at k = " + std::to_string(index.get_k()));
-    ColorsHandle col;
-    {
-        vector<uint64_t> rows((size_t)(n_columns * words));
-        if (sbwthost_colors_read_wide(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, rows.data(), n_columns * words) != 0)
-            throw std::runtime_error(sbwthost_last_error());
-        colors_check(sbwtgpu_colors_create_wide(index.device_handle(), (int)n_colors, rows.data(), &col.h));
-    }
-    compress_and_write(col.h, outfile);
+    ColorFile f;
+    load_color_file(colorsfile, indexfile, index, ColorFile::ROWS_ONLY, f);
+    compress_and_write(f.col.h, outfile);
     return 0;
 }
 
 // the colour-set object of a colour file of `index`: an "SBWTCOL3" file goes in directly, an "SBWTCOL1" or "SBWTCOL2" file is
 // compressed on the device first (sbwtgpu_colorsets_compress, as compress-colors does); a file of another index is refused
 void load_colorsets(const string &colorsfile, const string &indexfile, const plain_matrix_sbwt_t &index, ColorSetsHandle &out) {
-    const bool sets = file_has_magic(colorsfile, "SBWTCOL3");
-    int64_t n_columns = 0, n_colors = 0, ck = 0, words = 1, n_sets = 0;
-    if ((sets ? sbwthost_colorsets_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, &n_sets, nullptr, 0, nullptr, 0)
-              : sbwthost_colors_read_wide(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, nullptr, 0)) != 0)
-        throw std::runtime_error(sbwthost_last_error());
-    if (n_columns != index.number_of_subsets() || ck != index.get_k())
-        throw std::runtime_error("Error: " + colorsfile + " colours an index of " + std::to_string(n_columns) + " columns at k = " +
-                                 std::to_string(ck) + ", " + indexfile + " has " + std::to_string(index.number_of_subsets()) +
-                                 " columns at k = " + std::to_string(index.get_k()));
-    if (sets) {
-        vector<uint32_t> ids((size_t)n_columns);
-        vector<uint64_t> table((size_t)(n_sets * words));
-        if (sbwthost_colorsets_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, &n_sets, ids.data(), n_columns, table.data(),
-                                    n_sets * words) != 0)
-            throw std::runtime_error(sbwthost_last_error());
-        colors_check(sbwtgpu_colorsets_create(index.device_handle(), (int)n_colors, ids.data(), n_sets, table.data(), &out.h));
-        return;
-    }
-    ColorsHandle col;
-    vector<uint64_t> rows((size_t)(n_columns * words));
-    if (sbwthost_colors_read_wide(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, rows.data(), n_columns * words) != 0)
-        throw std::runtime_error(sbwthost_last_error());
-    colors_check(sbwtgpu_colors_create_wide(index.device_handle(), (int)n_colors, rows.data(), &col.h));
-    colors_check(sbwtgpu_colorsets_compress(col.h, &out.h));
+    ColorFile f;
+    load_color_file(colorsfile, indexfile, index, ColorFile::ANY_AS_WIDE, f);
+    if (f.sets.h) std::swap(out.h, f.sets.h);
+    else colors_check(sbwtgpu_colorsets_compress(f.col.h, &out.h));
 }
 
 // floor(shared * 10^6 / (ka + kb - shared)) in 128-bit integers, 0 where the denominator is 0: no floats, so the text is stable
@@ -1244,17 +1228,13 @@ int color_matrix_main(int argc, char **argv) {
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"help", 'h', false, "Print usage", ""},
     });
-    opts.parse(argc, argv);
-    if (argc == 1 || opts.count("help")) {
-        std::cerr << opts.help(argv[0], "Count the k-mers that each pair of references shares.") << std::endl;
-        exit(1);
-    }
+    parse_or_usage(opts, argc, argv, "Count the k-mers that each pair of references shares.");
     const string indexfile = opts.get("index-file"), colorsfile = opts.get("colors-file"), outfile = opts.get("out-file");
     const bool jaccard = opts.count("jaccard-ppm") > 0;
     check_readable(indexfile);
     check_readable(colorsfile);
     check_writable(outfile);
-    set_default_device(atoi(opts.get("gpu").c_str()));
+    use_gpu_option(opts);
     plain_matrix_sbwt_t index;
     load_plain_matrix(indexfile, index);
     ColorSetsHandle sets;
@@ -1272,8 +1252,7 @@ int color_matrix_main(int argc, char **argv) {
             append_int(jaccard ? jaccard_ppm(G[a * C + b], G[a * C + a], G[b * C + b]) : G[a * C + b], text);
             text.push_back(b + 1 == C ? '\n' : '\t');
         }
-    if (sbwthost_write_file(outfile.c_str(), text.data(), (int64_t)text.size(), 0, 0) != 0)
-        throw std::runtime_error(string("Error writing ") + outfile + ": " + sbwthost_last_error());
+    write_text_file(outfile, text, false);
     write_log("Wrote the shared k-mers of " + std::to_string(n_colors) + " references from " + std::to_string(info.n_sets_used) +
                   " colour sets (" + (info.used_mfma ? "matrix cores" : "plain kernel") + ")",
               LogLevel::MAJOR);
@@ -1298,11 +1277,7 @@ int screen_main(int argc, char **argv) {
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
     });
-    opts.parse(argc, argv);
-    if (argc == 1 || opts.count("help")) {
-        std::cerr << opts.help(argv[0], "Screen a read set against the references: per colour k-mers, k-mers seen, hits.") << std::endl;
-        exit(1);
-    }
+    parse_or_usage(opts, argc, argv, "Screen a read set against the references: per colour k-mers, k-mers seen, hits.");
     const string indexfile = opts.get("index-file"), colorsfile = opts.get("colors-file"), queryfile = opts.get("query-file"),
                  outfile = opts.get("out-file"), setsfile = opts.count("sets-out") ? opts.get("sets-out") : string();
     check_readable(indexfile);
@@ -1311,9 +1286,8 @@ int screen_main(int argc, char **argv) {
     check_writable(outfile);
     if (!setsfile.empty()) check_writable(setsfile);
     const int strands = opts.count("both-strands") ? 2 : 1;
-    set_default_device(atoi(opts.get("gpu").c_str()));
-    int64_t batch_bases = atoll(opts.get("batch-bases").c_str());
-    if (batch_bases < 1) batch_bases = 1;
+    use_gpu_option(opts);
+    const int64_t batch_bases = batch_bases_option(opts);
     plain_matrix_sbwt_t index;
     load_plain_matrix(indexfile, index);
     ColorSetsHandle sets;
@@ -1322,18 +1296,10 @@ int screen_main(int argc, char **argv) {
     int64_t total_reads = 0;
     {
         seq_io::Reader reader(queryfile);
-        bool more = true;
-        vector<char> bases;
-        vector<int64_t> read_off;
-        while (more) {
-            bases.clear();
-            read_off.assign(1, 0);
-            more = reader.read_batch(bases, read_off, batch_bases);
-            const int64_t n_reads = (int64_t)read_off.size() - 1;
-            if (n_reads <= 0) continue;
+        for_each_batch(reader, batch_bases, [&](const vector<char> &bases, const vector<int64_t> &read_off, int64_t n_reads) {
             screen.add(bases.data(), read_off.data(), n_reads, strands);
             total_reads += n_reads;
-        }
+        });
     }
     const plain_matrix_sbwt_t::Screen::Info info = screen.info();
     auto table = [](const plain_matrix_sbwt_t::Screen::Vectors &v, string &text) {
@@ -1351,13 +1317,11 @@ int screen_main(int argc, char **argv) {
     string text = "# windows " + std::to_string(info.n_windows) + " hits " + std::to_string(info.n_hits) + " seen " +
                   std::to_string(info.n_seen) + "\n";
     table(screen.colors(), text);
-    if (sbwthost_write_file(outfile.c_str(), text.data(), (int64_t)text.size(), 0, 0) != 0)
-        throw std::runtime_error(string("Error writing ") + outfile + ": " + sbwthost_last_error());
+    write_text_file(outfile, text, false);
     if (!setsfile.empty()) {
         text.clear();
         table(screen.sets(), text);
-        if (sbwthost_write_file(setsfile.c_str(), text.data(), (int64_t)text.size(), 0, 0) != 0)
-            throw std::runtime_error(string("Error writing ") + setsfile + ": " + sbwthost_last_error());
+        write_text_file(setsfile, text, false);
     }
     write_log("Screened " + std::to_string(total_reads) + " reads against " + std::to_string(info.n_colors) + " references: " +
                   std::to_string(info.n_hits) + " hits in " + std::to_string(info.n_windows) + " windows, " +
@@ -1391,8 +1355,7 @@ int dump_unitigs_colored(const plain_matrix_sbwt_t &index, const string &indexfi
             text.push_back('\n');
         }
     }
-    if (sbwthost_write_file(outfile.c_str(), text.data(), (int64_t)text.size(), gzip ? 1 : 0, 0) != 0)
-        throw std::runtime_error(string("Error writing ") + outfile + ": " + sbwthost_last_error());
+    write_text_file(outfile, text, gzip);
     if (!setsfile.empty()) {
         int32_t words = 0;
         int64_t n_columns = 0, n_sets = 0;
@@ -1403,15 +1366,10 @@ int dump_unitigs_colored(const plain_matrix_sbwt_t &index, const string &indexfi
         string lines;
         for (int64_t i = 0; i < n_sets; i++) {
             append_int(i, lines);
-            for (int w = 0; w < words; w++)
-                for (uint64_t bits = table[(size_t)(i * words + w)]; bits; bits &= bits - 1) {
-                    lines.push_back(' ');
-                    append_int((int64_t)w * 64 + __builtin_ctzll(bits), lines);
-                }
+            append_set_bits(table.data() + i * words, words, " ", " ", lines);
             lines.push_back('\n');
         }
-        if (sbwthost_write_file(setsfile.c_str(), lines.data(), (int64_t)lines.size(), 0, 0) != 0)
-            throw std::runtime_error(string("Error writing ") + setsfile + ": " + sbwthost_last_error());
+        write_text_file(setsfile, lines, false);
     }
     write_log("Wrote " + std::to_string(n) + " coloured unitigs, " + std::to_string(u.bases.size()) + " bases, " +
                   std::to_string(u.n_color_breaks) + " colour breaks, " + std::to_string(u.n_sets) + " colour sets" +
@@ -1439,11 +1397,7 @@ int thread_main(int argc, char **argv) {
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
     });
-    opts.parse(argc, argv);
-    if (argc == 1 || opts.count("help")) {
-        std::cerr << opts.help(argv[0], "Per read: the unitigs of the de Bruijn graph it runs along, as read_pos:unitig:offset:n_kmers steps.") << std::endl;
-        exit(1);
-    }
+    parse_or_usage(opts, argc, argv, "Per read: the unitigs of the de Bruijn graph it runs along, as read_pos:unitig:offset:n_kmers steps.");
     const string indexfile = opts.get("index-file"), queryfile = opts.get("query-file"), outfile = opts.get("out-file");
     const bool colored = opts.count("colors");
     const string colorsfile = colored ? opts.get("colors") : string();
@@ -1455,17 +1409,11 @@ int thread_main(int argc, char **argv) {
     if (!covfile.empty()) check_writable(covfile);
     if (!gfafile.empty()) check_writable(gfafile);
     const bool gzip_output = opts.count("gzip-output"), coverage = !covfile.empty() || !gfafile.empty();
-    set_default_device(atoi(opts.get("gpu").c_str()));
-    int64_t batch_bases = atoll(opts.get("batch-bases").c_str());
-    if (batch_bases < 1) batch_bases = 1;
+    use_gpu_option(opts);
+    const int64_t batch_bases = batch_bases_option(opts);
 
-    std::ifstream in(indexfile, std::ios::binary);
-    if (!in.good()) throw std::runtime_error("Error opening file: " + indexfile);
-    const string variant = load_string(in);
-    if (variant != "plain-matrix")
-        throw std::runtime_error("Error: only the plain-matrix variant is supported by the GPU path (got " + variant + ")");
     plain_matrix_sbwt_t index;
-    index.load(in);
+    load_plain_matrix(indexfile, index);
     ColorSetsHandle sets;
     if (colored) load_colorsets(colorsfile, indexfile, index, sets);
     const plain_matrix_sbwt_t::UnitigGraph graph = index.unitig_graph(colored ? sets.h : nullptr);
@@ -1475,16 +1423,8 @@ int thread_main(int argc, char **argv) {
         write_log("Threading the reads of " + queryfile + " to output file " + outfile, LogLevel::MAJOR);
         seq_io::Reader reader(queryfile);
         seq_io::Buffered_ofstream writer(outfile, gzip_output);
-        bool more = true;
-        vector<char> bases;
-        vector<int64_t> read_off;
         string text;
-        while (more) {
-            bases.clear();
-            read_off.assign(1, 0);
-            more = reader.read_batch(bases, read_off, batch_bases);
-            const int64_t n_reads = (int64_t)read_off.size() - 1;
-            if (n_reads <= 0) continue;
+        for_each_batch(reader, batch_bases, [&](const vector<char> &bases, const vector<int64_t> &read_off, int64_t n_reads) {
             const plain_matrix_sbwt_t::Walks w = index.walks(graph, bases.data(), read_off.data(), n_reads, coverage);
             text.clear();
             for (int64_t r = 0; r < n_reads; r++) {
@@ -1509,7 +1449,7 @@ int thread_main(int argc, char **argv) {
             }
             total_reads += n_reads;
             total_steps += (int64_t)w.steps.size();
-        }
+        });
     }
     if (coverage) {
         const plain_matrix_sbwt_t::ColoredUnitigs u = graph.unitigs();
@@ -1525,14 +1465,10 @@ int thread_main(int argc, char **argv) {
                 append_int(kmer_hits[(size_t)i], lines);
                 lines.push_back('\n');
             }
-            if (sbwthost_write_file(covfile.c_str(), lines.data(), (int64_t)lines.size(), 0, 0) != 0)
-                throw std::runtime_error(string("Error writing ") + covfile + ": " + sbwthost_last_error());
+            write_text_file(covfile, lines, false);
         }
-        if (!gfafile.empty()) {
-            const string text = gfa_text(u.bases, u.off, u.link_off, u.link_to, colored ? &u.set_id : nullptr, k, &kmer_hits);
-            if (sbwthost_write_file(gfafile.c_str(), text.data(), (int64_t)text.size(), 0, 0) != 0)
-                throw std::runtime_error(string("Error writing ") + gfafile + ": " + sbwthost_last_error());
-        }
+        if (!gfafile.empty())
+            write_text_file(gfafile, gfa_text(u.bases, u.off, u.link_off, u.link_to, colored ? &u.set_id : nullptr, k, &kmer_hits), false);
     }
     write_log("Threaded " + std::to_string(total_reads) + " reads: " + std::to_string(total_steps) + " steps; us/read end-to-end: " +
                   std::to_string((double)(cur_time_micros() - micros_start) / (double)std::max<int64_t>(1, total_reads)),
@@ -1542,14 +1478,9 @@ int thread_main(int argc, char **argv) {
 
 // the set bits of a `words`-word row as comma-separated ascending colours, "-" for none
 void append_color_list(const uint64_t *row, int32_t words, string &text) {
-    bool any = false;
-    for (int32_t w = 0; w < words; w++)
-        for (uint64_t x = row[w]; x; x &= x - 1) {
-            if (any) text.push_back(',');
-            append_int((int64_t)w * 64 + __builtin_ctzll(x), text);
-            any = true;
-        }
-    if (!any) text.push_back('-');
+    const size_t before = text.size();
+    append_set_bits(row, words, "", ",", text);
+    if (text.size() == before) text.push_back('-');
 }
 
 // sbwt bubbles: the variant sites of the plain unitig graph (include/sbwtgpu.h, "bubbles").  The output starts with
@@ -1567,18 +1498,14 @@ int bubbles_main(int argc, char **argv) {
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"help", 'h', false, "Print usage", ""},
     });
-    opts.parse(argc, argv);
-    if (argc == 1 || opts.count("help")) {
-        std::cerr << opts.help(argv[0], "Find the bubbles of the unitig graph: where the references differ, and which reference carries which allele.") << std::endl;
-        exit(1);
-    }
+    parse_or_usage(opts, argc, argv, "Find the bubbles of the unitig graph: where the references differ, and which reference carries which allele.");
     const string indexfile = opts.get("index-file"), outfile = opts.get("out-file");
     const bool colored = opts.count("colors-file") > 0, gzip_output = opts.count("gzip-output") > 0, snps_only = opts.count("snps-only") > 0;
     const string colorsfile = colored ? opts.get("colors-file") : string();
     check_readable(indexfile);
     if (colored) check_readable(colorsfile);
     check_writable(outfile);
-    set_default_device(atoi(opts.get("gpu").c_str()));
+    use_gpu_option(opts);
     plain_matrix_sbwt_t index;
     load_plain_matrix(indexfile, index);
     ColorSetsHandle sets;
@@ -1645,11 +1572,7 @@ int merge_colors_main(int argc, char **argv) {
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"help", 'h', false, "Print usage", ""},
     });
-    opts.parse(argc, argv);
-    if (argc == 1 || opts.count("help")) {
-        std::cerr << opts.help(argv[0], "Carry the colour sets of one or two indexes onto another index (merge-colors), without the sequences.") << std::endl;
-        exit(1);
-    }
+    parse_or_usage(opts, argc, argv, "Carry the colour sets of one or two indexes onto another index (merge-colors), without the sequences.");
     const string file_u = opts.get("index-u"), file_a = opts.get("index-a"), colors_a = opts.get("colors-a"), outfile = opts.get("out-file");
     const bool two = opts.count("index-b") || opts.count("colors-b");
     if (two && !(opts.count("index-b") && opts.count("colors-b")))
@@ -1663,7 +1586,7 @@ int merge_colors_main(int argc, char **argv) {
         check_readable(colors_b);
     }
     check_writable(outfile);
-    set_default_device(atoi(opts.get("gpu").c_str()));
+    use_gpu_option(opts);
     plain_matrix_sbwt_t U, A, B;
     load_plain_matrix(file_u, U);
     load_plain_matrix(file_a, A);
@@ -1746,11 +1669,7 @@ int color_select_main(int argc, char **argv) {
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"help", 'h', false, "Print usage", ""},
     });
-    opts.parse(argc, argv);
-    if (argc == 1 || opts.count("help")) {
-        std::cerr << opts.help(argv[0], "Select the k-mers of a coloured index by their colour sets (core, unique, accessory, soft core), as an index.") << std::endl;
-        exit(1);
-    }
+    parse_or_usage(opts, argc, argv, "Select the k-mers of a coloured index by their colour sets (core, unique, accessory, soft core), as an index.");
     const bool counts_only = opts.count("counts-only");
     const string indexfile = opts.get("index-file"), colorsfile = opts.get("colors-file");
     const string outfile = counts_only ? string() : opts.get("out-file");              // (--counts-only writes no file: no -o needed)
@@ -1759,7 +1678,7 @@ int color_select_main(int argc, char **argv) {
     check_readable(colorsfile);
     if (!counts_only) check_writable(outfile);
     if (!colors_out.empty()) check_writable(colors_out);
-    set_default_device(atoi(opts.get("gpu").c_str()));
+    use_gpu_option(opts);
     plain_matrix_sbwt_t index;
     load_plain_matrix(indexfile, index);
     ColorSetsHandle sets;
@@ -1787,23 +1706,11 @@ int color_select_main(int argc, char **argv) {
         std::cout << info.n_real << " " << info.n_selected << " " << info.n_sets_matched << std::endl;
         return 0;
     }
-    const int64_t k = index.get_k();
-    int64_t precalc = atoll(opts.get("precalc-length").c_str());
-    if (precalc > k) {
-        write_log("Warning: precalc length " + std::to_string(precalc) + " is longer than k = " + std::to_string(k), LogLevel::MAJOR);
-        write_log("Setting precalc length to " + std::to_string(k), LogLevel::MAJOR);
-        precalc = k;
-    }
+    const int64_t precalc = precalc_option(opts, index.get_k());
     PlainMatrixBits bits = index.color_select(sets.h, pred, !opts.count("no-streaming-support"), &info);
     log_counts(info);
     plain_matrix_sbwt_t sub(bits, 0);
-    {
-        std::ofstream out(outfile, std::ios::binary);
-        if (!out.good()) throw std::runtime_error("Error opening file: " + outfile);
-        serialize_string("plain-matrix", out);
-        sub.do_kmer_prefix_precalc(precalc);
-        sub.serialize(out);
-    }
+    write_index_file(sub, outfile, precalc);
     write_log("Wrote the index to " + outfile, LogLevel::MAJOR);
     if (!colors_out.empty()) {
         ColorSetsHandle carried;
@@ -1831,11 +1738,7 @@ int pseudoalign_main(int argc, char **argv) {
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
     });
-    opts.parse(argc, argv);
-    if (argc == 1 || opts.count("help")) {
-        std::cerr << opts.help(argv[0], "Per read: the references (colours) that hold it.") << std::endl;
-        exit(1);
-    }
+    parse_or_usage(opts, argc, argv, "Per read: the references (colours) that hold it.");
     const string indexfile = opts.get("index-file"), colorsfile = opts.get("colors-file");
     const string queryfile = opts.get("query-file"), outfile = opts.get("out-file");
     check_readable(indexfile);
@@ -1846,104 +1749,80 @@ int pseudoalign_main(int argc, char **argv) {
     const int denominator = opts.count("all-kmers") ? 1 : 0;
     const int strands = opts.count("both-strands") ? 2 : 1;
     const bool gzip_output = opts.count("gzip-output");
-    set_default_device(atoi(opts.get("gpu").c_str()));
-    int64_t batch_bases = atoll(opts.get("batch-bases").c_str());
-    if (batch_bases < 1) batch_bases = 1;
+    use_gpu_option(opts);
+    const int64_t batch_bases = batch_bases_option(opts);
     plain_matrix_sbwt_t index;
     load_plain_matrix(indexfile, index);
     // the colour file's magic says which calls it goes through: "SBWTCOL2" the wide ones, "SBWTCOL3" the colour-set ones
     // (whose records are the wide ones'), anything else where it always went
-    const bool sets = file_has_magic(colorsfile, "SBWTCOL3");
-    const bool wide = sets || file_has_magic(colorsfile, "SBWTCOL2");
-    int64_t n_columns = 0, n_colors = 0, ck = 0, words = 1, n_sets = 0;
-    if (sets ? sbwthost_colorsets_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, &n_sets, nullptr, 0, nullptr, 0) != 0 :
-        (wide ? sbwthost_colors_read_wide(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, nullptr, 0)
-              : sbwthost_colors_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, nullptr, 0)) != 0)
-        throw std::runtime_error(sbwthost_last_error());
-    if (n_columns != index.number_of_subsets() || ck != index.get_k())
-        throw std::runtime_error("Error: " + colorsfile + " colours an index of " + std::to_string(n_columns) + " columns at k = " +
-                                 std::to_string(ck) + ", " + indexfile + " has " + std::to_string(index.number_of_subsets()) +
-                                 " columns at k = " + std::to_string(index.get_k()));
-    ColorsHandle col;
-    ColorSetsHandle cset;
-    if (sets) {
-        vector<uint32_t> ids((size_t)n_columns);
-        vector<uint64_t> table((size_t)(n_sets * words));
-        if (sbwthost_colorsets_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, &n_sets, ids.data(), n_columns, table.data(),
-                                    n_sets * words) != 0)
-            throw std::runtime_error(sbwthost_last_error());
-        colors_check(sbwtgpu_colorsets_create(index.device_handle(), (int)n_colors, ids.data(), n_sets, table.data(), &cset.h));
-    } else {
-        vector<uint64_t> rows((size_t)(n_columns * words));
-        if ((wide ? sbwthost_colors_read_wide(colorsfile.c_str(), &n_columns, &n_colors, &ck, &words, rows.data(), n_columns * words)
-                  : sbwthost_colors_read(colorsfile.c_str(), &n_columns, &n_colors, &ck, rows.data(), n_columns)) != 0)
-            throw std::runtime_error(sbwthost_last_error());
-        if (wide) colors_check(sbwtgpu_colors_create_wide(index.device_handle(), (int)n_colors, rows.data(), &col.h));
-        else colors_check(sbwtgpu_colors_create(index.device_handle(), (int)n_colors, rows.data(), &col.h));
-    }
+    ColorFile cf;
+    load_color_file(colorsfile, indexfile, index, ColorFile::ANY, cf);
+    const bool sets = cf.sets.h != nullptr;
+    const int64_t words = cf.words;
     write_log("Running pseudoalignment from input file " + queryfile + " to output file " + outfile, LogLevel::MAJOR);
     seq_io::Reader reader(queryfile);
     seq_io::Buffered_ofstream writer(outfile, gzip_output);
-    bool more = true;
-    vector<char> bases;
-    vector<int64_t> read_off;
     vector<sbwtgpu_pseudoalignment> rec;
     vector<sbwtgpu_read_found> wrec;
     vector<uint64_t> wcol;
     string text;
     int64_t total_reads = 0;
-    while (more) {
-        bases.clear();
-        read_off.assign(1, 0);
-        more = reader.read_batch(bases, read_off, batch_bases);
-        const int64_t n_reads = (int64_t)read_off.size() - 1;
-        if (n_reads <= 0) continue;
+    for_each_batch(reader, batch_bases, [&](const vector<char> &bases, const vector<int64_t> &read_off, int64_t n_reads) {
         text.clear();
-        if (wide) {
+        if (cf.wide) {
             wrec.resize((size_t)n_reads);
             wcol.resize((size_t)(n_reads * words));
             if (sets)
-                colors_check(sbwtgpu_pseudoalign_sets_batch(cset.h, bases.data(), read_off.data(), n_reads, strands, threshold_ppm,
+                colors_check(sbwtgpu_pseudoalign_sets_batch(cf.sets.h, bases.data(), read_off.data(), n_reads, strands, threshold_ppm,
                                                             denominator, wrec.data(), wcol.data(), nullptr));
             else
-                colors_check(sbwtgpu_pseudoalign_wide_batch(col.h, bases.data(), read_off.data(), n_reads, strands, threshold_ppm,
+                colors_check(sbwtgpu_pseudoalign_wide_batch(cf.col.h, bases.data(), read_off.data(), n_reads, strands, threshold_ppm,
                                                             denominator, wrec.data(), wcol.data(), nullptr));
             for (int64_t r = 0; r < n_reads; r++) {
                 append_int(total_reads++, text);
-                for (int64_t w = 0; w < words; w++) {
-                    for (uint64_t left = wcol[(size_t)(r * words + w)]; left; left &= left - 1) {
-                        text.push_back(' ');
-                        append_int(w * 64 + __builtin_ctzll(left), text);
-                    }
-                }
+                append_set_bits(wcol.data() + r * words, words, " ", " ", text);
                 text.push_back('\n');
             }
         } else {
             rec.resize((size_t)n_reads);
-            colors_check(sbwtgpu_pseudoalign_batch(col.h, bases.data(), read_off.data(), n_reads, strands, threshold_ppm, denominator,
+            colors_check(sbwtgpu_pseudoalign_batch(cf.col.h, bases.data(), read_off.data(), n_reads, strands, threshold_ppm, denominator,
                                                    rec.data(), nullptr));
             for (const sbwtgpu_pseudoalignment &p : rec) {
                 append_int(total_reads++, text);
-                for (int c = 0; c < 64; c++)
-                    if ((p.colors >> c) & 1) {
-                        text.push_back(' ');
-                        append_int(c, text);
-                    }
+                append_set_bits(&p.colors, 1, " ", " ", text);
                 text.push_back('\n');
             }
         }
         writer.write(text.data(), (int64_t)text.size());
-    }
+    });
     write_log("us/read end-to-end: " + std::to_string((double)(cur_time_micros() - micros_start) / (double)std::max<int64_t>(1, total_reads)),
               LogLevel::MAJOR);
     return 0;
 }
 
-const vector<string> commands = {"build", "search", "matching-statistics", "dump-unitigs", "thread", "bubbles", "set-op", "read-hits", "build-colors", "compress-colors", "merge-colors", "color-matrix", "color-select", "screen", "pseudoalign"};
+// the subcommands, in the order "Available commands" lists them
+struct Command { const char *name; int (*main)(int, char **); };
+const Command commands[] = {
+    {"build", build_main},
+    {"search", search_main},
+    {"matching-statistics", matching_statistics_main},
+    {"dump-unitigs", dump_unitigs_main},
+    {"thread", thread_main},
+    {"bubbles", bubbles_main},
+    {"set-op", set_op_main},
+    {"read-hits", read_hits_main},
+    {"build-colors", build_colors_main},
+    {"compress-colors", compress_colors_main},
+    {"merge-colors", merge_colors_main},
+    {"color-matrix", color_matrix_main},
+    {"color-select", color_select_main},
+    {"screen", screen_main},
+    {"pseudoalign", pseudoalign_main},
+};
 
 void print_help(char **argv) {
     std::cerr << "Available commands: " << std::endl;
-    for (const string &S : commands) std::cerr << "   " << argv[0] << " " << S << std::endl;
+    for (const Command &c : commands) std::cerr << "   " << argv[0] << " " << c.name << std::endl;
     std::cerr << "Running a command without arguments prints the usage instructions for the command." << std::endl;
 }
 
@@ -1958,30 +1837,20 @@ int main(int argc, char **argv) {   // sbwt.cpp:19-57
     for (int i = 1; i < argc; i++) argv[i - 1] = argv[i];
     argc--;
     try {
-        if (command == "build") return build_main(argc, argv);
-        else if (command == "search") {
-            const int rc = search_main(argc, argv);
-            // every output file is closed: leave without the HIP runtime's teardown and the freeing of the index (a tenth
-            // of a second of a sub-second run)
-            std::cout.flush();
-            std::cerr.flush();
-            fflush(nullptr);
-            _exit(rc);
+        for (const Command &c : commands) {
+            if (command != c.name) continue;
+            const int rc = c.main(argc, argv);
+            if (c.main == search_main) {
+                // every output file is closed: leave without the HIP runtime's teardown and the freeing of the index (a tenth
+                // of a second of a sub-second run)
+                std::cout.flush();
+                std::cerr.flush();
+                fflush(nullptr);
+                _exit(rc);
+            }
+            return rc;
         }
-        else if (command == "matching-statistics") return matching_statistics_main(argc, argv);
-        else if (command == "dump-unitigs") return dump_unitigs_main(argc, argv);
-        else if (command == "thread") return thread_main(argc, argv);
-        else if (command == "bubbles") return bubbles_main(argc, argv);
-        else if (command == "set-op") return set_op_main(argc, argv);
-        else if (command == "read-hits") return read_hits_main(argc, argv);
-        else if (command == "build-colors") return build_colors_main(argc, argv);
-        else if (command == "compress-colors") return compress_colors_main(argc, argv);
-        else if (command == "merge-colors") return merge_colors_main(argc, argv);
-        else if (command == "color-matrix") return color_matrix_main(argc, argv);
-        else if (command == "color-select") return color_select_main(argc, argv);
-        else if (command == "screen") return screen_main(argc, argv);
-        else if (command == "pseudoalign") return pseudoalign_main(argc, argv);
-        else throw std::runtime_error("Invalid command: " + command);
+        throw std::runtime_error("Invalid command: " + command);
     } catch (const std::runtime_error &e) {
         std::cerr << "Runtime error: " << e.what() << '\n';
         return 1;
