@@ -120,6 +120,8 @@ int         sbwtgpu_device_count(int *count);
  *                        into chunks of whole reads of at most this many bases (a chunk always takes one read); 0 (default) = 64 Mi
  *   "screen_chunk_bases" sbwtgpu_screen_add_batch cuts its batch into chunks of whole reads of at most this many bases (a chunk
  *                        always takes one read); 0 (default) = 64 Mi
+ *   "genotype_chunk_bases" sbwtgpu_genotype_add_batch cuts its batch into chunks of whole reads of at most this many bases (a
+ *                        chunk always takes one read); 0 (default) = 64 Mi
  *   "trans_ext", "trans_wide"   accepted and ignored (round-2 table formats)
  * Read when an index is CREATED (derived acceleration structures inside the device image; environment
  * variables of the same meaning: SBWTGPU_SPARSE_PRECALC, SBWTGPU_PROBE_FILTER, SBWTGPU_PATH_ORDER):
@@ -1106,6 +1108,102 @@ int  sbwtgpu_bubbles_in_degrees_copy(const sbwtgpu_unitigs *u, uint32_t *indeg);
 /* measurement aid (tools/bubbles_bench.py): device-event times in ms of in-degrees, detect, compact, branch colours */
 int  sbwtgpu_bubbles_stats (const sbwtgpu_bubbles *b, double pass_ms[4]);
 void sbwtgpu_bubbles_destroy(sbwtgpu_bubbles *b);
+
+/* ---- genotype: which allele of every bubble a read set carries ----
+ * The sample-level counterpart of the bubbles: per allele the k-mer depth of a read set, per bubble a call, per reference
+ * how often the sample follows it where the references differ.  A genotype object is an accumulator on the device that
+ * lives across batches, like a screen object.
+ * Inputs
+ *   - idx: an index.
+ *   - u: a plain graph handle made from idx with SBWTGPU_UNITIGS_LINKS | SBWTGPU_UNITIGS_COLUMN_MAP.
+ *   - b: a bubbles object made from u, with or without colours.
+ * Slots and branch columns
+ *   - Slot s = 2i + j is branch j of bubble i.
+ *   - A branch column is a real column v whose col_unitig[v] is branch[j] of some bubble.
+ *   - A branch belongs to exactly one bubble, so its slot is unique.
+ *   - branch_off[s] is the exclusive prefix sum of n_kmers in slot order.  P = branch_off[2B] is the total.
+ *   - Branch column v has position p = branch_off[s] + col_offset[v].
+ * State
+ *   The state is exact uint64 / int64 and uses no floating point anywhere.
+ *   - kmer_hits[p], for p in [0, P).
+ *   - Three scalars: n_windows, n_hits and n_site_hits.
+ * What one add does
+ *   An add takes reads and strands in {1, 2}.
+ *   1. Every window is searched by the rule of sbwtgpu_search_batch: upper-case ACGT only.
+ *   2. With strands = 2, the mirrored batch of Screen / read-hits is searched too.
+ *   3. Every hit on a branch column adds 1 to that column's kmer_hits.  It is counted in n_site_hits.
+ *   4. Every hit anywhere is counted in n_hits.
+ *   5. Every window is counted in n_windows, once per strand searched, as Screen counts them.
+ *   6. Hits on sources, sinks and every other unitig change nothing else.
+ * Determinism
+ *   The state is a function of the index and of the multiset of reads and strands added.  It does not depend on batch
+ *   boundaries, chunking, tuning, image level, streams or the order of concurrent adds.
+ * Derived on demand
+ *   The object stays usable afterwards.  All values are int64 and each vector has 2B entries.
+ *   - seen[s] = #{ p in branch s : kmer_hits[p] > 0 }.
+ *   - hits[s] = the sum of kmer_hits over branch s.
+ *   - min_hits[s] = the minimum of kmer_hits over branch s.
+ * Calls
+ *   The parameters are breadth_ppm in [1, 10^6] and min_depth >= 0.
+ *   - Allele j of bubble i is present when both conditions hold, in 64-bit integers:
+ *       seen[s] * 10^6 >= breadth_ppm * n_kmers[s];
+ *       hits[s] >= min_depth * n_kmers[s]   (evaluated as hits[s] / n_kmers[s] >= min_depth, which no min_depth overflows).
+ *   - call[i] is a uint8: bit 0 = allele a present, bit 1 = allele b present.  So 0 is no call, 1 is a, 2 is b and 3 is both.
+ * Per colour
+ *   The colour vectors exist only when b was made with a colour-set object.  The genotype object copies b's inter rows at
+ *   create.
+ *   - Colour c is informative at bubble i when bit c is set in exactly one of inter[2i], inter[2i+1].  Call that allele j_c.
+ *   - ref_sites[c] = the informative bubbles with call != 0.
+ *   - ref_match[c] = those whose call has bit j_c set.
+ *   - ref_only[c] = those whose call equals 1 << j_c.
+ *   - All three vectors are int64[n_colors].
+ *   - ref_only[c] / ref_sites[c] answers "which reference does the sample follow where the references differ".
+ * Strands
+ *   On an index with reverse complements every bubble exists twice (section 24), and each twin keeps its own counters.
+ *   Pairing the twins stays out of scope.
+ * sbwtgpu_genotype_create allocates 8 P bytes of state and a few words, zeroed, and beside them what the adds read: n / 8
+ * bytes of branch bitmap, n / 16 of rank directory, 4 P of positions, 16 B of branch_off and, with colours, 16 W B of inter
+ * rows.  It runs three streaming passes and two scans on a stream of the object's own, with scratch (4 bytes per unitig, 16
+ * per slot, 16 per 64 columns) that it frees before it returns.  It keeps references to idx and u, which must outlive g,
+ * and none to b: it copies what it needs, and b may be destroyed before the first add.  B = 0 gives a valid object with
+ * empty outputs.  sbwtgpu_genotype_reset zeroes the state again (it waits for the device first).
+ * sbwtgpu_genotype_add_dev takes device pointers with the preconditions of sbwtgpu_read_hits_dev, is asynchronous on
+ * `stream`, never synchronises and never allocates.  Its workspace, of sbwtgpu_genotype_workspace_bytes (non-decreasing in
+ * total_bases and n_reads), is 16-byte aligned and begins with the search workspace: sbwtgpu_workspace_status on it reports
+ * the search's status word.  After the searches (the forward batch and, for two strands, the mirrored batch of the read-hit
+ * profiles; int32 results) one kernel launch feeds the accumulator.
+ * sbwtgpu_genotype_add_batch takes host buffers and cuts the batch into chunks of whole reads of at most
+ * "genotype_chunk_bases" bases (sbwtgpu_set_tuning; 0 = the default of 64 Mi; a chunk always takes one read), two in flight.
+ * Only bases and offsets go to the device; nothing but each chunk's status word comes back.
+ * sbwtgpu_genotype_info, _branches, _kmer_hits_copy and _calls run on a stream of the object's own; they see every add that
+ * has returned from sbwtgpu_genotype_add_batch, which finishes its streams before it returns.  A caller of
+ * sbwtgpu_genotype_add_dev on a stream of their own finishes that stream first.  They leave the object unchanged; any output
+ * may be NULL.
+ * Adds from several host threads or streams on one object are safe -- the object is built on atomics -- as long as each
+ * caller brings a workspace of its own; the queries serialise on the object.
+ * Refusals (SBWTGPU_ERR_INVALID_ARG with a message that names the cause): NULL arguments; a coloured handle; a handle without
+ * links, or without the column map; a handle whose n_nodes or k differ from the index's; a b that does not fit u (a record
+ * names a unitig >= n_unitigs, or its n_kmers is not that unitig's k-mer count, or two slots name one unitig; checked on the
+ * device while the slot table is filled); an index of 2^31 columns or more; a rank-only index; strands not 1 or 2; n_reads
+ * < 0 or >= 2^31; a workspace that is too small; breadth_ppm or min_depth out of range; colour outputs asked of an object
+ * made from a colourless b.  A b made from a handle of ANOTHER index is refused by the same check; where its record indices
+ * and k-mer counts happen to fit u's unitigs this is not detectable, and the object then counts at those unitigs.
+ * A read of 2^31 bases or more: SBWTGPU_ERR_READ_TOO_LONG.  SBWTGPU_ERR_OOM leaves everything usable and nothing allocated.
+ * Scratch of _branches and _calls, released before they return: 48 B + 24 n_colors bytes at the most. */
+typedef struct sbwtgpu_genotype sbwtgpu_genotype;
+int     sbwtgpu_genotype_create(const sbwtgpu_index *idx, const sbwtgpu_unitigs *u, const sbwtgpu_bubbles *b, sbwtgpu_genotype **out);
+int     sbwtgpu_genotype_reset(sbwtgpu_genotype *g);
+void    sbwtgpu_genotype_destroy(sbwtgpu_genotype *g);
+int64_t sbwtgpu_genotype_workspace_bytes(int64_t total_bases, int64_t n_reads, int strands);
+int     sbwtgpu_genotype_add_dev(sbwtgpu_genotype *g, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                                 int64_t n_reads, int strands, void *d_workspace, int64_t workspace_bytes, void *stream);
+int     sbwtgpu_genotype_add_batch(sbwtgpu_genotype *g, const char *bases, const int64_t *read_off, int64_t n_reads, int strands);
+int     sbwtgpu_genotype_info(const sbwtgpu_genotype *g, int64_t *n_bubbles, int64_t *n_branch_kmers /* P */, int64_t *n_windows,
+                              int64_t *n_hits, int64_t *n_site_hits, int32_t *n_colors);
+int     sbwtgpu_genotype_branches(const sbwtgpu_genotype *g, int64_t *seen, int64_t *hits, int64_t *min_hits /* 2 B each */);
+int     sbwtgpu_genotype_kmer_hits_copy(const sbwtgpu_genotype *g, int64_t *branch_off /* 2 B + 1 */, uint64_t *kmer_hits /* P */);
+int     sbwtgpu_genotype_calls(const sbwtgpu_genotype *g, int32_t breadth_ppm, int64_t min_depth, uint8_t *call /* B */,
+                               int64_t *ref_sites, int64_t *ref_match, int64_t *ref_only /* n_colors each, or NULL */);
 
 #ifdef __cplusplus
 }

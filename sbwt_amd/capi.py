@@ -79,6 +79,9 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_screen_seen_dev", "sbwtgpu_screen_seen_copy",
     "sbwtgpu_bubbles_create", "sbwtgpu_bubbles_info", "sbwtgpu_bubbles_dev", "sbwtgpu_bubbles_copy",
     "sbwtgpu_bubbles_in_degrees_copy", "sbwtgpu_bubbles_stats", "sbwtgpu_bubbles_destroy",
+    "sbwtgpu_genotype_create", "sbwtgpu_genotype_reset", "sbwtgpu_genotype_destroy", "sbwtgpu_genotype_workspace_bytes",
+    "sbwtgpu_genotype_add_dev", "sbwtgpu_genotype_add_batch", "sbwtgpu_genotype_info", "sbwtgpu_genotype_branches",
+    "sbwtgpu_genotype_kmer_hits_copy", "sbwtgpu_genotype_calls",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -376,6 +379,19 @@ def lib() -> C.CDLL:
         L.sbwtgpu_bubbles_stats.argtypes = [vp, C.POINTER(C.c_double)]
         L.sbwtgpu_bubbles_destroy.argtypes = [vp]
         L.sbwtgpu_bubbles_destroy.restype = None
+        L.sbwtgpu_genotype_create.argtypes = [vp, vp, vp, C.POINTER(vp)]
+        L.sbwtgpu_genotype_reset.argtypes = [vp]
+        L.sbwtgpu_genotype_destroy.argtypes = [vp]
+        L.sbwtgpu_genotype_destroy.restype = None
+        L.sbwtgpu_genotype_workspace_bytes.argtypes = [i64, i64, ci]
+        L.sbwtgpu_genotype_workspace_bytes.restype = i64
+        L.sbwtgpu_genotype_add_dev.argtypes = [vp, vp, i64, vp, i64, ci, vp, i64, vp]
+        L.sbwtgpu_genotype_add_batch.argtypes = [vp, vp, vp, i64, ci]
+        L.sbwtgpu_genotype_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
+                                            C.POINTER(C.c_int32)]
+        L.sbwtgpu_genotype_branches.argtypes = [vp, vp, vp, vp]
+        L.sbwtgpu_genotype_kmer_hits_copy.argtypes = [vp, vp, vp]
+        L.sbwtgpu_genotype_calls.argtypes = [vp, C.c_int32, i64, vp, vp, vp, vp]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -959,6 +975,13 @@ class Unitigs:
         _check(lib().sbwtgpu_bubbles_create(self._h, colorsets._h if colorsets is not None else None, C.byref(h)))
         return Bubbles(h)
 
+    def genotype(self, index: "Index", bubbles: "Bubbles") -> "Genotype":
+        """sbwtgpu_genotype_create: an accumulator of per-allele k-mer depth over the bubbles of this handle (made from `index`
+        with the links and the column map).  The object copies what it needs of `bubbles`."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_genotype_create(index._h, self._h, bubbles._h, C.byref(h)))
+        return Genotype(h, index, self)
+
     # ---- a coloured handle only (ColorSets.unitigs_dev) ----
     def set_ids_dev(self) -> int:
         """d_set_id (n_unitigs uint32) as an integer; valid until close()."""
@@ -1037,6 +1060,89 @@ class Bubbles:
         ms = (C.c_double * 4)()
         _check(lib().sbwtgpu_bubbles_stats(self._h, ms))
         return {"pass_ms": dict(zip(("in_degrees", "detect", "compact", "branch_colors"), (float(x) for x in ms)))}
+
+
+class Genotype:
+    """Owns an sbwtgpu_genotype handle: the accumulator of a read set genotyped at the bubbles of a plain unitig graph
+    (include/sbwtgpu.h, "genotype") -- per k-mer of every branch its hits, per branch seen / hits / min_hits, per bubble a call
+    and per colour how often the sample follows it.  Everything is exact int64.  The index and the handle are kept referenced."""
+
+    def __init__(self, handle, index: "Index", unitigs: "Unitigs"):
+        self._h = handle
+        self.index, self.unitigs = index, unitigs
+        i = self.info()
+        self.n_bubbles, self.n_branch_kmers, self.n_colors = i["n_bubbles"], i["n_branch_kmers"], i["n_colors"]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        if self._h:
+            lib().sbwtgpu_genotype_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def add(self, bases, read_off, strands: int = 1) -> None:
+        """sbwtgpu_genotype_add_batch: the reads (uint8 bases, int64 offsets) join the sample; strands = 2 adds the reverse
+        complement of every window too."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        _check(lib().sbwtgpu_genotype_add_batch(self._h, bases.ctypes.data, read_off.ctypes.data, len(read_off) - 1, strands))
+
+    def add_reads(self, reads: Sequence[bytes], strands: int = 1) -> None:
+        bases, off = concat_reads(reads)
+        self.add(bases, off, strands)
+
+    def add_dev(self, d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_ws: int, ws_bytes: int, strands: int = 1,
+                stream: int = 0) -> None:
+        """sbwtgpu_genotype_add_dev (raw device pointers; workspace of genotype_workspace_bytes): asynchronous on stream."""
+        _check(lib().sbwtgpu_genotype_add_dev(self._h, d_bases or None, total_bases, d_read_off or None, n_reads, strands, d_ws or None,
+                                              ws_bytes, stream or None))
+
+    def reset(self) -> None:
+        _check(lib().sbwtgpu_genotype_reset(self._h))
+
+    def info(self) -> dict:
+        """n_bubbles, n_branch_kmers (P), n_windows, n_hits, n_site_hits and n_colors."""
+        v = [C.c_int64() for _ in range(5)]
+        nc = C.c_int32()
+        _check(lib().sbwtgpu_genotype_info(self._h, *[C.byref(x) for x in v], C.byref(nc)))
+        return dict(zip(("n_bubbles", "n_branch_kmers", "n_windows", "n_hits", "n_site_hits"), (int(x.value) for x in v)),
+                    n_colors=int(nc.value))
+
+    def branches(self):
+        """(seen, hits, min_hits): int64[2 n_bubbles] each, slot 2 i + j = branch j of bubble i."""
+        out = [np.full(2 * self.n_bubbles, -12345, dtype=np.int64) for _ in range(3)]
+        _check(lib().sbwtgpu_genotype_branches(self._h, *[x.ctypes.data if x.size else None for x in out]))
+        return tuple(out)
+
+    def kmer_hits(self):
+        """(branch_off, kmer_hits): int64[2 n_bubbles + 1] and uint64[P]; branch s holds kmer_hits[branch_off[s] : branch_off[s + 1]]."""
+        off = np.full(2 * self.n_bubbles + 1, -12345, dtype=np.int64)
+        hits = np.full(self.n_branch_kmers, 12345, dtype=np.uint64)
+        _check(lib().sbwtgpu_genotype_kmer_hits_copy(self._h, off.ctypes.data, hits.ctypes.data if hits.size else None))
+        return off, hits
+
+    def calls(self, breadth_ppm: int = 1_000_000, min_depth: int = 1):
+        """(call, ref_sites, ref_match, ref_only): uint8[n_bubbles] (bit 0: allele a present, bit 1: allele b) and, for an
+        object made from bubbles with colours, int64[n_colors] each (None otherwise)."""
+        call = np.full(self.n_bubbles, 0xA5, dtype=np.uint8)
+        ref = [np.full(self.n_colors, -12345, dtype=np.int64) for _ in range(3)] if self.n_colors else [None] * 3
+        _check(lib().sbwtgpu_genotype_calls(self._h, breadth_ppm, min_depth, call.ctypes.data if call.size else None,
+                                            *[x.ctypes.data if x is not None else None for x in ref]))
+        return (call,) + tuple(ref)
 
 
 class Colors:
@@ -1633,6 +1739,10 @@ def read_hits_workspace_bytes(total_bases: int, n_reads: int, both_strands: bool
 
 def walks_workspace_bytes(total_bases: int, n_reads: int) -> int:
     return int(lib().sbwtgpu_unitigs_walks_workspace_bytes(total_bases, n_reads))
+
+
+def genotype_workspace_bytes(total_bases: int, n_reads: int, strands: int = 1) -> int:
+    return int(lib().sbwtgpu_genotype_workspace_bytes(total_bases, n_reads, strands))
 
 
 def screen_workspace_bytes(total_bases: int, n_reads: int, strands: int = 1) -> int:

@@ -612,6 +612,80 @@ public:
         detail::gpu_check(rc);
         return r;
     }
+    // A read set genotyped at the bubbles of a PLAIN graph handle of THIS index (include/sbwtgpu.h, "genotype"): the bubbles
+    // as bubbles() returns them, and an accumulator of per-allele k-mer depth that is kept for as many batches as the caller
+    // has.  The graph handle and the index must outlive the object; the vectors are exact int64.
+    class Genotype {
+    public:
+        Genotype() = default;
+        Genotype(const Genotype &) = delete;
+        Genotype &operator=(const Genotype &) = delete;
+        Genotype(Genotype &&o) noexcept : bubbles(std::move(o.bubbles)), h(o.h) { o.h = nullptr; }
+        Genotype &operator=(Genotype &&o) noexcept {
+            if (this != &o) { sbwtgpu_genotype_destroy(h); bubbles = std::move(o.bubbles); h = o.h; o.h = nullptr; }
+            return *this;
+        }
+        ~Genotype() { sbwtgpu_genotype_destroy(h); }
+        void add(const char *bases, const int64_t *read_off, int64_t n_reads, int strands = 1) {
+            detail::gpu_check(sbwtgpu_genotype_add_batch(h, bases, read_off, n_reads, strands));
+        }
+        void reset() { detail::gpu_check(sbwtgpu_genotype_reset(h)); }
+        struct Info { int64_t n_bubbles = 0, n_branch_kmers = 0, n_windows = 0, n_hits = 0, n_site_hits = 0; int32_t n_colors = 0; };
+        Info info() const {
+            Info i;
+            detail::gpu_check(sbwtgpu_genotype_info(h, &i.n_bubbles, &i.n_branch_kmers, &i.n_windows, &i.n_hits, &i.n_site_hits, &i.n_colors));
+            return i;
+        }
+        // per slot 2 i + j (branch j of bubble i)
+        struct Branches { std::vector<int64_t> seen, hits, min_hits; };
+        Branches branches() const {
+            Branches v;
+            const size_t n = 2 * bubbles.rec.size();
+            v.seen.resize(n); v.hits.resize(n); v.min_hits.resize(n);
+            detail::gpu_check(sbwtgpu_genotype_branches(h, v.seen.data(), v.hits.data(), v.min_hits.data()));
+            return v;
+        }
+        // branch s holds kmer_hits[branch_off[s] .. branch_off[s + 1])
+        struct KmerHits { std::vector<int64_t> branch_off; std::vector<uint64_t> kmer_hits; };
+        KmerHits kmer_hits() const {
+            KmerHits v;
+            v.branch_off.resize(2 * bubbles.rec.size() + 1);
+            v.kmer_hits.resize((size_t)info().n_branch_kmers);
+            detail::gpu_check(sbwtgpu_genotype_kmer_hits_copy(h, v.branch_off.data(), v.kmer_hits.data()));
+            return v;
+        }
+        // call[i]: bit 0 = allele a present, bit 1 = allele b; the three per-colour vectors are empty without colours
+        struct Calls { std::vector<uint8_t> call; std::vector<int64_t> ref_sites, ref_match, ref_only; };
+        Calls calls(int32_t breadth_ppm = 1000000, int64_t min_depth = 1) const {
+            Calls c;
+            const size_t nc = (size_t)bubbles.n_colors;
+            c.call.resize(bubbles.rec.size());
+            c.ref_sites.resize(nc); c.ref_match.resize(nc); c.ref_only.resize(nc);
+            detail::gpu_check(sbwtgpu_genotype_calls(h, breadth_ppm, min_depth, c.call.data(), nc ? c.ref_sites.data() : nullptr,
+                                                     nc ? c.ref_match.data() : nullptr, nc ? c.ref_only.data() : nullptr));
+            return c;
+        }
+        Bubbles bubbles;
+        sbwtgpu_genotype *h = nullptr;
+    };
+    Genotype genotype(const UnitigGraph &g, const sbwtgpu_colorsets *sets = nullptr) const {
+        const sbwtgpu_index *idx = need_device();
+        sbwtgpu_bubbles *b = nullptr;
+        detail::gpu_check(sbwtgpu_bubbles_create(g.h, sets, &b));
+        Genotype r;
+        int64_t n = 0;
+        int rc = sbwtgpu_bubbles_info(b, &n, &r.bubbles.n_snps, &r.bubbles.n_colors, &r.bubbles.words);
+        if (rc == SBWTGPU_OK) {
+            r.bubbles.rec.resize((size_t)n);
+            r.bubbles.inter.resize((size_t)n * 2 * (size_t)r.bubbles.words);
+            r.bubbles.uni.resize(r.bubbles.inter.size());
+            rc = sbwtgpu_bubbles_copy(b, r.bubbles.rec.data(), r.bubbles.inter.data(), r.bubbles.uni.data());
+        }
+        if (rc == SBWTGPU_OK) rc = sbwtgpu_genotype_create(idx, g.h, b, &r.h);      // (it copies what it needs of b)
+        sbwtgpu_bubbles_destroy(b);
+        detail::gpu_check(rc);
+        return r;
+    }
     // the links of a graph handle of n unitigs into host vectors
     static int copy_links(const sbwtgpu_unitigs *u, int64_t n, std::vector<int64_t> &link_off, std::vector<uint32_t> &link_to) {
         int64_t n_links = 0;

@@ -15,8 +15,10 @@
 //               the reads threaded through the unitig graph: one line per read, its number, then one
 //               `read_pos:unitig:offset:n_kmers` per step; --coverage: `unitig n_kmers kmer_hits` per unitig
 //   sbwt bubbles -i <index> [-c <colours>] -o <bubbles.tsv> [-z] [--snps-only]
+//               [-q <reads> [--both-strands] [--min-breadth 1.0] [--min-depth 1] [--refs-out <refs.tsv>] [--batch-bases <n>]]
 //               the variant sites of the unitig graph: a header line, then per bubble source, branches, sink, k-mers of each
-//               branch, SNP|OTHER and the two alleles; with -c the colours of each branch
+//               branch, SNP|OTHER and the two alleles; with -c the colours of each branch; with -q the reads genotyped at the
+//               bubbles: per allele the k-mers seen, the hits and the smallest k-mer depth, and the call (. a b ab)
 //   sbwt set-op -a <index A> -b <index B> [--op union|intersection|difference|symmetric-difference] -o <index> [--counts-only]
 //               two index files combined on the GPU without their input sequences: the index `sbwt build` would write for
 //               the result's k-mers
@@ -962,9 +964,10 @@ int set_op_main(int argc, char **argv) {
 }
 
 // ---- colours and pseudoalignment (include/sbwtgpu.h) ----
-// `--threshold` as parts per million, from its decimal text and without floating point: "0.7" -> 700000, "1" -> 1000000.
-// Digits (at least one), optionally '.' and digits; what comes after the sixth decimal must be zeros; 0 < value <= 1.
-int64_t parse_threshold_ppm(const string &s) {
+// `--threshold` (or the fraction of `option`) as parts per million, from its decimal text and without floating point:
+// "0.7" -> 700000, "1" -> 1000000.  Digits (at least one), optionally '.' and digits; what comes after the sixth decimal must
+// be zeros; 0 < value <= 1.
+int64_t parse_threshold_ppm(const string &s, const char *option = "--threshold") {
     const size_t dot = s.find('.');
     const string ip = s.substr(0, dot), fp = dot == string::npos ? string() : s.substr(dot + 1);
     bool ok = !ip.empty() && ip.size() <= 9 && (dot == string::npos || !fp.empty());
@@ -979,7 +982,7 @@ int64_t parse_threshold_ppm(const string &s) {
         }
     }
     if (!ok || ppm < 1 || ppm > 1000000)
-        throw std::runtime_error("Error: --threshold must be a decimal number in (0, 1] with at most six decimals, not '" + s + "'");
+        throw std::runtime_error(string("Error: ") + option + " must be a decimal number in (0, 1] with at most six decimals, not '" + s + "'");
     return ppm;
 }
 
@@ -1487,6 +1490,9 @@ void append_color_list(const uint64_t *row, int32_t words, string &text) {
 // "# unitigs U links L bubbles B snps S", then one line per bubble in record order: source, branch_a, branch_b, sink, n_a,
 // n_b, SNP|OTHER, allele_a, allele_b, tab-separated; with -c two more fields, the colours of each branch: those of inter,
 // comma-separated ascending ("-" for none), and "|" and those of uni where the two differ.  --snps-only keeps the SNP lines.
+// With -q the reads are genotyped at the bubbles (include/sbwtgpu.h, "genotype"): the header gains " windows W hits H
+// site_hits S", every line seen_a, hits_a, min_a, seen_b, hits_b, min_b and the call (. a b ab); --refs-out writes per colour
+// `colour sites match only`.  Batches go to the GPU one at a time and nothing comes back until the end.
 int bubbles_main(int argc, char **argv) {
     set_log_level(LogLevel::MINOR);
     Options opts({
@@ -1495,23 +1501,58 @@ int bubbles_main(int argc, char **argv) {
         {"out-file", 'o', true, "Output file: a header line, then one tab-separated line per bubble.", ""},
         {"gzip-output", 'z', false, "Writes the output in gzipped form.", ""},
         {"snps-only", 0, false, "Write only the bubbles of kind SNP (the header still counts all).", ""},
+        {"query-file", 'q', true, "Reads in FASTA or FASTQ format, possibly gzipped: genotype them at the bubbles (per allele k-mers seen, hits, smallest depth; the call).", ""},
+        {"both-strands", 0, false, "With -q: the reverse complement of every window counts as a window too.", ""},
+        {"min-breadth", 0, true, "With -q: an allele is present when at least this fraction of its k-mers is seen.", "1.0"},
+        {"min-depth", 0, true, "With -q: ... and its hits are at least this many times its k-mers.", "1"},
+        {"refs-out", 0, true, "With -q and -c: write per colour the called bubbles where it is informative, those that match it, those that carry only its allele.", ""},
         {"gpu", 0, true, "HIP device to run on.", "0"},
+        {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
     });
     parse_or_usage(opts, argc, argv, "Find the bubbles of the unitig graph: where the references differ, and which reference carries which allele.");
     const string indexfile = opts.get("index-file"), outfile = opts.get("out-file");
     const bool colored = opts.count("colors-file") > 0, gzip_output = opts.count("gzip-output") > 0, snps_only = opts.count("snps-only") > 0;
-    const string colorsfile = colored ? opts.get("colors-file") : string();
+    const bool query = opts.count("query-file") > 0;
+    const string colorsfile = colored ? opts.get("colors-file") : string(), queryfile = query ? opts.get("query-file") : string();
+    const string refsfile = opts.count("refs-out") ? opts.get("refs-out") : string();
+    for (const char *name : {"both-strands", "min-breadth", "min-depth", "refs-out"})
+        if (!query && opts.count(name)) throw std::runtime_error(string("Error: --") + name + " needs a query file (-q)");
+    if (!refsfile.empty() && !colored) throw std::runtime_error("Error: --refs-out needs a colour file (-c)");
+    const int strands = opts.count("both-strands") ? 2 : 1;
+    const int breadth_ppm = query ? (int)parse_threshold_ppm(opts.get("min-breadth"), "--min-breadth") : 1000000;
+    const string depth_text = opts.get("min-depth");
+    if (depth_text.empty() || depth_text.size() > 18 || depth_text.find_first_not_of("0123456789") != string::npos)
+        throw std::runtime_error("Error: --min-depth must be a non-negative integer, not '" + depth_text + "'");
+    const int64_t min_depth = atoll(depth_text.c_str());
     check_readable(indexfile);
     if (colored) check_readable(colorsfile);
+    if (query) check_readable(queryfile);
     check_writable(outfile);
+    if (!refsfile.empty()) check_writable(refsfile);
     use_gpu_option(opts);
+    const int64_t batch_bases = batch_bases_option(opts);
     plain_matrix_sbwt_t index;
     load_plain_matrix(indexfile, index);
     ColorSetsHandle sets;
     if (colored) load_colorsets(colorsfile, indexfile, index, sets);
     const plain_matrix_sbwt_t::UnitigGraph graph = index.unitig_graph();
-    const plain_matrix_sbwt_t::Bubbles bb = index.bubbles(graph, colored ? sets.h : nullptr);
+    plain_matrix_sbwt_t::Genotype gt;
+    plain_matrix_sbwt_t::Genotype::Info gi;
+    plain_matrix_sbwt_t::Genotype::Branches gb;
+    plain_matrix_sbwt_t::Genotype::Calls gc;
+    if (query) {
+        gt = index.genotype(graph, colored ? sets.h : nullptr);
+        seq_io::Reader reader(queryfile);
+        for_each_batch(reader, batch_bases, [&](const vector<char> &bases, const vector<int64_t> &read_off, int64_t n_reads) {
+            gt.add(bases.data(), read_off.data(), n_reads, strands);
+        });
+        gi = gt.info();
+        gb = gt.branches();
+        gc = gt.calls(breadth_ppm, min_depth);
+    }
+    const plain_matrix_sbwt_t::Bubbles own = query ? plain_matrix_sbwt_t::Bubbles() : index.bubbles(graph, colored ? sets.h : nullptr);
+    const plain_matrix_sbwt_t::Bubbles &bb = query ? gt.bubbles : own;
     const plain_matrix_sbwt_t::ColoredUnitigs u = graph.unitigs();
     string text = "# unitigs ";
     append_int((int64_t)u.first_col.size(), text);
@@ -1521,6 +1562,14 @@ int bubbles_main(int argc, char **argv) {
     append_int((int64_t)bb.rec.size(), text);
     text += " snps ";
     append_int(bb.n_snps, text);
+    if (query) {
+        text += " windows ";
+        append_int(gi.n_windows, text);
+        text += " hits ";
+        append_int(gi.n_hits, text);
+        text += " site_hits ";
+        append_int(gi.n_site_hits, text);
+    }
     text.push_back('\n');
     const size_t W = (size_t)bb.words;
     for (size_t i = 0; i < bb.rec.size(); i++) {
@@ -1546,11 +1595,33 @@ int bubbles_main(int argc, char **argv) {
                 append_color_list(un, bb.words, text);
             }
         }
+        if (query) {
+            static const char *const CALL[4] = {".", "a", "b", "ab"};
+            for (size_t s = 2 * i; s < 2 * i + 2; s++)
+                for (const int64_t x : {gb.seen[s], gb.hits[s], gb.min_hits[s]}) {
+                    text.push_back('\t');
+                    append_int(x, text);
+                }
+            text.push_back('\t');
+            text += CALL[gc.call[i] & 3];
+        }
         text.push_back('\n');
     }
     {
         seq_io::Buffered_ofstream writer(outfile, gzip_output);
         writer.write(text.data(), (int64_t)text.size());
+    }
+    if (!refsfile.empty()) {
+        string lines;
+        for (size_t c = 0; c < gc.ref_sites.size(); c++) {
+            append_int((int64_t)c, lines);
+            for (const int64_t x : {gc.ref_sites[c], gc.ref_match[c], gc.ref_only[c]}) {
+                lines.push_back('\t');
+                append_int(x, lines);
+            }
+            lines.push_back('\n');
+        }
+        write_text_file(refsfile, lines, false);
     }
     write_log("Wrote " + std::to_string(bb.rec.size()) + " bubbles (" + std::to_string(bb.n_snps) + " SNPs) of " +
                   std::to_string(u.first_col.size()) + " unitigs", LogLevel::MAJOR);

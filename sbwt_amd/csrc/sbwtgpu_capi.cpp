@@ -246,6 +246,7 @@ int sbwtgpu_set_tuning(const char *key, int64_t value) {
     if (!strcmp(key, "walks_chunk_bases")) { g_wk_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "pseudoalign_chunk_bases")) { g_pa_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "screen_chunk_bases")) { g_screen_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
+    if (!strcmp(key, "genotype_chunk_bases")) { g_gt_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "gram_mfma_min_sets")) { g_gram_mfma_min_sets = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "gram_flush_sets")) {
         if (value < 1 || value > SBWT_GM_FLUSH_MAX)

@@ -196,17 +196,16 @@ int64_t sbwtgpu_pseudoalign_workspace_bytes(int64_t total_bases, int64_t n_reads
     return sbwt_pa_layout(sbwtgpu_search_workspace_bytes(total_bases), total_bases, n_reads, strands == 2 ? 2 : 1).total;
 }
 
-// What colouring and the query share: the result offsets, the int32 search of the batch and, for two strands, of the mirrored
-// batch into the second result buffer; `tail` enqueues what turns the results into bits or records (res2: NULL with one strand,
-// and for a batch without any window, whose result buffers nobody wrote).
+// What colouring, the queries, screen and the genotype adds share: the result offsets, the int32 search of the batch and, for
+// two strands, of the mirrored batch into the second result buffer (res2: NULL with one strand, and for a batch without any
+// window, whose result buffers nobody wrote).  The workspace is that of sbwtgpu_pseudoalign_workspace_bytes.
 }  // extern "C"
-template <typename Tail>
-static int colors_dev_common(const sbwtgpu_colors *c, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
-                             int64_t n_reads, int strands, void *d_ws, int64_t ws_bytes, void *stream, Tail tail) {
+int sbwt_capi::search_strands_dev(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                                  int64_t n_reads, int strands, void *d_ws, int64_t ws_bytes, void *stream, StrandSearch &out) {
+    out = StrandSearch();
     STG_TRY(check_batch_dev(n_reads, total_bases, d_ws, ws_bytes, sbwtgpu_pseudoalign_workspace_bytes(total_bases, n_reads, strands)));
     if (n_reads == 0) return SBWTGPU_OK;
     if (!d_read_off || (total_bases > 0 && !d_bases)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
-    const sbwtgpu_index *idx = c->idx;
     DeviceGuard guard(idx->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t search_ws = sbwtgpu_search_workspace_bytes(total_bases);
@@ -219,7 +218,7 @@ static int colors_dev_common(const sbwtgpu_colors *c, const char *d_bases, int64
     HIP_TRY(hipMemsetAsync(hdr, 0, sizeof(SbwtPaHeader), st));
     sbwt_launch_rh_offsets(reinterpret_cast<const long long *>(d_read_off), n_reads, k, reinterpret_cast<long long *>(w + L.cnt),
                            reinterpret_cast<long long *>(w + L.bsum), ooff, st);
-    // (a batch of fewer than k bases has no window: nothing to search, and `tail` reads no result)
+    // (a batch of fewer than k bases has no window: nothing to search, and the caller's tail reads no result)
     const bool any = total_bases >= k;
     const SbwtWorkHeader *sws = reinterpret_cast<const SbwtWorkHeader *>(w);
     int *res2 = nullptr;
@@ -240,7 +239,23 @@ static int colors_dev_common(const sbwtgpu_colors *c, const char *d_bases, int64
         if (rc != SBWTGPU_OK) return rc;
         sbwt_launch_pa_note_status(sws, hdr, st);
     }
-    tail(res, res2, ooff, hdr, st);
+    out.res = res;
+    out.res2 = res2;
+    out.ooff = ooff;
+    out.hdr = hdr;
+    out.hdr_off = L.hdr;
+    out.enqueued = true;
+    return SBWTGPU_OK;
+}
+// `tail` enqueues what turns the results into bits or records
+template <typename Tail>
+static int colors_dev_common(const sbwtgpu_colors *c, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                             int64_t n_reads, int strands, void *d_ws, int64_t ws_bytes, void *stream, Tail tail) {
+    StrandSearch q;
+    STG_TRY(search_strands_dev(c->idx, d_bases, total_bases, d_read_off, n_reads, strands, d_ws, ws_bytes, stream, q));
+    if (!q.enqueued) return SBWTGPU_OK;
+    DeviceGuard guard(c->idx->device);
+    tail(q.res, q.res2, q.ooff, static_cast<SbwtPaHeader *>(q.hdr), static_cast<hipStream_t>(stream));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
     return SBWTGPU_OK;

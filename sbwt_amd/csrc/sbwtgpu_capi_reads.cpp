@@ -1,6 +1,6 @@
 // sbwtgpu_capi_reads.cpp -- the C ABI's layers over an index and its reads that know nothing of colours: matching statistics
 // with the LCS array, set operations and k-mer keys, per-read hit profiles, unitigs and their graph (links, column map,
-// locate), reads threaded through the graph (walks), bubbles.  What it shares with the other files: sbwtgpu_internal.h.
+// locate), reads threaded through the graph (walks), bubbles, genotype.  What it shares with the other files: sbwtgpu_internal.h.
 #include <cstdlib>
 
 #include "sbwtgpu_internal.h"
@@ -9,6 +9,8 @@
 #include "sbwt_readhits.h"
 #include "sbwt_walks.h"
 #include "sbwt_bubbles.h"
+#include "sbwt_colors.h"
+#include "sbwt_genotype.h"
 
 using namespace sbwt_capi;
 
@@ -19,6 +21,7 @@ int sbwt_capi::g_rh_wave_min = SBWT_RH_WAVE_MIN;
 int64_t sbwt_capi::g_rh_chunk_bases = 0;
 int sbwt_capi::g_rh_wide = 0;
 int64_t sbwt_capi::g_wk_chunk_bases = 0;      // "walks_chunk_bases": 0 = the default of 64 Mi
+int64_t sbwt_capi::g_gt_chunk_bases = 0;      // "genotype_chunk_bases": 0 = the default of 64 Mi
 
 extern "C" {
 
@@ -930,6 +933,239 @@ int sbwtgpu_bubbles_stats(const sbwtgpu_bubbles *b, double pass_ms[4]) {
     if (!b) return fail(SBWTGPU_ERR_INVALID_ARG, "bubbles: the object is NULL");
     if (pass_ms)
         for (int i = 0; i < SBWT_BB_N_PASSES; i++) pass_ms[i] = (double)b->run.ms[i];
+    return SBWTGPU_OK;
+}
+
+// ---- genotype: per-allele k-mer depth of a read set at the bubbles, and calls (sbwt_genotype.hip) ----
+}  // extern "C"
+// The adds only ever add to the state with atomics; the queries take `mu`, run on `stream` and bring their scratch with them.
+struct sbwtgpu_genotype {
+    const sbwtgpu_index *idx = nullptr;
+    const sbwtgpu_unitigs *u = nullptr;
+    int device = 0;
+    int n_colors = 0, words = 0;
+    SbwtGenotypeState st;
+    Stream stream;
+    mutable std::mutex mu;
+};
+// the object, and that its index and handle still are what it was made from
+static int genotype_check(const sbwtgpu_genotype *g) {
+    if (!g) return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: the object is NULL");
+    if (g->idx->h.n_nodes != g->st.n_nodes || g->u->n_nodes != g->st.n_nodes)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: the object was made for %lld columns, its index has %lld and its handle %lld",
+                    (long long)g->st.n_nodes, (long long)g->idx->h.n_nodes, (long long)g->u->n_nodes);
+    return SBWTGPU_OK;
+}
+static int genotype_check_batch(int64_t n_reads, int strands) {
+    if (strands != 1 && strands != 2) return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: strands must be 1 (forward) or 2 (either strand), not %d", strands);
+    if (n_reads < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: negative n_reads");
+    if (n_reads >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: 2^31 reads or more in one call: split the batch");
+    return SBWTGPU_OK;
+}
+extern "C" {
+
+int sbwtgpu_genotype_create(const sbwtgpu_index *idx, const sbwtgpu_unitigs *u, const sbwtgpu_bubbles *b, sbwtgpu_genotype **out) {
+    if (!idx || !u || !b || !out) return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: NULL argument (idx, u, b and out are needed)");
+    *out = nullptr;
+    // (the size first, as the colour layer does: an index of that size is refused for it whatever else is wrong with the call)
+    if (idx->h.n_nodes >= ((int64_t)1 << 31))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: the index has %lld columns, the adds read int32 search results (fewer than 2^31 columns)",
+                    (long long)idx->h.n_nodes);
+    if (idx->h.rank_only) return fail(SBWTGPU_ERR_INVALID_ARG, "%s", RANK_ONLY_MSG);
+    if (u->colored)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: a coloured handle cuts the branches at colour breaks: pass the plain handle "
+                    "(sbwtgpu_unitigs_create_graph with idx) the bubbles were made from");
+    if (!(u->graph & SBWTGPU_UNITIGS_LINKS))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: the handle was made without SBWTGPU_UNITIGS_LINKS (sbwtgpu_unitigs_create_graph takes the flag)");
+    if (!(u->graph & SBWTGPU_UNITIGS_COLUMN_MAP))
+        return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: the handle was made without SBWTGPU_UNITIGS_COLUMN_MAP (sbwtgpu_unitigs_create_graph takes the flag)");
+    if (u->n_nodes != idx->h.n_nodes || u->k != idx->h.k || u->device != idx->device)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: the handle (%lld columns, k = %lld, device %d) was not made from this index (%lld columns, k = %lld, device %d)",
+                    (long long)u->n_nodes, (long long)u->k, u->device, (long long)idx->h.n_nodes, (long long)idx->h.k, idx->device);
+    if (b->device != u->device)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: the bubbles are on device %d, the unitigs on device %d", b->device, u->device);
+    DeviceGuard guard(u->device);
+    if (!guard.ok) return fail(SBWTGPU_ERR_NO_DEVICE, "hipSetDevice(%d) failed", u->device);
+    sbwtgpu_genotype *g = new (std::nothrow) sbwtgpu_genotype();
+    if (!g) return fail(SBWTGPU_ERR_OOM, "out of host memory");
+    g->idx = idx;
+    g->u = u;
+    g->device = u->device;
+    g->n_colors = b->n_colors;
+    g->words = b->words;
+    SbwtGenotypeGraph gg;
+    gg.d_rec = b->run.d_rec;
+    gg.d_inter = b->words > 0 ? b->run.d_inter : nullptr;
+    gg.n_bubbles = b->run.n_bubbles;
+    gg.words = b->words;
+    gg.d_off = u->run.d_off;
+    gg.n_unitigs = u->run.n_unitigs;
+    gg.k = u->k;
+    gg.d_col_unitig = u->run.d_col_unitig;
+    gg.d_col_offset = u->run.d_col_offset;
+    gg.n_nodes = u->n_nodes;
+    int bad = 0;
+    hipError_t e = hipStreamCreateWithFlags(&g->stream.s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = sbwt_genotype_build(gg, &g->st, &bad, g->stream.s);
+    if (e != hipSuccess || bad) {
+        (void)hipGetLastError();
+        delete g;
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SBWTGPU_ERR_OOM : SBWTGPU_ERR_HIP, "genotype: %s", hipGetErrorString(e));
+        return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: the bubbles do not fit the handle (%s): they were made from another handle",
+                    (bad & SBWT_GT_BAD_UNITIG) ? "a record names a unitig the handle does not have, or its n_kmers is not that unitig's k-mer count"
+                    : (bad & SBWT_GT_BAD_SHARED) ? "two branches name one unitig"
+                                                 : "the branch columns of the column map are not the k-mers of the records");
+    }
+    *out = g;
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_genotype_reset(sbwtgpu_genotype *g) {
+    const int rc = genotype_check(g);
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(g->device);
+    std::lock_guard<std::mutex> lock(g->mu);
+    // (adds of the caller's on other streams have to be over, as for the queries: the device is waited for, then zeroed)
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemsetAsync(g->st.d_acc, 0, g->st.acc_bytes, g->stream.s));
+    HIP_TRY(hipStreamSynchronize(g->stream.s));
+    return SBWTGPU_OK;
+}
+
+void sbwtgpu_genotype_destroy(sbwtgpu_genotype *g) {
+    if (!g) return;
+    DeviceGuard guard(g->device);
+    sbwt_genotype_free(&g->st);
+    delete g;
+}
+
+int64_t sbwtgpu_genotype_workspace_bytes(int64_t total_bases, int64_t n_reads, int strands) {
+    return sbwtgpu_pseudoalign_workspace_bytes(total_bases, n_reads, strands);
+}
+
+int sbwtgpu_genotype_add_dev(sbwtgpu_genotype *g, const char *d_bases, int64_t total_bases, const int64_t *d_read_off, int64_t n_reads,
+                             int strands, void *d_ws, int64_t ws_bytes, void *stream) {
+    int rc = genotype_check(g);
+    if (rc == SBWTGPU_OK) rc = genotype_check_batch(n_reads, strands);
+    if (rc != SBWTGPU_OK) return rc;
+    StrandSearch q;
+    STG_TRY(search_strands_dev(g->idx, d_bases, total_bases, d_read_off, n_reads, strands, d_ws, ws_bytes, stream, q));
+    if (!q.enqueued) return SBWTGPU_OK;
+    DeviceGuard guard(g->device);
+    sbwt_launch_genotype_add(q.res, q.res2, q.ooff, n_reads, total_bases, g->st, static_cast<hipStream_t>(stream));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SBWTGPU_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
+    return SBWTGPU_OK;
+}
+
+// Host buffers: read_hits_batch's chunks of whole reads under "genotype_chunk_bases", two in flight on the parked slots of the
+// search pipeline.  Bases and offsets go down; only each chunk's status word comes back.
+int sbwtgpu_genotype_add_batch(sbwtgpu_genotype *g, const char *bases, const int64_t *read_off, int64_t n_reads, int strands) {
+    int rc = genotype_check(g);
+    if (rc == SBWTGPU_OK) rc = genotype_check_batch(n_reads, strands);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_reads == 0) return SBWTGPU_OK;
+    if (!read_off) return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: NULL argument (read_off)");
+    if (read_off[n_reads] > read_off[0] && !bases) return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: NULL argument (bases)");
+    SbwtReadChunks ch;
+    rc = cut_reads(read_off, n_reads, g_gt_chunk_bases > 0 ? g_gt_chunk_bases : (int64_t)64 << 20, (int64_t)1 << 24, g->idx->h.k, ch);
+    if (rc != SBWTGPU_OK) return rc;
+    DeviceGuard guard(g->device);
+    ReadPipe pipe(bases, read_off, ch);
+    rc = pipe.open(g->device, sbwtgpu_genotype_workspace_bytes(ch.max_bases, ch.max_reads, strands), ch.n_chunks() > 1 ? 2 : 1, "genotype buffers");
+    if (rc != SBWTGPU_OK) return rc;
+    return pipe.run([&](const ReadPipe::Chunk &c) -> int {
+        STG_TRY(sbwtgpu_genotype_add_dev(g, c.bases, c.nb, c.roff, c.nr, strands, c.ws, pipe.ws_bytes, c.P->st));
+        const SbwtPaLayout L = sbwt_pa_layout(sbwtgpu_search_workspace_bytes(c.nb), c.nb, c.nr, strands);
+        return pipe.fetch(c, c.ws + L.hdr, 4);
+    });
+}
+
+int sbwtgpu_genotype_info(const sbwtgpu_genotype *g, int64_t *n_bubbles, int64_t *n_branch_kmers, int64_t *n_windows, int64_t *n_hits,
+                          int64_t *n_site_hits, int32_t *n_colors) {
+    const int rc = genotype_check(g);
+    if (rc != SBWTGPU_OK) return rc;
+    if (n_bubbles) *n_bubbles = g->st.n_bubbles;
+    if (n_branch_kmers) *n_branch_kmers = g->st.n_positions;
+    if (n_colors) *n_colors = g->n_colors;
+    if (!n_windows && !n_hits && !n_site_hits) return SBWTGPU_OK;
+    DeviceGuard guard(g->device);
+    std::lock_guard<std::mutex> lock(g->mu);
+    SbwtGenotypeCounters h;
+    HIP_TRY(hipMemcpyAsync(&h, g->st.ctr(), sizeof(h), hipMemcpyDeviceToHost, g->stream.s));
+    HIP_TRY(hipStreamSynchronize(g->stream.s));
+    if (n_windows) *n_windows = (int64_t)h.n_windows;
+    if (n_hits) *n_hits = (int64_t)h.n_hits;
+    if (n_site_hits) *n_site_hits = (int64_t)h.n_site_hits;
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_genotype_branches(const sbwtgpu_genotype *g, int64_t *seen, int64_t *hits, int64_t *min_hits) {
+    const int rc = genotype_check(g);
+    if (rc != SBWTGPU_OK) return rc;
+    const int64_t n_slots = 2 * g->st.n_bubbles;
+    if (n_slots == 0 || (!seen && !hits && !min_hits)) return SBWTGPU_OK;
+    DeviceGuard guard(g->device);
+    std::lock_guard<std::mutex> lock(g->mu);
+    hipStream_t st = g->stream.s;
+    const size_t nb = (size_t)n_slots * 8;
+    DevBuf d;
+    HIP_TRY(d.alloc(3 * nb));
+    long long *v = static_cast<long long *>(d.p);
+    sbwt_launch_genotype_branches(g->st, v, v + n_slots, v + 2 * n_slots, st);
+    HIP_TRY(hipGetLastError());
+    if (seen) HIP_TRY(hipMemcpyAsync(seen, v, nb, hipMemcpyDeviceToHost, st));
+    if (hits) HIP_TRY(hipMemcpyAsync(hits, v + n_slots, nb, hipMemcpyDeviceToHost, st));
+    if (min_hits) HIP_TRY(hipMemcpyAsync(min_hits, v + 2 * n_slots, nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_genotype_kmer_hits_copy(const sbwtgpu_genotype *g, int64_t *branch_off, uint64_t *kmer_hits) {
+    const int rc = genotype_check(g);
+    if (rc != SBWTGPU_OK) return rc;
+    if (!branch_off && !kmer_hits) return SBWTGPU_OK;
+    DeviceGuard guard(g->device);
+    std::lock_guard<std::mutex> lock(g->mu);
+    hipStream_t st = g->stream.s;
+    if (branch_off) HIP_TRY(hipMemcpyAsync(branch_off, g->st.d_branch_off, (size_t)(2 * g->st.n_bubbles + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (kmer_hits && g->st.n_positions > 0)
+        HIP_TRY(hipMemcpyAsync(kmer_hits, g->st.kmer_hits(), (size_t)g->st.n_positions * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return SBWTGPU_OK;
+}
+
+int sbwtgpu_genotype_calls(const sbwtgpu_genotype *g, int32_t breadth_ppm, int64_t min_depth, uint8_t *call, int64_t *ref_sites,
+                           int64_t *ref_match, int64_t *ref_only) {
+    const int rc = genotype_check(g);
+    if (rc != SBWTGPU_OK) return rc;
+    if (breadth_ppm < 1 || breadth_ppm > 1000000)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: breadth_ppm must be in 1 .. 1000000, not %d", (int)breadth_ppm);
+    if (min_depth < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: min_depth must not be negative (%lld)", (long long)min_depth);
+    const bool colours = ref_sites || ref_match || ref_only;
+    if (colours && g->words == 0)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: the object was made from bubbles without colours (sbwtgpu_bubbles_create with a "
+                    "colour-set object carries them): ref_sites, ref_match and ref_only must be NULL");
+    if (!call && !colours) return SBWTGPU_OK;
+    DeviceGuard guard(g->device);
+    std::lock_guard<std::mutex> lock(g->mu);
+    hipStream_t st = g->stream.s;
+    const int64_t B = g->st.n_bubbles, n_slots = 2 * B;
+    const size_t nb = (size_t)n_slots * 8, cb = (size_t)g->n_colors * 8;
+    // scratch: [seen][hits][min_hits][ref: sites, match, only][call]
+    DevBuf d;
+    HIP_TRY(d.alloc(3 * nb + 3 * cb + (size_t)B));
+    long long *v = static_cast<long long *>(d.p);
+    unsigned long long *ref = colours ? reinterpret_cast<unsigned long long *>(static_cast<char *>(d.p) + 3 * nb) : nullptr;
+    unsigned char *d_call = reinterpret_cast<unsigned char *>(static_cast<char *>(d.p) + 3 * nb + 3 * cb);
+    sbwt_launch_genotype_branches(g->st, v, v + n_slots, v + 2 * n_slots, st);
+    sbwt_launch_genotype_calls(g->st, v, v + n_slots, breadth_ppm, min_depth, g->words, g->n_colors, call ? d_call : nullptr, ref, st);
+    HIP_TRY(hipGetLastError());
+    if (call && B > 0) HIP_TRY(hipMemcpyAsync(call, d_call, (size_t)B, hipMemcpyDeviceToHost, st));
+    if (ref_sites) HIP_TRY(hipMemcpyAsync(ref_sites, ref, cb, hipMemcpyDeviceToHost, st));
+    if (ref_match) HIP_TRY(hipMemcpyAsync(ref_match, reinterpret_cast<char *>(ref) + cb, cb, hipMemcpyDeviceToHost, st));
+    if (ref_only) HIP_TRY(hipMemcpyAsync(ref_only, reinterpret_cast<char *>(ref) + 2 * cb, cb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return SBWTGPU_OK;
 }
 

@@ -85,7 +85,7 @@ inline constexpr const char *RANK_ONLY_MSG =
 // is read before main (a knob with an environment default is a dynamic initialiser of its own file)
 extern int g_poison;                                        // sbwtgpu_capi.cpp; the derived layers poison their results too
 extern int g_rh_wave_min, g_rh_wide;                        // sbwtgpu_capi_reads.cpp
-extern int64_t g_rh_chunk_bases, g_wk_chunk_bases;
+extern int64_t g_rh_chunk_bases, g_wk_chunk_bases, g_gt_chunk_bases;
 extern int64_t g_pa_chunk_bases, g_screen_chunk_bases;      // sbwtgpu_capi_colors.cpp
 extern int64_t g_gram_mfma_min_sets, g_gram_flush_sets;
 
@@ -157,6 +157,19 @@ int unitigs_create_common(const sbwtgpu_index *idx, const unsigned *d_ids, const
 int setop_check_index(const sbwtgpu_index *idx, const char *who);
 // sbwtgpu_capi_colors.cpp
 int colorsets_check(const sbwtgpu_colorsets *s);
+// The searches of a batch and, for two strands, of its mirrored batch, int32 results, in a workspace of
+// sbwtgpu_pseudoalign_workspace_bytes: what the calls over colours and the genotype adds put in front of their own kernel.
+// enqueued: false for a batch of no reads, where nothing was launched.  hdr: the workspace's SbwtPaHeader, whose first word
+// is the searches' status, at byte hdr_off.
+struct StrandSearch {
+    const int *res = nullptr, *res2 = nullptr;
+    const long long *ooff = nullptr;
+    void *hdr = nullptr;
+    int64_t hdr_off = 0;
+    bool enqueued = false;
+};
+int search_strands_dev(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases, const int64_t *d_read_off, int64_t n_reads,
+                       int strands, void *d_ws, int64_t ws_bytes, void *stream, StrandSearch &out);
 
 // The length of read r as every host entry point checks it while it walks the offsets: not negative, below 2^31
 inline int check_read_length(const int64_t *read_off, int64_t r) {
