@@ -122,6 +122,11 @@ int         sbwtgpu_device_count(int *count);
  *                        always takes one read); 0 (default) = 64 Mi
  *   "genotype_chunk_bases" sbwtgpu_genotype_add_batch cuts its batch into chunks of whole reads of at most this many bases (a
  *                        chunk always takes one read); 0 (default) = 64 Mi
+ *   "positions_chunk_bases" sbwtgpu_positions_add_batch and sbwtgpu_positions_map_batch cut their batch into chunks of whole
+ *                        sequences of at most this many bases (a chunk always takes one sequence); 0 (default) = 64 Mi
+ *   "positions_map_table" the distinct placements per read that the map kernel keeps in LDS before the read goes to the exact
+ *                        second kernel: 1 .. SBWTGPU_POSITIONS_MAP_TABLE, 0 (default) = that compiled capacity; another value
+ *                        is refused.  No result depends on it (tests reach the second kernel with it)
  *   "trans_ext", "trans_wide"   accepted and ignored (round-2 table formats)
  * Read when an index is CREATED (derived acceleration structures inside the device image; environment
  * variables of the same meaning: SBWTGPU_SPARSE_PRECALC, SBWTGPU_PROBE_FILTER, SBWTGPU_PATH_ORDER):
@@ -1204,6 +1209,107 @@ int     sbwtgpu_genotype_branches(const sbwtgpu_genotype *g, int64_t *seen, int6
 int     sbwtgpu_genotype_kmer_hits_copy(const sbwtgpu_genotype *g, int64_t *branch_off /* 2 B + 1 */, uint64_t *kmer_hits /* P */);
 int     sbwtgpu_genotype_calls(const sbwtgpu_genotype *g, int32_t breadth_ppm, int64_t min_depth, uint8_t *call /* B */,
                                int64_t *ref_sites, int64_t *ref_match, int64_t *ref_only /* n_colors each, or NULL */);
+
+/* ---- positions: where on a reference a k-mer lies, and where a read maps ----
+ * One table, holding for every column the smallest reference coordinate at which its k-mer occurs, and one read-side call,
+ * which for every read finds the reference placement that most of its k-mers agree on: seed-and-vote mapping on the diagonal
+ * ref_pos - read_pos.  Everything is exact integers.  There is no floating point anywhere.
+ * The position table
+ *   A sbwtgpu_positions object is bound to one index of n columns and its k.  The index must have n < 2^31 and must not be
+ *   rank-only.
+ *   It holds first[v], one uint64 per column.  UINT64_MAX means "no position".
+ *   - Sequence numbers.  The caller numbers the reference sequences.  An add of n_reads sequences with first_seq gives
+ *     sequence i of the batch the number first_seq + i.  Numbers must be in 0 ... 2^30 - 1.
+ *   - Window and strand flag.  A window of sequence q at 0-based offset pos is x = q[pos .. pos+k).  It follows the rule of
+ *     sbwtgpu_search_batch: upper-case ACGT only.
+ *     - If the search of x gives column v >= 0, the key (seq << 32) | (pos << 1) | 0 is offered to first[v].
+ *     - With strands = 2, the search of the reverse complement of x gives v' >= 0, and the key with low bit 1 is offered to
+ *       first[v'].  The complement rule is that of the read-hit profiles.
+ *     - first[v] is the minimum of the keys offered.  The low bit t says that the column's k-mer is the reverse complement of
+ *       the reference window at pos.
+ *     - A palindromic window offers both keys to one column.  The minimum keeps t = 0.
+ *   - State.  The state is a function of the index and of the set of (sequence number, sequence, strands) triples added.  It
+ *     does not depend on batch boundaries, chunking, the order of adds, concurrent adds from several host threads, tuning,
+ *     image level or streams.
+ *     - Adding one sequence twice under the same number changes nothing.
+ *     - Adding it under two numbers leaves the smaller.
+ *   - Scalars.  These are exact int64:
+ *     - n_windows: windows offered, once per strand searched;
+ *     - n_hits;
+ *     - n_positioned: the number of columns with a position, derived on demand.
+ * Mapping a read
+ *   The read has W windows.  Window i, 0-based on the read as given, is searched as x.  With strands = 2 it is also searched
+ *   as rc(x), in the mirrored batch.  A result >= 0 is a hit (i, s) on column v, with s = 0 for the first search and s = 1 for
+ *   the second.  A hit whose first[v] is a position (seq, pos, t) is anchored.
+ *   An anchored hit votes for the placement (seq, o, start):
+ *   - o = s XOR t;
+ *   - start = pos - i if o = 0;
+ *   - start = pos - (W - 1 - i) if o = 1.
+ *   start is the reference coordinate of the read's leftmost base when the read lies on the reference in orientation o.  It
+ *   is signed and may be negative.
+ *   The record per read is 32 bytes (sbwtgpu_read_map):
+ *   - (seq, strand = o, start) is the placement with the most votes.  Ties go to the lexicographically smallest
+ *     (seq, o, start), with start compared as signed.
+ *   - votes is the winner's count.
+ *   - votes2 is the largest count among all other placements, and 0 if there is none.
+ *   - n_found is the number of hits over the strands searched.  It equals n_found of sbwtgpu_read_hits_* only with one strand.
+ *   - n_anchored is the number of anchored hits.
+ *   - With n_anchored = 0 the record is {0, -1, 0, 0, 0, n_found, 0}.
+ *   first keeps only the smallest occurrence.  A k-mer that several references share therefore votes for the one with the
+ *   smallest number.  This is a projection onto the first reference that holds each k-mer, not an enumeration of all
+ *   occurrences.
+ * sbwtgpu_positions_create allocates 8 n bytes and a few words, every entry "no position"; idx must outlive the object.
+ * sbwtgpu_positions_reset empties it again (it waits for the device first).  sbwtgpu_positions_upload makes an object from a
+ * copied table; it refuses, on the device, any entry that is neither UINT64_MAX nor a key with seq < 2^30 (n_windows and n_hits
+ * of an uploaded object are 0).
+ * sbwtgpu_positions_add_batch takes host buffers and cuts the batch into chunks of whole sequences of at most
+ * "positions_chunk_bases" bases (sbwtgpu_set_tuning; 0 = the default of 64 Mi; a chunk always takes one whole sequence), two
+ * in flight.  After the searches one kernel runs over the results, one lane per result: it finds each result's sequence and
+ * offset from the window offsets by bisection and issues one 64-bit atomic minimum per hit, and none when the value already
+ * there is smaller.  *n_windows: the windows of the batch; *n_hit_windows: those with a hit on either strand (both may be NULL).
+ * sbwtgpu_positions_info: any output may be NULL; device_bytes is what the object holds on the device.
+ * sbwtgpu_positions_first_copy copies first (n entries); sbwtgpu_positions_first_dev gives it in place, alive as long as p.
+ * sbwtgpu_positions_map_dev takes device pointers with the preconditions of sbwtgpu_read_hits_dev and writes n_reads records
+ * to d_out.  It is asynchronous on `stream`, never synchronises and never allocates.  Its workspace, of
+ * sbwtgpu_positions_map_workspace_bytes (non-decreasing in total_bases and n_reads), is 16-byte aligned and begins with the
+ * search workspace: sbwtgpu_workspace_status on it reports the search's status word.  After the searches two kernels run: one
+ * wave per read with a table of SBWTGPU_POSITIONS_MAP_TABLE distinct placements in LDS, and a second one, always launched,
+ * that recomputes exactly the reads whose placements outgrew that table.  Every read gets the exact record.  The second
+ * kernel gives a listed read one wave and compares every window's key with every other's: its time is quadratic in the read's
+ * WINDOWS (times the strands), about W^2 / 64 gather trips, whatever share of them hit.  That is meant for the odd junk read
+ * among short reads.  A long read that leaves the diagonal often -- a 100 kb read with indels, a contig -- has more than
+ * SBWTGPU_POSITIONS_MAP_TABLE placements, takes this path and holds its stream for a long time (10^5 windows: some 10^8
+ * trips of one wave): such reads are outside the intended use; cut them into pieces of a few thousand bases and map those.
+ * sbwtgpu_positions_map_batch is the same call on host buffers, chunked like the adds; out holds n_reads records.
+ * info, first_copy and reset serialise on the object and see every add that has returned.  Adds from several host threads on
+ * one object are safe: the table is built on atomic minima.  The map calls only read the object.
+ * Refusals (SBWTGPU_ERR_INVALID_ARG with a message that names the cause): NULL arguments; a rank-only index; an index of 2^31
+ * columns or more; strands not 1 or 2; n_reads < 0 or >= 2^31; first_seq < 0 or first_seq + n_reads > 2^30; a workspace that
+ * is too small; an object used after its index changed.  A read of 2^30 bases or more in the map calls gives
+ * SBWTGPU_ERR_READ_TOO_LONG, so the int32 counts cannot overflow with two strands, and a sequence of 2^31 bases or more in an
+ * add likewise.  sbwtgpu_positions_map_batch checks every read's length from the offsets.  sbwtgpu_positions_map_dev cannot
+ * see the lengths: it refuses only a batch of ONE read of 2^30 bases or more.  In a larger batch the lengths are the caller's
+ * to keep below 2^30: the record of a longer read is UNDEFINED (its start and its counts wrap); no memory outside the
+ * caller's buffers is read or written, and the records of the other reads are what they should be.  SBWTGPU_ERR_OOM leaves the index usable and nothing allocated. */
+#define SBWTGPU_POSITIONS_MAP_TABLE 256
+typedef struct { int64_t start; int32_t seq; int32_t strand; int32_t votes; int32_t votes2; int32_t n_found; int32_t n_anchored; } sbwtgpu_read_map;
+typedef struct sbwtgpu_positions sbwtgpu_positions;
+int     sbwtgpu_positions_create(const sbwtgpu_index *idx, sbwtgpu_positions **out);
+int     sbwtgpu_positions_upload(const sbwtgpu_index *idx, const uint64_t *first /* n */, sbwtgpu_positions **out);
+int     sbwtgpu_positions_reset(sbwtgpu_positions *p);
+void    sbwtgpu_positions_destroy(sbwtgpu_positions *p);
+int     sbwtgpu_positions_add_batch(sbwtgpu_positions *p, int64_t first_seq, const char *bases, const int64_t *read_off,
+                                    int64_t n_reads, int strands, int64_t *n_windows, int64_t *n_hit_windows);
+int     sbwtgpu_positions_info(const sbwtgpu_positions *p, int64_t *n_columns, int64_t *k, int64_t *n_windows, int64_t *n_hits,
+                               int64_t *n_positioned, int64_t *device_bytes);
+int     sbwtgpu_positions_first_copy(const sbwtgpu_positions *p, uint64_t *first /* n */);
+int     sbwtgpu_positions_first_dev(const sbwtgpu_positions *p, const uint64_t **d_first);
+int64_t sbwtgpu_positions_map_workspace_bytes(int64_t total_bases, int64_t n_reads, int strands);
+int     sbwtgpu_positions_map_dev(const sbwtgpu_positions *p, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                                  int64_t n_reads, int strands, sbwtgpu_read_map *d_out, void *d_workspace,
+                                  int64_t workspace_bytes, void *stream);
+int     sbwtgpu_positions_map_batch(const sbwtgpu_positions *p, const char *bases, const int64_t *read_off, int64_t n_reads,
+                                    int strands, sbwtgpu_read_map *out);
 
 #ifdef __cplusplus
 }

@@ -87,6 +87,17 @@ int  sbwthost_colorsets_write(const char *path, const uint32_t *ids, const uint6
                               int64_t k, int64_t n_sets);
 int  sbwthost_colorsets_read(const char *path, int64_t *n_columns, int64_t *n_colors, int64_t *k, int64_t *words_per_row,
                              int64_t *n_sets, uint32_t *ids_or_null, int64_t ids_cap, uint64_t *table_or_null, int64_t table_words_cap);
+/* Position files (the position table of include/sbwtgpu.h, "positions", beside its index file): 8 bytes "SBWTPOS1"; int64
+ * n_columns, k, n_seqs; per sequence int32 colour (the line of the reference list its file stood on), int32 0, int64 length;
+ * then n_columns little-endian uint64 of first (UINT64_MAX: no position, else (seq << 32) | (pos << 1) | t).  The read is
+ * the two-call pattern: with the three pointers NULL it gives the sizes, a second call with room for seqs_cap >= n_seqs
+ * entries and first_cap >= n_columns entries fills them.  Both calls check the header's ranges (n_columns < 2^31, n_seqs
+ * <= 2^30) and the exact file size, the filling call also that every position lies on a listed sequence.  Truncation, a
+ * wrong magic and any violation are errors with a message; the writer refuses the same violations. */
+int  sbwthost_positions_write(const char *path, const uint64_t *first, int64_t n_columns, int64_t k, const int32_t *seq_color,
+                              const int64_t *seq_len, int64_t n_seqs);
+int  sbwthost_positions_read(const char *path, int64_t *n_columns, int64_t *k, int64_t *n_seqs, int32_t *seq_color_or_null,
+                             int64_t *seq_len_or_null, int64_t seqs_cap, uint64_t *first_or_null, int64_t first_cap);
 
 #ifdef __cplusplus
 }

@@ -82,6 +82,9 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_genotype_create", "sbwtgpu_genotype_reset", "sbwtgpu_genotype_destroy", "sbwtgpu_genotype_workspace_bytes",
     "sbwtgpu_genotype_add_dev", "sbwtgpu_genotype_add_batch", "sbwtgpu_genotype_info", "sbwtgpu_genotype_branches",
     "sbwtgpu_genotype_kmer_hits_copy", "sbwtgpu_genotype_calls",
+    "sbwtgpu_positions_create", "sbwtgpu_positions_upload", "sbwtgpu_positions_reset", "sbwtgpu_positions_destroy",
+    "sbwtgpu_positions_add_batch", "sbwtgpu_positions_info", "sbwtgpu_positions_first_copy", "sbwtgpu_positions_first_dev",
+    "sbwtgpu_positions_map_workspace_bytes", "sbwtgpu_positions_map_dev", "sbwtgpu_positions_map_batch",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -203,6 +206,11 @@ class ColorsInfoC(C.Structure):
 PSEUDOALIGNMENT_DTYPE = np.dtype([("colors", np.uint64), ("n_kmers", np.int32), ("n_found", np.int32)])
 # a read's record over a wide colour matrix (sbwtgpu_read_found): 8 bytes, its colours are W words of their own
 READ_FOUND_DTYPE = np.dtype([("n_kmers", np.int32), ("n_found", np.int32)])
+# sbwtgpu_read_map: a read's placement on the references (32 bytes)
+READ_MAP_DTYPE = np.dtype([("start", np.int64), ("seq", np.int32), ("strand", np.int32), ("votes", np.int32), ("votes2", np.int32),
+                           ("n_found", np.int32), ("n_anchored", np.int32)])
+POSITIONS_MAP_TABLE = 256       # SBWTGPU_POSITIONS_MAP_TABLE
+POS_NONE = 0xFFFFFFFFFFFFFFFF   # first[v]: no position
 MAX_COLORS = 4096
 
 _lib: Optional[C.CDLL] = None
@@ -392,6 +400,19 @@ def lib() -> C.CDLL:
         L.sbwtgpu_genotype_branches.argtypes = [vp, vp, vp, vp]
         L.sbwtgpu_genotype_kmer_hits_copy.argtypes = [vp, vp, vp]
         L.sbwtgpu_genotype_calls.argtypes = [vp, C.c_int32, i64, vp, vp, vp, vp]
+        L.sbwtgpu_positions_create.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_positions_upload.argtypes = [vp, vp, C.POINTER(vp)]
+        L.sbwtgpu_positions_reset.argtypes = [vp]
+        L.sbwtgpu_positions_destroy.argtypes = [vp]
+        L.sbwtgpu_positions_destroy.restype = None
+        L.sbwtgpu_positions_add_batch.argtypes = [vp, i64, vp, vp, i64, ci, C.POINTER(i64), C.POINTER(i64)]
+        L.sbwtgpu_positions_info.argtypes = [vp] + [C.POINTER(i64)] * 6
+        L.sbwtgpu_positions_first_copy.argtypes = [vp, vp]
+        L.sbwtgpu_positions_first_dev.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_positions_map_workspace_bytes.argtypes = [i64, i64, ci]
+        L.sbwtgpu_positions_map_workspace_bytes.restype = i64
+        L.sbwtgpu_positions_map_dev.argtypes = [vp, vp, i64, vp, i64, ci, vp, vp, i64, vp]
+        L.sbwtgpu_positions_map_batch.argtypes = [vp, vp, vp, i64, ci, vp]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -822,6 +843,13 @@ class Index:
         st = C.c_int(0)
         _check(lib().sbwtgpu_workspace_status(d_ws, stream, C.byref(st)))
         return st.value
+
+    # ---- reference positions and read mapping (include/sbwtgpu.h, "positions") ----
+    def positions(self) -> "Positions":
+        """sbwtgpu_positions_create: an empty position table bound to this index."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_positions_create(self._h, C.byref(h)))
+        return Positions(h, self)
 
 
 class Unitigs:
@@ -1643,6 +1671,107 @@ class Screen:
 
     def reset(self) -> None:
         _check(lib().sbwtgpu_screen_reset(self._h))
+
+
+class Positions:
+    """Owns an sbwtgpu_positions handle: per column the smallest reference coordinate of its k-mer, and the reads placed on the
+    references by diagonal voting (include/sbwtgpu.h, "positions").  Everything is exact integers.  The index is kept
+    referenced."""
+
+    def __init__(self, handle, index: Index):
+        self._h = handle
+        self.index = index
+
+    @classmethod
+    def upload(cls, index: Index, first) -> "Positions":
+        """sbwtgpu_positions_upload: an object from a copied table (uint64[n_nodes])."""
+        first = np.ascontiguousarray(first, dtype=np.uint64)
+        if first.shape != (index.n_nodes,):
+            raise ValueError("first must have one uint64 per column (%d), not shape %r" % (index.n_nodes, first.shape))
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_positions_upload(index.handle, first.ctypes.data, C.byref(h)))
+        return cls(h, index)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        if self._h:
+            lib().sbwtgpu_positions_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def add_sequences(self, bases, read_off, first_seq: int, strands: int = 1):
+        """sbwtgpu_positions_add_batch: sequence i of the batch gets the number first_seq + i.  Returns (n_windows,
+        n_hit_windows) of the batch."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        nw, nh = C.c_int64(), C.c_int64()
+        _check(lib().sbwtgpu_positions_add_batch(self._h, first_seq, bases.ctypes.data, read_off.ctypes.data, len(read_off) - 1,
+                                                 strands, C.byref(nw), C.byref(nh)))
+        return nw.value, nh.value
+
+    def add(self, seqs: Sequence[bytes], first_seq: int, strands: int = 1):
+        """The same for a list of byte strings."""
+        bases, off = concat_reads(seqs)
+        return self.add_sequences(bases, off, first_seq, strands)
+
+    def info(self) -> dict:
+        """n_columns, k, n_windows, n_hits, n_positioned and device_bytes."""
+        v = [C.c_int64() for _ in range(6)]
+        _check(lib().sbwtgpu_positions_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("n_columns", "k", "n_windows", "n_hits", "n_positioned", "device_bytes"), (x.value for x in v)))
+
+    def first(self) -> np.ndarray:
+        """uint64[n_nodes]: (seq << 32) | (pos << 1) | t per column, POS_NONE where the column has no position."""
+        out = np.zeros(self.index.n_nodes, dtype=np.uint64)
+        _check(lib().sbwtgpu_positions_first_copy(self._h, out.ctypes.data))
+        return out
+
+    def first_dev(self) -> int:
+        p = C.c_void_p()
+        _check(lib().sbwtgpu_positions_first_dev(self._h, C.byref(p)))
+        return p.value or 0
+
+    def reset(self) -> None:
+        _check(lib().sbwtgpu_positions_reset(self._h))
+
+    def map(self, bases, read_off, strands: int = 1) -> np.ndarray:
+        """sbwtgpu_positions_map_batch: one READ_MAP_DTYPE record per read."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        n = max(len(read_off) - 1, 0)
+        out = np.zeros(n, dtype=READ_MAP_DTYPE)
+        _check(lib().sbwtgpu_positions_map_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n, strands, out.ctypes.data))
+        return out
+
+    def map_reads(self, reads: Sequence[bytes], strands: int = 1) -> np.ndarray:
+        """The same for a list of byte strings."""
+        bases, off = concat_reads(reads)
+        return self.map(bases, off, strands)
+
+    def map_dev(self, d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_out: int, d_ws: int, ws_bytes: int,
+                strands: int = 1, stream: int = 0) -> None:
+        """sbwtgpu_positions_map_dev (raw device pointers; d_out: n_reads records of 32 bytes; workspace of workspace_bytes):
+        asynchronous on stream."""
+        _check(lib().sbwtgpu_positions_map_dev(self._h, d_bases or None, total_bases, d_read_off or None, n_reads, strands,
+                                               d_out or None, d_ws or None, ws_bytes, stream or None))
+
+    @staticmethod
+    def workspace_bytes(total_bases: int, n_reads: int, strands: int = 1) -> int:
+        return lib().sbwtgpu_positions_map_workspace_bytes(total_bases, n_reads, strands)
 
 
 class ColorSetsBuilder:

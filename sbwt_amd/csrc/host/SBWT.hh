@@ -30,6 +30,7 @@
 #include "globals.hh"
 #include "index_builder.hh"
 #include "index_file.hh"
+#include "positions_file.hh"
 #include "seqio.hh"
 
 namespace sbwt {
@@ -745,6 +746,85 @@ public:
         Screen s;
         detail::gpu_check(sbwtgpu_screen_create(sets, &s.h));
         return s;
+    }
+    // Reference positions per column and reads placed on the references (include/sbwtgpu.h, "positions"): the table is kept on
+    // the device for as many adds as the caller has; `seqs` lists what was added, in the order of the sequence numbers, and
+    // travels with the table in the position file (positions_file.hh).  The index must outlive the object.
+    class Positions {
+    public:
+        Positions() = default;
+        Positions(const Positions &) = delete;
+        Positions &operator=(const Positions &) = delete;
+        Positions(Positions &&o) noexcept : seqs(std::move(o.seqs)), h(o.h), idx(o.idx), n_nodes(o.n_nodes), k(o.k) { o.h = nullptr; }
+        Positions &operator=(Positions &&o) noexcept {
+            if (this != &o) {
+                sbwtgpu_positions_destroy(h);
+                seqs = std::move(o.seqs); h = o.h; idx = o.idx; n_nodes = o.n_nodes; k = o.k; o.h = nullptr;
+            }
+            return *this;
+        }
+        ~Positions() { sbwtgpu_positions_destroy(h); }
+        // the sequences of the batch get the numbers seqs.size(), seqs.size() + 1, ... and the colour `colour` in the file
+        void add(const char *bases, const int64_t *read_off, int64_t n_reads, int strands = 1, int32_t colour = 0) {
+            detail::gpu_check(sbwtgpu_positions_add_batch(h, (int64_t)seqs.size(), bases, read_off, n_reads, strands, nullptr, nullptr));
+            for (int64_t r = 0; r < n_reads; r++) seqs.push_back({colour, 0, read_off[r + 1] - read_off[r]});
+        }
+        void map(const char *bases, const int64_t *read_off, int64_t n_reads, int strands, sbwtgpu_read_map *out) const {
+            detail::gpu_check(sbwtgpu_positions_map_batch(h, bases, read_off, n_reads, strands, out));
+        }
+        struct Info { int64_t n_columns = 0, k = 0, n_windows = 0, n_hits = 0, n_positioned = 0, device_bytes = 0; };
+        Info info() const {
+            Info i;
+            detail::gpu_check(sbwtgpu_positions_info(h, &i.n_columns, &i.k, &i.n_windows, &i.n_hits, &i.n_positioned, &i.device_bytes));
+            return i;
+        }
+        std::vector<uint64_t> first() const {
+            std::vector<uint64_t> f((size_t)n_nodes);
+            detail::gpu_check(sbwtgpu_positions_first_copy(h, f.data()));
+            return f;
+        }
+        void save(const std::string &filename) const {
+            const std::vector<uint64_t> f = first();
+            positions_file::write(filename, f.data(), n_nodes, k, seqs.data(), (int64_t)seqs.size());
+        }
+        // the table and the sequence list of a position file of the object's index take the place of what the object held (a
+        // file of another index is refused, and the object stays as it was)
+        void load(const std::string &filename) {
+            int64_t n = 0, fk = 0, ns = 0;
+            positions_file::read(filename, n, fk, ns, nullptr, nullptr, 0);
+            if (n != n_nodes || fk != k)
+                throw std::runtime_error("Error: " + filename + " holds the positions of an index of " + std::to_string(n) + " columns at k = " +
+                                         std::to_string(fk) + ", this index has " + std::to_string(n_nodes) + " columns at k = " + std::to_string(k));
+            std::vector<positions_file::Seq> file_seqs;
+            std::vector<uint64_t> f((size_t)n);
+            positions_file::read(filename, n, fk, ns, &file_seqs, f.data(), n);
+            sbwtgpu_positions *fresh = nullptr;
+            detail::gpu_check(sbwtgpu_positions_upload(idx, f.data(), &fresh));
+            sbwtgpu_positions_destroy(h);
+            h = fresh;
+            seqs = std::move(file_seqs);
+        }
+        std::vector<positions_file::Seq> seqs;
+        sbwtgpu_positions *h = nullptr;
+        const sbwtgpu_index *idx = nullptr;
+        int64_t n_nodes = 0, k = 0;
+    };
+    Positions positions() const {
+        Positions p;
+        p.idx = need_device();
+        p.n_nodes = n_nodes;
+        p.k = k;
+        detail::gpu_check(sbwtgpu_positions_create(p.idx, &p.h));
+        return p;
+    }
+    // the object of a position file of THIS index
+    Positions load_positions(const std::string &filename) const {
+        Positions p;
+        p.idx = need_device();
+        p.n_nodes = n_nodes;
+        p.k = k;
+        p.load(filename);
+        return p;
     }
     // the k-mers of the index whose colour set satisfies the predicate, as the columns of their index (include/sbwtgpu.h,
     // "colour select"): bit for bit what the builder gives for the selected k-mers.  The object is one of THIS index;

@@ -12,6 +12,7 @@
 
 #include "index_builder.hh"
 #include "index_file.hh"
+#include "positions_file.hh"
 #include "seqio.hh"
 
 namespace {
@@ -454,6 +455,42 @@ int sbwthost_colorsets_read(const char *path, int64_t *n_columns, int64_t *n_col
     if (words_per_row) *words_per_row = words;
     if (n_sets) *n_sets = ns;
     return 0;
+}
+
+// ---- position files: "SBWTPOS1" (positions_file.hh holds the format; SBWT::Positions::save / load go through the same code) ----
+int sbwthost_positions_write(const char *path, const uint64_t *first, int64_t n_columns, int64_t k, const int32_t *seq_color,
+                             const int64_t *seq_len, int64_t n_seqs) {
+    if (!path || n_columns < 0 || n_seqs < 0 || (n_columns > 0 && !first) || (n_seqs > 0 && (!seq_color || !seq_len))) return fail("invalid argument");
+    try {
+        std::vector<sbwt::positions_file::Seq> seqs((size_t)n_seqs);
+        for (int64_t i = 0; i < n_seqs; i++) seqs[(size_t)i] = {seq_color[i], 0, seq_len[i]};
+        sbwt::positions_file::write(path, first, n_columns, k, seqs.data(), n_seqs);
+        return 0;
+    } catch (const std::exception &e) {
+        return fail("%s", e.what());
+    }
+}
+
+int sbwthost_positions_read(const char *path, int64_t *n_columns, int64_t *k, int64_t *n_seqs, int32_t *seq_color_or_null,
+                            int64_t *seq_len_or_null, int64_t seqs_cap, uint64_t *first_or_null, int64_t first_cap) {
+    if (!path) return fail("invalid argument");
+    try {
+        int64_t n = 0, kk = 0, ns = 0;
+        std::vector<sbwt::positions_file::Seq> seqs;
+        const bool want_seqs = seq_color_or_null || seq_len_or_null;
+        sbwt::positions_file::read(path, n, kk, ns, want_seqs ? &seqs : nullptr, first_or_null, first_cap);
+        if (want_seqs && seqs_cap < ns) return fail("Error: room for %lld sequences, the position file lists %lld", (long long)seqs_cap, (long long)ns);
+        for (int64_t i = 0; want_seqs && i < ns; i++) {
+            if (seq_color_or_null) seq_color_or_null[i] = seqs[(size_t)i].colour;
+            if (seq_len_or_null) seq_len_or_null[i] = seqs[(size_t)i].length;
+        }
+        if (n_columns) *n_columns = n;
+        if (k) *k = kk;
+        if (n_seqs) *n_seqs = ns;
+        return 0;
+    } catch (const std::exception &e) {
+        return fail("%s", e.what());
+    }
 }
 
 }  // extern "C"

@@ -22,13 +22,16 @@
 //   sbwt set-op -a <index A> -b <index B> [--op union|intersection|difference|symmetric-difference] -o <index> [--counts-only]
 //               two index files combined on the GPU without their input sequences: the index `sbwt build` would write for
 //               the result's k-mers
-//   sbwt read-hits -i <index> -q <query> -o <out> [-z] [--both-strands]
-//               one line per read: n_kmers n_found covered_bases longest_run
+//   sbwt read-hits -i <index> -q <query> -o <out> [-z] [--both-strands] [--positions <index.pos>]
+//               one line per read: n_kmers n_found covered_bases longest_run; with --positions six more columns, the read's
+//               placement on the references by diagonal voting: seq strand start votes votes2 n_anchored
 //   sbwt build-colors -i <index> -r <refs.txt> -o <colours> [--both-strands] [--wide | --compress [--stream]]
+//               [--positions-out <index.pos>]
 //               one colour per listed reference file, set on the columns of the index's k-mers that the file holds
 //               (--wide: up to 4096 files, a colour file of several words per column; --compress: up to 4096 files, a
 //               colour-set file of one id per column and the distinct colour sets; --compress --stream: the same file, built
-//               one reference at a time without the wide matrix on the device)
+//               one reference at a time without the wide matrix on the device); --positions-out: also the position file,
+//               per column the smallest (sequence, offset) at which its k-mer occurs, the sequences numbered in reading order
 //   sbwt compress-colors -i <index> -c <colours> -o <colour sets>
 //               the colour-set file of a colour file written with or without --wide
 //   sbwt merge-colors -u <index U> -a <index A> --colors-a <colours of A> [-b <index B> --colors-b <colours of B>]
@@ -234,8 +237,10 @@ void write_text_file(const string &path, const string &text, bool gzip) {
 void append_int(int64_t x, string &out) {
     char buf[24];
     int i = 0;
-    if (x == 0) buf[i++] = '0';
-    while (x > 0) { buf[i++] = (char)('0' + x % 10); x /= 10; }
+    uint64_t u = (uint64_t)x;
+    if (x < 0) { out.push_back('-'); u = 0 - u; }        // (a read's start on a reference may be negative, its seq -1)
+    if (u == 0) buf[i++] = '0';
+    while (u > 0) { buf[i++] = (char)('0' + u % 10); u /= 10; }
     while (i > 0) out.push_back(buf[--i]);
 }
 // the set bits of a `words`-word row as ascending colour numbers: `first` before the first one, `sep` before every other
@@ -770,6 +775,7 @@ int read_hits_main(int argc, char **argv) {
          "list of query files, one per line, and --out-file as a list of output files.", ""},
         {"gzip-output", 'z', false, "Writes output in gzipped form.", ""},
         {"both-strands", 0, false, "A k-mer also counts as found when its reverse complement is in the index.", ""},
+        {"positions", 0, true, "A position file of the index (build-colors --positions-out): every line gains the read's placement on the references, seq strand start votes votes2 n_anchored (seq -1: no placement).", ""},
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
@@ -781,11 +787,16 @@ int read_hits_main(int argc, char **argv) {
     check_same_count(files);
     const bool gzip_output = opts.count("gzip-output");
     const int strands = opts.count("both-strands") ? 2 : 1;
+    const string posfile = opts.count("positions") ? opts.get("positions") : "";
+    if (!posfile.empty()) check_readable(posfile);
     use_gpu_option(opts);
     const int64_t batch_bases = batch_bases_option(opts);
 
     plain_matrix_sbwt_t index;
     load_plain_matrix(indexfile, index, "GPU search path");
+    plain_matrix_sbwt_t::Positions positions;
+    if (!posfile.empty()) positions = index.load_positions(posfile);
+    vector<sbwtgpu_read_map> placed;
     int64_t total_reads = 0;
     for (size_t f = 0; f < files.in.size(); f++) {
         write_log("Running read-hits from input file " + files.in[f] + " to output file " + files.out[f], LogLevel::MAJOR);
@@ -796,8 +807,13 @@ int read_hits_main(int argc, char **argv) {
         for_each_batch(reader, batch_bases, [&](const vector<char> &bases, const vector<int64_t> &read_off, int64_t n_reads) {
             rec.resize((size_t)n_reads);
             index.read_hits_batch(bases.data(), read_off.data(), n_reads, strands, rec.data());
+            if (positions.h) {
+                placed.resize((size_t)n_reads);
+                positions.map(bases.data(), read_off.data(), n_reads, strands, placed.data());
+            }
             text.clear();
-            for (const sbwtgpu_read_hits &h : rec) {
+            for (size_t r = 0; r < rec.size(); r++) {
+                const sbwtgpu_read_hits &h = rec[r];
                 append_int(h.n_kmers, text);
                 text.push_back(' ');
                 append_int(h.n_found, text);
@@ -805,6 +821,13 @@ int read_hits_main(int argc, char **argv) {
                 append_int(h.covered_bases, text);
                 text.push_back(' ');
                 append_int(h.longest_run, text);
+                if (positions.h) {
+                    const sbwtgpu_read_map &m = placed[r];
+                    for (int64_t v : {(int64_t)m.seq, (int64_t)m.strand, (int64_t)m.start, (int64_t)m.votes, (int64_t)m.votes2, (int64_t)m.n_anchored}) {
+                        text.push_back(' ');
+                        append_int(v, text);
+                    }
+                }
                 text.push_back('\n');
             }
             writer.write(text.data(), (int64_t)text.size());
@@ -1093,6 +1116,7 @@ int build_colors_main(int argc, char **argv) {
         {"wide", 0, false, "Up to 4096 lines in the list; writes a wide colour file (several 64-bit words per column).", ""},
         {"compress", 0, false, "Up to 4096 lines in the list; writes a colour-set file (one id per column and the distinct colour sets).", ""},
         {"stream", 0, false, "With --compress: merge one reference at a time into the colour sets, without the wide matrix on the device. The same file.", ""},
+        {"positions-out", 0, true, "Also write a position file: per column of the index the smallest (sequence, offset) at which its k-mer occurs; the sequences of the listed files are numbered 0, 1, ... in the order they are read.", ""},
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
@@ -1115,11 +1139,15 @@ int build_colors_main(int argc, char **argv) {
                                  " files; a colour file holds 1 to 64 colours (use --wide for more)");
     for (const string &file : refs) check_readable(file);
     check_writable(outfile);
+    const string posfile = opts.count("positions-out") ? opts.get("positions-out") : "";
+    if (!posfile.empty()) check_writable(posfile);
     const int strands = opts.count("both-strands") ? 2 : 1;
     use_gpu_option(opts);
     const int64_t batch_bases = batch_bases_option(opts);
     plain_matrix_sbwt_t index;
     load_plain_matrix(indexfile, index);
+    plain_matrix_sbwt_t::Positions positions;
+    if (!posfile.empty()) positions = index.positions();
     ColorsHandle col;
     ColorSetsBuilderHandle builder;
     if (stream) colors_check(sbwtgpu_colorsets_builder_create(index.device_handle(), (int)refs.size(), &builder.h));
@@ -1139,7 +1167,15 @@ int build_colors_main(int argc, char **argv) {
             }
             windows[c] += w;
             hit_windows[c] += h;
+            if (positions.h) positions.add(bases.data(), read_off.data(), n_reads, strands, (int32_t)c);
         });
+    }
+    if (positions.h) {
+        positions.save(posfile);
+        const plain_matrix_sbwt_t::Positions::Info pi = positions.info();
+        write_log("Wrote the positions of " + std::to_string(pi.n_positioned) + " columns on " + std::to_string(positions.seqs.size()) +
+                      " sequences to " + posfile,
+                  LogLevel::MAJOR);
     }
     int64_t n_columns = 0, ck = 0, n_colored = 0;
     int32_t n_colors = 0;

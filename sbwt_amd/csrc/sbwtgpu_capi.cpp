@@ -247,6 +247,14 @@ int sbwtgpu_set_tuning(const char *key, int64_t value) {
     if (!strcmp(key, "pseudoalign_chunk_bases")) { g_pa_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "screen_chunk_bases")) { g_screen_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "genotype_chunk_bases")) { g_gt_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
+    if (!strcmp(key, "positions_chunk_bases")) { g_pos_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
+    if (!strcmp(key, "positions_map_table")) {
+        if (value < 0 || value > SBWTGPU_POSITIONS_MAP_TABLE)
+            return fail(SBWTGPU_ERR_INVALID_ARG, "positions_map_table must be in 0 .. %d (0: the compiled capacity), not %lld",
+                        SBWTGPU_POSITIONS_MAP_TABLE, (long long)value);
+        g_pos_map_table = (int)value;
+        return SBWTGPU_OK;
+    }
     if (!strcmp(key, "gram_mfma_min_sets")) { g_gram_mfma_min_sets = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "gram_flush_sets")) {
         if (value < 1 || value > SBWT_GM_FLUSH_MAX)

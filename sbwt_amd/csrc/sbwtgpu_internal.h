@@ -1,6 +1,7 @@
 // sbwtgpu_internal.h -- what the translation units of the C ABI share: sbwtgpu_capi.cpp (index image, search, rank, text),
 // sbwtgpu_capi_reads.cpp (matching statistics, set operations, read hits, unitigs and their graph, walks, bubbles) and
-// sbwtgpu_capi_colors.cpp (colours, colour sets, pseudoalignment, screen).  Nothing here is part of the library's interface:
+// sbwtgpu_capi_colors.cpp (colours, colour sets, pseudoalignment, screen) and sbwtgpu_capi_positions.cpp (reference positions,
+// read mapping).  Nothing here is part of the library's interface:
 // every name has hidden visibility, and whatever holds state (the error text, the parked slots, the int32 switch of a search
 // call) is defined once, in sbwtgpu_capi.cpp.
 #pragma once
@@ -88,6 +89,8 @@ extern int g_rh_wave_min, g_rh_wide;                        // sbwtgpu_capi_read
 extern int64_t g_rh_chunk_bases, g_wk_chunk_bases, g_gt_chunk_bases;
 extern int64_t g_pa_chunk_bases, g_screen_chunk_bases;      // sbwtgpu_capi_colors.cpp
 extern int64_t g_gram_mfma_min_sets, g_gram_flush_sets;
+extern int64_t g_pos_chunk_bases;                           // sbwtgpu_capi_positions.cpp
+extern int g_pos_map_table;
 
 }  // namespace sbwt_capi
 

@@ -18,6 +18,7 @@ EXPORTED_SYMBOLS = [
     "sbwthost_file_words", "sbwthost_file_precalc", "sbwthost_read_sequences", "sbwthost_read_sequences_chunked", "sbwthost_free", "sbwthost_write_file",
     "sbwthost_rank_batch", "sbwthost_colors_write", "sbwthost_colors_read",
     "sbwthost_colors_write_wide", "sbwthost_colors_read_wide", "sbwthost_colorsets_write", "sbwthost_colorsets_read",
+    "sbwthost_positions_write", "sbwthost_positions_read",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -61,6 +62,8 @@ def lib() -> C.CDLL:
     L.sbwthost_colorsets_write.argtypes = [C.c_char_p, vp, vp, i64, i64, i64, i64]
     L.sbwthost_colorsets_read.argtypes = [C.c_char_p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
                                           vp, i64, vp, i64]
+    L.sbwthost_positions_write.argtypes = [C.c_char_p, vp, i64, i64, vp, vp, i64]
+    L.sbwthost_positions_read.argtypes = [C.c_char_p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp, vp, i64, vp, i64]
     _lib = L
     return L
 
@@ -256,3 +259,30 @@ def colorsets_read(path: str):
     if L.sbwthost_colorsets_read(path.encode(), *sizes, ids.ctypes.data if n.value else None, n.value, table.ctypes.data, table.size) != 0:
         raise RuntimeError(_err())
     return ids, table, nc.value, k.value
+
+
+def positions_write(path: str, first, k: int, seq_color, seq_len) -> None:
+    """Writes a position table (first uint64[n_columns]) with its sequence list as an "SBWTPOS1" file (include/sbwthost.h)."""
+    first = np.ascontiguousarray(first, dtype=np.uint64)
+    seq_color = np.ascontiguousarray(seq_color, dtype=np.int32)
+    seq_len = np.ascontiguousarray(seq_len, dtype=np.int64)
+    if len(seq_color) != len(seq_len):
+        raise RuntimeError("%d colours for %d lengths" % (len(seq_color), len(seq_len)))
+    if lib().sbwthost_positions_write(path.encode(), first.ctypes.data if len(first) else None, len(first), k,
+                                      seq_color.ctypes.data if len(seq_len) else None, seq_len.ctypes.data if len(seq_len) else None,
+                                      len(seq_len)) != 0:
+        raise RuntimeError(_err())
+
+
+def positions_read(path: str):
+    """(first uint64[n_columns], k, seq_color int32[n_seqs], seq_len int64[n_seqs]) of an "SBWTPOS1" position file."""
+    L = lib()
+    n, k, ns = C.c_int64(), C.c_int64(), C.c_int64()
+    sizes = (C.byref(n), C.byref(k), C.byref(ns))
+    if L.sbwthost_positions_read(path.encode(), *sizes, None, None, 0, None, 0) != 0:
+        raise RuntimeError(_err())
+    first = np.empty(max(n.value, 1), dtype=np.uint64)
+    col, ln = np.empty(max(ns.value, 1), dtype=np.int32), np.empty(max(ns.value, 1), dtype=np.int64)
+    if L.sbwthost_positions_read(path.encode(), *sizes, col.ctypes.data, ln.ctypes.data, ns.value, first.ctypes.data, n.value) != 0:
+        raise RuntimeError(_err())
+    return first[: n.value], k.value, col[: ns.value], ln[: ns.value]
