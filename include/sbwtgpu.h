@@ -127,6 +127,11 @@ int         sbwtgpu_device_count(int *count);
  *   "positions_map_table" the distinct placements per read that the map kernel keeps in LDS before the read goes to the exact
  *                        second kernel: 1 .. SBWTGPU_POSITIONS_MAP_TABLE, 0 (default) = that compiled capacity; another value
  *                        is refused.  No result depends on it (tests reach the second kernel with it)
+ *   "occurrences_chunk_bases" sbwtgpu_occurrences_builder_add_batch and sbwtgpu_occurrences_map_batch cut their batch into chunks
+ *                        of whole sequences of at most this many bases (a chunk always takes one sequence); 0 (default) = 64 Mi
+ *   "occurrences_map_table" the distinct placements per read that the occurrence map kernel keeps in LDS before the read goes to
+ *                        the exact second kernel: 1 .. SBWTGPU_OCCURRENCES_MAP_TABLE, 0 (default) = that compiled capacity;
+ *                        another value is refused.  No result depends on it (tests reach the second kernel with it)
  *   "trans_ext", "trans_wide"   accepted and ignored (round-2 table formats)
  * Read when an index is CREATED (derived acceleration structures inside the device image; environment
  * variables of the same meaning: SBWTGPU_SPARSE_PRECALC, SBWTGPU_PROBE_FILTER, SBWTGPU_PATH_ORDER):
@@ -1310,6 +1315,119 @@ int     sbwtgpu_positions_map_dev(const sbwtgpu_positions *p, const char *d_base
                                   int64_t workspace_bytes, void *stream);
 int     sbwtgpu_positions_map_batch(const sbwtgpu_positions *p, const char *bases, const int64_t *read_off, int64_t n_reads,
                                     int strands, sbwtgpu_read_map *out);
+
+/* ---- occurrences: EVERY place on the references where a k-mer lies, and reads mapped by all of them ----
+ * The positions object above keeps one coordinate per column.  This object keeps all of them, as CSR arrays, and its map call
+ * votes with all of them: a read lands on the reference it fits best, and an equally good placement shows as votes2 == votes.
+ * Everything is exact integers.
+ * The occurrence table
+ *   A sbwtgpu_occurrences object is bound to one index of n columns and its k.  The index must have n < 2^31 and must not be
+ *   rank-only.
+ *   - It holds off[0..n] as uint64, with off[0] = 0, non-decreasing and off[n] = N.
+ *   - It holds occ[0..N) as uint64, the keys of "positions": (seq << 32) | (pos << 1) | t.  Within a column they are strictly
+ *     ascending, so they are distinct.
+ *   - occ[off[v] .. off[v+1]) is exactly the set of keys that the rules of "positions" OFFER to first[v], over all
+ *     (number, sequence, strands) triples added.  The rules are the same: the window x = q[pos .. pos+k), upper-case ACGT only,
+ *     with strands = 2 the search of the reverse complement of x offers the key with t = 1 to its column v', the t bit says that
+ *     the column's k-mer is the reverse complement of the reference window at pos.
+ *   - Consequences:
+ *     - occ[off[v]] == first[v] wherever the column has an occurrence.
+ *     - A palindromic window with two strands leaves both keys, t = 0 and t = 1, in one column.
+ *     - One sequence added twice under one number changes nothing.
+ *     - One sequence added under two numbers leaves both.
+ *     - The state is a function of the index and of the SET of triples.  It does not depend on batch boundaries, chunking,
+ *       order, host threads, tuning, image level or streams.
+ *   - Scalars, exact int64:
+ *     - n_windows and n_hits, as in "positions" (0 for an uploaded object);
+ *     - n_occurrences = N;
+ *     - n_positioned, the columns with at least one occurrence;
+ *     - max_count, the largest occurrence count of a column.
+ * Building
+ *   The sizes are unknown until every reference is seen, so the object comes from a builder.
+ *   sbwtgpu_occurrences_builder_create starts one on idx, which must outlive the builder and the object.
+ *   sbwtgpu_occurrences_builder_add_batch takes host buffers with the arguments of sbwtgpu_positions_add_batch.  It cuts the
+ *   batch into chunks of whole sequences of at most "occurrences_chunk_bases" bases, two in flight.  After the searches one kernel
+ *   runs over the results, one lane per result: it finds each result's sequence and offset by bisection and appends
+ *   (column, key) to a log on the device, with one atomic per wave on the log's length.  Before a chunk is launched the log has
+ *   room for what it holds plus the chunk's windows x strands; it grows by doubling (which waits for the device).  Adds from
+ *   several host threads on one builder are safe: THEY ARE SERIALISED on the builder, one add runs at a time.
+ *   sbwtgpu_occurrences_builder_finish sorts the log by (column, key) with two stable radix sorts, flags the first entry of each
+ *   run of equal pairs, selects the flagged keys into occ, counts them per column and scans the counts into off.  On success it
+ *   consumes the builder (the log is freed) and gives the object; on failure the builder is still the caller's to destroy.
+ *   Device memory: a logged hit takes 12 bytes in the log, whose capacity is at most twice its length; finish needs another
+ *   12 bytes per logged hit for the sort's second buffer, then (that buffer freed) 1 byte per logged hit of flags and 8 bytes per
+ *   distinct occurrence: the peak is at most 36 bytes per logged hit, plus 8 (n + 1) bytes of off and rocPRIM's scratch.
+ *   sbwtgpu_occurrences_builder_destroy frees an unfinished builder.
+ * sbwtgpu_occurrences_upload makes an object from copied arrays (off: n + 1 entries, occ: n_occ).  It checks them on the
+ * device: off[0] = 0, off non-decreasing, off[n] = n_occ, the keys of a column strictly ascending, seq < 2^30.  Its message
+ * names the first (smallest) offending column.
+ * sbwtgpu_occurrences_info: any output may be NULL; device_bytes is what the object holds on the device.
+ * sbwtgpu_occurrences_offsets_copy / _keys_copy copy off (n + 1 entries) and occ (N entries); _offsets_dev / _keys_dev give
+ * them in place, alive as long as the object.
+ * sbwtgpu_occurrences_to_positions makes a positions object of the same index with first[v] = occ[off[v]], or "no position"
+ * for an empty column: what the same adds give sbwtgpu_positions_add_batch.  Its n_windows and n_hits are 0.
+ * Mapping a read with every occurrence
+ *   It is the mapping of "positions" with one change.  A hit (i, s) on column v has c = off[v+1] - off[v] occurrences.
+ *   - With c = 0 the hit is found and not anchored.
+ *   - With c > max_occ the k-mer is repetitive.  The hit is found, casts no vote and is not anchored.
+ *   - Otherwise the hit is anchored.  It casts ONE VOTE FOR EACH of its c occurrences (seq, pos, t): the placement
+ *     (seq, o = s XOR t, start) with start = pos - i if o = 0 and start = pos - (W - 1 - i) if o = 1.
+ *   Two occurrences of one k-mer never give the same placement: within one (seq, t) a distinct pos gives a distinct start, and
+ *   a distinct t gives a distinct o.  So a hit votes at most once per placement.
+ *   The record is sbwtgpu_read_map:
+ *   - the winner (seq, strand = o, start) has the most votes, ties to the smallest (seq, o, start), start signed;
+ *   - votes is its count; votes2 is the largest count among all other placements, 0 if there is none;
+ *   - n_found is the hits over the strands searched;
+ *   - n_anchored is the hits that voted, not the number of votes cast;
+ *   - with n_anchored = 0 the record is {0, -1, 0, 0, 0, n_found, 0}.
+ *   max_occ must be in 1 .. SBWTGPU_OCCURRENCES_MAX_OCC (2^20); anything else is refused.
+ * sbwtgpu_occurrences_map_dev takes device pointers with the preconditions of sbwtgpu_positions_map_dev and writes n_reads
+ * records to d_out.  It is asynchronous on `stream`, never synchronises and never allocates.  Its workspace, of
+ * sbwtgpu_occurrences_map_workspace_bytes (non-decreasing in total_bases and n_reads), is 16-byte aligned and begins with the
+ * search workspace: sbwtgpu_workspace_status on it reports the search's status word.  After the searches three kernels run.
+ * The first gives a read one wave and keeps SBWTGPU_OCCURRENCES_MAP_TABLE distinct placements in LDS (256: at 12 bytes an entry
+ * a block of four waves takes 12 KiB, so eight blocks, the CU's 32 waves, take 96 of its 160 KiB; 512 would cut the resident
+ * waves to 24).  The second, always launched, recomputes exactly the reads whose placements outgrew the table: it enumerates
+ * the read's votes again in P slices of the key space, a hash of the placement modulo P, only the current slice's placements
+ * enter the table, and P doubles from 2 until every slice fits.  A slice that overflows ends its P at once, so the cost is
+ * about P enumerations of the read's votes for the final P, which is a few times (distinct placements / table capacity), and
+ * a part of an enumeration for every smaller P; the gathers of the re-enumerations stay in L2.  A read that no P up to 1024
+ * fits goes to the third kernel, also always launched, which counts placement by placement in ascending order without a
+ * table: one enumeration per distinct placement.  Together they terminate on every input, and every read gets the exact record.
+ * sbwtgpu_occurrences_map_batch is the same call on host buffers, chunked like the adds; out holds n_reads records.
+ * The map calls and the copies only read the object; they may run from several host threads.
+ * Refusals (SBWTGPU_ERR_INVALID_ARG with a message that names the cause): NULL arguments; a rank-only index; an index of 2^31
+ * columns or more; strands not 1 or 2; n_reads < 0 or >= 2^31; first_seq < 0 or first_seq + n_reads > 2^30; max_occ outside
+ * 1 .. 2^20; a workspace that is too small; an object or builder used after its index changed.  A read of 2^30 bases or more
+ * in the map calls gives SBWTGPU_ERR_READ_TOO_LONG, and a sequence of 2^31 bases or more in an add likewise; the lengths in
+ * sbwtgpu_occurrences_map_dev are the caller's to keep below 2^30, as in sbwtgpu_positions_map_dev.  SBWTGPU_ERR_OOM leaves the
+ * index usable and nothing allocated. */
+#define SBWTGPU_OCCURRENCES_MAP_TABLE 256
+#define SBWTGPU_OCCURRENCES_MAX_OCC (1 << 20)
+typedef struct sbwtgpu_occurrences sbwtgpu_occurrences;
+typedef struct sbwtgpu_occurrences_builder sbwtgpu_occurrences_builder;
+int     sbwtgpu_occurrences_builder_create(const sbwtgpu_index *idx, sbwtgpu_occurrences_builder **out);
+int     sbwtgpu_occurrences_builder_add_batch(sbwtgpu_occurrences_builder *b, int64_t first_seq, const char *bases,
+                                              const int64_t *read_off, int64_t n_reads, int strands, int64_t *n_windows,
+                                              int64_t *n_hit_windows);
+int     sbwtgpu_occurrences_builder_finish(sbwtgpu_occurrences_builder *b, sbwtgpu_occurrences **out);
+void    sbwtgpu_occurrences_builder_destroy(sbwtgpu_occurrences_builder *b);
+int     sbwtgpu_occurrences_upload(const sbwtgpu_index *idx, const uint64_t *off /* n + 1 */, const uint64_t *occ /* n_occ */,
+                                   int64_t n_occ, sbwtgpu_occurrences **out);
+void    sbwtgpu_occurrences_destroy(sbwtgpu_occurrences *o);
+int     sbwtgpu_occurrences_info(const sbwtgpu_occurrences *o, int64_t *n_columns, int64_t *k, int64_t *n_windows, int64_t *n_hits,
+                                 int64_t *n_occurrences, int64_t *n_positioned, int64_t *max_count, int64_t *device_bytes);
+int     sbwtgpu_occurrences_offsets_copy(const sbwtgpu_occurrences *o, uint64_t *off /* n + 1 */);
+int     sbwtgpu_occurrences_keys_copy(const sbwtgpu_occurrences *o, uint64_t *occ /* n_occurrences */);
+int     sbwtgpu_occurrences_offsets_dev(const sbwtgpu_occurrences *o, const uint64_t **d_off);
+int     sbwtgpu_occurrences_keys_dev(const sbwtgpu_occurrences *o, const uint64_t **d_occ);
+int     sbwtgpu_occurrences_to_positions(const sbwtgpu_occurrences *o, sbwtgpu_positions **out);
+int64_t sbwtgpu_occurrences_map_workspace_bytes(int64_t total_bases, int64_t n_reads, int strands);
+int     sbwtgpu_occurrences_map_dev(const sbwtgpu_occurrences *o, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                                    int64_t n_reads, int strands, int max_occ, sbwtgpu_read_map *d_out, void *d_workspace,
+                                    int64_t workspace_bytes, void *stream);
+int     sbwtgpu_occurrences_map_batch(const sbwtgpu_occurrences *o, const char *bases, const int64_t *read_off, int64_t n_reads,
+                                      int strands, int max_occ, sbwtgpu_read_map *out);
 
 #ifdef __cplusplus
 }

@@ -98,6 +98,18 @@ int  sbwthost_positions_write(const char *path, const uint64_t *first, int64_t n
                               const int64_t *seq_len, int64_t n_seqs);
 int  sbwthost_positions_read(const char *path, int64_t *n_columns, int64_t *k, int64_t *n_seqs, int32_t *seq_color_or_null,
                              int64_t *seq_len_or_null, int64_t seqs_cap, uint64_t *first_or_null, int64_t first_cap);
+/* Occurrence files (the occurrence table of include/sbwtgpu.h, "occurrences", beside its index file): 8 bytes "SBWTOCC1"; int64
+ * n_columns, k, n_seqs, n_occ; per sequence int32 colour, int32 0, int64 length, as in "SBWTPOS1"; then n_columns + 1
+ * little-endian uint64 of off; then n_occ uint64 of occ.  The read is the two-call pattern: with the pointers NULL it gives the
+ * sizes, a second call with room for seqs_cap >= n_seqs, off_cap >= n_columns + 1 and occ_cap >= n_occ entries fills them.
+ * Both calls check the header's ranges and the exact file size (truncation, trailing bytes, another magic); the filling call
+ * also refuses non-monotone offsets, unsorted keys within a column, a key on an unlisted sequence and a key whose pos + k lies
+ * beyond its sequence's length, each with a message that names the cause.  The writer refuses the same violations. */
+int  sbwthost_occurrences_write(const char *path, const uint64_t *off, const uint64_t *occ, int64_t n_columns, int64_t k, int64_t n_occ,
+                                const int32_t *seq_color, const int64_t *seq_len, int64_t n_seqs);
+int  sbwthost_occurrences_read(const char *path, int64_t *n_columns, int64_t *k, int64_t *n_seqs, int64_t *n_occ,
+                               int32_t *seq_color_or_null, int64_t *seq_len_or_null, int64_t seqs_cap, uint64_t *off_or_null,
+                               int64_t off_cap, uint64_t *occ_or_null, int64_t occ_cap);
 
 #ifdef __cplusplus
 }

@@ -85,6 +85,11 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_positions_create", "sbwtgpu_positions_upload", "sbwtgpu_positions_reset", "sbwtgpu_positions_destroy",
     "sbwtgpu_positions_add_batch", "sbwtgpu_positions_info", "sbwtgpu_positions_first_copy", "sbwtgpu_positions_first_dev",
     "sbwtgpu_positions_map_workspace_bytes", "sbwtgpu_positions_map_dev", "sbwtgpu_positions_map_batch",
+    "sbwtgpu_occurrences_builder_create", "sbwtgpu_occurrences_builder_add_batch", "sbwtgpu_occurrences_builder_finish",
+    "sbwtgpu_occurrences_builder_destroy", "sbwtgpu_occurrences_upload", "sbwtgpu_occurrences_destroy", "sbwtgpu_occurrences_info",
+    "sbwtgpu_occurrences_offsets_copy", "sbwtgpu_occurrences_keys_copy", "sbwtgpu_occurrences_offsets_dev",
+    "sbwtgpu_occurrences_keys_dev", "sbwtgpu_occurrences_to_positions", "sbwtgpu_occurrences_map_workspace_bytes",
+    "sbwtgpu_occurrences_map_dev", "sbwtgpu_occurrences_map_batch",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -211,6 +216,8 @@ READ_MAP_DTYPE = np.dtype([("start", np.int64), ("seq", np.int32), ("strand", np
                            ("n_found", np.int32), ("n_anchored", np.int32)])
 POSITIONS_MAP_TABLE = 256       # SBWTGPU_POSITIONS_MAP_TABLE
 POS_NONE = 0xFFFFFFFFFFFFFFFF   # first[v]: no position
+OCCURRENCES_MAP_TABLE = 256     # SBWTGPU_OCCURRENCES_MAP_TABLE
+OCCURRENCES_MAX_OCC = 1 << 20   # SBWTGPU_OCCURRENCES_MAX_OCC
 MAX_COLORS = 4096
 
 _lib: Optional[C.CDLL] = None
@@ -413,6 +420,24 @@ def lib() -> C.CDLL:
         L.sbwtgpu_positions_map_workspace_bytes.restype = i64
         L.sbwtgpu_positions_map_dev.argtypes = [vp, vp, i64, vp, i64, ci, vp, vp, i64, vp]
         L.sbwtgpu_positions_map_batch.argtypes = [vp, vp, vp, i64, ci, vp]
+        L.sbwtgpu_occurrences_builder_create.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_occurrences_builder_add_batch.argtypes = [vp, i64, vp, vp, i64, ci, C.POINTER(i64), C.POINTER(i64)]
+        L.sbwtgpu_occurrences_builder_finish.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_occurrences_builder_destroy.argtypes = [vp]
+        L.sbwtgpu_occurrences_builder_destroy.restype = None
+        L.sbwtgpu_occurrences_upload.argtypes = [vp, vp, vp, i64, C.POINTER(vp)]
+        L.sbwtgpu_occurrences_destroy.argtypes = [vp]
+        L.sbwtgpu_occurrences_destroy.restype = None
+        L.sbwtgpu_occurrences_info.argtypes = [vp] + [C.POINTER(i64)] * 8
+        L.sbwtgpu_occurrences_offsets_copy.argtypes = [vp, vp]
+        L.sbwtgpu_occurrences_keys_copy.argtypes = [vp, vp]
+        L.sbwtgpu_occurrences_offsets_dev.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_occurrences_keys_dev.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_occurrences_to_positions.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_occurrences_map_workspace_bytes.argtypes = [i64, i64, ci]
+        L.sbwtgpu_occurrences_map_workspace_bytes.restype = i64
+        L.sbwtgpu_occurrences_map_dev.argtypes = [vp, vp, i64, vp, i64, ci, ci, vp, vp, i64, vp]
+        L.sbwtgpu_occurrences_map_batch.argtypes = [vp, vp, vp, i64, ci, ci, vp]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -850,6 +875,12 @@ class Index:
         h = C.c_void_p()
         _check(lib().sbwtgpu_positions_create(self._h, C.byref(h)))
         return Positions(h, self)
+
+    def occurrences_builder(self) -> "OccurrencesBuilder":
+        """sbwtgpu_occurrences_builder_create: an empty builder of an occurrence table bound to this index."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_occurrences_builder_create(self._h, C.byref(h)))
+        return OccurrencesBuilder(h, self)
 
 
 class Unitigs:
@@ -1772,6 +1803,161 @@ class Positions:
     @staticmethod
     def workspace_bytes(total_bases: int, n_reads: int, strands: int = 1) -> int:
         return lib().sbwtgpu_positions_map_workspace_bytes(total_bases, n_reads, strands)
+
+
+class OccurrencesBuilder:
+    """Owns an sbwtgpu_occurrences_builder handle: the log of (column, key) hits that finish() turns into an Occurrences object
+    (include/sbwtgpu.h, "occurrences").  Adds from several threads are safe; they are serialised.  The index is kept
+    referenced."""
+
+    def __init__(self, handle, index: Index):
+        self._h = handle
+        self.index = index
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        if self._h:
+            lib().sbwtgpu_occurrences_builder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def add_sequences(self, bases, read_off, first_seq: int, strands: int = 1):
+        """sbwtgpu_occurrences_builder_add_batch: sequence i of the batch gets the number first_seq + i.  Returns (n_windows,
+        n_hit_windows) of the batch."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        nw, nh = C.c_int64(), C.c_int64()
+        _check(lib().sbwtgpu_occurrences_builder_add_batch(self._h, first_seq, bases.ctypes.data, read_off.ctypes.data, len(read_off) - 1,
+                                                           strands, C.byref(nw), C.byref(nh)))
+        return nw.value, nh.value
+
+    def add(self, seqs: Sequence[bytes], first_seq: int, strands: int = 1):
+        """The same for a list of byte strings."""
+        bases, off = concat_reads(seqs)
+        return self.add_sequences(bases, off, first_seq, strands)
+
+    def finish(self) -> "Occurrences":
+        """sbwtgpu_occurrences_builder_finish: the object; the builder is consumed."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_occurrences_builder_finish(self._h, C.byref(h)))
+        self._h = None
+        return Occurrences(h, self.index)
+
+
+class Occurrences:
+    """Owns an sbwtgpu_occurrences handle: every reference coordinate of every column's k-mer as CSR arrays (off, occ), and the
+    reads placed on the references by diagonal voting over all of them (include/sbwtgpu.h, "occurrences").  Everything is exact
+    integers.  The index is kept referenced."""
+
+    def __init__(self, handle, index: Index):
+        self._h = handle
+        self.index = index
+
+    @classmethod
+    def upload(cls, index: Index, off, occ) -> "Occurrences":
+        """sbwtgpu_occurrences_upload: an object from copied arrays (off uint64[n_nodes + 1], occ uint64[off[-1]])."""
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        occ = np.ascontiguousarray(occ, dtype=np.uint64)
+        if off.shape != (index.n_nodes + 1,):
+            raise ValueError("off must have n_nodes + 1 = %d entries, not shape %r" % (index.n_nodes + 1, off.shape))
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_occurrences_upload(index.handle, off.ctypes.data, occ.ctypes.data if len(occ) else None, len(occ), C.byref(h)))
+        return cls(h, index)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        if self._h:
+            lib().sbwtgpu_occurrences_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self) -> dict:
+        """n_columns, k, n_windows, n_hits, n_occurrences, n_positioned, max_count and device_bytes."""
+        v = [C.c_int64() for _ in range(8)]
+        _check(lib().sbwtgpu_occurrences_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("n_columns", "k", "n_windows", "n_hits", "n_occurrences", "n_positioned", "max_count", "device_bytes"),
+                        (x.value for x in v)))
+
+    def offsets(self) -> np.ndarray:
+        """uint64[n_nodes + 1]: column v's keys are keys()[off[v]:off[v + 1]]."""
+        out = np.zeros(self.index.n_nodes + 1, dtype=np.uint64)
+        _check(lib().sbwtgpu_occurrences_offsets_copy(self._h, out.ctypes.data))
+        return out
+
+    def keys(self) -> np.ndarray:
+        """uint64[n_occurrences]: (seq << 32) | (pos << 1) | t, strictly ascending within a column."""
+        out = np.zeros(self.info()["n_occurrences"], dtype=np.uint64)
+        _check(lib().sbwtgpu_occurrences_keys_copy(self._h, out.ctypes.data if len(out) else None))
+        return out
+
+    def offsets_dev(self) -> int:
+        p = C.c_void_p()
+        _check(lib().sbwtgpu_occurrences_offsets_dev(self._h, C.byref(p)))
+        return p.value or 0
+
+    def keys_dev(self) -> int:
+        p = C.c_void_p()
+        _check(lib().sbwtgpu_occurrences_keys_dev(self._h, C.byref(p)))
+        return p.value or 0
+
+    def positions(self) -> "Positions":
+        """sbwtgpu_occurrences_to_positions: the Positions object with first[v] = the smallest key of column v."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_occurrences_to_positions(self._h, C.byref(h)))
+        return Positions(h, self.index)
+
+    def map(self, bases, read_off, strands: int = 1, max_occ: int = 1024) -> np.ndarray:
+        """sbwtgpu_occurrences_map_batch: one READ_MAP_DTYPE record per read."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        n = max(len(read_off) - 1, 0)
+        out = np.zeros(n, dtype=READ_MAP_DTYPE)
+        _check(lib().sbwtgpu_occurrences_map_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n, strands, max_occ, out.ctypes.data))
+        return out
+
+    def map_reads(self, reads: Sequence[bytes], strands: int = 1, max_occ: int = 1024) -> np.ndarray:
+        """The same for a list of byte strings."""
+        bases, off = concat_reads(reads)
+        return self.map(bases, off, strands, max_occ)
+
+    def map_dev(self, d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_out: int, d_ws: int, ws_bytes: int,
+                strands: int = 1, max_occ: int = 1024, stream: int = 0) -> None:
+        """sbwtgpu_occurrences_map_dev (raw device pointers; d_out: n_reads records of 32 bytes; workspace of workspace_bytes):
+        asynchronous on stream."""
+        _check(lib().sbwtgpu_occurrences_map_dev(self._h, d_bases or None, total_bases, d_read_off or None, n_reads, strands, max_occ,
+                                                 d_out or None, d_ws or None, ws_bytes, stream or None))
+
+    @staticmethod
+    def workspace_bytes(total_bases: int, n_reads: int, strands: int = 1) -> int:
+        return lib().sbwtgpu_occurrences_map_workspace_bytes(total_bases, n_reads, strands)
 
 
 class ColorSetsBuilder:

@@ -30,6 +30,7 @@
 #include "globals.hh"
 #include "index_builder.hh"
 #include "index_file.hh"
+#include "occurrences_file.hh"
 #include "positions_file.hh"
 #include "seqio.hh"
 
@@ -825,6 +826,111 @@ public:
         p.k = k;
         p.load(filename);
         return p;
+    }
+    // Every reference occurrence of every column's k-mer and reads mapped by voting over all of them (include/sbwtgpu.h,
+    // "occurrences"): a builder on the device takes as many adds as the caller has, finish() makes the object; `seqs` lists what
+    // was added, in the order of the sequence numbers, and travels with the arrays in the occurrence file
+    // (occurrences_file.hh).  The index must outlive the object.
+    class Occurrences {
+    public:
+        Occurrences() = default;
+        Occurrences(const Occurrences &) = delete;
+        Occurrences &operator=(const Occurrences &) = delete;
+        Occurrences(Occurrences &&o) noexcept : seqs(std::move(o.seqs)), b(o.b), h(o.h), idx(o.idx), n_nodes(o.n_nodes), k(o.k) { o.b = nullptr; o.h = nullptr; }
+        Occurrences &operator=(Occurrences &&o) noexcept {
+            if (this != &o) {
+                sbwtgpu_occurrences_builder_destroy(b);
+                sbwtgpu_occurrences_destroy(h);
+                seqs = std::move(o.seqs); b = o.b; h = o.h; idx = o.idx; n_nodes = o.n_nodes; k = o.k; o.b = nullptr; o.h = nullptr;
+            }
+            return *this;
+        }
+        ~Occurrences() { sbwtgpu_occurrences_builder_destroy(b); sbwtgpu_occurrences_destroy(h); }
+        // before finish(): the sequences of the batch get the numbers seqs.size(), seqs.size() + 1, ... and the colour `colour`
+        void add(const char *bases, const int64_t *read_off, int64_t n_reads, int strands = 1, int32_t colour = 0) {
+            if (!b) throw std::runtime_error("Error: the occurrence table is finished, it takes no more sequences");
+            detail::gpu_check(sbwtgpu_occurrences_builder_add_batch(b, (int64_t)seqs.size(), bases, read_off, n_reads, strands, nullptr, nullptr));
+            for (int64_t r = 0; r < n_reads; r++) seqs.push_back({colour, 0, read_off[r + 1] - read_off[r]});
+        }
+        void finish() {
+            if (!b) return;
+            detail::gpu_check(sbwtgpu_occurrences_builder_finish(b, &h));
+            b = nullptr;
+        }
+        void map(const char *bases, const int64_t *read_off, int64_t n_reads, int strands, int max_occ, sbwtgpu_read_map *out) const {
+            detail::gpu_check(sbwtgpu_occurrences_map_batch(h, bases, read_off, n_reads, strands, max_occ, out));
+        }
+        struct Info { int64_t n_columns = 0, k = 0, n_windows = 0, n_hits = 0, n_occurrences = 0, n_positioned = 0, max_count = 0, device_bytes = 0; };
+        Info info() const {
+            Info i;
+            detail::gpu_check(sbwtgpu_occurrences_info(h, &i.n_columns, &i.k, &i.n_windows, &i.n_hits, &i.n_occurrences, &i.n_positioned,
+                                                       &i.max_count, &i.device_bytes));
+            return i;
+        }
+        std::vector<uint64_t> offsets() const {
+            std::vector<uint64_t> f((size_t)n_nodes + 1);
+            detail::gpu_check(sbwtgpu_occurrences_offsets_copy(h, f.data()));
+            return f;
+        }
+        std::vector<uint64_t> keys() const {
+            std::vector<uint64_t> f((size_t)info().n_occurrences);
+            detail::gpu_check(sbwtgpu_occurrences_keys_copy(h, f.data()));
+            return f;
+        }
+        void save(const std::string &filename) const {
+            const std::vector<uint64_t> off = offsets(), occ = keys();
+            occurrences_file::write(filename, off.data(), occ.data(), n_nodes, k, (int64_t)occ.size(), seqs.data(), (int64_t)seqs.size());
+        }
+        // the arrays and the sequence list of an occurrence file of the object's index take the place of what the object held
+        void load(const std::string &filename) {
+            int64_t n = 0, fk = 0, ns = 0, no = 0;
+            occurrences_file::read(filename, n, fk, ns, no, nullptr, nullptr, 0, nullptr, 0);
+            if (n != n_nodes || fk != k)
+                throw std::runtime_error("Error: " + filename + " holds the occurrences of an index of " + std::to_string(n) + " columns at k = " +
+                                         std::to_string(fk) + ", this index has " + std::to_string(n_nodes) + " columns at k = " + std::to_string(k));
+            std::vector<occurrences_file::Seq> file_seqs;
+            std::vector<uint64_t> off((size_t)n + 1), occ((size_t)no + 1);
+            occurrences_file::read(filename, n, fk, ns, no, &file_seqs, off.data(), n + 1, occ.data(), no);
+            sbwtgpu_occurrences *fresh = nullptr;
+            detail::gpu_check(sbwtgpu_occurrences_upload(idx, off.data(), occ.data(), no, &fresh));
+            sbwtgpu_occurrences_builder_destroy(b);
+            b = nullptr;
+            sbwtgpu_occurrences_destroy(h);
+            h = fresh;
+            seqs = std::move(file_seqs);
+        }
+        // the positions object with first[v] = the smallest occurrence of column v, and this object's sequence list
+        Positions to_positions() const {
+            Positions p;
+            p.idx = idx;
+            p.n_nodes = n_nodes;
+            p.k = k;
+            p.seqs = seqs;
+            detail::gpu_check(sbwtgpu_occurrences_to_positions(h, &p.h));
+            return p;
+        }
+        std::vector<occurrences_file::Seq> seqs;
+        sbwtgpu_occurrences_builder *b = nullptr;   // until finish()
+        sbwtgpu_occurrences *h = nullptr;           // from finish() or load() on
+        const sbwtgpu_index *idx = nullptr;
+        int64_t n_nodes = 0, k = 0;
+    };
+    Occurrences occurrences() const {
+        Occurrences o;
+        o.idx = need_device();
+        o.n_nodes = n_nodes;
+        o.k = k;
+        detail::gpu_check(sbwtgpu_occurrences_builder_create(o.idx, &o.b));
+        return o;
+    }
+    // the object of an occurrence file of THIS index
+    Occurrences load_occurrences(const std::string &filename) const {
+        Occurrences o;
+        o.idx = need_device();
+        o.n_nodes = n_nodes;
+        o.k = k;
+        o.load(filename);
+        return o;
     }
     // the k-mers of the index whose colour set satisfies the predicate, as the columns of their index (include/sbwtgpu.h,
     // "colour select"): bit for bit what the builder gives for the selected k-mers.  The object is one of THIS index;

@@ -12,6 +12,7 @@
 
 #include "index_builder.hh"
 #include "index_file.hh"
+#include "occurrences_file.hh"
 #include "positions_file.hh"
 #include "seqio.hh"
 
@@ -487,6 +488,45 @@ int sbwthost_positions_read(const char *path, int64_t *n_columns, int64_t *k, in
         if (n_columns) *n_columns = n;
         if (k) *k = kk;
         if (n_seqs) *n_seqs = ns;
+        return 0;
+    } catch (const std::exception &e) {
+        return fail("%s", e.what());
+    }
+}
+
+// ---- occurrence files: "SBWTOCC1" (occurrences_file.hh holds the format; SBWT::Occurrences::save / load go through the same code) ----
+int sbwthost_occurrences_write(const char *path, const uint64_t *off, const uint64_t *occ, int64_t n_columns, int64_t k, int64_t n_occ,
+                               const int32_t *seq_color, const int64_t *seq_len, int64_t n_seqs) {
+    if (!path || !off || n_columns < 0 || n_seqs < 0 || n_occ < 0 || (n_occ > 0 && !occ) || (n_seqs > 0 && (!seq_color || !seq_len)))
+        return fail("invalid argument");
+    try {
+        std::vector<sbwt::occurrences_file::Seq> seqs((size_t)n_seqs);
+        for (int64_t i = 0; i < n_seqs; i++) seqs[(size_t)i] = {seq_color[i], 0, seq_len[i]};
+        sbwt::occurrences_file::write(path, off, occ, n_columns, k, n_occ, seqs.data(), n_seqs);
+        return 0;
+    } catch (const std::exception &e) {
+        return fail("%s", e.what());
+    }
+}
+
+int sbwthost_occurrences_read(const char *path, int64_t *n_columns, int64_t *k, int64_t *n_seqs, int64_t *n_occ, int32_t *seq_color_or_null,
+                              int64_t *seq_len_or_null, int64_t seqs_cap, uint64_t *off_or_null, int64_t off_cap, uint64_t *occ_or_null,
+                              int64_t occ_cap) {
+    if (!path) return fail("invalid argument");
+    try {
+        int64_t n = 0, kk = 0, ns = 0, no = 0;
+        std::vector<sbwt::occurrences_file::Seq> seqs;
+        const bool want_seqs = seq_color_or_null || seq_len_or_null;
+        sbwt::occurrences_file::read(path, n, kk, ns, no, (want_seqs || off_or_null) ? &seqs : nullptr, off_or_null, off_cap, occ_or_null, occ_cap);
+        if (want_seqs && seqs_cap < ns) return fail("Error: room for %lld sequences, the occurrence file lists %lld", (long long)seqs_cap, (long long)ns);
+        for (int64_t i = 0; want_seqs && i < ns; i++) {
+            if (seq_color_or_null) seq_color_or_null[i] = seqs[(size_t)i].colour;
+            if (seq_len_or_null) seq_len_or_null[i] = seqs[(size_t)i].length;
+        }
+        if (n_columns) *n_columns = n;
+        if (k) *k = kk;
+        if (n_seqs) *n_seqs = ns;
+        if (n_occ) *n_occ = no;
         return 0;
     } catch (const std::exception &e) {
         return fail("%s", e.what());

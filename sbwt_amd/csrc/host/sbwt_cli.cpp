@@ -22,16 +22,19 @@
 //   sbwt set-op -a <index A> -b <index B> [--op union|intersection|difference|symmetric-difference] -o <index> [--counts-only]
 //               two index files combined on the GPU without their input sequences: the index `sbwt build` would write for
 //               the result's k-mers
-//   sbwt read-hits -i <index> -q <query> -o <out> [-z] [--both-strands] [--positions <index.pos>]
+//   sbwt read-hits -i <index> -q <query> -o <out> [-z] [--both-strands] [--positions <index.pos> | --occurrences <index.occ> [--max-occ N]]
 //               one line per read: n_kmers n_found covered_bases longest_run; with --positions six more columns, the read's
-//               placement on the references by diagonal voting: seq strand start votes votes2 n_anchored
+//               placement on the references by diagonal voting: seq strand start votes votes2 n_anchored; with --occurrences
+//               the same six columns from the vote over every occurrence of every k-mer (--max-occ, default 1024: a k-mer
+//               with more occurrences casts no vote)
 //   sbwt build-colors -i <index> -r <refs.txt> -o <colours> [--both-strands] [--wide | --compress [--stream]]
-//               [--positions-out <index.pos>]
+//               [--positions-out <index.pos>] [--occurrences-out <index.occ>]
 //               one colour per listed reference file, set on the columns of the index's k-mers that the file holds
 //               (--wide: up to 4096 files, a colour file of several words per column; --compress: up to 4096 files, a
 //               colour-set file of one id per column and the distinct colour sets; --compress --stream: the same file, built
 //               one reference at a time without the wide matrix on the device); --positions-out: also the position file,
-//               per column the smallest (sequence, offset) at which its k-mer occurs, the sequences numbered in reading order
+//               per column the smallest (sequence, offset) at which its k-mer occurs, the sequences numbered in reading order;
+//               --occurrences-out: also the occurrence file, per column every (sequence, offset, strand) of its k-mer
 //   sbwt compress-colors -i <index> -c <colours> -o <colour sets>
 //               the colour-set file of a colour file written with or without --wide
 //   sbwt merge-colors -u <index U> -a <index A> --colors-a <colours of A> [-b <index B> --colors-b <colours of B>]
@@ -776,6 +779,8 @@ int read_hits_main(int argc, char **argv) {
         {"gzip-output", 'z', false, "Writes output in gzipped form.", ""},
         {"both-strands", 0, false, "A k-mer also counts as found when its reverse complement is in the index.", ""},
         {"positions", 0, true, "A position file of the index (build-colors --positions-out): every line gains the read's placement on the references, seq strand start votes votes2 n_anchored (seq -1: no placement).", ""},
+        {"occurrences", 0, true, "An occurrence file of the index (build-colors --occurrences-out): every line gains the same six columns, seq strand start votes votes2 n_anchored, from the vote over every occurrence of every k-mer; votes2 == votes says that an equally good placement exists. Cannot be combined with --positions.", ""},
+        {"max-occ", 0, true, "With --occurrences: a k-mer with more occurrences than this casts no vote (1 .. 1048576). The default is 1024.", "1024"},
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
@@ -789,6 +794,18 @@ int read_hits_main(int argc, char **argv) {
     const int strands = opts.count("both-strands") ? 2 : 1;
     const string posfile = opts.count("positions") ? opts.get("positions") : "";
     if (!posfile.empty()) check_readable(posfile);
+    const string occfile = opts.count("occurrences") ? opts.get("occurrences") : "";
+    if (!occfile.empty() && !posfile.empty()) throw std::runtime_error("Error: --positions and --occurrences cannot be combined");
+    if (!occfile.empty()) check_readable(occfile);
+    int64_t max_occ = 1024;
+    if (opts.count("max-occ")) {
+        if (occfile.empty()) throw std::runtime_error("Error: --max-occ needs --occurrences");
+        const string text = opts.get("max-occ");
+        char *end = nullptr;
+        max_occ = strtoll(text.c_str(), &end, 10);
+        if (text.empty() || *end != 0 || max_occ < 1 || max_occ > SBWTGPU_OCCURRENCES_MAX_OCC)
+            throw std::runtime_error("Error: --max-occ must be a number in 1 .. 1048576, not " + text);
+    }
     use_gpu_option(opts);
     const int64_t batch_bases = batch_bases_option(opts);
 
@@ -796,6 +813,9 @@ int read_hits_main(int argc, char **argv) {
     load_plain_matrix(indexfile, index, "GPU search path");
     plain_matrix_sbwt_t::Positions positions;
     if (!posfile.empty()) positions = index.load_positions(posfile);
+    plain_matrix_sbwt_t::Occurrences occurrences;
+    if (!occfile.empty()) occurrences = index.load_occurrences(occfile);
+    const bool placing = positions.h || occurrences.h;
     vector<sbwtgpu_read_map> placed;
     int64_t total_reads = 0;
     for (size_t f = 0; f < files.in.size(); f++) {
@@ -807,10 +827,9 @@ int read_hits_main(int argc, char **argv) {
         for_each_batch(reader, batch_bases, [&](const vector<char> &bases, const vector<int64_t> &read_off, int64_t n_reads) {
             rec.resize((size_t)n_reads);
             index.read_hits_batch(bases.data(), read_off.data(), n_reads, strands, rec.data());
-            if (positions.h) {
-                placed.resize((size_t)n_reads);
-                positions.map(bases.data(), read_off.data(), n_reads, strands, placed.data());
-            }
+            if (placing) placed.resize((size_t)n_reads);
+            if (positions.h) positions.map(bases.data(), read_off.data(), n_reads, strands, placed.data());
+            if (occurrences.h) occurrences.map(bases.data(), read_off.data(), n_reads, strands, (int)max_occ, placed.data());
             text.clear();
             for (size_t r = 0; r < rec.size(); r++) {
                 const sbwtgpu_read_hits &h = rec[r];
@@ -821,7 +840,7 @@ int read_hits_main(int argc, char **argv) {
                 append_int(h.covered_bases, text);
                 text.push_back(' ');
                 append_int(h.longest_run, text);
-                if (positions.h) {
+                if (placing) {
                     const sbwtgpu_read_map &m = placed[r];
                     for (int64_t v : {(int64_t)m.seq, (int64_t)m.strand, (int64_t)m.start, (int64_t)m.votes, (int64_t)m.votes2, (int64_t)m.n_anchored}) {
                         text.push_back(' ');
@@ -1117,6 +1136,7 @@ int build_colors_main(int argc, char **argv) {
         {"compress", 0, false, "Up to 4096 lines in the list; writes a colour-set file (one id per column and the distinct colour sets).", ""},
         {"stream", 0, false, "With --compress: merge one reference at a time into the colour sets, without the wide matrix on the device. The same file.", ""},
         {"positions-out", 0, true, "Also write a position file: per column of the index the smallest (sequence, offset) at which its k-mer occurs; the sequences of the listed files are numbered 0, 1, ... in the order they are read.", ""},
+        {"occurrences-out", 0, true, "Also write an occurrence file: per column of the index every (sequence, offset, strand) at which its k-mer occurs, the sequences numbered as for --positions-out. May be given together with --positions-out.", ""},
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
@@ -1141,6 +1161,8 @@ int build_colors_main(int argc, char **argv) {
     check_writable(outfile);
     const string posfile = opts.count("positions-out") ? opts.get("positions-out") : "";
     if (!posfile.empty()) check_writable(posfile);
+    const string occfile = opts.count("occurrences-out") ? opts.get("occurrences-out") : "";
+    if (!occfile.empty()) check_writable(occfile);
     const int strands = opts.count("both-strands") ? 2 : 1;
     use_gpu_option(opts);
     const int64_t batch_bases = batch_bases_option(opts);
@@ -1148,6 +1170,8 @@ int build_colors_main(int argc, char **argv) {
     load_plain_matrix(indexfile, index);
     plain_matrix_sbwt_t::Positions positions;
     if (!posfile.empty()) positions = index.positions();
+    plain_matrix_sbwt_t::Occurrences occurrences;
+    if (!occfile.empty()) occurrences = index.occurrences();
     ColorsHandle col;
     ColorSetsBuilderHandle builder;
     if (stream) colors_check(sbwtgpu_colorsets_builder_create(index.device_handle(), (int)refs.size(), &builder.h));
@@ -1168,6 +1192,7 @@ int build_colors_main(int argc, char **argv) {
             windows[c] += w;
             hit_windows[c] += h;
             if (positions.h) positions.add(bases.data(), read_off.data(), n_reads, strands, (int32_t)c);
+            if (occurrences.b) occurrences.add(bases.data(), read_off.data(), n_reads, strands, (int32_t)c);
         });
     }
     if (positions.h) {
@@ -1175,6 +1200,14 @@ int build_colors_main(int argc, char **argv) {
         const plain_matrix_sbwt_t::Positions::Info pi = positions.info();
         write_log("Wrote the positions of " + std::to_string(pi.n_positioned) + " columns on " + std::to_string(positions.seqs.size()) +
                       " sequences to " + posfile,
+                  LogLevel::MAJOR);
+    }
+    if (occurrences.b) {
+        occurrences.finish();
+        occurrences.save(occfile);
+        const plain_matrix_sbwt_t::Occurrences::Info oi = occurrences.info();
+        write_log("Wrote " + std::to_string(oi.n_occurrences) + " occurrences of " + std::to_string(oi.n_positioned) + " columns on " +
+                      std::to_string(occurrences.seqs.size()) + " sequences to " + occfile,
                   LogLevel::MAJOR);
     }
     int64_t n_columns = 0, ck = 0, n_colored = 0;

@@ -255,6 +255,14 @@ int sbwtgpu_set_tuning(const char *key, int64_t value) {
         g_pos_map_table = (int)value;
         return SBWTGPU_OK;
     }
+    if (!strcmp(key, "occurrences_chunk_bases")) { g_occ_chunk_bases = value < 0 ? 0 : value; return SBWTGPU_OK; }
+    if (!strcmp(key, "occurrences_map_table")) {
+        if (value < 0 || value > SBWTGPU_OCCURRENCES_MAP_TABLE)
+            return fail(SBWTGPU_ERR_INVALID_ARG, "occurrences_map_table must be in 0 .. %d (0: the compiled capacity), not %lld",
+                        SBWTGPU_OCCURRENCES_MAP_TABLE, (long long)value);
+        g_occ_map_table = (int)value;
+        return SBWTGPU_OK;
+    }
     if (!strcmp(key, "gram_mfma_min_sets")) { g_gram_mfma_min_sets = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "gram_flush_sets")) {
         if (value < 1 || value > SBWT_GM_FLUSH_MAX)

@@ -85,6 +85,13 @@ static int pos_clear(sbwtgpu_positions *p) {
     return SBWTGPU_OK;
 }
 
+// what sbwtgpu_occurrences_to_positions fills: an object with every entry "no position", and its table on the device
+int sbwt_capi::positions_alloc_cleared(const sbwtgpu_index *idx, sbwtgpu_positions **out, unsigned long long **d_first) {
+    STG_TRY(sbwtgpu_positions_create(idx, out));
+    *d_first = (*out)->d_first;
+    return SBWTGPU_OK;
+}
+
 extern "C" {
 
 int sbwtgpu_positions_create(const sbwtgpu_index *idx, sbwtgpu_positions **out) {

@@ -1,7 +1,7 @@
 // sbwtgpu_internal.h -- what the translation units of the C ABI share: sbwtgpu_capi.cpp (index image, search, rank, text),
 // sbwtgpu_capi_reads.cpp (matching statistics, set operations, read hits, unitigs and their graph, walks, bubbles) and
 // sbwtgpu_capi_colors.cpp (colours, colour sets, pseudoalignment, screen) and sbwtgpu_capi_positions.cpp (reference positions,
-// read mapping).  Nothing here is part of the library's interface:
+// read mapping) and sbwtgpu_capi_occurrences.cpp (all occurrences per column, mapping over them).  Nothing here is part of the library's interface:
 // every name has hidden visibility, and whatever holds state (the error text, the parked slots, the int32 switch of a search
 // call) is defined once, in sbwtgpu_capi.cpp.
 #pragma once
@@ -91,6 +91,8 @@ extern int64_t g_pa_chunk_bases, g_screen_chunk_bases;      // sbwtgpu_capi_colo
 extern int64_t g_gram_mfma_min_sets, g_gram_flush_sets;
 extern int64_t g_pos_chunk_bases;                           // sbwtgpu_capi_positions.cpp
 extern int g_pos_map_table;
+extern int64_t g_occ_chunk_bases;                           // sbwtgpu_capi_occurrences.cpp
+extern int g_occ_map_table;
 
 }  // namespace sbwt_capi
 
@@ -158,6 +160,9 @@ int build_columns(SbwtBuildState &S, int64_t k, int build_streaming_support, sbw
 int unitigs_create_common(const sbwtgpu_index *idx, const unsigned *d_ids, const unsigned long long *d_table, int words, int64_t n_sets,
                           int n_colors, unsigned graph, sbwtgpu_unitigs **out);
 int setop_check_index(const sbwtgpu_index *idx, const char *who);
+// sbwtgpu_capi_positions.cpp: a positions object with every entry "no position" and its table on the device, for a caller that
+// fills the table itself (sbwtgpu_occurrences_to_positions)
+int positions_alloc_cleared(const sbwtgpu_index *idx, sbwtgpu_positions **out, unsigned long long **d_first);
 // sbwtgpu_capi_colors.cpp
 int colorsets_check(const sbwtgpu_colorsets *s);
 // The searches of a batch and, for two strands, of its mirrored batch, int32 results, in a workspace of

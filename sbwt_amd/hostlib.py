@@ -18,7 +18,7 @@ EXPORTED_SYMBOLS = [
     "sbwthost_file_words", "sbwthost_file_precalc", "sbwthost_read_sequences", "sbwthost_read_sequences_chunked", "sbwthost_free", "sbwthost_write_file",
     "sbwthost_rank_batch", "sbwthost_colors_write", "sbwthost_colors_read",
     "sbwthost_colors_write_wide", "sbwthost_colors_read_wide", "sbwthost_colorsets_write", "sbwthost_colorsets_read",
-    "sbwthost_positions_write", "sbwthost_positions_read",
+    "sbwthost_positions_write", "sbwthost_positions_read", "sbwthost_occurrences_write", "sbwthost_occurrences_read",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -64,6 +64,8 @@ def lib() -> C.CDLL:
                                           vp, i64, vp, i64]
     L.sbwthost_positions_write.argtypes = [C.c_char_p, vp, i64, i64, vp, vp, i64]
     L.sbwthost_positions_read.argtypes = [C.c_char_p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp, vp, i64, vp, i64]
+    L.sbwthost_occurrences_write.argtypes = [C.c_char_p, vp, vp, i64, i64, i64, vp, vp, i64]
+    L.sbwthost_occurrences_read.argtypes = [C.c_char_p] + [C.POINTER(i64)] * 4 + [vp, vp, i64, vp, i64, vp, i64]
     _lib = L
     return L
 
@@ -286,3 +288,35 @@ def positions_read(path: str):
     if L.sbwthost_positions_read(path.encode(), *sizes, col.ctypes.data, ln.ctypes.data, ns.value, first.ctypes.data, n.value) != 0:
         raise RuntimeError(_err())
     return first[: n.value], k.value, col[: ns.value], ln[: ns.value]
+
+
+def occurrences_write(path: str, off, occ, k: int, seq_color, seq_len) -> None:
+    """Writes an occurrence table (off uint64[n_columns + 1], occ uint64[off[-1]]) with its sequence list as an "SBWTOCC1" file
+    (include/sbwthost.h)."""
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    occ = np.ascontiguousarray(occ, dtype=np.uint64)
+    seq_color = np.ascontiguousarray(seq_color, dtype=np.int32)
+    seq_len = np.ascontiguousarray(seq_len, dtype=np.int64)
+    if len(seq_color) != len(seq_len):
+        raise RuntimeError("%d colours for %d lengths" % (len(seq_color), len(seq_len)))
+    if len(off) < 1:
+        raise RuntimeError("off needs n_columns + 1 entries")
+    if lib().sbwthost_occurrences_write(path.encode(), off.ctypes.data, occ.ctypes.data if len(occ) else None, len(off) - 1, k, len(occ),
+                                        seq_color.ctypes.data if len(seq_len) else None, seq_len.ctypes.data if len(seq_len) else None,
+                                        len(seq_len)) != 0:
+        raise RuntimeError(_err())
+
+
+def occurrences_read(path: str):
+    """(off uint64[n_columns + 1], occ uint64[n_occ], k, seq_color int32[n_seqs], seq_len int64[n_seqs]) of an "SBWTOCC1" file."""
+    L = lib()
+    n, k, ns, no = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    sizes = (C.byref(n), C.byref(k), C.byref(ns), C.byref(no))
+    if L.sbwthost_occurrences_read(path.encode(), *sizes, None, None, 0, None, 0, None, 0) != 0:
+        raise RuntimeError(_err())
+    off, occ = np.empty(n.value + 1, dtype=np.uint64), np.empty(max(no.value, 1), dtype=np.uint64)
+    col, ln = np.empty(max(ns.value, 1), dtype=np.int32), np.empty(max(ns.value, 1), dtype=np.int64)
+    if L.sbwthost_occurrences_read(path.encode(), *sizes, col.ctypes.data, ln.ctypes.data, ns.value, off.ctypes.data, n.value + 1,
+                                   occ.ctypes.data, no.value) != 0:
+        raise RuntimeError(_err())
+    return off, occ[: no.value], k.value, col[: ns.value], ln[: ns.value]
