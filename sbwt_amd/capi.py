@@ -514,7 +514,34 @@ def build_bits_gpu(seqs: Sequence[bytes], k: int, add_revcomp: bool = False, str
     return _take_bits(out)
 
 
-class Index:
+class _Owner:
+    """What every handle-owning class shares: the handle in `_h`, and `_destroy`, the name of the library call that frees it."""
+
+    _destroy = ""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+
+class Index(_Owner):
     """Owning wrapper of a `sbwtgpu_index*` (one GPU)."""
 
     def __init__(self, handle: int, keepalive=None):
@@ -531,10 +558,6 @@ class Index:
         self.blob_bytes = info.blob_bytes
         self.image_level = info.image_level
         self.n_paths, self.n_branch, self.default_search_variant = info.n_paths, info.n_branch, info.default_search_variant
-
-    @property
-    def handle(self) -> C.c_void_p:
-        return self._h
 
     @classmethod
     def create(cls, A, Cb, G, T, ssup, n_nodes: int, k: int, n_kmers: int = 0, precalc_k: int = 0,
@@ -556,16 +579,10 @@ class Index:
         _check(lib().sbwtgpu_index_adopt(buf, len(header), C.c_void_p(dev_ptr), blob_bytes, device, C.byref(h)))
         return cls(h.value, keepalive=keepalive)
 
-    def close(self) -> None:
+    def close(self) -> None:                   # (its own: the handle stays a c_void_p, and `_keep` lives as long as the object)
         if self._h:
             lib().sbwtgpu_index_destroy(self._h)
             self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- replication helpers ----
     def export_header(self) -> bytes:
@@ -883,8 +900,10 @@ class Index:
         return OccurrencesBuilder(h, self)
 
 
-class Unitigs:
+class Unitigs(_Owner):
     """Owns an sbwtgpu_unitigs handle."""
+
+    _destroy = "sbwtgpu_unitigs_destroy"
 
     def __init__(self, handle, n_nodes: int = 0):
         self._h = handle
@@ -892,23 +911,6 @@ class Unitigs:
         n, total, nk = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         _check(lib().sbwtgpu_unitigs_info(self._h, C.byref(n), C.byref(total), C.byref(nk)))
         self.n_unitigs, self.total_bases, self.n_kmers = n.value, total.value, nk.value
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self) -> None:
-        if self._h:
-            lib().sbwtgpu_unitigs_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def dev_ptrs(self):
         """(d_bases, d_off, d_first_col) as integers; valid until close()."""
@@ -1060,30 +1062,15 @@ class Unitigs:
         return {"n_color_breaks": int(nb.value), "n_sets": int(ns.value), "n_colors": int(nc.value)}
 
 
-class Bubbles:
+class Bubbles(_Owner):
     """Owns an sbwtgpu_bubbles handle: the variant sites of a plain unitig graph (Unitigs.bubbles)."""
+
+    _destroy = "sbwtgpu_bubbles_destroy"
 
     def __init__(self, handle):
         self._h = handle
         i = self.info()
         self.n_bubbles, self.n_snps, self.n_colors, self.words = i["n_bubbles"], i["n_snps"], i["n_colors"], i["words"]
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self) -> None:
-        if self._h:
-            lib().sbwtgpu_bubbles_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def info(self) -> dict:
         nb, ns, nc, w = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
@@ -1121,37 +1108,18 @@ class Bubbles:
         return {"pass_ms": dict(zip(("in_degrees", "detect", "compact", "branch_colors"), (float(x) for x in ms)))}
 
 
-class Genotype:
+class Genotype(_Owner):
     """Owns an sbwtgpu_genotype handle: the accumulator of a read set genotyped at the bubbles of a plain unitig graph
     (include/sbwtgpu.h, "genotype") -- per k-mer of every branch its hits, per branch seen / hits / min_hits, per bubble a call
     and per colour how often the sample follows it.  Everything is exact int64.  The index and the handle are kept referenced."""
+
+    _destroy = "sbwtgpu_genotype_destroy"
 
     def __init__(self, handle, index: "Index", unitigs: "Unitigs"):
         self._h = handle
         self.index, self.unitigs = index, unitigs
         i = self.info()
         self.n_bubbles, self.n_branch_kmers, self.n_colors = i["n_bubbles"], i["n_branch_kmers"], i["n_colors"]
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self) -> None:
-        if self._h:
-            lib().sbwtgpu_genotype_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
 
     def add(self, bases, read_off, strands: int = 1) -> None:
         """sbwtgpu_genotype_add_batch: the reads (uint8 bases, int64 offsets) join the sample; strands = 2 adds the reverse
@@ -1204,9 +1172,11 @@ class Genotype:
         return (call,) + tuple(ref)
 
 
-class Colors:
+class Colors(_Owner):
     """Owns an sbwtgpu_colors handle: the colour matrix of an index (one uint64 row per column, bit c = reference c holds the
     column's k-mer) and pseudoalignment over it.  The index must stay alive as long as the object (it is kept referenced)."""
+
+    _destroy = "sbwtgpu_colors_destroy"
 
     def __init__(self, handle, index: Index, n_colors: int):
         self._h = handle
@@ -1230,27 +1200,6 @@ class Colors:
         h = C.c_void_p()
         _check(lib().sbwtgpu_colors_create(index.handle, n_colors, rows.ctypes.data, C.byref(h)))
         return cls(h, index, n_colors)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self) -> None:
-        if self._h:
-            lib().sbwtgpu_colors_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
 
     def add_sequences(self, color: int, bases, read_off, both_strands: bool = False):
         """sbwtgpu_colors_add_batch: colours every k-mer of the sequences that the index holds; (n_windows, n_hit_windows).
@@ -1384,10 +1333,12 @@ class WideColors(Colors):
                                                   threshold_ppm, denominator, d_out, d_colors, d_counts or None, d_ws, ws_bytes, stream))
 
 
-class ColorSets:
+class ColorSets(_Owner):
     """Owns an sbwtgpu_colorsets handle: the deduplicated colour sets of an index -- one uint32 id per column and a table of the
     distinct rows of W = ceil(n_colors / 64) words (include/sbwtgpu.h, "colour sets").  It means the wide matrix
     table[ids[j]]; the queries return what WideColors' return on that matrix.  The index is kept referenced."""
+
+    _destroy = "sbwtgpu_colorsets_destroy"
 
     def __init__(self, handle, index: Index):
         self._h = handle
@@ -1435,27 +1386,6 @@ class ColorSets:
         out = cls(h, u)
         out.merge_info = info.as_dict()
         return out
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self) -> None:
-        if self._h:
-            lib().sbwtgpu_colorsets_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
 
     def info(self) -> dict:
         """n_columns, k, n_colors, words, n_sets, n_colored_columns and device_bytes."""
@@ -1622,36 +1552,17 @@ class ColorSets:
                                                   threshold_ppm, denominator, d_out, d_colors, d_counts or None, d_ws, ws_bytes, stream))
 
 
-class Screen:
+class Screen(_Owner):
     """Owns an sbwtgpu_screen handle: the accumulator of a read set screened against the references of a colour-set object
     (include/sbwtgpu.h, "screen") -- per set and per colour the index k-mers, the distinct ones the sample holds and the hits.
     Everything is exact int64.  The colour sets (and through them the index) are kept referenced."""
+
+    _destroy = "sbwtgpu_screen_destroy"
 
     def __init__(self, handle, sets: "ColorSets"):
         self._h = handle
         self.sets_object = sets
         self.n_sets, self.n_colors = sets.n_sets, sets.n_colors
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self) -> None:
-        if self._h:
-            lib().sbwtgpu_screen_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
 
     def add(self, bases, read_off, strands: int = 1) -> None:
         """sbwtgpu_screen_add_batch: the reads (uint8 bases, int64 offsets) join the sample; strands = 2 adds the reverse
@@ -1704,14 +1615,51 @@ class Screen:
         _check(lib().sbwtgpu_screen_reset(self._h))
 
 
-class Positions:
-    """Owns an sbwtgpu_positions handle: per column the smallest reference coordinate of its k-mer, and the reads placed on the
-    references by diagonal voting (include/sbwtgpu.h, "positions").  Everything is exact integers.  The index is kept
-    referenced."""
+class _Placement(_Owner):
+    """What Positions, OccurrencesBuilder and Occurrences share: a handle bound to its index (kept referenced), and the add and
+    map calls, which differ between the classes in `_abi`, the prefix of their library functions, and in the arguments that
+    the occurrence maps put behind `strands` (max_occ)."""
+
+    _abi = ""
 
     def __init__(self, handle, index: Index):
         self._h = handle
         self.index = index
+        self._destroy = self._abi + "_destroy"
+
+    def _call(self, name: str, *args) -> None:
+        _check(getattr(lib(), self._abi + name)(self._h, *args))
+
+    def _add_batch(self, bases, read_off, first_seq: int, strands: int):
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        nw, nh = C.c_int64(), C.c_int64()
+        self._call("_add_batch", first_seq, bases.ctypes.data, read_off.ctypes.data, len(read_off) - 1, strands, C.byref(nw), C.byref(nh))
+        return nw.value, nh.value
+
+    def _map_batch(self, bases, read_off, strands: int, *extra) -> np.ndarray:
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        n = max(len(read_off) - 1, 0)
+        out = np.zeros(n, dtype=READ_MAP_DTYPE)
+        self._call("_map_batch", bases.ctypes.data, read_off.ctypes.data, n, strands, *extra, out.ctypes.data)
+        return out
+
+    def _map_dev(self, d_bases, total_bases, d_read_off, n_reads, d_out, d_ws, ws_bytes, stream, strands: int, *extra) -> None:
+        self._call("_map_dev", d_bases or None, total_bases, d_read_off or None, n_reads, strands, *extra, d_out or None, d_ws or None,
+                   ws_bytes, stream or None)
+
+    @classmethod
+    def _map_workspace_bytes(cls, total_bases: int, n_reads: int, strands: int) -> int:
+        return getattr(lib(), cls._abi + "_map_workspace_bytes")(total_bases, n_reads, strands)
+
+
+class Positions(_Placement):
+    """Owns an sbwtgpu_positions handle: per column the smallest reference coordinate of its k-mer, and the reads placed on the
+    references by diagonal voting (include/sbwtgpu.h, "positions").  Everything is exact integers.  The index is kept
+    referenced."""
+
+    _abi = "sbwtgpu_positions"
 
     @classmethod
     def upload(cls, index: Index, first) -> "Positions":
@@ -1723,149 +1671,84 @@ class Positions:
         _check(lib().sbwtgpu_positions_upload(index.handle, first.ctypes.data, C.byref(h)))
         return cls(h, index)
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self) -> None:
-        if self._h:
-            lib().sbwtgpu_positions_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
-
     def add_sequences(self, bases, read_off, first_seq: int, strands: int = 1):
         """sbwtgpu_positions_add_batch: sequence i of the batch gets the number first_seq + i.  Returns (n_windows,
         n_hit_windows) of the batch."""
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
-        nw, nh = C.c_int64(), C.c_int64()
-        _check(lib().sbwtgpu_positions_add_batch(self._h, first_seq, bases.ctypes.data, read_off.ctypes.data, len(read_off) - 1,
-                                                 strands, C.byref(nw), C.byref(nh)))
-        return nw.value, nh.value
+        return self._add_batch(bases, read_off, first_seq, strands)
 
     def add(self, seqs: Sequence[bytes], first_seq: int, strands: int = 1):
         """The same for a list of byte strings."""
-        bases, off = concat_reads(seqs)
-        return self.add_sequences(bases, off, first_seq, strands)
+        return self._add_batch(*concat_reads(seqs), first_seq, strands)
 
     def info(self) -> dict:
         """n_columns, k, n_windows, n_hits, n_positioned and device_bytes."""
         v = [C.c_int64() for _ in range(6)]
-        _check(lib().sbwtgpu_positions_info(self._h, *[C.byref(x) for x in v]))
+        self._call("_info", *[C.byref(x) for x in v])
         return dict(zip(("n_columns", "k", "n_windows", "n_hits", "n_positioned", "device_bytes"), (x.value for x in v)))
 
     def first(self) -> np.ndarray:
         """uint64[n_nodes]: (seq << 32) | (pos << 1) | t per column, POS_NONE where the column has no position."""
         out = np.zeros(self.index.n_nodes, dtype=np.uint64)
-        _check(lib().sbwtgpu_positions_first_copy(self._h, out.ctypes.data))
+        self._call("_first_copy", out.ctypes.data)
         return out
 
     def first_dev(self) -> int:
         p = C.c_void_p()
-        _check(lib().sbwtgpu_positions_first_dev(self._h, C.byref(p)))
+        self._call("_first_dev", C.byref(p))
         return p.value or 0
 
     def reset(self) -> None:
-        _check(lib().sbwtgpu_positions_reset(self._h))
+        self._call("_reset")
 
     def map(self, bases, read_off, strands: int = 1) -> np.ndarray:
         """sbwtgpu_positions_map_batch: one READ_MAP_DTYPE record per read."""
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
-        n = max(len(read_off) - 1, 0)
-        out = np.zeros(n, dtype=READ_MAP_DTYPE)
-        _check(lib().sbwtgpu_positions_map_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n, strands, out.ctypes.data))
-        return out
+        return self._map_batch(bases, read_off, strands)
 
     def map_reads(self, reads: Sequence[bytes], strands: int = 1) -> np.ndarray:
         """The same for a list of byte strings."""
-        bases, off = concat_reads(reads)
-        return self.map(bases, off, strands)
+        return self._map_batch(*concat_reads(reads), strands)
 
     def map_dev(self, d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_out: int, d_ws: int, ws_bytes: int,
                 strands: int = 1, stream: int = 0) -> None:
         """sbwtgpu_positions_map_dev (raw device pointers; d_out: n_reads records of 32 bytes; workspace of workspace_bytes):
         asynchronous on stream."""
-        _check(lib().sbwtgpu_positions_map_dev(self._h, d_bases or None, total_bases, d_read_off or None, n_reads, strands,
-                                               d_out or None, d_ws or None, ws_bytes, stream or None))
+        self._map_dev(d_bases, total_bases, d_read_off, n_reads, d_out, d_ws, ws_bytes, stream, strands)
 
     @staticmethod
     def workspace_bytes(total_bases: int, n_reads: int, strands: int = 1) -> int:
-        return lib().sbwtgpu_positions_map_workspace_bytes(total_bases, n_reads, strands)
+        return Positions._map_workspace_bytes(total_bases, n_reads, strands)
 
 
-class OccurrencesBuilder:
+class OccurrencesBuilder(_Placement):
     """Owns an sbwtgpu_occurrences_builder handle: the log of (column, key) hits that finish() turns into an Occurrences object
     (include/sbwtgpu.h, "occurrences").  Adds from several threads are safe; they are serialised.  The index is kept
     referenced."""
 
-    def __init__(self, handle, index: Index):
-        self._h = handle
-        self.index = index
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self) -> None:
-        if self._h:
-            lib().sbwtgpu_occurrences_builder_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
+    _abi = "sbwtgpu_occurrences_builder"
 
     def add_sequences(self, bases, read_off, first_seq: int, strands: int = 1):
         """sbwtgpu_occurrences_builder_add_batch: sequence i of the batch gets the number first_seq + i.  Returns (n_windows,
         n_hit_windows) of the batch."""
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
-        nw, nh = C.c_int64(), C.c_int64()
-        _check(lib().sbwtgpu_occurrences_builder_add_batch(self._h, first_seq, bases.ctypes.data, read_off.ctypes.data, len(read_off) - 1,
-                                                           strands, C.byref(nw), C.byref(nh)))
-        return nw.value, nh.value
+        return self._add_batch(bases, read_off, first_seq, strands)
 
     def add(self, seqs: Sequence[bytes], first_seq: int, strands: int = 1):
         """The same for a list of byte strings."""
-        bases, off = concat_reads(seqs)
-        return self.add_sequences(bases, off, first_seq, strands)
+        return self._add_batch(*concat_reads(seqs), first_seq, strands)
 
     def finish(self) -> "Occurrences":
         """sbwtgpu_occurrences_builder_finish: the object; the builder is consumed."""
         h = C.c_void_p()
-        _check(lib().sbwtgpu_occurrences_builder_finish(self._h, C.byref(h)))
+        self._call("_finish", C.byref(h))
         self._h = None
         return Occurrences(h, self.index)
 
 
-class Occurrences:
+class Occurrences(_Placement):
     """Owns an sbwtgpu_occurrences handle: every reference coordinate of every column's k-mer as CSR arrays (off, occ), and the
     reads placed on the references by diagonal voting over all of them (include/sbwtgpu.h, "occurrences").  Everything is exact
     integers.  The index is kept referenced."""
 
-    def __init__(self, handle, index: Index):
-        self._h = handle
-        self.index = index
+    _abi = "sbwtgpu_occurrences"
 
     @classmethod
     def upload(cls, index: Index, off, occ) -> "Occurrences":
@@ -1878,93 +1761,67 @@ class Occurrences:
         _check(lib().sbwtgpu_occurrences_upload(index.handle, off.ctypes.data, occ.ctypes.data if len(occ) else None, len(occ), C.byref(h)))
         return cls(h, index)
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self) -> None:
-        if self._h:
-            lib().sbwtgpu_occurrences_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
-
     def info(self) -> dict:
         """n_columns, k, n_windows, n_hits, n_occurrences, n_positioned, max_count and device_bytes."""
         v = [C.c_int64() for _ in range(8)]
-        _check(lib().sbwtgpu_occurrences_info(self._h, *[C.byref(x) for x in v]))
+        self._call("_info", *[C.byref(x) for x in v])
         return dict(zip(("n_columns", "k", "n_windows", "n_hits", "n_occurrences", "n_positioned", "max_count", "device_bytes"),
                         (x.value for x in v)))
 
     def offsets(self) -> np.ndarray:
         """uint64[n_nodes + 1]: column v's keys are keys()[off[v]:off[v + 1]]."""
         out = np.zeros(self.index.n_nodes + 1, dtype=np.uint64)
-        _check(lib().sbwtgpu_occurrences_offsets_copy(self._h, out.ctypes.data))
+        self._call("_offsets_copy", out.ctypes.data)
         return out
 
     def keys(self) -> np.ndarray:
         """uint64[n_occurrences]: (seq << 32) | (pos << 1) | t, strictly ascending within a column."""
         out = np.zeros(self.info()["n_occurrences"], dtype=np.uint64)
-        _check(lib().sbwtgpu_occurrences_keys_copy(self._h, out.ctypes.data if len(out) else None))
+        self._call("_keys_copy", out.ctypes.data if len(out) else None)
         return out
 
     def offsets_dev(self) -> int:
         p = C.c_void_p()
-        _check(lib().sbwtgpu_occurrences_offsets_dev(self._h, C.byref(p)))
+        self._call("_offsets_dev", C.byref(p))
         return p.value or 0
 
     def keys_dev(self) -> int:
         p = C.c_void_p()
-        _check(lib().sbwtgpu_occurrences_keys_dev(self._h, C.byref(p)))
+        self._call("_keys_dev", C.byref(p))
         return p.value or 0
 
     def positions(self) -> "Positions":
         """sbwtgpu_occurrences_to_positions: the Positions object with first[v] = the smallest key of column v."""
         h = C.c_void_p()
-        _check(lib().sbwtgpu_occurrences_to_positions(self._h, C.byref(h)))
+        self._call("_to_positions", C.byref(h))
         return Positions(h, self.index)
 
     def map(self, bases, read_off, strands: int = 1, max_occ: int = 1024) -> np.ndarray:
         """sbwtgpu_occurrences_map_batch: one READ_MAP_DTYPE record per read."""
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
-        n = max(len(read_off) - 1, 0)
-        out = np.zeros(n, dtype=READ_MAP_DTYPE)
-        _check(lib().sbwtgpu_occurrences_map_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n, strands, max_occ, out.ctypes.data))
-        return out
+        return self._map_batch(bases, read_off, strands, max_occ)
 
     def map_reads(self, reads: Sequence[bytes], strands: int = 1, max_occ: int = 1024) -> np.ndarray:
         """The same for a list of byte strings."""
-        bases, off = concat_reads(reads)
-        return self.map(bases, off, strands, max_occ)
+        return self._map_batch(*concat_reads(reads), strands, max_occ)
 
     def map_dev(self, d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_out: int, d_ws: int, ws_bytes: int,
                 strands: int = 1, max_occ: int = 1024, stream: int = 0) -> None:
         """sbwtgpu_occurrences_map_dev (raw device pointers; d_out: n_reads records of 32 bytes; workspace of workspace_bytes):
         asynchronous on stream."""
-        _check(lib().sbwtgpu_occurrences_map_dev(self._h, d_bases or None, total_bases, d_read_off or None, n_reads, strands, max_occ,
-                                                 d_out or None, d_ws or None, ws_bytes, stream or None))
+        self._map_dev(d_bases, total_bases, d_read_off, n_reads, d_out, d_ws, ws_bytes, stream, strands, max_occ)
 
     @staticmethod
     def workspace_bytes(total_bases: int, n_reads: int, strands: int = 1) -> int:
-        return lib().sbwtgpu_occurrences_map_workspace_bytes(total_bases, n_reads, strands)
+        return Occurrences._map_workspace_bytes(total_bases, n_reads, strands)
 
 
-class ColorSetsBuilder:
+class ColorSetsBuilder(_Owner):
     """Owns an sbwtgpu_colorsets_builder handle: colour sets made one colour at a time, without the wide matrix
     (include/sbwtgpu.h, "the builder").  The sequences of one colour come in consecutive add calls; finish() gives the
     ColorSets that ColorSets.from_colors gives for a WideColors coloured by the same adds, and consumes the builder.  Not
     thread-safe.  The index is kept referenced."""
+
+    _destroy = "sbwtgpu_colorsets_builder_destroy"
 
     def __init__(self, handle, index: Index, n_colors: int):
         self._h = handle
@@ -1977,27 +1834,6 @@ class ColorSetsBuilder:
         h = C.c_void_p()
         _check(lib().sbwtgpu_colorsets_builder_create(index.handle, n_colors, C.byref(h)))
         return cls(h, index, n_colors)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self) -> None:
-        if self._h:
-            lib().sbwtgpu_colorsets_builder_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
 
     def add_sequences(self, color: int, bases, read_off, both_strands: bool = False):
         """sbwtgpu_colorsets_builder_add_batch: marks every k-mer of the sequences that the index holds for `color`, which

@@ -30,11 +30,6 @@
 #define OM_T SBWT_OM_TABLE
 #define OM_NP SBWT_OM_PENDING
 
-static inline unsigned occ_grid(i64 n, i64 most) {
-    const i64 g = (n + 255) / 256;
-    return (unsigned)(g < 1 ? 1 : g > most ? most : g);
-}
-
 // ---------------------------------------------------------------------------------------------
 // results -> log
 // ---------------------------------------------------------------------------------------------
@@ -43,60 +38,27 @@ __global__ void __launch_bounds__(256) k_occ_add(const int *__restrict__ res, co
                                                  unsigned *__restrict__ log_col, u64 *__restrict__ log_key, u64 log_cap,
                                                  SbwtOccCounters *ctr, u64 *n_hit_windows) {
     const int lane = threadIdx.x & 63;
-    const i64 W = out_off[n_reads];
-    const i64 total = res2 ? 2 * W : W;                    // the mirrored batch's results follow the forward ones
-    if (blockIdx.x == 0 && threadIdx.x == 0 && total > 0) atomicAdd(&ctr->n_windows, (u64)total);
-    u64 hits = 0, hit_windows = 0;                         // of this lane's wave (the same in every lane)
-    // (whole waves go round together: the bound is rounded up to the wave, and a lane past the end sits the ballots out)
-    for (i64 i0 = (i64)blockIdx.x * 256 + (threadIdx.x & ~63u); i0 < total; i0 += (i64)gridDim.x * 256) {
-        const i64 i = i0 + lane;
-        i64 v = -1, p = 0;
-        u64 t = 0;
-        bool either = false;
-        if (i < W) {
-            v = res[i];
-            p = i;
-            either = v >= 0 || (res2 && res2[W - 1 - i] >= 0);
-        } else if (i < total) {
-            v = res2[i - W];
-            p = W - 1 - (i - W);                           // the window of the batch as given that this result belongs to
-            t = 1;
-        }
-        const bool hit = v >= 0 && v < n_nodes;
-        u64 key = 0;
-        if (hit) {
-            i64 lo = 0, hi = n_reads;                      // out_off[lo] <= p < out_off[hi]
-            while (hi - lo > 1) {
-                const i64 mid = (lo + hi) >> 1;
-                if (out_off[mid] <= p) lo = mid;
-                else hi = mid;
-            }
-            key = ((u64)(first_seq + lo) << 32) | ((u64)(p - out_off[lo]) << 1) | t;
-        }
+    pm_for_each_result(res, res2, out_off, n_reads, first_seq, n_nodes, &ctr->n_windows, &ctr->n_hits, n_hit_windows,
+                       [&](bool hit, i64 v, u64 key) {
         const u64 hm = __ballot(hit);
-        if (hm) {                                          // one atomic per wave, then every hit its own slot
-            u64 base = 0;
-            if (lane == 0) base = atomicAdd(&ctr->log_len, (u64)__popcll(hm));
-            base = pm_readlane64(base, 0);
-            if (hit) {
-                const u64 e = base + (u64)__popcll(hm & ((1ull << lane) - 1ull));
-                if (e < log_cap) { log_col[e] = (unsigned)v; log_key[e] = key; }
-                else ctr->bad_kind = 1;                    // (never: the host makes room for every result before the launch)
-            }
+        if (!hm) return;                                   // one atomic per wave, then every hit its own slot
+        u64 base = 0;
+        if (lane == 0) base = atomicAdd(&ctr->log_len, (u64)__popcll(hm));
+        base = pm_readlane64(base, 0);
+        if (hit) {
+            const u64 e = base + (u64)__popcll(hm & ((1ull << lane) - 1ull));
+            if (e < log_cap) { log_col[e] = (unsigned)v; log_key[e] = key; }
+            else ctr->bad_kind = 1;                        // (never: the host makes room for every result before the launch)
         }
-        hits += (u64)__popcll(hm);
-        hit_windows += (u64)__popcll(__ballot(either));
-    }
-    if (lane == 0 && hits) atomicAdd(&ctr->n_hits, hits);
-    if (lane == 0 && hit_windows) atomicAdd(n_hit_windows, hit_windows);
+    });
 }
 
 void sbwt_launch_occ_add(const int *d_res, const int *d_res2, const long long *d_out_off, long long n_reads, long long max_results,
                          long long first_seq, long long n_nodes, unsigned *d_log_col, unsigned long long *d_log_key,
                          unsigned long long log_cap, SbwtOccCounters *ctr, unsigned long long *d_n_hit_windows, hipStream_t stream) {
-    const i64 total = d_res2 ? 2 * max_results : max_results;
-    hipLaunchKernelGGL(k_occ_add, dim3(occ_grid(total, 4096)), dim3(256), 0, stream, d_res, d_res2, d_out_off, (i64)n_reads,
-                       (i64)first_seq, (i64)n_nodes, d_log_col, (u64 *)d_log_key, (u64)log_cap, ctr, (u64 *)d_n_hit_windows);
+    hipLaunchKernelGGL(k_occ_add, dim3(pm_grid(d_res2 ? 2 * max_results : max_results, 256, 4096)), dim3(256), 0, stream, d_res, d_res2,
+                       d_out_off, (i64)n_reads, (i64)first_seq, (i64)n_nodes, d_log_col, (u64 *)d_log_key, (u64)log_cap, ctr,
+                       (u64 *)d_n_hit_windows);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -148,7 +110,7 @@ void sbwt_launch_occ_flag(const unsigned *d_col, const unsigned long long *d_key
     (void)hipMemsetAsync(d_off, 0, (size_t)(n_nodes + 1) * 8, stream);
     (void)hipMemsetAsync(&ctr->n_unique, 0, 8, stream);
     if (n > 0)
-        hipLaunchKernelGGL(k_occ_flag, dim3(occ_grid(n, 4096)), dim3(256), 0, stream, d_col, (const u64 *)d_key, (i64)n, d_flag,
+        hipLaunchKernelGGL(k_occ_flag, dim3(pm_grid(n, 256, 4096)), dim3(256), 0, stream, d_col, (const u64 *)d_key, (i64)n, d_flag,
                            (u64 *)d_off, ctr);
 }
 
@@ -194,7 +156,7 @@ __global__ void __launch_bounds__(256) k_occ_stats(const u64 *__restrict__ off, 
 
 void sbwt_launch_occ_stats(const unsigned long long *d_off, long long n_nodes, SbwtOccCounters *ctr, hipStream_t stream) {
     (void)hipMemsetAsync(&ctr->n_positioned, 0, 16, stream);       // (n_positioned and max_count are neighbours)
-    hipLaunchKernelGGL(k_occ_stats, dim3(occ_grid(n_nodes, 1024)), dim3(256), 0, stream, (const u64 *)d_off, (i64)n_nodes, ctr);
+    hipLaunchKernelGGL(k_occ_stats, dim3(pm_grid(n_nodes, 256, 1024)), dim3(256), 0, stream, (const u64 *)d_off, (i64)n_nodes, ctr);
 }
 
 __device__ __forceinline__ void occ_bad(SbwtOccCounters *ctr, i64 column, u64 kind) {
@@ -225,12 +187,12 @@ __global__ void __launch_bounds__(256) k_occ_check_keys(const u64 *__restrict__ 
 }
 void sbwt_launch_occ_check_off(const unsigned long long *d_off, long long n_nodes, unsigned long long n_occ, SbwtOccCounters *ctr,
                                hipStream_t stream) {
-    hipLaunchKernelGGL(k_occ_check_off, dim3(occ_grid(n_nodes + 1, 1024)), dim3(256), 0, stream, (const u64 *)d_off, (i64)n_nodes,
+    hipLaunchKernelGGL(k_occ_check_off, dim3(pm_grid(n_nodes + 1, 256, 1024)), dim3(256), 0, stream, (const u64 *)d_off, (i64)n_nodes,
                        (u64)n_occ, ctr);
 }
 void sbwt_launch_occ_check_keys(const unsigned long long *d_off, const unsigned long long *d_occ, long long n_nodes, SbwtOccCounters *ctr,
                                 hipStream_t stream) {
-    hipLaunchKernelGGL(k_occ_check_keys, dim3(occ_grid(n_nodes, 1024)), dim3(256), 0, stream, (const u64 *)d_off, (const u64 *)d_occ,
+    hipLaunchKernelGGL(k_occ_check_keys, dim3(pm_grid(n_nodes, 256, 1024)), dim3(256), 0, stream, (const u64 *)d_off, (const u64 *)d_occ,
                        (i64)n_nodes, ctr);
 }
 
@@ -243,7 +205,7 @@ __global__ void __launch_bounds__(256) k_occ_first(const u64 *__restrict__ off, 
 }
 void sbwt_launch_occ_first(const unsigned long long *d_off, const unsigned long long *d_occ, long long n_nodes, unsigned long long *d_first,
                            hipStream_t stream) {
-    hipLaunchKernelGGL(k_occ_first, dim3(occ_grid(n_nodes, 1024)), dim3(256), 0, stream, (const u64 *)d_off, (const u64 *)d_occ,
+    hipLaunchKernelGGL(k_occ_first, dim3(pm_grid(n_nodes, 256, 1024)), dim3(256), 0, stream, (const u64 *)d_off, (const u64 *)d_occ,
                        (i64)n_nodes, (u64 *)d_first);
 }
 
@@ -264,37 +226,6 @@ __device__ __forceinline__ void om_window(const int *__restrict__ res, const int
     base = off[v];
     const u64 cc = off[v + 1] - base;
     c = cc > max_occ ? 0 : (int)cc;
-}
-
-// The iteration's distinct keys of one trip, peeled (readlane, ballot, popcount), against a pending run: a key that continues
-// the run adds to it, another one sends the run to the table and starts the next.
-__device__ __forceinline__ void om_peel_pending(u64 mine, u64 &pend_key, int &pend_n, u64 *keys, int *cnt, int &n_ent, int cap, bool &fits,
-                                                int lane) {
-    u64 live = __ballot(mine != PM_NOKEY);
-    while (live) {
-        const int src = __ffsll((i64)live) - 1;
-        const u64 k0 = pm_readlane64(mine, src);
-        const u64 eq = __ballot(mine == k0);
-        live &= ~eq;
-        if (pend_n != 0 && k0 == pend_key) {
-            pend_n += __popcll(eq);
-        } else {
-            if (pend_n != 0 && fits) fits = pm_put(keys, cnt, n_ent, cap, pend_key, pend_n, lane);
-            pend_key = k0;
-            pend_n = __popcll(eq);
-        }
-    }
-}
-// the same without a run: every distinct key goes to the table
-__device__ __forceinline__ void om_peel_put(u64 mine, u64 *keys, int *cnt, int &n_ent, int cap, bool &fits, int lane) {
-    u64 live = __ballot(mine != PM_NOKEY);
-    while (live && fits) {
-        const int src = __ffsll((i64)live) - 1;
-        const u64 k0 = pm_readlane64(mine, src);
-        const u64 eq = __ballot(mine == k0);
-        live &= ~eq;
-        fits = pm_put(keys, cnt, n_ent, cap, k0, __popcll(eq), lane);
-    }
 }
 
 template <bool TWO>
@@ -331,10 +262,10 @@ __global__ void __launch_bounds__(256) k_occ_map(const int *__restrict__ res, co
                     if (j < OM_NP) {
                         u64 pk = pm_readlane64(pend_key, j);
                         int pn = __builtin_amdgcn_readlane(pend_n, j);
-                        om_peel_pending(mine, pk, pn, keys, cnt, n_ent, cap, fits, lane);
+                        pm_peel_pending(mine, pk, pn, keys, cnt, n_ent, cap, fits, lane);
                         if (lane == j) { pend_key = pk; pend_n = pn; }
                     } else {
-                        om_peel_put(mine, keys, cnt, n_ent, cap, fits, lane);
+                        pm_peel_put(mine, keys, cnt, n_ent, cap, fits, lane);
                     }
                 }
             }
@@ -344,14 +275,7 @@ __global__ void __launch_bounds__(256) k_occ_map(const int *__restrict__ res, co
             const int pn = __builtin_amdgcn_readlane(pend_n, j);
             if (pn != 0) fits = pm_put(keys, cnt, n_ent, cap, pk, pn, lane);
         }
-        if (!fits) {                                      // the second kernel writes this read's record
-            if (lane == 0) slow[atomicAdd(&hdr->n_slow, 1u)] = (unsigned)r;
-            continue;
-        }
-        PmBest b = {PM_NOKEY, 0, 0};
-        for (int j = lane; j < n_ent; j += 64) pm_offer(b, keys[j], cnt[j]);
-        __builtin_amdgcn_wave_barrier();                  // (the next read's first entry comes after these loads)
-        pm_write(b, found, anchored, out + r, lane);
+        pm_end_read(fits, keys, cnt, n_ent, found, anchored, r, out, hdr, slow, lane);
     }
 }
 
@@ -424,7 +348,7 @@ __global__ void __launch_bounds__(256) k_occ_map_slow(const int *__restrict__ re
                 int n_ent = 0;
                 om_enumerate<TWO>(res, res2, W, at, m, off, occ, n_nodes, max_occ, lane, found, anchored, [&](u64 mine) {
                     if (mine != PM_NOKEY && om_slice(mine, P) != sl) mine = PM_NOKEY;
-                    om_peel_put(mine, keys, cnt, n_ent, cap, fits, lane);
+                    pm_peel_put(mine, keys, cnt, n_ent, cap, fits, lane);
                     return fits;
                 });
                 if (fits)
@@ -492,23 +416,15 @@ void sbwt_launch_occ_map(const int *d_res, const int *d_res2, const long long *d
     if (cap < 1 || cap > OM_T) cap = OM_T;
     (void)hipMemsetAsync(hdr, 0, sizeof(SbwtPosMapHeader), stream);
     // a block's four waves take four reads per round
-    const i64 gb = (n_reads + 3) / 4;
-    const dim3 grid((unsigned)(gb < 1 ? 1 : gb > (1 << 20) ? (1 << 20) : gb)), slow_grid((unsigned)(gb < 1 ? 1 : gb > 1024 ? 1024 : gb)),
-        block(256);
+    const dim3 grid(pm_grid(n_reads, 4, 1 << 20)), slow_grid(pm_grid(n_reads, 4, 1024)), block(256);
     const u64 *off = (const u64 *)d_off, *occ = (const u64 *)d_occ;
-    if (d_res2) {
-        hipLaunchKernelGGL((k_occ_map<true>), grid, block, 0, stream, d_res, d_res2, d_out_off, (i64)n_reads, off, occ, (i64)n_nodes,
+    pm_strands(d_res2 != nullptr, [&](auto two) {
+        constexpr bool TWO = decltype(two)::value;
+        hipLaunchKernelGGL((k_occ_map<TWO>), grid, block, 0, stream, d_res, d_res2, d_out_off, (i64)n_reads, off, occ, (i64)n_nodes,
                            (u64)max_occ, cap, d_out, hdr, d_slow);
-        hipLaunchKernelGGL((k_occ_map_slow<true>), slow_grid, block, 0, stream, d_res, d_res2, d_out_off, (i64)n_reads, off, occ,
+        hipLaunchKernelGGL((k_occ_map_slow<TWO>), slow_grid, block, 0, stream, d_res, d_res2, d_out_off, (i64)n_reads, off, occ,
                            (i64)n_nodes, (u64)max_occ, cap, d_out, hdr, d_slow);
-        hipLaunchKernelGGL((k_occ_map_last<true>), slow_grid, block, 0, stream, d_res, d_res2, d_out_off, (i64)n_reads, off, occ,
+        hipLaunchKernelGGL((k_occ_map_last<TWO>), slow_grid, block, 0, stream, d_res, d_res2, d_out_off, (i64)n_reads, off, occ,
                            (i64)n_nodes, (u64)max_occ, d_out, hdr, d_slow);
-    } else {
-        hipLaunchKernelGGL((k_occ_map<false>), grid, block, 0, stream, d_res, d_res2, d_out_off, (i64)n_reads, off, occ, (i64)n_nodes,
-                           (u64)max_occ, cap, d_out, hdr, d_slow);
-        hipLaunchKernelGGL((k_occ_map_slow<false>), slow_grid, block, 0, stream, d_res, d_res2, d_out_off, (i64)n_reads, off, occ,
-                           (i64)n_nodes, (u64)max_occ, cap, d_out, hdr, d_slow);
-        hipLaunchKernelGGL((k_occ_map_last<false>), slow_grid, block, 0, stream, d_res, d_res2, d_out_off, (i64)n_reads, off, occ,
-                           (i64)n_nodes, (u64)max_occ, d_out, hdr, d_slow);
-    }
+    });
 }

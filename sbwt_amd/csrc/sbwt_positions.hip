@@ -26,51 +26,15 @@
 __global__ void __launch_bounds__(256) k_pos_add(const int *__restrict__ res, const int *__restrict__ res2,
                                                  const i64 *__restrict__ out_off, i64 n_reads, i64 first_seq, i64 n_nodes,
                                                  u64 *first, SbwtPosCounters *ctr, u64 *n_hit_windows) {
-    const int lane = threadIdx.x & 63;
-    const i64 W = out_off[n_reads];
-    const i64 total = res2 ? 2 * W : W;                    // the mirrored batch's results follow the forward ones
-    if (blockIdx.x == 0 && threadIdx.x == 0 && total > 0) atomicAdd(&ctr->n_windows, (u64)total);
-    u64 hits = 0, hit_windows = 0;                         // of this lane's wave (the same in every lane)
-    // (whole waves go round together: the bound is rounded up to the wave, and a lane past the end sits the ballots out)
-    for (i64 i0 = (i64)blockIdx.x * 256 + (threadIdx.x & ~63u); i0 < total; i0 += (i64)gridDim.x * 256) {
-        const i64 i = i0 + lane;
-        i64 v = -1, p = 0;
-        u64 t = 0;
-        bool either = false;
-        if (i < W) {
-            v = res[i];
-            p = i;
-            either = v >= 0 || (res2 && res2[W - 1 - i] >= 0);
-        } else if (i < total) {
-            v = res2[i - W];
-            p = W - 1 - (i - W);                           // the window of the batch as given that this result belongs to
-            t = 1;
-        }
-        const bool hit = v >= 0 && v < n_nodes;
-        if (hit) {
-            i64 lo = 0, hi = n_reads;                      // out_off[lo] <= p < out_off[hi]
-            while (hi - lo > 1) {
-                const i64 mid = (lo + hi) >> 1;
-                if (out_off[mid] <= p) lo = mid;
-                else hi = mid;
-            }
-            const u64 key = ((u64)(first_seq + lo) << 32) | ((u64)(p - out_off[lo]) << 1) | t;
-            if (first[v] > key) atomicMin(first + v, key);
-        }
-        hits += (u64)__popcll(__ballot(hit));
-        hit_windows += (u64)__popcll(__ballot(either));
-    }
-    if (lane == 0 && hits) atomicAdd(&ctr->n_hits, hits);
-    if (lane == 0 && hit_windows) atomicAdd(n_hit_windows, hit_windows);
+    pm_for_each_result(res, res2, out_off, n_reads, first_seq, n_nodes, &ctr->n_windows, &ctr->n_hits, n_hit_windows,
+                       [&](bool hit, i64 v, u64 key) { if (hit && first[v] > key) atomicMin(first + v, key); });
 }
 
 void sbwt_launch_pos_add(const int *d_res, const int *d_res2, const long long *d_out_off, long long n_reads, long long max_results,
                          long long first_seq, long long n_nodes, unsigned long long *d_first, SbwtPosCounters *ctr,
                          unsigned long long *d_n_hit_windows, hipStream_t stream) {
-    const i64 total = d_res2 ? 2 * max_results : max_results;
-    const i64 gb = (total + 255) / 256;
-    hipLaunchKernelGGL(k_pos_add, dim3((unsigned)(gb < 1 ? 1 : gb > 4096 ? 4096 : gb)), dim3(256), 0, stream, d_res, d_res2, d_out_off,
-                       (i64)n_reads, (i64)first_seq, (i64)n_nodes, (u64 *)d_first, ctr, (u64 *)d_n_hit_windows);
+    hipLaunchKernelGGL(k_pos_add, dim3(pm_grid(d_res2 ? 2 * max_results : max_results, 256, 4096)), dim3(256), 0, stream, d_res, d_res2,
+                       d_out_off, (i64)n_reads, (i64)first_seq, (i64)n_nodes, (u64 *)d_first, ctr, (u64 *)d_n_hit_windows);
 }
 
 __global__ void __launch_bounds__(256) k_pos_check(const u64 *__restrict__ first, i64 n, SbwtPosCounters *ctr) {
@@ -83,9 +47,7 @@ __global__ void __launch_bounds__(256) k_pos_check(const u64 *__restrict__ first
 }
 
 void sbwt_launch_pos_check(const unsigned long long *d_first, long long n_nodes, SbwtPosCounters *ctr, hipStream_t stream) {
-    const i64 g = (n_nodes + 255) / 256;
-    hipLaunchKernelGGL(k_pos_check, dim3((unsigned)(g < 1 ? 1 : g > 1024 ? 1024 : g)), dim3(256), 0, stream, (const u64 *)d_first,
-                       (i64)n_nodes, ctr);
+    hipLaunchKernelGGL(k_pos_check, dim3(pm_grid(n_nodes, 256, 1024)), dim3(256), 0, stream, (const u64 *)d_first, (i64)n_nodes, ctr);
 }
 
 // *out += the entries with a position (the caller zeroes it first)
@@ -99,9 +61,8 @@ __global__ void __launch_bounds__(256) k_pos_count(const u64 *__restrict__ first
 
 void sbwt_launch_pos_count(const unsigned long long *d_first, long long n_nodes, unsigned long long *d_out, hipStream_t stream) {
     (void)hipMemsetAsync(d_out, 0, 8, stream);
-    const i64 g = (n_nodes + 255) / 256;
-    hipLaunchKernelGGL(k_pos_count, dim3((unsigned)(g < 1 ? 1 : g > 1024 ? 1024 : g)), dim3(256), 0, stream, (const u64 *)d_first,
-                       (i64)n_nodes, (u64 *)d_out);
+    hipLaunchKernelGGL(k_pos_count, dim3(pm_grid(n_nodes, 256, 1024)), dim3(256), 0, stream, (const u64 *)d_first, (i64)n_nodes,
+                       (u64 *)d_out);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -148,33 +109,12 @@ __global__ void __launch_bounds__(256) k_pos_map(const int *__restrict__ res, co
             found += __popcll(__ballot(hit0)) + (TWO ? __popcll(__ballot(hit1)) : 0);
 #pragma unroll
             for (int s = 0; s < (TWO ? 2 : 1); s++) {
-                const u64 mine = key[s];
-                u64 live = __ballot(mine != PM_NOKEY);
-                anchored += __popcll(live);
-                while (live) {                            // one trip per distinct key of the iteration
-                    const int src = __ffsll((i64)live) - 1;
-                    const u64 k0 = pm_readlane64(mine, src);
-                    const u64 eq = __ballot(mine == k0);
-                    live &= ~eq;
-                    if (pend_n != 0 && k0 == pend_key) {
-                        pend_n += __popcll(eq);
-                    } else {
-                        if (pend_n != 0 && fits) fits = pm_put(keys, cnt, n_ent, cap, pend_key, pend_n, lane);
-                        pend_key = k0;
-                        pend_n = __popcll(eq);
-                    }
-                }
+                anchored += __popcll(__ballot(key[s] != PM_NOKEY));
+                pm_peel_pending(key[s], pend_key, pend_n, keys, cnt, n_ent, cap, fits, lane);
             }
         }
         if (pend_n != 0 && fits) fits = pm_put(keys, cnt, n_ent, cap, pend_key, pend_n, lane);
-        if (!fits) {                                      // the second kernel writes this read's record
-            if (lane == 0) slow[atomicAdd(&hdr->n_slow, 1u)] = (unsigned)r;
-            continue;
-        }
-        PmBest b = {PM_NOKEY, 0, 0};
-        for (int j = lane; j < n_ent; j += 64) pm_offer(b, keys[j], cnt[j]);
-        __builtin_amdgcn_wave_barrier();                  // (the next read's first entry comes after these loads)
-        pm_write(b, found, anchored, out + r, lane);
+        pm_end_read(fits, keys, cnt, n_ent, found, anchored, r, out, hdr, slow, lane);
     }
 }
 
@@ -232,18 +172,12 @@ void sbwt_launch_pos_map(const int *d_res, const int *d_res2, const long long *d
     if (cap < 1 || cap > PM_T) cap = PM_T;
     (void)hipMemsetAsync(hdr, 0, sizeof(SbwtPosMapHeader), stream);
     // a block's four waves take four reads per round
-    const i64 gb = (n_reads + 3) / 4;
-    const dim3 grid((unsigned)(gb < 1 ? 1 : gb > (1 << 20) ? (1 << 20) : gb)), slow_grid((unsigned)(gb < 1 ? 1 : gb > 1024 ? 1024 : gb)),
-        block(256);
-    if (d_res2) {
-        hipLaunchKernelGGL((k_pos_map<true>), grid, block, 0, stream, d_res, d_res2, d_out_off, (i64)n_reads, (const u64 *)d_first,
+    const dim3 grid(pm_grid(n_reads, 4, 1 << 20)), slow_grid(pm_grid(n_reads, 4, 1024)), block(256);
+    pm_strands(d_res2 != nullptr, [&](auto two) {
+        constexpr bool TWO = decltype(two)::value;
+        hipLaunchKernelGGL((k_pos_map<TWO>), grid, block, 0, stream, d_res, d_res2, d_out_off, (i64)n_reads, (const u64 *)d_first,
                            (i64)n_nodes, cap, d_out, hdr, d_slow);
-        hipLaunchKernelGGL((k_pos_map_slow<true>), slow_grid, block, 0, stream, d_res, d_res2, d_out_off, (i64)n_reads,
+        hipLaunchKernelGGL((k_pos_map_slow<TWO>), slow_grid, block, 0, stream, d_res, d_res2, d_out_off, (i64)n_reads,
                            (const u64 *)d_first, (i64)n_nodes, d_out, hdr, d_slow);
-    } else {
-        hipLaunchKernelGGL((k_pos_map<false>), grid, block, 0, stream, d_res, d_res2, d_out_off, (i64)n_reads, (const u64 *)d_first,
-                           (i64)n_nodes, cap, d_out, hdr, d_slow);
-        hipLaunchKernelGGL((k_pos_map_slow<false>), slow_grid, block, 0, stream, d_res, d_res2, d_out_off, (i64)n_reads,
-                           (const u64 *)d_first, (i64)n_nodes, d_out, hdr, d_slow);
-    }
+    });
 }

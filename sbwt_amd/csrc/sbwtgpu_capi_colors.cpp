@@ -55,12 +55,6 @@ static int colors_check(const sbwtgpu_colors *c) {
                     (long long)c->n_nodes, (long long)c->k, (long long)c->idx->h.n_nodes, (long long)c->idx->h.k);
     return colors_check_index(c->idx);
 }
-static int colors_check_batch(int64_t n_reads, int strands) {
-    if (strands != 1 && strands != 2) return fail(SBWTGPU_ERR_INVALID_ARG, "strands must be 1 (forward) or 2 (either strand), not %d", strands);
-    if (n_reads < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "negative n_reads");
-    if (n_reads >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_INVALID_ARG, "2^31 reads or more in one call: split the batch");
-    return SBWTGPU_OK;
-}
 static int colors_check_query(int threshold_ppm, int denominator) {
     if (threshold_ppm < 1 || threshold_ppm > 1000000)
         return fail(SBWTGPU_ERR_INVALID_ARG, "threshold_ppm must be in 1 .. 1000000, not %d", threshold_ppm);
@@ -266,7 +260,7 @@ int sbwtgpu_pseudoalign_dev(const sbwtgpu_colors *c, const char *d_bases, int64_
                             int64_t n_reads, int strands, int threshold_ppm, int denominator, sbwtgpu_pseudoalignment *d_out,
                             int32_t *d_counts_or_null, void *d_ws, int64_t ws_bytes, void *stream) {
     int rc = colors_check(c);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = check_strands_batch("", n_reads, strands);
     if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
     if (rc != SBWTGPU_OK) return rc;
     if (c->n_colors > 64)
@@ -284,7 +278,7 @@ int sbwtgpu_pseudoalign_wide_dev(const sbwtgpu_colors *c, const char *d_bases, i
                                  int64_t n_reads, int strands, int threshold_ppm, int denominator, sbwtgpu_read_found *d_out,
                                  uint64_t *d_colors, int32_t *d_counts_or_null, void *d_ws, int64_t ws_bytes, void *stream) {
     int rc = colors_check(c);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = check_strands_batch("", n_reads, strands);
     if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
     if (rc != SBWTGPU_OK) return rc;
     if (n_reads > 0 && (!d_out || !d_colors)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
@@ -376,7 +370,7 @@ static int colors_host_batch(const sbwtgpu_colors *c, const char *bases, const i
 int sbwtgpu_colors_add_batch(sbwtgpu_colors *c, int color, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
                              int64_t *n_windows, int64_t *n_hit_windows) {
     int rc = colors_check(c);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = check_strands_batch("", n_reads, strands);
     if (rc != SBWTGPU_OK) return rc;
     if (color < 0 || color >= c->n_colors)
         return fail(SBWTGPU_ERR_INVALID_ARG, "color %d is out of range: the colours object has %d colours", color, c->n_colors);
@@ -386,7 +380,7 @@ int sbwtgpu_colors_add_batch(sbwtgpu_colors *c, int color, const char *bases, co
 int sbwtgpu_pseudoalign_batch(const sbwtgpu_colors *c, const char *bases, const int64_t *read_off, int64_t n_reads, int strands,
                               int threshold_ppm, int denominator, sbwtgpu_pseudoalignment *out, int32_t *counts_or_null) {
     int rc = colors_check(c);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = check_strands_batch("", n_reads, strands);
     if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
     if (rc != SBWTGPU_OK) return rc;
     if (c->n_colors > 64)
@@ -401,7 +395,7 @@ int sbwtgpu_pseudoalign_wide_batch(const sbwtgpu_colors *c, const char *bases, c
                                    int threshold_ppm, int denominator, sbwtgpu_read_found *out, uint64_t *colors_out,
                                    int32_t *counts_or_null) {
     int rc = colors_check(c);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = check_strands_batch("", n_reads, strands);
     if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
     if (rc != SBWTGPU_OK) return rc;
     if (n_reads > 0 && (!out || !colors_out)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
@@ -604,7 +598,7 @@ int sbwtgpu_pseudoalign_sets_dev(const sbwtgpu_colorsets *s, const char *d_bases
                                  int64_t n_reads, int strands, int threshold_ppm, int denominator, sbwtgpu_read_found *d_out,
                                  uint64_t *d_colors, int32_t *d_counts_or_null, void *d_ws, int64_t ws_bytes, void *stream) {
     int rc = colorsets_check(s);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = check_strands_batch("", n_reads, strands);
     if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
     if (rc != SBWTGPU_OK) return rc;
     if (n_reads > 0 && (!d_out || !d_colors)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL device pointer");
@@ -621,7 +615,7 @@ int sbwtgpu_pseudoalign_sets_batch(const sbwtgpu_colorsets *s, const char *bases
                                    int threshold_ppm, int denominator, sbwtgpu_read_found *out, uint64_t *colors_out,
                                    int32_t *counts_or_null) {
     int rc = colorsets_check(s);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = check_strands_batch("", n_reads, strands);
     if (rc == SBWTGPU_OK) rc = colors_check_query(threshold_ppm, denominator);
     if (rc != SBWTGPU_OK) return rc;
     if (n_reads > 0 && (!out || !colors_out)) return fail(SBWTGPU_ERR_INVALID_ARG, "NULL argument");
@@ -700,7 +694,7 @@ void sbwtgpu_colorsets_builder_destroy(sbwtgpu_colorsets_builder *b) {
 int sbwtgpu_colorsets_builder_add_batch(sbwtgpu_colorsets_builder *b, int color, const char *bases, const int64_t *read_off,
                                         int64_t n_reads, int strands, int64_t *n_windows, int64_t *n_hit_windows) {
     int rc = builder_check(b);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = check_strands_batch("", n_reads, strands);
     if (rc != SBWTGPU_OK) return rc;
     if (color < 0 || color >= b->base.n_colors)
         return fail(SBWTGPU_ERR_INVALID_ARG, "color %d is out of range: the colour-set builder has %d colours", color, b->base.n_colors);
@@ -997,7 +991,7 @@ int64_t sbwtgpu_screen_workspace_bytes(int64_t total_bases, int64_t n_reads, int
 int sbwtgpu_screen_add_dev(sbwtgpu_screen *x, const char *d_bases, int64_t total_bases, const int64_t *d_read_off, int64_t n_reads,
                            int strands, void *d_ws, int64_t ws_bytes, void *stream) {
     int rc = screen_check(x);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = check_strands_batch("", n_reads, strands);
     if (rc != SBWTGPU_OK) return rc;
     const sbwtgpu_colorsets *s = x->s;
     return colors_dev_common(&s->base, d_bases, total_bases, d_read_off, n_reads, strands, d_ws, ws_bytes, stream,
@@ -1011,7 +1005,7 @@ int sbwtgpu_screen_add_dev(sbwtgpu_screen *x, const char *d_bases, int64_t total
 // search pipeline.  Bases and offsets go down; only each chunk's status word comes back.
 int sbwtgpu_screen_add_batch(sbwtgpu_screen *x, const char *bases, const int64_t *read_off, int64_t n_reads, int strands) {
     int rc = screen_check(x);
-    if (rc == SBWTGPU_OK) rc = colors_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = check_strands_batch("", n_reads, strands);
     if (rc != SBWTGPU_OK) return rc;
     if (n_reads == 0) return SBWTGPU_OK;
     if (!read_off) return fail(SBWTGPU_ERR_INVALID_ARG, "screen: NULL argument (read_off)");

@@ -956,12 +956,6 @@ static int genotype_check(const sbwtgpu_genotype *g) {
                     (long long)g->st.n_nodes, (long long)g->idx->h.n_nodes, (long long)g->u->n_nodes);
     return SBWTGPU_OK;
 }
-static int genotype_check_batch(int64_t n_reads, int strands) {
-    if (strands != 1 && strands != 2) return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: strands must be 1 (forward) or 2 (either strand), not %d", strands);
-    if (n_reads < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: negative n_reads");
-    if (n_reads >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: 2^31 reads or more in one call: split the batch");
-    return SBWTGPU_OK;
-}
 extern "C" {
 
 int sbwtgpu_genotype_create(const sbwtgpu_index *idx, const sbwtgpu_unitigs *u, const sbwtgpu_bubbles *b, sbwtgpu_genotype **out) {
@@ -1046,7 +1040,7 @@ int64_t sbwtgpu_genotype_workspace_bytes(int64_t total_bases, int64_t n_reads, i
 int sbwtgpu_genotype_add_dev(sbwtgpu_genotype *g, const char *d_bases, int64_t total_bases, const int64_t *d_read_off, int64_t n_reads,
                              int strands, void *d_ws, int64_t ws_bytes, void *stream) {
     int rc = genotype_check(g);
-    if (rc == SBWTGPU_OK) rc = genotype_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = check_strands_batch("genotype: ", n_reads, strands);
     if (rc != SBWTGPU_OK) return rc;
     StrandSearch q;
     STG_TRY(search_strands_dev(g->idx, d_bases, total_bases, d_read_off, n_reads, strands, d_ws, ws_bytes, stream, q));
@@ -1062,7 +1056,7 @@ int sbwtgpu_genotype_add_dev(sbwtgpu_genotype *g, const char *d_bases, int64_t t
 // search pipeline.  Bases and offsets go down; only each chunk's status word comes back.
 int sbwtgpu_genotype_add_batch(sbwtgpu_genotype *g, const char *bases, const int64_t *read_off, int64_t n_reads, int strands) {
     int rc = genotype_check(g);
-    if (rc == SBWTGPU_OK) rc = genotype_check_batch(n_reads, strands);
+    if (rc == SBWTGPU_OK) rc = check_strands_batch("genotype: ", n_reads, strands);
     if (rc != SBWTGPU_OK) return rc;
     if (n_reads == 0) return SBWTGPU_OK;
     if (!read_off) return fail(SBWTGPU_ERR_INVALID_ARG, "genotype: NULL argument (read_off)");

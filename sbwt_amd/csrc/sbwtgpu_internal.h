@@ -1,7 +1,7 @@
 // sbwtgpu_internal.h -- what the translation units of the C ABI share: sbwtgpu_capi.cpp (index image, search, rank, text),
 // sbwtgpu_capi_reads.cpp (matching statistics, set operations, read hits, unitigs and their graph, walks, bubbles) and
-// sbwtgpu_capi_colors.cpp (colours, colour sets, pseudoalignment, screen) and sbwtgpu_capi_positions.cpp (reference positions,
-// read mapping) and sbwtgpu_capi_occurrences.cpp (all occurrences per column, mapping over them).  Nothing here is part of the library's interface:
+// sbwtgpu_capi_colors.cpp (colours, colour sets, pseudoalignment, screen) and sbwtgpu_capi_placement.cpp (reference positions and
+// all occurrences per column, read mapping over either).  Nothing here is part of the library's interface:
 // every name has hidden visibility, and whatever holds state (the error text, the parked slots, the int32 switch of a search
 // call) is defined once, in sbwtgpu_capi.cpp.
 #pragma once
@@ -89,10 +89,8 @@ extern int g_rh_wave_min, g_rh_wide;                        // sbwtgpu_capi_read
 extern int64_t g_rh_chunk_bases, g_wk_chunk_bases, g_gt_chunk_bases;
 extern int64_t g_pa_chunk_bases, g_screen_chunk_bases;      // sbwtgpu_capi_colors.cpp
 extern int64_t g_gram_mfma_min_sets, g_gram_flush_sets;
-extern int64_t g_pos_chunk_bases;                           // sbwtgpu_capi_positions.cpp
-extern int g_pos_map_table;
-extern int64_t g_occ_chunk_bases;                           // sbwtgpu_capi_occurrences.cpp
-extern int g_occ_map_table;
+extern int64_t g_pos_chunk_bases, g_occ_chunk_bases;        // sbwtgpu_capi_placement.cpp
+extern int g_pos_map_table, g_occ_map_table;
 
 }  // namespace sbwt_capi
 
@@ -160,9 +158,6 @@ int build_columns(SbwtBuildState &S, int64_t k, int build_streaming_support, sbw
 int unitigs_create_common(const sbwtgpu_index *idx, const unsigned *d_ids, const unsigned long long *d_table, int words, int64_t n_sets,
                           int n_colors, unsigned graph, sbwtgpu_unitigs **out);
 int setop_check_index(const sbwtgpu_index *idx, const char *who);
-// sbwtgpu_capi_positions.cpp: a positions object with every entry "no position" and its table on the device, for a caller that
-// fills the table itself (sbwtgpu_occurrences_to_positions)
-int positions_alloc_cleared(const sbwtgpu_index *idx, sbwtgpu_positions **out, unsigned long long **d_first);
 // sbwtgpu_capi_colors.cpp
 int colorsets_check(const sbwtgpu_colorsets *s);
 // The searches of a batch and, for two strands, of its mirrored batch, int32 results, in a workspace of
@@ -184,6 +179,16 @@ inline int check_read_length(const int64_t *read_off, int64_t r) {
     const int64_t len = read_off[r + 1] - read_off[r];
     if (len < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "read_off is not non-decreasing at read %lld", (long long)r);
     if (len >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_READ_TOO_LONG, "read %lld has >= 2^31 bases", (long long)r);
+    return SBWTGPU_OK;
+}
+
+// What every call over reads on one or two strands asks of `strands` and `n_reads`.  who: what the layer's texts begin with
+// ("positions: ", "genotype: "; "" for the colour layer, whose texts carry no name)
+inline int check_strands_batch(const char *who, int64_t n_reads, int strands) {
+    if (strands != 1 && strands != 2)
+        return fail(SBWTGPU_ERR_INVALID_ARG, "%sstrands must be 1 (forward) or 2 (either strand), not %d", who, strands);
+    if (n_reads < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "%snegative n_reads", who);
+    if (n_reads >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_INVALID_ARG, "%s2^31 reads or more in one call: split the batch", who);
     return SBWTGPU_OK;
 }
 

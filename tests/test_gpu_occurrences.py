@@ -306,6 +306,34 @@ def test_references_without_a_shared_kmer_map_like_the_projection(gpu, reads):
     side.idx.close()
 
 
+def test_both_adds_walk_the_same_results(gpu):
+    """The frame that k_pos_add and k_occ_add share, on the smallest batch in which one wave holds forward and mirrored results
+    and the last wave is partial: k = 5, references of 69 and 5 bases, two strands -- 66 windows, 132 results; the second wave
+    holds forward results 64, 65 and mirrored results 0 .. 61, the third has four live lanes."""
+    k, strands = 5, 2
+    rng = random.Random(2801)
+    a = rand_seq(rng, 69, "ACG")
+    refs = [a, a[10:15]]                                    # (the one window of sequence 1 repeats a k-mer of sequence 0)
+    side = tp.Side(refs, k, True)
+    nums = numbered(refs, strands)
+    assert sum(len(s) - k + 1 for s in refs) == 66
+    want_first = pb.first_table(side.kmers, k, nums)
+    want_occ = ob.table(side.kmers, k, nums)
+    assert max(len(v) for v in want_occ.values()) >= 2      # k-mers repeat: the minimum and the runs of a column have work
+    assert {f & 1 for v in want_occ.values() for f in v} == {0, 1}      # and both halves of the results hit
+    with side.idx.positions() as pos, side.idx.occurrences_builder() as b:
+        added = pos.add(enc(refs), 0, strands)
+        assert added == b.add(enc(refs), 0, strands) == (66, tp.hit_windows(side.kmers, k, refs, strands))
+        with b.finish() as occ, occ.positions() as proj:
+            assert pos.info()["n_hits"] == occ.info()["n_hits"] == pb.scalars(side.kmers, k, nums)[1]
+            assert pos.info()["n_windows"] == occ.info()["n_windows"] == 132
+            assert pos.first().tolist() == pb.table_array(want_first, side.labels)
+            off, keys = ob.arrays(want_occ, side.labels)
+            assert occ.offsets().tolist() == off and occ.keys().tolist() == keys
+            assert proj.first().tobytes() == pos.first().tobytes()
+    side.idx.close()
+
+
 # ---- 4. the placement table's edge -----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("rc,strands", [(False, 1), (True, 2)])
 def test_table_edge_with_a_small_capacity(world, reads, rc, strands):
