@@ -132,6 +132,9 @@ int         sbwtgpu_device_count(int *count);
  *   "occurrences_map_table" the distinct placements per read that the occurrence map kernel keeps in LDS before the read goes to
  *                        the exact second kernel: 1 .. SBWTGPU_OCCURRENCES_MAP_TABLE, 0 (default) = that compiled capacity;
  *                        another value is refused.  No result depends on it (tests reach the second kernel with it)
+ *   "verify_fast_bases"  the longest read, in bases, that the first verify kernel takes (its rows in registers) before the read
+ *                        goes to the second kernel (rows in LDS): 1 .. 256, 0 (default) = 256; another value is refused.  No
+ *                        result depends on it (tests reach the second kernel with short reads)
  *   "trans_ext", "trans_wide"   accepted and ignored (round-2 table formats)
  * Read when an index is CREATED (derived acceleration structures inside the device image; environment
  * variables of the same meaning: SBWTGPU_SPARSE_PRECALC, SBWTGPU_PROBE_FILTER, SBWTGPU_PATH_ORDER):
@@ -1428,6 +1431,97 @@ int     sbwtgpu_occurrences_map_dev(const sbwtgpu_occurrences *o, const char *d_
                                     int64_t workspace_bytes, void *stream);
 int     sbwtgpu_occurrences_map_batch(const sbwtgpu_occurrences *o, const char *bases, const int64_t *read_off, int64_t n_reads,
                                       int strands, int max_occ, sbwtgpu_read_map *out);
+
+/* ---- reference sequences and verification ----
+ * The map calls above place a read by counting k-mer votes; their record is a hypothesis about a diagonal.  These calls look
+ * at the bases: a packed copy of the reference sequences on the device, and one call that takes reads and their map records and
+ * returns, per read, the mismatches on the voted diagonal and the best edit distance in a window around it.  They need no
+ * index: they take reads, records and the reference object.  Everything is exact integers.
+ * The reference object
+ *   sbwtgpu_refseqs lives on one device and holds sequences numbered 0, 1, ... densely.
+ *   sbwtgpu_refseqs_add_batch(r, first_seq, bases, read_off, n) appends n sequences.
+ *   - first_seq must equal the number of sequences held so far.  Otherwise the call is refused and the message names both
+ *     numbers.
+ *   - The numbering rule is the one --positions-out and --occurrences-out use, so a record's seq indexes this object.
+ *   - A base is valid if it is one of upper-case A C G T.  Every other byte (lower case, N, NUL) is stored as "invalid" and
+ *     matches nothing, not even itself.
+ *   Layout:
+ *   - 2 bits per base, 32 bases per uint64.
+ *   - One validity bit per base, 64 per uint64.
+ *   - Every sequence starts at a multiple of 64 bases in both arrays, so no two sequences share a word.
+ *   - Padding bits, and the 2-bit fields of invalid bases, are zero.
+ *   - That is 0.375 bytes per base.  The arrays grow by doubling, as the occurrence builder's log does.
+ *   Concurrency:
+ *   - Adds are serialised on the object's mutex.
+ *   - The verify calls only read the object and MUST NOT RUN CONCURRENTLY WITH AN ADD (an add may move the arrays; it waits
+ *     for the device before it frees the old ones).  Verify calls from several host threads on one object are safe.
+ * Oriented read
+ *   For a record with strand = o, the oriented read is r = read for o = 0 and r = rc(read) for o = 1.  The complement rule is
+ *   that of the read-hit profiles, and an invalid byte stays invalid.  L is the read's length and T is sequence seq of length n.
+ *   Reference coordinate p matches r[j] iff 0 <= p < n, T[p] and r[j] are both valid, and they are equal.
+ * The result record
+ *   sbwtgpu_read_verify is 16 bytes: int64 ref_end; int32 mismatches; int32 edit.
+ *   - mismatches is the number of j in [0, L) for which start + j does not match r[j].  An overhang beyond either end of the
+ *     sequence counts base by base.
+ *   - edit, with band B = band (0 ... SBWTGPU_VERIFY_MAX_BAND = 256), is defined on the window of reference coordinates
+ *     [start - B, start + L + B).
+ *     - edit is the smallest Levenshtein distance between r and any substring of the window.  The empty substring is included.
+ *     - Substitution, insertion and deletion cost 1 each.
+ *     - A pair is equal only if it matches as defined above.
+ *     - This is the last row of Sellers' table: D[0][t] = 0 for t = 0 ... L + 2B, D[i][0] = i, and edit = min_t D[L][t].
+ *   - ref_end is the smallest exclusive end coordinate start - B + t at which that minimum is attained.
+ *   - The path is not band-limited.  The band only sizes the window.
+ * Special cases
+ *   - The unverified record is {0, -1, -1}.  It is returned for a record with seq < 0, seq >= n_seqs, strand outside {0, 1}, or
+ *     |start| >= 2^40.
+ *   - A read longer than SBWTGPU_VERIFY_MAX_READ = 1024 bases gets its exact mismatches, with edit = -1 and ref_end = 0.  The
+ *     window table is quadratic, and such reads are to be cut into pieces, as the map calls' text above already says.
+ *   - L = 0 gives {start - B, 0, 0}.
+ * Properties that follow from the definitions
+ *   - edit <= mismatches for every B.
+ *   - edit is non-increasing in B.
+ *   - edit = 0 iff r occurs in the window.
+ *   - (rc(read), 1 - strand) gives the same record as (read, strand).
+ *   - The result does not depend on what the neighbouring sequences in the packed arrays hold.
+ * Not built: the begin of the best alignment (a reverse pass), CIGAR strings, the runner-up's verification (the map record does
+ * not carry its placement), a reference file format (the CLI re-reads the sequence files).
+ * sbwtgpu_refseqs_create makes an empty object on `device` (SBWTGPU_ERR_NO_DEVICE without one).  sbwtgpu_refseqs_add_batch
+ * takes host buffers (sequence i is bases[read_off[i] .. read_off[i + 1])), stages the batch on the device in one piece and
+ * packs it with one kernel, one lane per 2-bit word; it returns when the sequences are in place.
+ * sbwtgpu_refseqs_info: any output may be NULL; n_invalid counts the bases that are not upper-case ACGT; device_bytes is what
+ * the object holds on the device.  sbwtgpu_refseqs_lengths_copy copies the n_seqs lengths.  sbwtgpu_refseqs_get unpacks bases
+ * pos .. pos + len of sequence seq to ASCII (no NUL), N for every invalid base.
+ * sbwtgpu_refseqs_verify_dev takes device pointers (d_bases: total_bases bytes; d_read_off: n_reads + 1 offsets that begin at
+ * 0; d_map: n_reads map records, of which it reads only seq, strand and start; d_out: n_reads records).  It is asynchronous on
+ * `stream`, never synchronises and never allocates.  Its workspace, of sbwtgpu_refseqs_verify_workspace_bytes (non-decreasing
+ * in both arguments, a multiple of 256), is 16-byte aligned: a 256-byte header and 4 bytes per read.  Two kernels run.  The
+ * first gives every read ONE LANE: Myers' bit-vector form of the table is sequential over the window's columns and parallel
+ * over 64 rows per machine word, so 64 reads per wave keep every lane busy; the rows of a read of up to 256 bases live in
+ * registers, and a wave runs the code of its longest read.  Longer reads go onto a list in the workspace.  The second kernel,
+ * always launched, runs over that list with the rows in LDS (reads of up to 1024 bases) or counts the mismatches of a still
+ * longer read in a linear pass.  "verify_fast_bases" (sbwtgpu_set_tuning: 1 .. 256, 0 = 256) lowers the first kernel's limit; no
+ * result depends on it (tests reach the second kernel with short reads).  A record whose offsets are not those of a batch
+ * (negative length, a read outside the base buffer) is answered with the unverified record.
+ * sbwtgpu_refseqs_verify_batch is the same call on host buffers: one staged range, not pipelined.
+ * Refusals (SBWTGPU_ERR_INVALID_ARG with a message that names the cause): NULL arguments; band outside 0 ... 256; n_reads < 0
+ * or >= 2^31; first_seq not equal to the next number; more than 2^30 sequences; a workspace that is too small; get outside its
+ * sequence.  A sequence of 2^31 bases or more gives SBWTGPU_ERR_READ_TOO_LONG.  SBWTGPU_ERR_OOM leaves the object as it was. */
+typedef struct { int64_t ref_end; int32_t mismatches; int32_t edit; } sbwtgpu_read_verify;
+typedef struct sbwtgpu_refseqs sbwtgpu_refseqs;
+#define SBWTGPU_VERIFY_MAX_BAND 256
+#define SBWTGPU_VERIFY_MAX_READ 1024
+int     sbwtgpu_refseqs_create(int device, sbwtgpu_refseqs **out);
+void    sbwtgpu_refseqs_destroy(sbwtgpu_refseqs *r);
+int     sbwtgpu_refseqs_add_batch(sbwtgpu_refseqs *r, int64_t first_seq, const char *bases, const int64_t *read_off, int64_t n_seqs);
+int     sbwtgpu_refseqs_info(const sbwtgpu_refseqs *r, int64_t *n_seqs, int64_t *total_bases, int64_t *n_invalid, int64_t *device_bytes);
+int     sbwtgpu_refseqs_lengths_copy(const sbwtgpu_refseqs *r, int64_t *len /* n_seqs */);
+int     sbwtgpu_refseqs_get(const sbwtgpu_refseqs *r, int64_t seq, int64_t pos, int64_t len, char *out);
+int64_t sbwtgpu_refseqs_verify_workspace_bytes(int64_t total_bases, int64_t n_reads);
+int     sbwtgpu_refseqs_verify_dev(const sbwtgpu_refseqs *r, const char *d_bases, int64_t total_bases, const int64_t *d_read_off,
+                                   int64_t n_reads, const sbwtgpu_read_map *d_map, int band, sbwtgpu_read_verify *d_out,
+                                   void *d_workspace, int64_t workspace_bytes, void *stream);
+int     sbwtgpu_refseqs_verify_batch(const sbwtgpu_refseqs *r, const char *bases, const int64_t *read_off, int64_t n_reads,
+                                     const sbwtgpu_read_map *map, int band, sbwtgpu_read_verify *out);
 
 #ifdef __cplusplus
 }

@@ -90,6 +90,9 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_occurrences_offsets_copy", "sbwtgpu_occurrences_keys_copy", "sbwtgpu_occurrences_offsets_dev",
     "sbwtgpu_occurrences_keys_dev", "sbwtgpu_occurrences_to_positions", "sbwtgpu_occurrences_map_workspace_bytes",
     "sbwtgpu_occurrences_map_dev", "sbwtgpu_occurrences_map_batch",
+    "sbwtgpu_refseqs_create", "sbwtgpu_refseqs_destroy", "sbwtgpu_refseqs_add_batch", "sbwtgpu_refseqs_info",
+    "sbwtgpu_refseqs_lengths_copy", "sbwtgpu_refseqs_get", "sbwtgpu_refseqs_verify_workspace_bytes", "sbwtgpu_refseqs_verify_dev",
+    "sbwtgpu_refseqs_verify_batch",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -218,6 +221,10 @@ POSITIONS_MAP_TABLE = 256       # SBWTGPU_POSITIONS_MAP_TABLE
 POS_NONE = 0xFFFFFFFFFFFFFFFF   # first[v]: no position
 OCCURRENCES_MAP_TABLE = 256     # SBWTGPU_OCCURRENCES_MAP_TABLE
 OCCURRENCES_MAX_OCC = 1 << 20   # SBWTGPU_OCCURRENCES_MAX_OCC
+# sbwtgpu_read_verify: what the verification of a mapped read against the reference sequences gives
+READ_VERIFY_DTYPE = np.dtype([("ref_end", np.int64), ("mismatches", np.int32), ("edit", np.int32)])
+VERIFY_MAX_BAND = 256           # SBWTGPU_VERIFY_MAX_BAND
+VERIFY_MAX_READ = 1024          # SBWTGPU_VERIFY_MAX_READ
 MAX_COLORS = 4096
 
 _lib: Optional[C.CDLL] = None
@@ -438,6 +445,17 @@ def lib() -> C.CDLL:
         L.sbwtgpu_occurrences_map_workspace_bytes.restype = i64
         L.sbwtgpu_occurrences_map_dev.argtypes = [vp, vp, i64, vp, i64, ci, ci, vp, vp, i64, vp]
         L.sbwtgpu_occurrences_map_batch.argtypes = [vp, vp, vp, i64, ci, ci, vp]
+        L.sbwtgpu_refseqs_create.argtypes = [ci, C.POINTER(vp)]
+        L.sbwtgpu_refseqs_destroy.argtypes = [vp]
+        L.sbwtgpu_refseqs_destroy.restype = None
+        L.sbwtgpu_refseqs_add_batch.argtypes = [vp, i64, vp, vp, i64]
+        L.sbwtgpu_refseqs_info.argtypes = [vp] + [C.POINTER(i64)] * 4
+        L.sbwtgpu_refseqs_lengths_copy.argtypes = [vp, vp]
+        L.sbwtgpu_refseqs_get.argtypes = [vp, i64, i64, i64, vp]
+        L.sbwtgpu_refseqs_verify_workspace_bytes.argtypes = [i64, i64]
+        L.sbwtgpu_refseqs_verify_workspace_bytes.restype = i64
+        L.sbwtgpu_refseqs_verify_dev.argtypes = [vp, vp, i64, vp, i64, vp, ci, vp, vp, i64, vp]
+        L.sbwtgpu_refseqs_verify_batch.argtypes = [vp, vp, vp, i64, vp, ci, vp]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -1813,6 +1831,86 @@ class Occurrences(_Placement):
     @staticmethod
     def workspace_bytes(total_bases: int, n_reads: int, strands: int = 1) -> int:
         return Occurrences._map_workspace_bytes(total_bases, n_reads, strands)
+
+
+class RefSeqs(_Owner):
+    """Owns an sbwtgpu_refseqs handle: the reference sequences packed on the device (2 bits and one validity bit per base), and
+    the verification of mapped reads against them: per read the mismatches on the voted diagonal and the best edit distance in
+    a window around it (include/sbwtgpu.h, "reference sequences and verification").  Everything is exact integers.  Needs no
+    index.  The verify calls must not run while an add does."""
+
+    _destroy = "sbwtgpu_refseqs_destroy"
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def create(cls, device: int = 0) -> "RefSeqs":
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_refseqs_create(device, C.byref(h)))
+        return cls(h)
+
+    def add_sequences(self, bases, read_off, first_seq: Optional[int] = None) -> None:
+        """sbwtgpu_refseqs_add_batch: sequence i of the batch gets the number first_seq + i, which must be the next number
+        (None: whatever it is)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        if first_seq is None:
+            first_seq = self.info()["n_seqs"]
+        _check(lib().sbwtgpu_refseqs_add_batch(self._h, first_seq, bases.ctypes.data, read_off.ctypes.data, max(len(read_off) - 1, 0)))
+
+    def add(self, seqs: Sequence[bytes], first_seq: Optional[int] = None) -> None:
+        """The same for a list of byte strings."""
+        self.add_sequences(*concat_reads(seqs), first_seq)
+
+    def info(self) -> dict:
+        """n_seqs, total_bases, n_invalid (bases that are not upper-case ACGT) and device_bytes."""
+        v = [C.c_int64() for _ in range(4)]
+        _check(lib().sbwtgpu_refseqs_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("n_seqs", "total_bases", "n_invalid", "device_bytes"), (x.value for x in v)))
+
+    def lengths(self) -> np.ndarray:
+        out = np.zeros(self.info()["n_seqs"], dtype=np.int64)
+        _check(lib().sbwtgpu_refseqs_lengths_copy(self._h, out.ctypes.data if len(out) else None))
+        return out
+
+    def get(self, seq: int, pos: int = 0, length: Optional[int] = None) -> bytes:
+        """sbwtgpu_refseqs_get: bases pos .. pos + length of sequence seq as ASCII, N for an invalid base (None: to its end)."""
+        if length is None:
+            lens = self.lengths()
+            length = int(lens[seq]) - pos if 0 <= seq < len(lens) else 0
+        out = np.zeros(max(length, 0), dtype=np.uint8)
+        _check(lib().sbwtgpu_refseqs_get(self._h, seq, pos, length, out.ctypes.data if len(out) else None))
+        return out.tobytes()
+
+    def verify(self, bases, read_off, records, band: int = 8) -> np.ndarray:
+        """sbwtgpu_refseqs_verify_batch: one READ_VERIFY_DTYPE record per read from its READ_MAP_DTYPE record (seq, strand and
+        start are read)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        records = np.ascontiguousarray(records, dtype=READ_MAP_DTYPE)
+        n = max(len(read_off) - 1, 0)
+        if len(records) != n:
+            raise ValueError("%d map records for %d reads" % (len(records), n))
+        out = np.zeros(n, dtype=READ_VERIFY_DTYPE)
+        _check(lib().sbwtgpu_refseqs_verify_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n, records.ctypes.data if n else None,
+                                                  band, out.ctypes.data if n else None))
+        return out
+
+    def verify_reads(self, reads: Sequence[bytes], records, band: int = 8) -> np.ndarray:
+        """The same for a list of byte strings."""
+        return self.verify(*concat_reads(reads), records, band)
+
+    def verify_dev(self, d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_map: int, d_out: int, d_ws: int, ws_bytes: int,
+                   band: int = 8, stream: int = 0) -> None:
+        """sbwtgpu_refseqs_verify_dev (raw device pointers; d_map: n_reads records of 32 bytes; d_out: n_reads records of 16 bytes;
+        workspace of workspace_bytes): asynchronous on stream."""
+        _check(lib().sbwtgpu_refseqs_verify_dev(self._h, d_bases or None, total_bases, d_read_off or None, n_reads, d_map or None, band,
+                                                d_out or None, d_ws or None, ws_bytes, stream or None))
+
+    @staticmethod
+    def workspace_bytes(total_bases: int, n_reads: int) -> int:
+        return int(lib().sbwtgpu_refseqs_verify_workspace_bytes(total_bases, n_reads))
 
 
 class ColorSetsBuilder(_Owner):

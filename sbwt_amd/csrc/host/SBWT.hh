@@ -1178,4 +1178,43 @@ private:
 
 typedef SBWT plain_matrix_sbwt_t;                         // variants.hh:19
 
+// The reference sequences packed on the device and mapped reads verified against them (include/sbwtgpu.h, "reference sequences
+// and verification"): per read the mismatches on the voted diagonal and the best edit distance in a window around it.  Needs no
+// index.  The sequences get the numbers 0, 1, ... in the order they are added: the numbering of Positions and Occurrences.
+class RefSeqs {
+public:
+    RefSeqs() = default;
+    RefSeqs(const RefSeqs &) = delete;
+    RefSeqs &operator=(const RefSeqs &) = delete;
+    RefSeqs(RefSeqs &&o) noexcept : h(o.h) { o.h = nullptr; }
+    RefSeqs &operator=(RefSeqs &&o) noexcept {
+        if (this != &o) {
+            sbwtgpu_refseqs_destroy(h);
+            h = o.h; o.h = nullptr;
+        }
+        return *this;
+    }
+    ~RefSeqs() { sbwtgpu_refseqs_destroy(h); }
+    // an empty object on the default device
+    static RefSeqs create() {
+        RefSeqs r;
+        detail::gpu_check(sbwtgpu_refseqs_create(detail::default_device(), &r.h));
+        return r;
+    }
+    void add(const char *bases, const int64_t *read_off, int64_t n_seqs) {
+        detail::gpu_check(sbwtgpu_refseqs_add_batch(h, info().n_seqs, bases, read_off, n_seqs));
+    }
+    struct Info { int64_t n_seqs = 0, total_bases = 0, n_invalid = 0, device_bytes = 0; };
+    Info info() const {
+        Info i;
+        detail::gpu_check(sbwtgpu_refseqs_info(h, &i.n_seqs, &i.total_bases, &i.n_invalid, &i.device_bytes));
+        return i;
+    }
+    void verify(const char *bases, const int64_t *read_off, int64_t n_reads, const sbwtgpu_read_map *map, int band,
+                sbwtgpu_read_verify *out) const {
+        detail::gpu_check(sbwtgpu_refseqs_verify_batch(h, bases, read_off, n_reads, map, band, out));
+    }
+    sbwtgpu_refseqs *h = nullptr;
+};
+
 }  // namespace sbwt

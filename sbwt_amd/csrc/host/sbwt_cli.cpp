@@ -23,10 +23,14 @@
 //               two index files combined on the GPU without their input sequences: the index `sbwt build` would write for
 //               the result's k-mers
 //   sbwt read-hits -i <index> -q <query> -o <out> [-z] [--both-strands] [--positions <index.pos> | --occurrences <index.occ> [--max-occ N]]
+//               [--refs <refs.txt> [--band N]]
 //               one line per read: n_kmers n_found covered_bases longest_run; with --positions six more columns, the read's
 //               placement on the references by diagonal voting: seq strand start votes votes2 n_anchored; with --occurrences
 //               the same six columns from the vote over every occurrence of every k-mer (--max-occ, default 1024: a k-mer
-//               with more occurrences casts no vote)
+//               with more occurrences casts no vote); with --refs (the list build-colors -r took, its files read in order and
+//               their sequences numbered as the position file numbers them) beside a placement option three more columns,
+//               the placement checked against the reference's bases: mismatches edit ref_end (--band, default 8: the edit
+//               distance is the best over the window of band bases either side; -1 -1 0: no placement to check)
 //   sbwt build-colors -i <index> -r <refs.txt> -o <colours> [--both-strands] [--wide | --compress [--stream]]
 //               [--positions-out <index.pos>] [--occurrences-out <index.occ>]
 //               one colour per listed reference file, set on the columns of the index's k-mers that the file holds
@@ -781,11 +785,13 @@ int read_hits_main(int argc, char **argv) {
         {"positions", 0, true, "A position file of the index (build-colors --positions-out): every line gains the read's placement on the references, seq strand start votes votes2 n_anchored (seq -1: no placement).", ""},
         {"occurrences", 0, true, "An occurrence file of the index (build-colors --occurrences-out): every line gains the same six columns, seq strand start votes votes2 n_anchored, from the vote over every occurrence of every k-mer; votes2 == votes says that an equally good placement exists. Cannot be combined with --positions.", ""},
         {"max-occ", 0, true, "With --occurrences: a k-mer with more occurrences than this casts no vote (1 .. 1048576). The default is 1024.", "1024"},
+        {"refs", 0, true, "With --positions or --occurrences: the list of reference files that build-colors -r took (FASTA or FASTQ, possibly gzipped, one per line). They are read in order and their sequences numbered 0, 1, ... as the position file numbers them; every line gains three more columns behind the six of the placement, the read checked against the reference's bases there: mismatches edit ref_end (mismatches on the voted diagonal, the best edit distance in the window of --band bases either side, the end of that alignment on the reference; -1 -1 0: no placement to check, and a read of more than 1024 bases gets its mismatches only, edit -1).", ""},
+        {"band", 0, true, "With --refs: the bases either side of the voted placement that the edit distance may use (0 .. 256). The default is 8.", "8"},
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
     });
-    parse_or_usage(opts, argc, argv, "Per read: k-mers, k-mers found in the index, bases they cover, longest run of found k-mers.");
+    parse_or_usage(opts, argc, argv, "Per read: k-mers, k-mers found in the index, bases they cover, longest run of found k-mers; with a placement option the read's placement on the references, and with --refs that placement checked against the reference's bases.");
     const string indexfile = opts.get("index-file");
     check_readable(indexfile);
     const QueryFiles files = query_and_output_files(opts);
@@ -806,6 +812,24 @@ int read_hits_main(int argc, char **argv) {
         if (text.empty() || *end != 0 || max_occ < 1 || max_occ > SBWTGPU_OCCURRENCES_MAX_OCC)
             throw std::runtime_error("Error: --max-occ must be a number in 1 .. 1048576, not " + text);
     }
+    const string refsfile = opts.count("refs") ? opts.get("refs") : "";
+    if (!refsfile.empty() && posfile.empty() && occfile.empty())
+        throw std::runtime_error("Error: --refs needs --positions or --occurrences (it checks the placement they give)");
+    int64_t band = 8;
+    if (opts.count("band")) {
+        if (refsfile.empty()) throw std::runtime_error("Error: --band needs --refs");
+        const string text = opts.get("band");
+        char *end = nullptr;
+        band = strtoll(text.c_str(), &end, 10);
+        if (text.empty() || *end != 0 || band < 0 || band > SBWTGPU_VERIFY_MAX_BAND)
+            throw std::runtime_error("Error: --band must be a number in 0 .. 256, not " + text);
+    }
+    vector<string> refs;
+    if (!refsfile.empty()) {
+        check_readable(refsfile);
+        refs = readlines(refsfile);
+        for (const string &file : refs) check_readable(file);
+    }
     use_gpu_option(opts);
     const int64_t batch_bases = batch_bases_option(opts);
 
@@ -817,6 +841,22 @@ int read_hits_main(int argc, char **argv) {
     if (!occfile.empty()) occurrences = index.load_occurrences(occfile);
     const bool placing = positions.h || occurrences.h;
     vector<sbwtgpu_read_map> placed;
+    // the reference sequences, numbered in reading order as build-colors numbered them
+    RefSeqs refseqs;
+    if (!refsfile.empty()) {
+        refseqs = RefSeqs::create();
+        for (const string &file : refs) {
+            seq_io::Reader reader(file);
+            for_each_batch(reader, batch_bases, [&](const vector<char> &bases, const vector<int64_t> &read_off, int64_t n_reads) {
+                refseqs.add(bases.data(), read_off.data(), n_reads);
+            });
+        }
+        const size_t listed = positions.h ? positions.seqs.size() : occurrences.seqs.size();
+        if ((size_t)refseqs.info().n_seqs != listed)
+            throw std::runtime_error("Error: " + refsfile + " holds " + std::to_string(refseqs.info().n_seqs) + " sequences, the placement file lists " +
+                                     std::to_string(listed));
+    }
+    vector<sbwtgpu_read_verify> verified;
     int64_t total_reads = 0;
     for (size_t f = 0; f < files.in.size(); f++) {
         write_log("Running read-hits from input file " + files.in[f] + " to output file " + files.out[f], LogLevel::MAJOR);
@@ -830,6 +870,10 @@ int read_hits_main(int argc, char **argv) {
             if (placing) placed.resize((size_t)n_reads);
             if (positions.h) positions.map(bases.data(), read_off.data(), n_reads, strands, placed.data());
             if (occurrences.h) occurrences.map(bases.data(), read_off.data(), n_reads, strands, (int)max_occ, placed.data());
+            if (refseqs.h) {
+                verified.resize((size_t)n_reads);
+                refseqs.verify(bases.data(), read_off.data(), n_reads, placed.data(), (int)band, verified.data());
+            }
             text.clear();
             for (size_t r = 0; r < rec.size(); r++) {
                 const sbwtgpu_read_hits &h = rec[r];
@@ -845,6 +889,13 @@ int read_hits_main(int argc, char **argv) {
                     for (int64_t v : {(int64_t)m.seq, (int64_t)m.strand, (int64_t)m.start, (int64_t)m.votes, (int64_t)m.votes2, (int64_t)m.n_anchored}) {
                         text.push_back(' ');
                         append_int(v, text);
+                    }
+                }
+                if (refseqs.h) {
+                    const sbwtgpu_read_verify &v = verified[r];
+                    for (int64_t x : {(int64_t)v.mismatches, (int64_t)v.edit, (int64_t)v.ref_end}) {
+                        text.push_back(' ');
+                        append_int(x, text);
                     }
                 }
                 text.push_back('\n');

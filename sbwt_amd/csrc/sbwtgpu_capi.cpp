@@ -263,6 +263,12 @@ int sbwtgpu_set_tuning(const char *key, int64_t value) {
         g_occ_map_table = (int)value;
         return SBWTGPU_OK;
     }
+    if (!strcmp(key, "verify_fast_bases")) {
+        if (value < 0 || value > 256)
+            return fail(SBWTGPU_ERR_INVALID_ARG, "verify_fast_bases must be in 0 .. 256 (0: the compiled limit of 256), not %lld", (long long)value);
+        g_verify_fast_bases = (int)value;
+        return SBWTGPU_OK;
+    }
     if (!strcmp(key, "gram_mfma_min_sets")) { g_gram_mfma_min_sets = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "gram_flush_sets")) {
         if (value < 1 || value > SBWT_GM_FLUSH_MAX)

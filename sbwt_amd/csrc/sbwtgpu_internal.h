@@ -1,7 +1,8 @@
 // sbwtgpu_internal.h -- what the translation units of the C ABI share: sbwtgpu_capi.cpp (index image, search, rank, text),
 // sbwtgpu_capi_reads.cpp (matching statistics, set operations, read hits, unitigs and their graph, walks, bubbles) and
 // sbwtgpu_capi_colors.cpp (colours, colour sets, pseudoalignment, screen) and sbwtgpu_capi_placement.cpp (reference positions and
-// all occurrences per column, read mapping over either).  Nothing here is part of the library's interface:
+// all occurrences per column, read mapping over either) and sbwtgpu_capi_verify.cpp (the packed reference sequences and the
+// verification of mapped reads against them).  Nothing here is part of the library's interface:
 // every name has hidden visibility, and whatever holds state (the error text, the parked slots, the int32 switch of a search
 // call) is defined once, in sbwtgpu_capi.cpp.
 #pragma once
@@ -91,6 +92,7 @@ extern int64_t g_pa_chunk_bases, g_screen_chunk_bases;      // sbwtgpu_capi_colo
 extern int64_t g_gram_mfma_min_sets, g_gram_flush_sets;
 extern int64_t g_pos_chunk_bases, g_occ_chunk_bases;        // sbwtgpu_capi_placement.cpp
 extern int g_pos_map_table, g_occ_map_table;
+extern int g_verify_fast_bases;                             // sbwtgpu_capi_verify.cpp
 
 }  // namespace sbwt_capi
 

@@ -2,7 +2,10 @@
 .vgpr_count, .sgpr_count, .sgpr_spill_count, .vgpr_spill_count, LDS (.group_segment_fixed_size) and scratch
 (.private_segment_fixed_size) of every kernel whose name matches the pattern, keyed by the full (demangled) name.
 
-    python tools/kernel_resources.py [library.so] [name-regex]        (defaults: sbwt_amd/lib/libsbwtgpu.so, k_search)
+    python tools/kernel_resources.py [library.so] [name-regex | layer]        (defaults: sbwt_amd/lib/libsbwtgpu.so, k_search)
+
+A layer's name stands for the regex of its kernels (LAYERS): `verify` is the reference pack / unpack and the two verify kernels
+of sbwt_verify.hip (profiles/verify_kernel_resources.txt).
 
 tools/summarize_profile.py appends this table to every profiles/*_rocprof_summary.txt, so that the occupancy and spill
 claims of DESIGN.md section 3 can be checked from profiles/ (the trace's VGPR_Count row is the granule
@@ -23,6 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 CXXFILT = "c++filt"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+LAYERS = {"search": "k_search", "positions": "k_pos_", "occurrences": "k_occ_", "verify": "k_ref_|k_verify"}
 FIELDS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".group_segment_fixed_size",
           ".private_segment_fixed_size", ".max_flat_workgroup_size")
 
@@ -92,6 +96,7 @@ def table(lib, pattern="k_search"):
 if __name__ == "__main__":
     lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "sbwt_amd", "lib", "libsbwtgpu.so")
     pat = sys.argv[2] if len(sys.argv) > 2 else "k_search"
+    pat = LAYERS.get(pat, pat)
     print("== code-object resources (%s, kernels matching /%s/) ==" % (os.path.relpath(lib, ROOT) if lib.startswith(ROOT) else lib, pat))
     for ln in table(lib, pat):
         print(ln)
