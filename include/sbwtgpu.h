@@ -135,6 +135,9 @@ int         sbwtgpu_device_count(int *count);
  *   "verify_fast_bases"  the longest read, in bases, that the first verify kernel takes (its rows in registers) before the read
  *                        goes to the second kernel (rows in LDS): 1 .. 256, 0 (default) = 256; another value is refused.  No
  *                        result depends on it (tests reach the second kernel with short reads)
+ *   "align_fast_edit"    the largest edit that the first align kernel takes (a band of 2 edit + 1 diagonals, one mask word per
+ *                        row) before the read goes to the second kernel (the whole window, one wave per read): 1 .. 31, 0
+ *                        (default) = 31; another value is refused.  No result depends on it
  *   "trans_ext", "trans_wide"   accepted and ignored (round-2 table formats)
  * Read when an index is CREATED (derived acceleration structures inside the device image; environment
  * variables of the same meaning: SBWTGPU_SPARSE_PRECALC, SBWTGPU_PROBE_FILTER, SBWTGPU_PATH_ORDER):
@@ -1483,8 +1486,9 @@ int     sbwtgpu_occurrences_map_batch(const sbwtgpu_occurrences *o, const char *
  *   - edit = 0 iff r occurs in the window.
  *   - (rc(read), 1 - strand) gives the same record as (read, strand).
  *   - The result does not depend on what the neighbouring sequences in the packed arrays hold.
- * Not built: the begin of the best alignment (a reverse pass), CIGAR strings, the runner-up's verification (the map record does
- * not carry its placement), a reference file format (the CLI re-reads the sequence files).
+ * Not built: the runner-up's verification (the map record does not carry its placement), a reference file format (the CLI
+ * re-reads the sequence files), SAM/PAF files, clipping of overhangs.  The begin of the best alignment and its CIGAR: "alignment
+ * of mapped reads" below.
  * sbwtgpu_refseqs_create makes an empty object on `device` (SBWTGPU_ERR_NO_DEVICE without one).  sbwtgpu_refseqs_add_batch
  * takes host buffers (sequence i is bases[read_off[i] .. read_off[i + 1])), stages the batch on the device in one piece and
  * packs it with one kernel, one lane per 2-bit word; it returns when the sequences are in place.
@@ -1522,6 +1526,82 @@ int     sbwtgpu_refseqs_verify_dev(const sbwtgpu_refseqs *r, const char *d_bases
                                    void *d_workspace, int64_t workspace_bytes, void *stream);
 int     sbwtgpu_refseqs_verify_batch(const sbwtgpu_refseqs *r, const char *bases, const int64_t *read_off, int64_t n_reads,
                                      const sbwtgpu_read_map *map, int band, sbwtgpu_read_verify *out);
+
+/* ---- alignment of mapped reads ----
+ * The verify calls above say that a read fits its placement with `edit` edits and where the best alignment ends.  These calls
+ * say where it begins and what it is: the runs of = X I D, as a CIGAR.  The terms of "reference sequences and verification"
+ * apply unchanged: valid base, oriented read r, "coordinate p matches r[j]", the window [start - B, start + L + B), Sellers'
+ * table D with D[0][t] = 0 and D[i][0] = i, edit, ref_end.
+ * Column t >= 1 of D stands for reference coordinate start - B + t - 1.  Let tE = ref_end - (start - B).
+ * The alignment of a read with edit >= 0 and L > 0 is the path found by walking back from (i, t) = (L, tE) until i = 0.  At
+ * each cell take the FIRST step that applies:
+ *   1. Diagonal.  Applies if t > 0 and D[i-1][t-1] + c == D[i][t], where c = 0 if column t's coordinate matches r[i-1] and c = 1
+ *      otherwise.  Emit = when c = 0 and X when c = 1.  Then i--, t--.
+ *   2. Insertion.  Applies if D[i-1][t] + 1 == D[i][t].  Emit I: read base r[i-1] faces nothing.  Then i--.
+ *   3. Deletion.  Otherwise t > 0 and D[i][t-1] + 1 == D[i][t].  Emit D: a reference coordinate faces nothing.  Then t--.
+ * When i = 0, ref_begin = start - B + t.  The emitted operations are reversed into read order, and equal neighbours are merged
+ * into runs.
+ * A run is one uint32 as in BAM: length << 4 | code, with I = 1, D = 2, = = 7, X = 8.  A coordinate outside [0, n) or on an
+ * invalid base is an ordinary column that matches nothing.  It can only be X or D.  ref_begin may be negative and ref_end may
+ * exceed n, exactly as ref_end can today.
+ * The record
+ *   sbwtgpu_read_align is 16 bytes: int64 ref_begin; int32 n_ops; int32 n_eq.  n_ops is the number of runs.  n_eq is the number
+ *   of = columns.
+ * Special cases
+ *   - An unverified record, or a read of more than 1024 bases (edit = -1), gives {0, 0, 0} and no runs.
+ *   - L = 0 gives {start - B, 0, 0}.
+ *   - n_ops = 0 holds in no other case.
+ * Properties that follow
+ *   - #= + #X + #I = L.
+ *   - #= + #X + #D = ref_end - ref_begin.
+ *   - #X + #I + #D = edit.
+ *   - The first and the last run are never D.  The start is free, and tE is the smallest minimiser.
+ *   - n_ops <= 2 edit + 1.
+ *   - No two neighbouring runs have the same code.
+ *   - edit = 0 gives the single run L= and ref_begin = ref_end - L.
+ *   - ref_begin >= start - B.
+ *   - (rc(read), 1 - strand) gives the same alignment as (read, strand).
+ *   - The alignment does not depend on neighbouring sequences.
+ * The band lemma
+ *   Restrict the table to the diagonals d = t - i with |d - (tE - L)| <= edit, and treat every cell outside as infinite.  The
+ *   walk over this banded table takes exactly the same steps as the walk over the full table.
+ *   - Every cell the walk visits lies on an optimal path to (L, tE).
+ *   - Such a path has at most edit indels, so it cannot leave the band, and its cells' banded values equal the true ones.
+ *   - A neighbour that fails its test in the full table has a banded value at least as large, so it fails there too.
+ *   So the traceback needs 2 edit + 1 cells per row, not the window.
+ * sbwtgpu_align_dev takes the device pointers of sbwtgpu_refseqs_verify_dev and runs that call's kernels first, unchanged:
+ * d_verify_out receives exactly what sbwtgpu_refseqs_verify_dev writes for the same input.  Then d_out receives the n_reads
+ * records, d_op_off the n_reads + 1 run offsets, and d_ops the runs: read i's are d_ops[d_op_off[i] .. d_op_off[i + 1]), in read
+ * order.  ops_cap follows the rule of sbwtgpu_unitigs_walks_dev: d_op_off[n_reads] always receives the true total, only runs
+ * numbered below ops_cap are stored, and nothing is written at or beyond d_ops[ops_cap] (d_ops may be NULL for ops_cap = 0).  The
+ * call is asynchronous on `stream`, never synchronises and never allocates; the offsets come from a device scan on that stream.
+ * Its workspace, of sbwtgpu_align_workspace_bytes (a multiple of 256, non-decreasing in both arguments, 16-byte aligned), holds
+ * the verify workspace first, then a 256-byte header, 12 bytes per read and the scratch of a fixed grid of waves (at most 288 MiB,
+ * whatever the batch).
+ * The kernels: the first gives every read ONE LANE.  A lane with edit = 0 needs no table.  The others run the banded table row
+ * by row, the row in registers, and record per row which of tests 1 and 2 hold for each band cell, two bit masks of at most 64
+ * bits, in the wave's [row][lane] scratch; then they walk back over those masks.  A wave runs the code of its widest member
+ * (bands for edit <= 1, 3, 7, 15, 31).  Reads with edit > 31, or of more than 256 bases, go onto a list; the second kernel
+ * gives each of them one wave, which runs the whole window (up to 1536 columns, 24 per lane) and is exact for every edit.
+ * THE SECOND KERNEL IS FAR SLOWER: it is a fixed grid of 64 waves, one read each, some 6 % of an MI355X's SIMDs.  A batch of
+ * reads of more than 256 bases runs entirely there; the layer's measured throughput is that of reads of
+ * up to 256 bases and 31 edits.
+ * "align_fast_edit" (sbwtgpu_set_tuning: 1 .. 31, 0 = 31) lowers the first kernel's limit; no result depends on it (tests
+ * reach the second kernel with short reads).  Both kernels run twice around the scan: count the runs, then store them.
+ * sbwtgpu_align_batch is the same call on host buffers: one staged range, not pipelined.  verify_out, out and op_off
+ * (n_reads + 1) are the caller's; *ops_out is memory of the library that holds the *n_ops runs (release it with
+ * sbwtgpu_free_host), NULL when there are no runs.
+ * Both calls are safe from several host threads on one object and, like the verify calls, must not run during an add.
+ * Refusals (SBWTGPU_ERR_INVALID_ARG with a message that names the cause): those of the verify calls, ops_cap < 0, and NULL
+ * outputs (d_verify_out, d_out, d_op_off; d_ops with ops_cap > 0; verify_out, out, op_off, ops_out, n_ops). */
+typedef struct { int64_t ref_begin; int32_t n_ops; int32_t n_eq; } sbwtgpu_read_align;
+int64_t sbwtgpu_align_workspace_bytes(int64_t total_bases, int64_t n_reads);
+int     sbwtgpu_align_dev(const sbwtgpu_refseqs *r, const char *d_bases, int64_t total_bases, const int64_t *d_read_off, int64_t n_reads,
+                          const sbwtgpu_read_map *d_map, int band, sbwtgpu_read_verify *d_verify_out, sbwtgpu_read_align *d_out,
+                          int64_t *d_op_off /* n_reads + 1 */, uint32_t *d_ops, int64_t ops_cap,
+                          void *d_workspace, int64_t workspace_bytes, void *stream);
+int     sbwtgpu_align_batch(const sbwtgpu_refseqs *r, const char *bases, const int64_t *read_off, int64_t n_reads, const sbwtgpu_read_map *map,
+                            int band, sbwtgpu_read_verify *verify_out, sbwtgpu_read_align *out, int64_t *op_off, uint32_t **ops_out, int64_t *n_ops);
 
 #ifdef __cplusplus
 }

@@ -93,6 +93,7 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_refseqs_create", "sbwtgpu_refseqs_destroy", "sbwtgpu_refseqs_add_batch", "sbwtgpu_refseqs_info",
     "sbwtgpu_refseqs_lengths_copy", "sbwtgpu_refseqs_get", "sbwtgpu_refseqs_verify_workspace_bytes", "sbwtgpu_refseqs_verify_dev",
     "sbwtgpu_refseqs_verify_batch",
+    "sbwtgpu_align_workspace_bytes", "sbwtgpu_align_dev", "sbwtgpu_align_batch",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -223,6 +224,10 @@ OCCURRENCES_MAP_TABLE = 256     # SBWTGPU_OCCURRENCES_MAP_TABLE
 OCCURRENCES_MAX_OCC = 1 << 20   # SBWTGPU_OCCURRENCES_MAX_OCC
 # sbwtgpu_read_verify: what the verification of a mapped read against the reference sequences gives
 READ_VERIFY_DTYPE = np.dtype([("ref_end", np.int64), ("mismatches", np.int32), ("edit", np.int32)])
+# sbwtgpu_read_align: where the best alignment of a verified read begins, its number of runs and of = columns
+READ_ALIGN_DTYPE = np.dtype([("ref_begin", np.int64), ("n_ops", np.int32), ("n_eq", np.int32)])
+CIGAR_LETTERS = {1: "I", 2: "D", 7: "=", 8: "X"}       # the codes of a run, as in BAM
+
 VERIFY_MAX_BAND = 256           # SBWTGPU_VERIFY_MAX_BAND
 VERIFY_MAX_READ = 1024          # SBWTGPU_VERIFY_MAX_READ
 MAX_COLORS = 4096
@@ -456,11 +461,23 @@ def lib() -> C.CDLL:
         L.sbwtgpu_refseqs_verify_workspace_bytes.restype = i64
         L.sbwtgpu_refseqs_verify_dev.argtypes = [vp, vp, i64, vp, i64, vp, ci, vp, vp, i64, vp]
         L.sbwtgpu_refseqs_verify_batch.argtypes = [vp, vp, vp, i64, vp, ci, vp]
+        L.sbwtgpu_align_workspace_bytes.argtypes = [i64, i64]
+        L.sbwtgpu_align_workspace_bytes.restype = i64
+        L.sbwtgpu_align_dev.argtypes = [vp, vp, i64, vp, i64, vp, ci, vp, vp, vp, vp, i64, vp, i64, vp]
+        L.sbwtgpu_align_batch.argtypes = [vp, vp, vp, i64, vp, ci, vp, vp, vp, C.POINTER(vp), C.POINTER(i64)]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
     _lib = L
     return L
+
+
+def cigar_string(ops) -> str:
+    """The runs of one read (uint32: length << 4 | code) as a CIGAR string, 57=1X92=; * for no runs."""
+    ops = np.asarray(ops, dtype=np.uint32)
+    if len(ops) == 0:
+        return "*"
+    return "".join("%d%s" % (int(o) >> 4, CIGAR_LETTERS[int(o) & 15]) for o in ops)
 
 
 def _check(rc: int) -> None:
@@ -1911,6 +1928,47 @@ class RefSeqs(_Owner):
     @staticmethod
     def workspace_bytes(total_bases: int, n_reads: int) -> int:
         return int(lib().sbwtgpu_refseqs_verify_workspace_bytes(total_bases, n_reads))
+
+    def align(self, bases, read_off, records, band: int = 8):
+        """sbwtgpu_align_batch: (verify, align, op_off, ops).  verify is what verify() gives; align holds one READ_ALIGN_DTYPE
+        record per read; read i's runs are ops[op_off[i]:op_off[i + 1]] (uint32, length << 4 | code; cigar_string)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        records = np.ascontiguousarray(records, dtype=READ_MAP_DTYPE)
+        n = max(len(read_off) - 1, 0)
+        if len(records) != n:
+            raise ValueError("%d map records for %d reads" % (len(records), n))
+        verify = np.zeros(n, dtype=READ_VERIFY_DTYPE)
+        out = np.zeros(n, dtype=READ_ALIGN_DTYPE)
+        op_off = np.zeros(n + 1, dtype=np.int64)
+        p, total = C.c_void_p(), C.c_int64(0)
+        _check(lib().sbwtgpu_align_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n, records.ctypes.data if n else None, band,
+                                         verify.ctypes.data if n else None, out.ctypes.data if n else None, op_off.ctypes.data,
+                                         C.byref(p), C.byref(total)))
+        try:
+            ops = np.empty(total.value, dtype=np.uint32)
+            if total.value:
+                C.memmove(ops.ctypes.data, p.value, total.value * 4)
+        finally:
+            if p.value:
+                lib().sbwtgpu_free_host(p)
+        return verify, out, op_off, ops
+
+    def align_reads(self, reads: Sequence[bytes], records, band: int = 8):
+        """The same for a list of byte strings."""
+        return self.align(*concat_reads(reads), records, band)
+
+    def align_dev(self, d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_map: int, d_verify_out: int, d_out: int,
+                  d_op_off: int, d_ops: int, ops_cap: int, d_ws: int, ws_bytes: int, band: int = 8, stream: int = 0) -> None:
+        """sbwtgpu_align_dev (raw device pointers; d_verify_out and d_out: n_reads records of 16 bytes; d_op_off: n_reads + 1
+        int64; d_ops: ops_cap uint32; workspace of align_workspace_bytes): asynchronous on stream."""
+        _check(lib().sbwtgpu_align_dev(self._h, d_bases or None, total_bases, d_read_off or None, n_reads, d_map or None, band,
+                                       d_verify_out or None, d_out or None, d_op_off or None, d_ops or None, ops_cap, d_ws or None,
+                                       ws_bytes, stream or None))
+
+    @staticmethod
+    def align_workspace_bytes(total_bases: int, n_reads: int) -> int:
+        return int(lib().sbwtgpu_align_workspace_bytes(total_bases, n_reads))
 
 
 class ColorSetsBuilder(_Owner):

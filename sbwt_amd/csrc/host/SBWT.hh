@@ -1214,6 +1214,17 @@ public:
                 sbwtgpu_read_verify *out) const {
         detail::gpu_check(sbwtgpu_refseqs_verify_batch(h, bases, read_off, n_reads, map, band, out));
     }
+    // sbwtgpu_align_batch: the verify records, and per read where its best alignment begins and its runs of = X I D (uint32,
+    // length << 4 | code: I 1, D 2, = 7, X 8); read i's runs are ops[op_off[i] .. op_off[i + 1])
+    void align(const char *bases, const int64_t *read_off, int64_t n_reads, const sbwtgpu_read_map *map, int band,
+               sbwtgpu_read_verify *verify_out, sbwtgpu_read_align *out, std::vector<int64_t> &op_off, std::vector<uint32_t> &ops) const {
+        uint32_t *p = nullptr;
+        int64_t n = 0;
+        op_off.assign((size_t)n_reads + 1, 0);
+        detail::gpu_check(sbwtgpu_align_batch(h, bases, read_off, n_reads, map, band, verify_out, out, op_off.data(), &p, &n));
+        struct Free { uint32_t *p; ~Free() { sbwtgpu_free_host(p); } } guard{p};      // (assign may throw)
+        ops.assign(p, p + n);
+    }
     sbwtgpu_refseqs *h = nullptr;
 };
 

@@ -23,14 +23,15 @@
 //               two index files combined on the GPU without their input sequences: the index `sbwt build` would write for
 //               the result's k-mers
 //   sbwt read-hits -i <index> -q <query> -o <out> [-z] [--both-strands] [--positions <index.pos> | --occurrences <index.occ> [--max-occ N]]
-//               [--refs <refs.txt> [--band N]]
+//               [--refs <refs.txt> [--band N] [--cigar]]
 //               one line per read: n_kmers n_found covered_bases longest_run; with --positions six more columns, the read's
 //               placement on the references by diagonal voting: seq strand start votes votes2 n_anchored; with --occurrences
 //               the same six columns from the vote over every occurrence of every k-mer (--max-occ, default 1024: a k-mer
 //               with more occurrences casts no vote); with --refs (the list build-colors -r took, its files read in order and
 //               their sequences numbered as the position file numbers them) beside a placement option three more columns,
 //               the placement checked against the reference's bases: mismatches edit ref_end (--band, default 8: the edit
-//               distance is the best over the window of band bases either side; -1 -1 0: no placement to check)
+//               distance is the best over the window of band bases either side; -1 -1 0: no placement to check); with --cigar
+//               two more, the best alignment in that window: ref_begin cigar (runs of = X I D; 0 *: no alignment)
 //   sbwt build-colors -i <index> -r <refs.txt> -o <colours> [--both-strands] [--wide | --compress [--stream]]
 //               [--positions-out <index.pos>] [--occurrences-out <index.occ>]
 //               one colour per listed reference file, set on the columns of the index's k-mers that the file holds
@@ -787,6 +788,7 @@ int read_hits_main(int argc, char **argv) {
         {"max-occ", 0, true, "With --occurrences: a k-mer with more occurrences than this casts no vote (1 .. 1048576). The default is 1024.", "1024"},
         {"refs", 0, true, "With --positions or --occurrences: the list of reference files that build-colors -r took (FASTA or FASTQ, possibly gzipped, one per line). They are read in order and their sequences numbered 0, 1, ... as the position file numbers them; every line gains three more columns behind the six of the placement, the read checked against the reference's bases there: mismatches edit ref_end (mismatches on the voted diagonal, the best edit distance in the window of --band bases either side, the end of that alignment on the reference; -1 -1 0: no placement to check, and a read of more than 1024 bases gets its mismatches only, edit -1).", ""},
         {"band", 0, true, "With --refs: the bases either side of the voted placement that the edit distance may use (0 .. 256). The default is 8.", "8"},
+        {"cigar", 0, false, "With --refs: every line gains two more columns behind mismatches edit ref_end, the best alignment in that window: ref_begin cigar (where the alignment begins on the reference, and its runs with the four letters = X I D: match, substitution, a read base that faces nothing, a reference base that faces nothing; 0 *: no alignment, for a read without a placement or of more than 1024 bases). A batch then holds room for its runs on the device, 8 bytes per base of --batch-bases beside some 300 MB of scratch (2 GB more at the default batch): lower --batch-bases on a small device. Reads of more than 256 bases, and reads of more than 31 edits, are aligned by a far slower kernel.", ""},
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
@@ -824,6 +826,8 @@ int read_hits_main(int argc, char **argv) {
         if (text.empty() || *end != 0 || band < 0 || band > SBWTGPU_VERIFY_MAX_BAND)
             throw std::runtime_error("Error: --band must be a number in 0 .. 256, not " + text);
     }
+    const bool cigar = opts.count("cigar");
+    if (cigar && refsfile.empty()) throw std::runtime_error("Error: --cigar needs --refs");
     vector<string> refs;
     if (!refsfile.empty()) {
         check_readable(refsfile);
@@ -857,6 +861,9 @@ int read_hits_main(int argc, char **argv) {
                                      std::to_string(listed));
     }
     vector<sbwtgpu_read_verify> verified;
+    vector<sbwtgpu_read_align> aligned;
+    vector<int64_t> op_off;
+    vector<uint32_t> ops;
     int64_t total_reads = 0;
     for (size_t f = 0; f < files.in.size(); f++) {
         write_log("Running read-hits from input file " + files.in[f] + " to output file " + files.out[f], LogLevel::MAJOR);
@@ -872,7 +879,12 @@ int read_hits_main(int argc, char **argv) {
             if (occurrences.h) occurrences.map(bases.data(), read_off.data(), n_reads, strands, (int)max_occ, placed.data());
             if (refseqs.h) {
                 verified.resize((size_t)n_reads);
-                refseqs.verify(bases.data(), read_off.data(), n_reads, placed.data(), (int)band, verified.data());
+                if (cigar) {
+                    aligned.resize((size_t)n_reads);
+                    refseqs.align(bases.data(), read_off.data(), n_reads, placed.data(), (int)band, verified.data(), aligned.data(), op_off, ops);
+                } else {
+                    refseqs.verify(bases.data(), read_off.data(), n_reads, placed.data(), (int)band, verified.data());
+                }
             }
             text.clear();
             for (size_t r = 0; r < rec.size(); r++) {
@@ -896,6 +908,16 @@ int read_hits_main(int argc, char **argv) {
                     for (int64_t x : {(int64_t)v.mismatches, (int64_t)v.edit, (int64_t)v.ref_end}) {
                         text.push_back(' ');
                         append_int(x, text);
+                    }
+                }
+                if (cigar) {
+                    text.push_back(' ');
+                    append_int(aligned[r].ref_begin, text);
+                    text.push_back(' ');
+                    if (op_off[r + 1] == op_off[r]) text.push_back('*');
+                    for (int64_t o = op_off[r]; o < op_off[r + 1]; o++) {
+                        append_int((int64_t)(ops[(size_t)o] >> 4), text);
+                        text.push_back("?ID????=X???????"[ops[(size_t)o] & 15u]);
                     }
                 }
                 text.push_back('\n');

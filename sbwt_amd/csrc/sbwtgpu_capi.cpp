@@ -269,6 +269,12 @@ int sbwtgpu_set_tuning(const char *key, int64_t value) {
         g_verify_fast_bases = (int)value;
         return SBWTGPU_OK;
     }
+    if (!strcmp(key, "align_fast_edit")) {
+        if (value < 0 || value > 31)
+            return fail(SBWTGPU_ERR_INVALID_ARG, "align_fast_edit must be in 0 .. 31 (0: the compiled limit of 31), not %lld", (long long)value);
+        g_align_fast_edit = (int)value;
+        return SBWTGPU_OK;
+    }
     if (!strcmp(key, "gram_mfma_min_sets")) { g_gram_mfma_min_sets = value < 0 ? 0 : value; return SBWTGPU_OK; }
     if (!strcmp(key, "gram_flush_sets")) {
         if (value < 1 || value > SBWT_GM_FLUSH_MAX)

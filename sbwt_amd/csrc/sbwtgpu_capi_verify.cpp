@@ -84,18 +84,22 @@ static int ref_reserve(sbwtgpu_refseqs *r, int64_t slots, int64_t seqs) {
 }
 
 // [SbwtVerifyHeader][the list: 4 bytes per read]
-static int64_t verify_workspace_bytes(int64_t n_reads) {
+int64_t sbwt_capi::verify_workspace_bytes(int64_t n_reads) {
     if (n_reads < 0) n_reads = 0;
     return (int64_t)sizeof(SbwtVerifyHeader) + align256(n_reads * 4);
 }
 
-static int check_verify(const sbwtgpu_refseqs *r, int64_t n_reads, int band) {
+int sbwt_capi::check_verify(const sbwtgpu_refseqs *r, int64_t n_reads, int band) {
     if (!r) return fail(SBWTGPU_ERR_INVALID_ARG, "refseqs: the object is NULL");
     if (band < 0 || band > SBWTGPU_VERIFY_MAX_BAND)
         return fail(SBWTGPU_ERR_INVALID_ARG, "refseqs: band must be in 0 .. %d, not %d", SBWTGPU_VERIFY_MAX_BAND, band);
     if (n_reads < 0) return fail(SBWTGPU_ERR_INVALID_ARG, "refseqs: negative n_reads");
     if (n_reads >= ((int64_t)1 << 31)) return fail(SBWTGPU_ERR_INVALID_ARG, "refseqs: 2^31 reads or more in one call: split the batch");
     return SBWTGPU_OK;
+}
+
+RefSeqsView sbwt_capi::refseqs_view(const sbwtgpu_refseqs *r) {
+    return RefSeqsView{r->device, r->d_tab, (int64_t)r->len.size(), r->d_bits, r->d_valid};
 }
 
 extern "C" {

@@ -2,7 +2,7 @@
 // sbwtgpu_capi_reads.cpp (matching statistics, set operations, read hits, unitigs and their graph, walks, bubbles) and
 // sbwtgpu_capi_colors.cpp (colours, colour sets, pseudoalignment, screen) and sbwtgpu_capi_placement.cpp (reference positions and
 // all occurrences per column, read mapping over either) and sbwtgpu_capi_verify.cpp (the packed reference sequences and the
-// verification of mapped reads against them).  Nothing here is part of the library's interface:
+// verification of mapped reads against them) and sbwtgpu_capi_align.cpp (the alignment of verified reads).  Nothing here is part of the library's interface:
 // every name has hidden visibility, and whatever holds state (the error text, the parked slots, the int32 switch of a search
 // call) is defined once, in sbwtgpu_capi.cpp.
 #pragma once
@@ -93,6 +93,7 @@ extern int64_t g_gram_mfma_min_sets, g_gram_flush_sets;
 extern int64_t g_pos_chunk_bases, g_occ_chunk_bases;        // sbwtgpu_capi_placement.cpp
 extern int g_pos_map_table, g_occ_map_table;
 extern int g_verify_fast_bases;                             // sbwtgpu_capi_verify.cpp
+extern int g_align_fast_edit;                               // sbwtgpu_capi_align.cpp
 
 }  // namespace sbwt_capi
 
@@ -175,6 +176,18 @@ struct StrandSearch {
 };
 int search_strands_dev(const sbwtgpu_index *idx, const char *d_bases, int64_t total_bases, const int64_t *d_read_off, int64_t n_reads,
                        int strands, void *d_ws, int64_t ws_bytes, void *stream, StrandSearch &out);
+
+// sbwtgpu_capi_verify.cpp, for the align calls (sbwtgpu_capi_align.cpp): what a verify call asks of its arguments, the bytes of
+// its workspace, and what the kernels get of a reference object (d_tab: its SbwtRefSeq entries)
+struct RefSeqsView {
+    int device;
+    const void *d_tab;
+    int64_t n_seqs;
+    const unsigned long long *d_bits, *d_valid;
+};
+int check_verify(const sbwtgpu_refseqs *r, int64_t n_reads, int band);
+int64_t verify_workspace_bytes(int64_t n_reads);
+RefSeqsView refseqs_view(const sbwtgpu_refseqs *r);
 
 // The length of read r as every host entry point checks it while it walks the offsets: not negative, below 2^31
 inline int check_read_length(const int64_t *read_off, int64_t r) {

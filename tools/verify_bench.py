@@ -32,9 +32,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def draw_reads(genomes, n_reads, seed, dev, read_len, sub_rate, indel_share):
+def draw_reads(genomes, n_reads, seed, dev, read_len, sub_rate, indel_share, planted=False):
     """reads of known origin: substitutions at sub_rate, and in indel_share of them one indel of 1 .. 3 bases (inserted into
-    the read or deleted from it, at a random place); (bases, the genome of each, its offset there, whether it has an indel)"""
+    the read or deleted from it, at a random place); (bases, the genome of each, its offset there, whether it has an indel);
+    planted: also the indel's length per read, positive for an insertion into the read, negative for a deletion, 0 for none"""
     import torch
     gen = torch.Generator(device=dev)
     gen.manual_seed(seed)
@@ -48,6 +49,7 @@ def draw_reads(genomes, n_reads, seed, dev, read_len, sub_rate, indel_share):
     origin = torch.empty(n_reads, dtype=torch.int64, device=dev)
     at = torch.empty(n_reads, dtype=torch.int64, device=dev)
     has = torch.zeros(n_reads, dtype=torch.bool, device=dev)
+    length = torch.zeros(n_reads, dtype=torch.int64, device=dev)
     ar = torch.arange(read_len, device=dev)
     chunk = 1 << 20
     for lo in range(0, n_reads, chunk):
@@ -75,7 +77,8 @@ def draw_reads(genomes, n_reads, seed, dev, read_len, sub_rate, indel_share):
         origin[lo:lo + n] = which
         at[lo:lo + n] = pos
         has[lo:lo + n] = indel
-    return out, origin, at, has
+        length[lo:lo + n] = torch.where(ins, d, torch.where(dele, -d, torch.zeros_like(d)))
+    return (out, origin, at, has, length) if planted else (out, origin, at, has)
 
 
 def main():
