@@ -1603,6 +1603,122 @@ int     sbwtgpu_align_dev(const sbwtgpu_refseqs *r, const char *d_bases, int64_t
 int     sbwtgpu_align_batch(const sbwtgpu_refseqs *r, const char *bases, const int64_t *read_off, int64_t n_reads, const sbwtgpu_read_map *map,
                             int band, sbwtgpu_read_verify *verify_out, sbwtgpu_read_align *out, int64_t *op_off, uint32_t **ops_out, int64_t *n_ops);
 
+/* ---- pileup of aligned reads ----
+ * The align calls above end in a per-read record.  A pileup sums those records over a read set: what the sample says about
+ * reference base p -- depth, the bases seen, deletions and insertions -- in an accumulator that lives on the device across
+ * batches.  It is the reference-coordinate counterpart of sbwtgpu_genotype_*, which works on the graph.  The terms of the two
+ * headings above hold unchanged: valid base, oriented read r, "coordinate p matches r[j]", edit, ref_begin, ref_end, and the
+ * runs.  Everything is exact integers.
+ * Filter
+ *   sbwtgpu_pileup_filter is 16 bytes: int32 min_votes, require_unique, max_edit, reserved.  A read is PILED iff all of these
+ *   hold:
+ *   - Its align record has n_ops > 0.
+ *   - 0 <= seq < n_seqs of the pileup.
+ *   - votes >= min_votes.
+ *   - require_unique == 0 or votes > votes2.
+ *   - max_edit < 0 or edit <= max_edit.
+ *   reserved must be 0.  Every other read is OFFERED only.
+ * Columns
+ *   Replay the runs of a piled read from p = ref_begin, j = 0.  Let n be the length of sequence seq.
+ *   - = at p: covers p.
+ *   - X at p: covers p.  Let b = r[j], the base of the ORIENTED read.  For strand 1 that is the complement of read[L - 1 - j].
+ *     - If b is valid, it is an observation of base b at p.
+ *     - If b is not valid, it is an observation of `other`.
+ *   - D at p: covers p and is an observation of `del`.
+ *   - I run of length l:
+ *     - If it is the first or the last run of the alignment it is a CLIP.  It adds l to the scalar n_clipped and nothing else.
+ *     - Otherwise it is one observation of `ins` at its anchor, the coordinate p - 1 of the column before it.  This is VCF's
+ *       convention.  The inserted bases themselves are not kept.
+ *   A column or anchor with p outside [0, n) adds one to the scalar n_overhang and nothing per base.
+ * The per-base record
+ *   sbwtgpu_pileup_base is 32 bytes, uint32 depth, n[4], n_del, n_ins, n_other.
+ *   - depth is the number of columns covering p.
+ *   - n[c] counts observations of base code c (A 0, C 1, G 2, T 3).  The = columns count under the reference's own code.
+ *   - n_del, n_ins and n_other are as above.
+ *   Properties:
+ *   - depth = n[0] + n[1] + n[2] + n[3] + n_del + n_other.
+ *   - At an invalid reference base no = exists, so the record holds only what the X and D columns gave.
+ *   - n_ins <= depth.
+ *   - The sum of depth over all bases, plus the overhang columns, is the sum of ref_end - ref_begin over the piled reads.
+ *   - The pileup of a read set does not depend on batch boundaries, order, chunking or the number of host threads.
+ *   - (rc(read), 1 - strand) piles as (read, strand).
+ * Calls
+ *   Thresholds are min_depth >= 1, min_alt >= 1 and min_frac_ppm in 0 ... 10^6.  Calls are made at a VALID reference base p only.
+ *   - A candidate allele a runs through 0 ... 3 except the reference's code, then 4 (DEL, count n_del), then 5 (INS, count n_ins).
+ *   - A candidate with count c is CALLED iff depth >= min_depth, c >= min_alt and c*10^6 >= min_frac_ppm*depth.  The
+ *     products are 64-bit.
+ *   - sbwtgpu_pileup_call is 32 bytes: int64 pos; int32 seq, allele, ref, depth, count, ref_count.  ref is the reference's code
+ *     and ref_count is n[ref].
+ *   - Calls come in ascending (seq, pos, allele).
+ * Not built: consecutive deleted bases joined into one event, the inserted sequence, base qualities, a consensus sequence, VCF
+ * or SAM files, the runner-up placement.
+ * The object
+ *   sbwtgpu_pileup_create(r, out) covers the sequences r holds at that moment.  r must outlive the pileup, and, as for the verify
+ *   calls, no call on the pileup may run during an add to r.  It allocates 32 bytes per base of r's slots (units of 64 bases, as
+ *   the packed layout has them), one entry more, 256 bytes of scalars and 8 bytes per 1024 entries for the read-outs.
+ *   SBWTGPU_ERR_OOM leaves nothing allocated.  sbwtgpu_pileup_reset zeroes everything; it waits for the device first.
+ *   The counters lie at the coordinates of r's layout: base p of sequence s is entry 64 * slot(s) + p.  One of the eight words
+ *   of an entry is a DIFFERENCE ARRAY: every coordinate of [ref_begin, ref_end) is exactly one of = X D, so the = columns need
+ *   no counter.  A piled read adds +1 at ref_begin and -1 at ref_end (both clamped to [0, n]) and one to a counter per X and D
+ *   column and per interior I run.  At read-out the depth is the prefix sum over ALL entries, and the matches are the depth
+ *   minus the rest.  A read's -1 at n of a sequence whose length is a multiple of 64 lands on the entry that the next
+ *   sequence's coordinate 0 uses; the prefix sum over all entries still gives every base its true value.
+ * Adding
+ *   sbwtgpu_pileup_add_aligned_dev takes what sbwtgpu_align_dev took and wrote for the same batch: bases, offsets, map records,
+ *   d_verify, d_align, d_op_off and d_ops.  THE RUNS MUST ALL BE THERE: it is the caller's duty to have given sbwtgpu_align_dev
+ *   an ops_cap >= the total.  It has no workspace, is asynchronous on `stream`, never synchronises and never allocates.  One
+ *   kernel, ONE LANE per read: the filter, the walk over the read's runs, two atomics on the difference array and one 32-bit
+ *   atomic per X or D column and per interior I run; the scalars go to the 256-byte block once per wave.
+ *   A lane loops once per column of its X and D runs, so a wave takes as long as its read with the most such columns: one
+ *   long D run (a read of several hundred bases beside a large deletion, band permitting) holds its 63 neighbours for that many
+ *   steps.  The run lengths are trusted as sbwtgpu_align_dev wrote them.
+ *   sbwtgpu_pileup_add_dev takes reads and map records and runs sbwtgpu_align_dev first, unchanged, then the same kernel.  Its
+ *   workspace, of sbwtgpu_pileup_workspace_bytes (a multiple of 256, non-decreasing in both arguments, 16-byte aligned), holds
+ *   the align workspace first, then the verify and align records and the run offsets, then room for 2 L runs per read (the bound
+ *   of sbwtgpu_align_batch).  sbwtgpu_pileup_add_batch is the same call on host buffers: one staged range, not pipelined.
+ *   Overflow: an add that would take the reads offered since the last reset above 2^31 - 1 is refused, so no 32-bit counter can
+ *   wrap.
+ * Reading out
+ *   sbwtgpu_pileup_info: any output may be NULL.  n_columns is the sum of depth over all bases.  sbwtgpu_pileup_counts_copy
+ *   writes the len records of coordinates pos .. pos + len of sequence seq to host memory; sbwtgpu_pileup_counts_dev writes them
+ *   to device memory, asynchronously on `stream` (it sees the adds that `stream` is ordered after).  sbwtgpu_pileup_calls
+ *   returns the calls in memory of the library (release it with sbwtgpu_free_host), NULL with *n = 0 for no calls: count, device
+ *   scan, fill.  Read-out does not disturb the accumulators: an add after a read-out continues the same pileup.
+ *   COST OF A READ-OUT: every counts and calls call first sums the difference array over ALL entries (one pass over the
+ *   table's 32 bytes per base), however small the range asked for; nothing is cached between calls.  Ask for long ranges.
+ *   counts_copy and calls also allocate their result on the device per call.
+ * Concurrency: adds from several host threads on one object are safe, since the table is built on atomic adds.  info, counts,
+ * calls and reset serialise on the object; info, counts_copy, calls and reset wait for the device and so see every add that has
+ * returned.  That wait is hipDeviceSynchronize: it waits for EVERY stream of the device, work that has nothing to do with the
+ * pileup included, and holds the object's mutex meanwhile.  counts_dev waits for nothing.
+ * Refusals (SBWTGPU_ERR_INVALID_ARG with a message that names the cause): NULL arguments; reserved != 0; band outside 0 ... 256;
+ * n_reads < 0 or >= 2^31; the overflow rule; a workspace that is too small; counts outside its sequence; thresholds out of
+ * range. */
+typedef struct { int32_t min_votes; int32_t require_unique; int32_t max_edit; int32_t reserved; } sbwtgpu_pileup_filter;
+typedef struct { uint32_t depth; uint32_t n[4]; uint32_t n_del; uint32_t n_ins; uint32_t n_other; } sbwtgpu_pileup_base;
+typedef struct { int64_t pos; int32_t seq; int32_t allele; int32_t ref; int32_t depth; int32_t count; int32_t ref_count; } sbwtgpu_pileup_call;
+typedef struct sbwtgpu_pileup sbwtgpu_pileup;
+#define SBWTGPU_PILEUP_DEL 4
+#define SBWTGPU_PILEUP_INS 5
+int     sbwtgpu_pileup_create(const sbwtgpu_refseqs *r, sbwtgpu_pileup **out);
+int     sbwtgpu_pileup_reset(sbwtgpu_pileup *p);
+void    sbwtgpu_pileup_destroy(sbwtgpu_pileup *p);
+int     sbwtgpu_pileup_add_aligned_dev(sbwtgpu_pileup *p, const char *d_bases, int64_t total_bases, const int64_t *d_read_off, int64_t n_reads,
+                                       const sbwtgpu_read_map *d_map, const sbwtgpu_read_verify *d_verify, const sbwtgpu_read_align *d_align,
+                                       const int64_t *d_op_off, const uint32_t *d_ops, const sbwtgpu_pileup_filter *f, void *stream);
+int64_t sbwtgpu_pileup_workspace_bytes(int64_t total_bases, int64_t n_reads);
+int     sbwtgpu_pileup_add_dev(sbwtgpu_pileup *p, const char *d_bases, int64_t total_bases, const int64_t *d_read_off, int64_t n_reads,
+                               const sbwtgpu_read_map *d_map, int band, const sbwtgpu_pileup_filter *f,
+                               void *d_workspace, int64_t workspace_bytes, void *stream);
+int     sbwtgpu_pileup_add_batch(sbwtgpu_pileup *p, const char *bases, const int64_t *read_off, int64_t n_reads, const sbwtgpu_read_map *map,
+                                 int band, const sbwtgpu_pileup_filter *f);
+int     sbwtgpu_pileup_info(const sbwtgpu_pileup *p, int64_t *n_seqs, int64_t *total_bases, int64_t *n_offered, int64_t *n_piled,
+                            int64_t *n_columns, int64_t *n_clipped, int64_t *n_overhang, int64_t *device_bytes);
+int     sbwtgpu_pileup_counts_copy(const sbwtgpu_pileup *p, int64_t seq, int64_t pos, int64_t len, sbwtgpu_pileup_base *out);
+int     sbwtgpu_pileup_counts_dev(const sbwtgpu_pileup *p, int64_t seq, int64_t pos, int64_t len, sbwtgpu_pileup_base *d_out, void *stream);
+int     sbwtgpu_pileup_calls(const sbwtgpu_pileup *p, int32_t min_depth, int32_t min_alt, int32_t min_frac_ppm, sbwtgpu_pileup_call **out,
+                             int64_t *n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,8 +43,8 @@ def _glob(d, exts):
 
 
 GPU_SRCS = [os.path.join(CSRC, f) for f in ("sbwt_search.hip", "sbwt_search_fused.hip", "sbwt_api_kernels.hip", "sbwt_derived.hip", "sbwt_build.hip", "sbwt_sort.hip",
-                                              "sbwt_format.hip", "sbwt_ms.hip", "sbwt_unitigs.hip", "sbwt_setops.hip", "sbwt_readhits.hip", "sbwt_walks.hip", "sbwt_colors.hip", "sbwt_colorsets.hip", "sbwt_colormerge.hip", "sbwt_colormatrix.hip", "sbwt_colorselect.hip", "sbwt_screen.hip", "sbwt_bubbles.hip", "sbwt_genotype.hip", "sbwt_positions.hip", "sbwt_occurrences.hip", "sbwt_verify.hip", "sbwt_align.hip", "sbwtgpu_capi.cpp", "sbwtgpu_capi_reads.cpp", "sbwtgpu_capi_colors.cpp", "sbwtgpu_capi_placement.cpp", "sbwtgpu_capi_verify.cpp", "sbwtgpu_capi_align.cpp")]
-GPU_DEPS = GPU_SRCS + [os.path.join(CSRC, f) for f in ("sbwt_device.h", "sbwt_kernels_common.h", "sbwt_scan.h", "sbwt_ms.h", "sbwt_unitigs.h", "sbwt_colwalk.h", "sbwt_setops.h", "sbwt_readhits.h", "sbwt_walks.h", "sbwt_colors.h", "sbwt_colorsets.h", "sbwt_colormerge.h", "sbwt_colormatrix.h", "sbwt_colorselect.h", "sbwt_screen.h", "sbwt_bubbles.h", "sbwt_genotype.h", "sbwt_positions.h", "sbwt_posmap.h", "sbwt_occurrences.h", "sbwt_verify.h", "sbwt_verify_text.h", "sbwt_align.h", "sbwt_search_fused_loop.inc", "sbwtgpu_internal.h", "sbwt_read_chunks.h")] + \
+                                              "sbwt_format.hip", "sbwt_ms.hip", "sbwt_unitigs.hip", "sbwt_setops.hip", "sbwt_readhits.hip", "sbwt_walks.hip", "sbwt_colors.hip", "sbwt_colorsets.hip", "sbwt_colormerge.hip", "sbwt_colormatrix.hip", "sbwt_colorselect.hip", "sbwt_screen.hip", "sbwt_bubbles.hip", "sbwt_genotype.hip", "sbwt_positions.hip", "sbwt_occurrences.hip", "sbwt_verify.hip", "sbwt_align.hip", "sbwt_pileup.hip", "sbwtgpu_capi.cpp", "sbwtgpu_capi_reads.cpp", "sbwtgpu_capi_colors.cpp", "sbwtgpu_capi_placement.cpp", "sbwtgpu_capi_verify.cpp", "sbwtgpu_capi_align.cpp", "sbwtgpu_capi_pileup.cpp")]
+GPU_DEPS = GPU_SRCS + [os.path.join(CSRC, f) for f in ("sbwt_device.h", "sbwt_kernels_common.h", "sbwt_scan.h", "sbwt_ms.h", "sbwt_unitigs.h", "sbwt_colwalk.h", "sbwt_setops.h", "sbwt_readhits.h", "sbwt_walks.h", "sbwt_colors.h", "sbwt_colorsets.h", "sbwt_colormerge.h", "sbwt_colormatrix.h", "sbwt_colorselect.h", "sbwt_screen.h", "sbwt_bubbles.h", "sbwt_genotype.h", "sbwt_positions.h", "sbwt_posmap.h", "sbwt_occurrences.h", "sbwt_verify.h", "sbwt_verify_text.h", "sbwt_align.h", "sbwt_pileup.h", "sbwt_search_fused_loop.inc", "sbwtgpu_internal.h", "sbwt_read_chunks.h")] + \
     [os.path.join(INC, "sbwtgpu.h")]
 MEGA_TEST_SHIFT = 12
 MEGA_TEST_LIB = os.path.join(LIB, "libsbwtgpu_mega%d.so" % MEGA_TEST_SHIFT)

@@ -94,6 +94,9 @@ EXPORTED_SYMBOLS = [
     "sbwtgpu_refseqs_lengths_copy", "sbwtgpu_refseqs_get", "sbwtgpu_refseqs_verify_workspace_bytes", "sbwtgpu_refseqs_verify_dev",
     "sbwtgpu_refseqs_verify_batch",
     "sbwtgpu_align_workspace_bytes", "sbwtgpu_align_dev", "sbwtgpu_align_batch",
+    "sbwtgpu_pileup_create", "sbwtgpu_pileup_reset", "sbwtgpu_pileup_destroy", "sbwtgpu_pileup_add_aligned_dev",
+    "sbwtgpu_pileup_workspace_bytes", "sbwtgpu_pileup_add_dev", "sbwtgpu_pileup_add_batch", "sbwtgpu_pileup_info",
+    "sbwtgpu_pileup_counts_copy", "sbwtgpu_pileup_counts_dev", "sbwtgpu_pileup_calls",
 ]
 
 SETOP_UNION, SETOP_INTERSECTION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -227,6 +230,13 @@ READ_VERIFY_DTYPE = np.dtype([("ref_end", np.int64), ("mismatches", np.int32), (
 # sbwtgpu_read_align: where the best alignment of a verified read begins, its number of runs and of = columns
 READ_ALIGN_DTYPE = np.dtype([("ref_begin", np.int64), ("n_ops", np.int32), ("n_eq", np.int32)])
 CIGAR_LETTERS = {1: "I", 2: "D", 7: "=", 8: "X"}       # the codes of a run, as in BAM
+# the pileup of aligned reads: sbwtgpu_pileup_base (one per reference base), sbwtgpu_pileup_call, sbwtgpu_pileup_filter
+PILEUP_BASE_DTYPE = np.dtype([("depth", np.uint32), ("n", np.uint32, (4,)), ("n_del", np.uint32), ("n_ins", np.uint32),
+                              ("n_other", np.uint32)])
+PILEUP_CALL_DTYPE = np.dtype([("pos", np.int64), ("seq", np.int32), ("allele", np.int32), ("ref", np.int32), ("depth", np.int32),
+                              ("count", np.int32), ("ref_count", np.int32)])
+PILEUP_FILTER_DTYPE = np.dtype([("min_votes", np.int32), ("require_unique", np.int32), ("max_edit", np.int32), ("reserved", np.int32)])
+PILEUP_DEL, PILEUP_INS = 4, 5   # SBWTGPU_PILEUP_DEL, SBWTGPU_PILEUP_INS: the alleles of a call beside the base codes 0 .. 3
 
 VERIFY_MAX_BAND = 256           # SBWTGPU_VERIFY_MAX_BAND
 VERIFY_MAX_READ = 1024          # SBWTGPU_VERIFY_MAX_READ
@@ -465,6 +475,19 @@ def lib() -> C.CDLL:
         L.sbwtgpu_align_workspace_bytes.restype = i64
         L.sbwtgpu_align_dev.argtypes = [vp, vp, i64, vp, i64, vp, ci, vp, vp, vp, vp, i64, vp, i64, vp]
         L.sbwtgpu_align_batch.argtypes = [vp, vp, vp, i64, vp, ci, vp, vp, vp, C.POINTER(vp), C.POINTER(i64)]
+        L.sbwtgpu_pileup_create.argtypes = [vp, C.POINTER(vp)]
+        L.sbwtgpu_pileup_reset.argtypes = [vp]
+        L.sbwtgpu_pileup_destroy.argtypes = [vp]
+        L.sbwtgpu_pileup_destroy.restype = None
+        L.sbwtgpu_pileup_add_aligned_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+        L.sbwtgpu_pileup_workspace_bytes.argtypes = [i64, i64]
+        L.sbwtgpu_pileup_workspace_bytes.restype = i64
+        L.sbwtgpu_pileup_add_dev.argtypes = [vp, vp, i64, vp, i64, vp, ci, vp, vp, i64, vp]
+        L.sbwtgpu_pileup_add_batch.argtypes = [vp, vp, vp, i64, vp, ci, vp]
+        L.sbwtgpu_pileup_info.argtypes = [vp] + [C.POINTER(i64)] * 8
+        L.sbwtgpu_pileup_counts_copy.argtypes = [vp, i64, i64, i64, vp]
+        L.sbwtgpu_pileup_counts_dev.argtypes = [vp, i64, i64, i64, vp, vp]
+        L.sbwtgpu_pileup_calls.argtypes = [vp, ci, ci, ci, C.POINTER(vp), C.POINTER(i64)]
     except AttributeError:
         if not os.environ.get("SBWTGPU_LIB"):
             raise
@@ -1969,6 +1992,106 @@ class RefSeqs(_Owner):
     @staticmethod
     def align_workspace_bytes(total_bases: int, n_reads: int) -> int:
         return int(lib().sbwtgpu_align_workspace_bytes(total_bases, n_reads))
+
+    def pileup(self) -> "Pileup":
+        """sbwtgpu_pileup_create: an empty pileup over the sequences the object holds now."""
+        h = C.c_void_p()
+        _check(lib().sbwtgpu_pileup_create(self._h, C.byref(h)))
+        return Pileup(h, self)
+
+
+def pileup_filter(min_votes: int = 0, unique: bool = False, max_edit: int = -1, reserved: int = 0) -> np.ndarray:
+    """One PILEUP_FILTER_DTYPE record."""
+    f = np.zeros(1, dtype=PILEUP_FILTER_DTYPE)
+    f[0] = (min_votes, 1 if unique else 0, max_edit, reserved)
+    return f
+
+
+class Pileup(_Owner):
+    """Owns an sbwtgpu_pileup handle: the per-base counters of a read set's alignments on the sequences of a RefSeqs object,
+    which live on the device across adds (include/sbwtgpu.h, "pileup of aligned reads").  Everything is exact integers.  The
+    RefSeqs object is kept referenced and must not be added to while a call on the pileup runs."""
+
+    _destroy = "sbwtgpu_pileup_destroy"
+
+    def __init__(self, handle, refseqs: "RefSeqs"):
+        self._h = handle
+        self.refseqs = refseqs
+
+    def add(self, bases, read_off, records, band: int = 8, min_votes: int = 0, unique: bool = False, max_edit: int = -1) -> None:
+        """sbwtgpu_pileup_add_batch: the reads (uint8 bases, int64 offsets) with their READ_MAP_DTYPE records are verified,
+        aligned and, where the filter passes, piled."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        records = np.ascontiguousarray(records, dtype=READ_MAP_DTYPE)
+        n = max(len(read_off) - 1, 0)
+        if len(records) != n:
+            raise ValueError("%d map records for %d reads" % (len(records), n))
+        f = pileup_filter(min_votes, unique, max_edit)
+        _check(lib().sbwtgpu_pileup_add_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n, records.ctypes.data if n else None, band,
+                                              f.ctypes.data))
+
+    def add_reads(self, reads: Sequence[bytes], records, band: int = 8, min_votes: int = 0, unique: bool = False, max_edit: int = -1) -> None:
+        """The same for a list of byte strings."""
+        self.add(*concat_reads(reads), records, band, min_votes, unique, max_edit)
+
+    def add_dev(self, d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_map: int, d_ws: int, ws_bytes: int, band: int = 8,
+                min_votes: int = 0, unique: bool = False, max_edit: int = -1, stream: int = 0) -> None:
+        """sbwtgpu_pileup_add_dev (raw device pointers; d_map: n_reads records of 32 bytes; workspace of workspace_bytes):
+        asynchronous on stream."""
+        f = pileup_filter(min_votes, unique, max_edit)
+        _check(lib().sbwtgpu_pileup_add_dev(self._h, d_bases or None, total_bases, d_read_off or None, n_reads, d_map or None, band,
+                                            f.ctypes.data, d_ws or None, ws_bytes, stream or None))
+
+    def add_aligned_dev(self, d_bases: int, total_bases: int, d_read_off: int, n_reads: int, d_map: int, d_verify: int, d_align: int,
+                        d_op_off: int, d_ops: int, min_votes: int = 0, unique: bool = False, max_edit: int = -1, stream: int = 0) -> None:
+        """sbwtgpu_pileup_add_aligned_dev (raw device pointers: what align_dev took and wrote, every run stored): asynchronous on
+        stream."""
+        f = pileup_filter(min_votes, unique, max_edit)
+        _check(lib().sbwtgpu_pileup_add_aligned_dev(self._h, d_bases or None, total_bases, d_read_off or None, n_reads, d_map or None,
+                                                    d_verify or None, d_align or None, d_op_off or None, d_ops or None, f.ctypes.data,
+                                                    stream or None))
+
+    @staticmethod
+    def workspace_bytes(total_bases: int, n_reads: int) -> int:
+        return int(lib().sbwtgpu_pileup_workspace_bytes(total_bases, n_reads))
+
+    def info(self) -> dict:
+        """n_seqs, total_bases, n_offered, n_piled, n_columns (the sum of depth), n_clipped, n_overhang and device_bytes."""
+        v = [C.c_int64() for _ in range(8)]
+        _check(lib().sbwtgpu_pileup_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("n_seqs", "total_bases", "n_offered", "n_piled", "n_columns", "n_clipped", "n_overhang", "device_bytes"),
+                        (x.value for x in v)))
+
+    def counts(self, seq: int, pos: int = 0, length: Optional[int] = None) -> np.ndarray:
+        """sbwtgpu_pileup_counts_copy: the PILEUP_BASE_DTYPE records of bases pos .. pos + length of sequence seq (None: to its
+        end)."""
+        if length is None:
+            lens = self.refseqs.lengths()
+            length = int(lens[seq]) - pos if 0 <= seq < len(lens) else 0
+        out = np.zeros(max(length, 0), dtype=PILEUP_BASE_DTYPE)
+        _check(lib().sbwtgpu_pileup_counts_copy(self._h, seq, pos, length, out.ctypes.data if len(out) else None))
+        return out
+
+    def counts_dev(self, seq: int, pos: int, length: int, d_out: int, stream: int = 0) -> None:
+        """sbwtgpu_pileup_counts_dev (d_out: length records of 32 bytes on the device): asynchronous on stream."""
+        _check(lib().sbwtgpu_pileup_counts_dev(self._h, seq, pos, length, d_out or None, stream or None))
+
+    def calls(self, min_depth: int = 1, min_alt: int = 1, min_frac_ppm: int = 0) -> np.ndarray:
+        """sbwtgpu_pileup_calls: the PILEUP_CALL_DTYPE records in ascending (seq, pos, allele)."""
+        p, n = C.c_void_p(), C.c_int64(0)
+        _check(lib().sbwtgpu_pileup_calls(self._h, min_depth, min_alt, min_frac_ppm, C.byref(p), C.byref(n)))
+        try:
+            out = np.empty(n.value, dtype=PILEUP_CALL_DTYPE)
+            if n.value:
+                C.memmove(out.ctypes.data, p.value, n.value * PILEUP_CALL_DTYPE.itemsize)
+        finally:
+            if p.value:
+                lib().sbwtgpu_free_host(p)
+        return out
+
+    def reset(self) -> None:
+        _check(lib().sbwtgpu_pileup_reset(self._h))
 
 
 class ColorSetsBuilder(_Owner):

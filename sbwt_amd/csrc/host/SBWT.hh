@@ -1228,4 +1228,57 @@ public:
     sbwtgpu_refseqs *h = nullptr;
 };
 
+// The pileup of a read set's alignments on the sequences of a RefSeqs object (include/sbwtgpu.h, "pileup of aligned reads"):
+// per-base counters that live on the device across adds, read out as records and as calls.  The RefSeqs object must outlive it
+// and must not be added to while a call on the pileup runs.
+class Pileup {
+public:
+    Pileup() = default;
+    Pileup(const Pileup &) = delete;
+    Pileup &operator=(const Pileup &) = delete;
+    Pileup(Pileup &&o) noexcept : h(o.h) { o.h = nullptr; }
+    Pileup &operator=(Pileup &&o) noexcept {
+        if (this != &o) {
+            sbwtgpu_pileup_destroy(h);
+            h = o.h; o.h = nullptr;
+        }
+        return *this;
+    }
+    ~Pileup() { sbwtgpu_pileup_destroy(h); }
+    // an empty pileup over the sequences r holds now
+    static Pileup create(const RefSeqs &r) {
+        Pileup p;
+        detail::gpu_check(sbwtgpu_pileup_create(r.h, &p.h));
+        return p;
+    }
+    // sbwtgpu_pileup_add_batch: the reads are verified and aligned at their map records and, where the filter passes, piled
+    void add(const char *bases, const int64_t *read_off, int64_t n_reads, const sbwtgpu_read_map *map, int band,
+             const sbwtgpu_pileup_filter &f = sbwtgpu_pileup_filter{0, 0, -1, 0}) {
+        detail::gpu_check(sbwtgpu_pileup_add_batch(h, bases, read_off, n_reads, map, band, &f));
+    }
+    void reset() { detail::gpu_check(sbwtgpu_pileup_reset(h)); }
+    struct Info { int64_t n_seqs = 0, total_bases = 0, n_offered = 0, n_piled = 0, n_columns = 0, n_clipped = 0, n_overhang = 0, device_bytes = 0; };
+    Info info() const {
+        Info i;
+        detail::gpu_check(sbwtgpu_pileup_info(h, &i.n_seqs, &i.total_bases, &i.n_offered, &i.n_piled, &i.n_columns, &i.n_clipped, &i.n_overhang,
+                                              &i.device_bytes));
+        return i;
+    }
+    // the records of bases pos .. pos + len of sequence seq
+    std::vector<sbwtgpu_pileup_base> counts(int64_t seq, int64_t pos, int64_t len) const {
+        std::vector<sbwtgpu_pileup_base> out((size_t)std::max<int64_t>(len, 0));
+        detail::gpu_check(sbwtgpu_pileup_counts_copy(h, seq, pos, len, out.data()));
+        return out;
+    }
+    // the calls in ascending (seq, pos, allele)
+    std::vector<sbwtgpu_pileup_call> calls(int32_t min_depth = 1, int32_t min_alt = 1, int32_t min_frac_ppm = 0) const {
+        sbwtgpu_pileup_call *p = nullptr;
+        int64_t n = 0;
+        detail::gpu_check(sbwtgpu_pileup_calls(h, min_depth, min_alt, min_frac_ppm, &p, &n));
+        struct Free { sbwtgpu_pileup_call *p; ~Free() { sbwtgpu_free_host(p); } } guard{p};      // (the copy may throw)
+        return std::vector<sbwtgpu_pileup_call>(p, p + n);
+    }
+    sbwtgpu_pileup *h = nullptr;
+};
+
 }  // namespace sbwt

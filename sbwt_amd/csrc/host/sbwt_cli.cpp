@@ -23,7 +23,8 @@
 //               two index files combined on the GPU without their input sequences: the index `sbwt build` would write for
 //               the result's k-mers
 //   sbwt read-hits -i <index> -q <query> -o <out> [-z] [--both-strands] [--positions <index.pos> | --occurrences <index.occ> [--max-occ N]]
-//               [--refs <refs.txt> [--band N] [--cigar]]
+//               [--refs <refs.txt> [--band N] [--cigar] [--pileup-out <pile.tsv>] [--calls-out <calls.tsv>] [--min-votes N] [--unique]
+//               [--max-edit N] [--min-depth N] [--min-alt N] [--min-frac F]]
 //               one line per read: n_kmers n_found covered_bases longest_run; with --positions six more columns, the read's
 //               placement on the references by diagonal voting: seq strand start votes votes2 n_anchored; with --occurrences
 //               the same six columns from the vote over every occurrence of every k-mer (--max-occ, default 1024: a k-mer
@@ -31,7 +32,10 @@
 //               their sequences numbered as the position file numbers them) beside a placement option three more columns,
 //               the placement checked against the reference's bases: mismatches edit ref_end (--band, default 8: the edit
 //               distance is the best over the window of band bases either side; -1 -1 0: no placement to check); with --cigar
-//               two more, the best alignment in that window: ref_begin cigar (runs of = X I D; 0 *: no alignment)
+//               two more, the best alignment in that window: ref_begin cigar (runs of = X I D; 0 *: no alignment); with
+//               --pileup-out and --calls-out the alignments of all reads are piled up on the references (--min-votes, --unique,
+//               --max-edit say which reads count) and written per base with depth > 0, seq pos ref depth A C G T del ins other,
+//               and per call (--min-depth, --min-alt, --min-frac), seq pos ref alt depth count; the hits file does not change
 //   sbwt build-colors -i <index> -r <refs.txt> -o <colours> [--both-strands] [--wide | --compress [--stream]]
 //               [--positions-out <index.pos>] [--occurrences-out <index.occ>]
 //               one colour per listed reference file, set on the columns of the index's k-mers that the file holds
@@ -769,6 +773,80 @@ int matching_statistics_main(int argc, char **argv) {
     return 0;
 }
 
+// a fraction option as parts per million (defined with the colour helpers, below); allow_zero: 0 .. 1, not (0, 1]
+int64_t parse_threshold_ppm(const string &s, const char *option, bool allow_zero);
+
+// The two files of read-hits' pileup.  Both begin with a # line of the totals; pile.tsv has one line per base with depth > 0,
+// seq pos ref depth A C G T del ins other, and calls.tsv one per call, seq pos ref alt depth count (alt: A C G T - +).
+static void write_pileup_files(const RefSeqs &refseqs, const Pileup &pileup, const string &pilefile, const string &callsfile, int32_t min_depth,
+                               int32_t min_alt, int32_t min_frac_ppm) {
+    const Pileup::Info pi = pileup.info();
+    string head = "#";
+    const std::pair<const char *, int64_t> totals[] = {{"n_seqs", pi.n_seqs}, {"total_bases", pi.total_bases}, {"n_offered", pi.n_offered},
+                                                       {"n_piled", pi.n_piled}, {"n_columns", pi.n_columns}, {"n_clipped", pi.n_clipped},
+                                                       {"n_overhang", pi.n_overhang}};
+    for (const auto &t : totals) {
+        head.push_back(' ');
+        head.append(t.first);
+        head.push_back('=');
+        append_int(t.second, head);
+    }
+    head.push_back('\n');
+    if (!pilefile.empty()) {
+        seq_io::Buffered_ofstream writer(pilefile, false);
+        writer.write(head.data(), (int64_t)head.size());
+        vector<int64_t> len((size_t)pi.n_seqs);
+        if (sbwtgpu_refseqs_lengths_copy(refseqs.h, len.data()) != SBWTGPU_OK) throw std::runtime_error(string("Error: ") + sbwtgpu_last_error());
+        vector<char> ref;
+        string text;
+        const int64_t piece = (int64_t)1 << 20;
+        for (int64_t s = 0; s < pi.n_seqs; s++) {
+            for (int64_t pos = 0; pos < len[(size_t)s]; pos += piece) {
+                const int64_t n = std::min(piece, len[(size_t)s] - pos);
+                const vector<sbwtgpu_pileup_base> rec = pileup.counts(s, pos, n);
+                ref.resize((size_t)n);
+                if (sbwtgpu_refseqs_get(refseqs.h, s, pos, n, ref.data()) != SBWTGPU_OK) throw std::runtime_error(string("Error: ") + sbwtgpu_last_error());
+                text.clear();
+                for (int64_t q = 0; q < n; q++) {
+                    const sbwtgpu_pileup_base &b = rec[(size_t)q];
+                    if (b.depth == 0) continue;
+                    append_int(s, text);
+                    text.push_back('\t');
+                    append_int(pos + q, text);
+                    text.push_back('\t');
+                    text.push_back(ref[(size_t)q]);
+                    for (int64_t v : {(int64_t)b.depth, (int64_t)b.n[0], (int64_t)b.n[1], (int64_t)b.n[2], (int64_t)b.n[3], (int64_t)b.n_del, (int64_t)b.n_ins,
+                                      (int64_t)b.n_other}) {
+                        text.push_back('\t');
+                        append_int(v, text);
+                    }
+                    text.push_back('\n');
+                }
+                writer.write(text.data(), (int64_t)text.size());
+            }
+        }
+    }
+    if (!callsfile.empty()) {
+        seq_io::Buffered_ofstream writer(callsfile, false);
+        string text = head;
+        for (const sbwtgpu_pileup_call &c : pileup.calls(min_depth, min_alt, min_frac_ppm)) {
+            append_int(c.seq, text);
+            text.push_back('\t');
+            append_int(c.pos, text);
+            text.push_back('\t');
+            text.push_back("ACGT"[c.ref & 3]);
+            text.push_back('\t');
+            text.push_back("ACGT-+"[c.allele >= 0 && c.allele < 6 ? c.allele : 0]);
+            text.push_back('\t');
+            append_int(c.depth, text);
+            text.push_back('\t');
+            append_int(c.count, text);
+            text.push_back('\n');
+        }
+        writer.write(text.data(), (int64_t)text.size());
+    }
+}
+
 // sbwt read-hits: one line per read, `n_kmers n_found covered_bases longest_run` (include/sbwtgpu.h: the profile a screen of
 // reads against the index needs, 16 bytes per read from the GPU instead of a value per k-mer).  Batches go to the GPU one at a
 // time; the table is formatted on the host.
@@ -789,6 +867,14 @@ int read_hits_main(int argc, char **argv) {
         {"refs", 0, true, "With --positions or --occurrences: the list of reference files that build-colors -r took (FASTA or FASTQ, possibly gzipped, one per line). They are read in order and their sequences numbered 0, 1, ... as the position file numbers them; every line gains three more columns behind the six of the placement, the read checked against the reference's bases there: mismatches edit ref_end (mismatches on the voted diagonal, the best edit distance in the window of --band bases either side, the end of that alignment on the reference; -1 -1 0: no placement to check, and a read of more than 1024 bases gets its mismatches only, edit -1).", ""},
         {"band", 0, true, "With --refs: the bases either side of the voted placement that the edit distance may use (0 .. 256). The default is 8.", "8"},
         {"cigar", 0, false, "With --refs: every line gains two more columns behind mismatches edit ref_end, the best alignment in that window: ref_begin cigar (where the alignment begins on the reference, and its runs with the four letters = X I D: match, substitution, a read base that faces nothing, a reference base that faces nothing; 0 *: no alignment, for a read without a placement or of more than 1024 bases). A batch then holds room for its runs on the device, 8 bytes per base of --batch-bases beside some 300 MB of scratch (2 GB more at the default batch): lower --batch-bases on a small device. Reads of more than 256 bases, and reads of more than 31 edits, are aligned by a far slower kernel.", ""},
+        {"pileup-out", 0, true, "With --refs: the alignments of all reads of all query files are piled up on the references, and this file receives one line per reference base with depth > 0, tab-separated: seq pos ref depth A C G T del ins other (ref is N at a base that is not upper-case ACGT; the matches count under the reference's own base; ins counts the insertions behind the base). The first line is a # line with the totals: n_seqs total_bases n_offered n_piled n_columns n_clipped n_overhang. The hits file is what it is without the option.", ""},
+        {"calls-out", 0, true, "With --refs: the same pileup's calls, tab-separated: seq pos ref alt depth count, alt one of A C G T - + (- a deleted base, + an insertion behind the base), behind the same # line. See --min-depth, --min-alt and --min-frac.", ""},
+        {"min-votes", 0, true, "With --pileup-out or --calls-out: only reads whose placement has at least this many votes are piled. The default is 0.", "0"},
+        {"unique", 0, false, "With --pileup-out or --calls-out: only reads whose placement has more votes than the runner-up (votes > votes2) are piled.", ""},
+        {"max-edit", 0, true, "With --pileup-out or --calls-out: only reads of at most this many edits are piled (-1: no limit). The default is -1.", "-1"},
+        {"min-depth", 0, true, "With --calls-out: a call needs at least this depth at its base (at least 1). The default is 1.", "1"},
+        {"min-alt", 0, true, "With --calls-out: a call needs at least this many observations of its allele (at least 1). The default is 1.", "1"},
+        {"min-frac", 0, true, "With --calls-out: a call needs at least this fraction of the depth, a decimal number in 0 .. 1 with at most six decimals. The default is 0.", "0"},
         {"gpu", 0, true, "HIP device to run on.", "0"},
         {"batch-bases", 0, true, "Bases sent to the GPU per batch.", "268435456"},
         {"help", 'h', false, "Print usage", ""},
@@ -828,6 +914,36 @@ int read_hits_main(int argc, char **argv) {
     }
     const bool cigar = opts.count("cigar");
     if (cigar && refsfile.empty()) throw std::runtime_error("Error: --cigar needs --refs");
+    const string pilefile = opts.count("pileup-out") ? opts.get("pileup-out") : "";
+    const string callsfile = opts.count("calls-out") ? opts.get("calls-out") : "";
+    if (!pilefile.empty() && refsfile.empty()) throw std::runtime_error("Error: --pileup-out needs --refs");
+    if (!callsfile.empty() && refsfile.empty()) throw std::runtime_error("Error: --calls-out needs --refs");
+    const bool piling = !pilefile.empty() || !callsfile.empty();
+    // a number option of the pileup: `needs` names what it is for
+    auto pile_number = [&](const char *name, int64_t lo, int64_t hi, int64_t fallback, bool present, const char *needs) -> int64_t {
+        if (!opts.count(name)) return fallback;
+        if (!present) throw std::runtime_error(string("Error: --") + name + " needs " + needs);
+        const string text = opts.get(name);
+        char *end = nullptr;
+        const int64_t v = strtoll(text.c_str(), &end, 10);
+        if (text.empty() || *end != 0 || v < lo || v > hi)
+            throw std::runtime_error(string("Error: --") + name + " must be a number in " + std::to_string(lo) + " .. " + std::to_string(hi) + ", not " + text);
+        return v;
+    };
+    sbwtgpu_pileup_filter pile_filter{0, 0, -1, 0};
+    pile_filter.min_votes = (int32_t)pile_number("min-votes", 0, INT32_MAX, 0, piling, "--pileup-out or --calls-out");
+    pile_filter.max_edit = (int32_t)pile_number("max-edit", -1, INT32_MAX, -1, piling, "--pileup-out or --calls-out");
+    if (opts.count("unique")) {
+        if (!piling) throw std::runtime_error("Error: --unique needs --pileup-out or --calls-out");
+        pile_filter.require_unique = 1;
+    }
+    const int32_t min_depth = (int32_t)pile_number("min-depth", 1, INT32_MAX, 1, !callsfile.empty(), "--calls-out");
+    const int32_t min_alt = (int32_t)pile_number("min-alt", 1, INT32_MAX, 1, !callsfile.empty(), "--calls-out");
+    int32_t min_frac_ppm = 0;
+    if (opts.count("min-frac")) {
+        if (callsfile.empty()) throw std::runtime_error("Error: --min-frac needs --calls-out");
+        min_frac_ppm = (int32_t)parse_threshold_ppm(opts.get("min-frac"), "--min-frac", true);
+    }
     vector<string> refs;
     if (!refsfile.empty()) {
         check_readable(refsfile);
@@ -860,6 +976,8 @@ int read_hits_main(int argc, char **argv) {
             throw std::runtime_error("Error: " + refsfile + " holds " + std::to_string(refseqs.info().n_seqs) + " sequences, the placement file lists " +
                                      std::to_string(listed));
     }
+    Pileup pileup;
+    if (piling) pileup = Pileup::create(refseqs);
     vector<sbwtgpu_read_verify> verified;
     vector<sbwtgpu_read_align> aligned;
     vector<int64_t> op_off;
@@ -885,6 +1003,7 @@ int read_hits_main(int argc, char **argv) {
                 } else {
                     refseqs.verify(bases.data(), read_off.data(), n_reads, placed.data(), (int)band, verified.data());
                 }
+                if (piling) pileup.add(bases.data(), read_off.data(), n_reads, placed.data(), (int)band, pile_filter);
             }
             text.clear();
             for (size_t r = 0; r < rec.size(); r++) {
@@ -926,6 +1045,7 @@ int read_hits_main(int argc, char **argv) {
             total_reads += n_reads;
         });
     }
+    if (piling) write_pileup_files(refseqs, pileup, pilefile, callsfile, min_depth, min_alt, min_frac_ppm);
     write_log("us/read end-to-end: " + std::to_string((double)(cur_time_micros() - micros_start) / (double)std::max<int64_t>(1, total_reads)),
               LogLevel::MAJOR);
     return 0;
@@ -1081,8 +1201,8 @@ int set_op_main(int argc, char **argv) {
 // ---- colours and pseudoalignment (include/sbwtgpu.h) ----
 // `--threshold` (or the fraction of `option`) as parts per million, from its decimal text and without floating point:
 // "0.7" -> 700000, "1" -> 1000000.  Digits (at least one), optionally '.' and digits; what comes after the sixth decimal must
-// be zeros; 0 < value <= 1.
-int64_t parse_threshold_ppm(const string &s, const char *option = "--threshold") {
+// be zeros; 0 < value <= 1, or with allow_zero 0 <= value <= 1.
+int64_t parse_threshold_ppm(const string &s, const char *option = "--threshold", bool allow_zero = false) {
     const size_t dot = s.find('.');
     const string ip = s.substr(0, dot), fp = dot == string::npos ? string() : s.substr(dot + 1);
     bool ok = !ip.empty() && ip.size() <= 9 && (dot == string::npos || !fp.empty());
@@ -1096,8 +1216,9 @@ int64_t parse_threshold_ppm(const string &s, const char *option = "--threshold")
             else if (fp[i] != '0') ok = false;
         }
     }
-    if (!ok || ppm < 1 || ppm > 1000000)
-        throw std::runtime_error(string("Error: ") + option + " must be a decimal number in (0, 1] with at most six decimals, not '" + s + "'");
+    if (!ok || ppm < (allow_zero ? 0 : 1) || ppm > 1000000)
+        throw std::runtime_error(string("Error: ") + option + " must be a decimal number in " + (allow_zero ? "0 .. 1" : "(0, 1]") +
+                                 " with at most six decimals, not '" + s + "'");
     return ppm;
 }
 

@@ -6,7 +6,8 @@
 
 A layer's name stands for the regex of its kernels (LAYERS): `verify` is the reference pack / unpack and the two verify kernels
 of sbwt_verify.hip (profiles/verify_kernel_resources.txt), `align` the two align kernels of sbwt_align.hip in their two passes
-(profiles/align_kernel_resources.txt).
+(profiles/align_kernel_resources.txt), `pileup` the accumulate kernel and the read-out kernels of sbwt_pileup.hip
+(profiles/pileup_kernel_resources.txt).
 
 tools/summarize_profile.py appends this table to every profiles/*_rocprof_summary.txt, so that the occupancy and spill
 claims of DESIGN.md section 3 can be checked from profiles/ (the trace's VGPR_Count row is the granule
@@ -27,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 CXXFILT = "c++filt"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
-LAYERS = {"search": "k_search", "positions": "k_pos_", "occurrences": "k_occ_", "verify": "k_ref_|k_verify", "align": "k_align"}
+LAYERS = {"search": "k_search", "positions": "k_pos_", "occurrences": "k_occ_", "verify": "k_ref_|k_verify", "align": "k_align", "pileup": "k_pile_"}
 FIELDS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".group_segment_fixed_size",
           ".private_segment_fixed_size", ".max_flat_workgroup_size")
 
